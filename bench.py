@@ -10,7 +10,13 @@ Everything parameter-independent (locations, neighbour indices, cond flags, data
 resident in HBM before the timed region, as in the reference where vecchia_specify()
 runs once and vecchia_likelihood() once per optimiser step (R/vecchia_wrappers.R:55,72-78).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the result line (headline and roofline from the timed
+steps).  --full adds everything else the line can carry, each in runs of its own after the timed region: the same steps
+from an idle GPU (config.from_idle), the secondary modes and configurations, the CPU baseline and the parity legs
+against the oracle, and at N > 1 rank 0's evaluation of the unsharded plan (self_check) and the instrumented repeat the
+kernel time comes from.  --dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy (float64).
 
 With N > 1 and no RANK in the environment the parent starts the N ranks itself
 (`python -m torch.distributed.run --nproc-per-node N bench.py ...`, before anything touches the
@@ -395,6 +401,21 @@ def self_launch(args):
     return rc
 
 
+def dump_outputs(path, loglik, sums, plan=None, row0=0):
+    """--dump-outputs: what the last timed step returned to its caller, as float64 .npy files: the log-likelihood and the
+    8 sums it comes from.  `plan` (mode U, where the step also leaves the U entries in HBM): a fixed, seeded sample of the
+    plan's rows of Lentries (at most 48 MB) and the global indices of those rows."""
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loglik.npy"), np.array([loglik], dtype=np.float64))
+    np.save(os.path.join(path, "sums.npy"), np.asarray(sums, dtype=np.float64))
+    if plan is not None:
+        L = plan.Lentries()
+        k = min(L.shape[0], (48 << 20) // (8 * L.shape[1]))
+        rows = np.sort(np.random.default_rng(0).choice(L.shape[0], size=k, replace=False))
+        np.save(os.path.join(path, "Lentries_sample.npy"), np.ascontiguousarray(L[rows], dtype=np.float64))
+        np.save(os.path.join(path, "Lentries_sample_rows.npy"), (rows + row0).astype(np.float64))
+
+
 def other_config(name, device, measure_with, steps=10, b2b=None):
     """BASELINE.json configs[1] / configs[3] on one GPU, mode L: evals/s, set-kernel ms, FP64 fraction."""
     import gpvecchia_amd as G
@@ -529,7 +550,7 @@ def per_rank_step(args, emulate=8, steps=200):
     a real all-reduce adds its xGMI round."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.abspath(__file__), "--gpus", "1", "--steps", str(steps), "--warmup", "20",
-           "--emulate-world", str(emulate), "--no-cpu-baseline", "--no-secondary", "--config", args.config,
+           "--emulate-world", str(emulate), "--full", "--no-cpu-baseline", "--no-secondary", "--config", args.config,
            "--clock-warmup-s", str(args.clock_warmup_s)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
@@ -566,6 +587,12 @@ def main():
                     help="BASELINE.json configs (SURVEY.md §8d): C2 n=1e5 m=20 d=2; C3 n=1e6 m=30 d=2 (default, the "
                          "configuration the metric is quoted on); C4 n=1e6 m=60 d=3 exponential")
     ap.add_argument("--nu", type=float, default=None)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check beyond the headline (from_idle, secondary, CPU baseline, parity legs; N > 1: "
+                         "self-check against the unsharded plan, instrumented kernel timing); off: only what the headline needs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (loglik, sums; mode U: a row sample of the U entries) as "
+                         "DIR/<name>.npy, float64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the mode U / mode S secondary measurements")
     ap.add_argument("--no-vl-parity", action="store_true",
@@ -578,10 +605,10 @@ def main():
     ap.add_argument("--emulate-world", type=int, default=1,
                     help="developer/secondary measurement: this rank takes the row shard rank 0 of a job of that many ranks "
                          "would own (rows = n / E) while the collectives run over the real world; NOT a scaling number")
-    ap.add_argument("--self-check", action="store_true", help="(default for N > 1; kept for old command lines)")
+    ap.add_argument("--self-check", action="store_true", help="(default for N > 1 with --full; kept for old command lines)")
     ap.add_argument("--no-self-check", action="store_true",
-                    help="N > 1: skip rank 0's evaluation of the unsharded plan (by default it runs after the timed region and "
-                         "the N-rank log-likelihood must equal it to 1e-12; exit 3 otherwise)")
+                    help="N > 1 with --full: skip rank 0's evaluation of the unsharded plan (by default --full runs it after the "
+                         "timed region and the N-rank log-likelihood must equal it to 1e-12; exit 3 otherwise)")
     ap.add_argument("--comm-guard-s", type=float, default=300.0,
                     help="N > 1: wall-clock limit for communicator creation + the first all-reduced evaluation (exit 4 beyond it)")
     args = ap.parse_args()
@@ -852,33 +879,42 @@ def main():
     timing_note = "hipEvent pair around every launch of the timed region, on the launch stream"
     from_idle = None
     k_b2b = None
+    k_ms = None
     if use_dist:
         # at a fraction of a millisecond per step the event pair itself costs 7-10 us (two queue packets per launch): the K
-        # timed steps run without it, the kernel's duration comes from an instrumented repeat of the same K steps
+        # timed steps run without it, the kernel's duration comes from an instrumented repeat of the same K steps (--full)
         plan.set_kernel_timing(False)
         elapsed, _, loglik = measure(plan, flags, denom, args.steps, args.warmup)
-        plan.set_kernel_timing(True)
-        _, k_ms, _ = measure(plan, flags, denom, args.steps, 1)
-        timing_note = "hipEvent pair around every launch of an instrumented repeat of the K timed steps (events off while timing)"
-        k_b2b = kernel_ms_back_to_back(plan, flags, covparms, tau) if (world == 1 and args.mode != "S") else None
+        if args.full:
+            plan.set_kernel_timing(True)
+            _, k_ms, _ = measure(plan, flags, denom, args.steps, 1)
+            timing_note = "hipEvent pair around every launch of an instrumented repeat of the K timed steps (events off while timing)"
+            k_b2b = kernel_ms_back_to_back(plan, flags, covparms, tau) if (world == 1 and args.mode != "S") else None
     else:
-        # first, the protocol of rounds 1 and 2 for the record: W warm-up + K timed steps straight from an idle GPU (no clock
-        # warm-up): what a caller sees who evaluates a handful of times and stops; reported as config.from_idle, never as value
-        if args.clock_warmup_s > 0 and world == 1:
+        if args.full and args.clock_warmup_s > 0 and world == 1:
+            # first, the protocol of rounds 1 and 2 for the record: W warm-up + K timed steps straight from an idle GPU (no clock
+            # warm-up): what a caller sees who evaluates a handful of times and stops; reported as config.from_idle, never as value
             time.sleep(0.05)
             el0, km0, _ = measure_with(plan, flags, denom, args.steps, args.warmup, covparms, tau, n, clock_warmup_s=0.0)
             from_idle = {"value": args.steps / el0, "ms_per_step": 1e3 * el0 / args.steps, "kernel_ms": km0,
                          "what": "the same W + K steps started on an idle GPU (shader clock still ramping, DESIGN.md §5); not `value`"}
+        else:
+            # one untimed evaluation that carries the plan's one-time costs (first launch, graph capture of the posterior
+            # pass): the clock warm-up sizes itself from the duration of its first evaluations
+            measure_with(plan, flags, denom, 0, 1, covparms, tau, n, clock_warmup_s=0.0)
         elapsed, k_ms, loglik = measure(plan, flags, denom, args.steps, args.warmup)
     if use_dist:
         te = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         all_reduce_(te, dist.ReduceOp.MAX)
         elapsed = float(te.item())
-        km = torch.tensor([k_ms], dtype=torch.float64, device="cuda")
-        all_reduce_(km, dist.ReduceOp.MAX)
-        k_ms = float(km.item())
+        if k_ms is not None:
+            km = torch.tensor([k_ms], dtype=torch.float64, device="cuda")
+            all_reduce_(km, dist.ReduceOp.MAX)
+            k_ms = float(km.item())
 
     sums_job = last_sums.copy()                           # totals of the last timed step (N > 1: all-reduced over the ranks)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loglik, sums_job, plan if args.mode == "U" else None, row0=a)
     shard_info = None
     if use_dist and world > 1:
         # every rank's shard and what its GPU holds (after the timed region): rows it owns, device memory in use on its
@@ -890,21 +926,21 @@ def main():
         dist.all_gather_object(gathered, mine)
         shard_info = gathered
     gpu_U = None
-    if world == 1 and not use_dist and args.mode == "L" and not args.no_cpu_baseline and p <= 64:
+    if args.full and world == 1 and not use_dist and args.mode == "L" and not args.no_cpu_baseline and p <= 64:
         # parity_in_run, GPU half (untimed): one more evaluation that also writes the U entries, copied to the host
         plan.eval("matern", covparms, tau, flags | G.GPV_WANT_U, stream=stream)
         s_u = plan.sums()
         gpu_U = {"L": plan.Lentries(), "loglik": G.loglik_z_from_sums(s_u, n), "n_failed": int(s_u[6])}
 
-    # N > 1 proves itself (default; --no-self-check skips the second half): (1) the all-reduced row count sums[7] must equal n
-    # — every rank contributed its rows exactly once; (2) rank 0 evaluates the UNSHARDED plan after the timed region and the
+    # N > 1 proves itself (the second half with --full; --no-self-check skips it): (1) the all-reduced row count sums[7] must equal
+    # n — every rank contributed its rows exactly once; (2) rank 0 evaluates the UNSHARDED plan after the timed region and the
     # N-rank log-likelihood must equal it to 1e-12 (the shards only change the summation tree, src/U_NZentries.cpp:37-39)
     check = None
     if world > 1 and rank == 0 and args.mode != "S":
         check = {"rows_reduced": float(sums_job[7]), "rows_expected": n, "ranks": world,
                  "rows_ok": bool(sums_job[7] == n), "chol_failures_reduced": float(sums_job[6])}
         check["ok"] = check["rows_ok"]
-        if not args.no_self_check:
+        if args.full and not args.no_self_check:
             l1, z1, nn1, cd1, _, _ = build_workload(n, m, d, 0, 1, device=local_rank)
             full = G.Plan(l1, nn1, cd1, device=local_rank)
             full.set_data(z1)
@@ -949,7 +985,7 @@ def main():
                        "sharding": f"rows/{world}", "loglik": loglik, "setup_s": round(t_setup, 2),
                        "collective": route, "ranks": world, "rows_reduced": float(sums_job[7]),
                        "shards": shard_info},
-            "roofline": roofline(k_ms, rows_rank, args.mode, traffic),
+            "roofline": roofline(k_ms, rows_rank, args.mode, traffic) if k_ms is not None else None,
         }
         if k_b2b is not None:
             out["roofline"]["kernel_ms_back_to_back"] = k_b2b   # (kernel + the rank's all-reduce, no event pair per launch)
@@ -957,7 +993,7 @@ def main():
             out["config"]["from_idle"] = from_idle
         if check is not None:
             out["self_check"] = check
-        if world == 1 and not args.no_secondary and args.mode == "L":
+        if args.full and world == 1 and not args.no_secondary and args.mode == "L":
             # secondary measurements of the same workload (same JSON line, not `value`):
             #   mode U: the U entries materialised in HBM (the literal createU product, 8*(m+1) B per set written)
             #   mode S: the reference's DEFAULTS, ordering='maxmin' + cond.yz='SGV', denominator (U2V) on the GPU
@@ -1069,7 +1105,7 @@ def main():
                 except Exception as e:
                     sec["per_rank_step"] = {"error": repr(e)}
             out["secondary"] = sec
-        if world == 1 and not args.no_cpu_baseline and args.mode != "S":
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode != "S":
             cal = cpu_baseline(locs, revNN, revCond, covparms, tau, (b - min(b - a - 2 * p, 60000), b), repeats=2, sweep=False)
             kept = {}
             if n / cal["sets_per_s"] <= args.cpu_budget_s:

@@ -73,3 +73,30 @@ def test_cpu_baseline_times_the_c_function_alone(monkeypatch):
     kept2 = {}
     res2 = bench.cpu_baseline(locs, revNN, revCond, [1., .1, 1.5], .1, (n - 500, n), repeats=1, keep=kept2, sweep=False)
     assert res2["extrapolated"] and np.array_equal(kept2["Lentries"], want[n - 500:])
+
+
+def test_dump_outputs_writes_float64_within_64_mb_and_a_fixed_row_sample(tmp_path):
+    """--dump-outputs: loglik and the 8 sums as float64; mode U adds a seeded row sample of the U entries (with its global
+    row indices) that stays under 64 MB in all and is the same sample from run to run."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+
+    class FakePlan:
+        def Lentries(self):
+            return np.asfortranarray(np.arange(120_000 * 64, dtype=np.float64).reshape(120_000, 64))
+    sums = np.arange(8, dtype=np.float64)
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), -12.5, sums, FakePlan(), row0=1000)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == ["Lentries_sample.npy", "Lentries_sample_rows.npy", "loglik.npy", "sums.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= 64 << 20
+    got = {f: np.load(tmp_path / "a" / f) for f in files}
+    assert all(v.dtype == np.float64 for v in got.values())
+    assert got["loglik.npy"].tolist() == [-12.5] and np.array_equal(got["sums.npy"], sums)
+    rows = got["Lentries_sample_rows.npy"].astype(np.int64) - 1000
+    assert np.all(np.diff(rows) > 0) and rows[0] >= 0 and rows[-1] < 120_000
+    assert np.array_equal(got["Lentries_sample.npy"], FakePlan().Lentries()[rows])
+    assert all(np.array_equal(v, np.load(tmp_path / "b" / f)) for f, v in got.items())
+    bench.dump_outputs(str(tmp_path / "c"), -12.5, sums)
+    assert sorted(os.listdir(tmp_path / "c")) == ["loglik.npy", "sums.npy"]

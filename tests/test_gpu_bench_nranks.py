@@ -23,7 +23,7 @@ def _bench(extra, env=None, timeout=600):
     e.update(env or {})
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", str(N), "--steps", "5",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-secondary"] + extra,
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary"] + extra,
                        capture_output=True, text=True, timeout=timeout, env=e)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     tag = "_".join(f"{k[10:]}-{v}" for k, v in sorted((env or {}).items())).replace(":", "-") or "plain"
@@ -81,7 +81,8 @@ def test_eight_ranks_the_target_world_size_at_full_size_on_one_gpu():
         e.pop(k, None)
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--n", "1000000", "--steps", "5",
-                        "--warmup", "1", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900, env=e)
+                        "--warmup", "1", "--full", "--no-cpu-baseline", "--no-secondary"], capture_output=True, text=True, timeout=900,
+                       env=e)
     elapsed = time.time() - t0
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
     try:

@@ -7,7 +7,7 @@ tail -14 $O/gpu_tests.txt
 timeout 1500 python tools/fuzz_vl.py 0 150 > $O/vl.txt 2>&1; tail -8 $O/vl.txt
 timeout 1200 python tools/fuzz_posterior.py 9000 9400 --oracle > $O/posterior.txt 2>&1; tail -4 $O/posterior.txt
 timeout 900 python tools/fuzz_more.py 24 424 > $O/sets.txt 2>&1; tail -7 $O/sets.txt
-( time python bench.py ) > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
+( time python bench.py --full ) > $O/bench.json 2> $O/bench.err; tail -3 $O/bench.err
 python3 - <<'PY'
 import json
 j = json.loads([l for l in open('gpurun_out/r06fix/bench.json') if l.startswith('{')][-1])

@@ -32,7 +32,7 @@ for nu, rg in ((0.3, 0.05), (1.1, 0.02), (1.1, 0.3), (2.2, 0.1), (7.5, 0.05), (0
     err = np.abs(out["Lentries"] - ref["Lentries"]).max(axis=1) / np.abs(ref["Lentries"]).max(axis=1)
     print(f"shipped table nu={nu} range={rg}: max row err {err.max():.2e}, rows beyond 1e-8: {(err > 1e-8).sum()}, beyond 1e-10: {(err > 1e-10).sum()}, median {np.median(err):.1e}, failed rows hip {out['n_failed']} oracle {ref['n_failed']}")
 PY
-python bench.py --no-secondary --steps 20 --warmup 5 2>/dev/null | python3 -c "
+python bench.py --full --no-secondary --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('headline', j['value'], j['roofline']['frac'], 'speedup', j['speedup_vs_cpu_port']); print(json.dumps(j['cpu_baseline'])[:3000])" | tee $O/cpu_baseline.txt

@@ -52,7 +52,7 @@ done
 unset GPV_LIB
 # the changed default library: new GPU tests of this round + cpu_baseline evidence
 timeout 1200 python -m pytest tests/test_gpu_parity.py tests/test_gpu_prediction.py -m gpu -x -q -k "speculative or long_rows or generic or nu" 2>&1 | tail -5
-python bench.py --no-secondary --steps 20 --warmup 5 2>/dev/null | python3 -c "
+python bench.py --full --no-secondary --steps 20 --warmup 5 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 print('headline', j['value'], j['roofline']['frac']); print(json.dumps(j['cpu_baseline'])[:2500])" | tee $O/cpu_baseline.txt
