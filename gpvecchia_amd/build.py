@@ -25,6 +25,12 @@ SPLIT_FROM_P = 41          # row lengths from here on compile one TU per spatial
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-variable"]
 
 
+def lik_p(P):
+    """Row lengths with the likelihood-only kernels (k_lik in gpv_sets_kernel.hpp, default settings: the 16-lane geometry
+    with two row slots and a spare one for the data row); they compile in a TU of their own."""
+    return 16 < P < 32
+
+
 def plist():
     txt = open(os.path.join(CSRC, "gpv_plist.h")).read()
     line = [l for l in txt.splitlines() if l.startswith("#define GPV_P_LIST")][0]
@@ -80,6 +86,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
                          kern, force))
         else:
             work.append((inst, os.path.join(BUILD, f"sets_p{P}.o"), [f"-DGPV_INST_P={P}"] + extra_flags, kern, force))
+        if lik_p(P):
+            work.append((inst, os.path.join(BUILD, f"sets_p{P}_lik.o"), [f"-DGPV_INST_P={P}", "-DGPV_INST_LIK"] + extra_flags,
+                         kern, force))
     work.append((os.path.join(CSRC, "gpv_aux_kernels.hip"), os.path.join(BUILD, "aux.o"), list(extra_flags),
                  kern + H("gpv_plist.h"), force))
     work.append((os.path.join(CSRC, "gpv_api.hip"), os.path.join(BUILD, "api.o"), list(extra_flags), internal + [pub] + H("gpv_laplace.h", "gpv_generic.h", "gpv_posterior_ext.h"), force))

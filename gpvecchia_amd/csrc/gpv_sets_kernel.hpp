@@ -154,6 +154,24 @@ struct Geo {
     static constexpr int MINW = (P <= 32) ? GPV_MINW_SMALL : (RPL >= 2 ? 1 : GPV_MINW_LARGE);   // launch_bounds waves/SIMD
 };
 
+// Likelihood-only launches (no U row, no compact block, no a vector) need v and -mu_k only, which FORWARD elimination alone
+// yields: the LIK variant of the set kernel runs a lower-triangle LDL^T sweep instead of Gauss-Jordan.  It pays where the
+// 16-lane geometry has two or more row slots (one slot: the same FMAs) and a data row (without one, -mu_k is formed from b).
+#ifndef GPV_LIK_MAXP
+#define GPV_LIK_MAXP 32        // (P = 41: three rows per lane, AGPR parking: not built)
+#endif
+template <int P>
+__host__ __device__ constexpr bool k_lik()
+{
+    return Geo<P>::DPP && !Geo<P>::DPP2 && Geo<P>::RPL >= 2 && Geo<P>::ZROW && P <= GPV_LIK_MAXP;
+}
+// the last column a row of slot q can own on or left of its diagonal (the data row ends at column P - 1)
+template <int P>
+__host__ __device__ constexpr int lik_maxcol(int q)
+{
+    return (q + 1) * Geo<P>::LPS - 1 < P - 1 ? (q + 1) * Geo<P>::LPS - 1 : P - 1;
+}
+
 // compile-time loop: f(std::integral_constant<int, B>{}), ..., f(std::integral_constant<int, E-1>{})
 template <int B, class F, int... Is>
 __device__ __forceinline__ void static_for_impl(F &&f, std::integer_sequence<int, Is...>)
@@ -236,6 +254,22 @@ __device__ __forceinline__ void pivot_lane_fix(double &nw, double &pr, double ri
                  "v_mov_b64 %[pr], %[ri]\n\t"
                  "s_mov_b64 exec, %[sv]"
                  : [sv] "=&s"(sv), [nw] "+v"(nw), [pr] "+v"(pr)
+                 : [m] "n"(M), [ri] "v"(rinv)
+                 : "scc");
+}
+// The lower-triangle sweep's half of it: pr = rinv in the lane that owns the pivot row (one VALU instruction; no nw to clear,
+// the pivot row's own update only touches cells above its diagonal, which nothing reads)
+template <int SH>
+__device__ __forceinline__ void pivot_lane_keep(double &pr, double rinv)
+{
+    constexpr unsigned M = 0x00010001u << SH;
+    unsigned long long sv;
+    asm volatile("s_mov_b64 %[sv], exec\n\t"
+                 "s_and_b32 exec_lo, exec_lo, %[m]\n\t"
+                 "s_and_b32 exec_hi, exec_hi, %[m]\n\t"
+                 "v_mov_b64 %[pr], %[ri]\n\t"
+                 "s_mov_b64 exec, %[sv]"
+                 : [sv] "=&s"(sv), [pr] "+v"(pr)
                  : [m] "n"(M), [ri] "v"(rinv)
                  : "scc");
 }
@@ -748,12 +782,14 @@ __device__ __forceinline__ double cov_closed(double r2, double sig0, double sA, 
     }
 }
 
-template <int P, int D, int COV>
+// LIK: the likelihood-only variant (k_lik): lower-triangle sweep, no U row, no compact block, no a vector
+template <int P, int D, int COV, bool LIK = false>
 __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_sets_kernel(const SetArgs A)
 {
     using G = Geo<P>;
     constexpr int RPL = G::RPL, LPS = G::LPS, SPW = G::SPW, W = wpb<P, D, COV>();
     constexpr bool ZROW = G::ZROW;
+    static_assert(!LIK || (k_lik<P>() && COV != COV_DENSE), "the lower-triangle sweep is built for k_lik geometries only");
     using Lds = SetsLds<P, D, COV>;
     constexpr int COLS = Lds::COLS;
     __shared__ Lds lds_all[W];
@@ -819,8 +855,8 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
     // (the set kernel of --mode S ran 1.30 ms against 1.18 in mode L, and all but 0.02 ms of that WITHOUT the pass running in
     // between: tools/sessions/r4_modeS.sh; SQ_WAIT_ANY +50 %).  Now the output row travels with the indices one task ahead and
     // the block offset with the location records from the middle of the previous sweep.
-    const bool want_row = GPV_OPT_PFOUT != 0 && ((A.flags & (1 | kFlagFused)) != 0 || A.aout != nullptr);
-    const bool want_cb = GPV_OPT_PFOUT != 0 && (A.flags & kFlagFused) != 0;
+    const bool want_row = !LIK && GPV_OPT_PFOUT != 0 && ((A.flags & (1 | kFlagFused)) != 0 || A.aout != nullptr);
+    const bool want_cb = !LIK && GPV_OPT_PFOUT != 0 && (A.flags & kFlagFused) != 0;
     typedef __attribute__((address_space(1))) const int32_t gl_ci32_t;
     gl_ci32_t *cboff_pf = nullptr;                           // (fused: from the header in front of aout, once)
     if (want_cb) {
@@ -1266,6 +1302,16 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
             const double *extra = (ZROW && r == P) ? &L.col[Lds::NCOL - 1][sub][0] : &L.zero[0];
             // spare slots (r >= P) always take the "c <= r" branch below: point it at the staged row instead
             const double *rowA = (RPL * LPS > P && r >= P) ? extra : &L.tri[sub][(int)(__umul24(rc, rc + 1) >> 1)];
+            if constexpr (LIK) {
+                // lower triangle only: the columns a row of this slot can own on or left of its diagonal, all in the row part
+                // of the triangle (cells right of a lane's diagonal inside the slot's block read whatever lies there, in
+                // bounds, and are never read back)
+                static_for<0, P>([&](auto cc) __attribute__((always_inline)) {
+                    constexpr int c = decltype(cc)::value;
+                    if (c <= lik_maxcol<P>(q)) a[q][c] = rowA[c];
+                });
+                continue;
+            }
             const double *colB = &L.tri[sub][rc];
 #pragma unroll
             for (int c = 0; c < P; ++c) {
@@ -1281,13 +1327,45 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         }
         wave_sync();
 
-        // ---- Gauss-Jordan sweep over pivots 0..P-2 ------------------------------------
+        // ---- Gauss-Jordan sweep over pivots 0..P-2 (LIK: lower-triangle sweep) --------
         double prinv[RPL];                             // reciprocal of each row's own pivot (kept out of a[] indexing)
 #pragma unroll
         for (int q = 0; q < RPL; ++q) prinv[q] = 1.0;
         double vlast;                                  // Schur complement of the point itself (row P-1)
         double negmu_z = 0.0;                          // data row after the sweep: -mu_k (ZROW geometries)
-        if constexpr (G::DPP) {
+        if constexpr (LIK) {
+            // Lower-triangle LDL^T sweep (dpotf2's outer-product form) over pivots 0..P-2.  Row r keeps its cells c <= r; pivot j
+            // takes the multiplier nw = -a_rj / p_j from its own register and updates a_rc += nw a_cj for j < c <= r, where a_cj is
+            // register a[c / 16][j] of lane c % 16: column j of the trailing matrix, stored once.  Lanes whose row is shorter
+            // than the slot's last column (and the pivot row itself) update cells above their diagonal, which nothing reads.
+            // A slot stops once its last column is behind the pivot.  After pivot P-2 the diagonal of row P-1 is v and the data
+            // row's last cell -mu_k; b = S11^-1 s_l is never formed (no U row, no a_k vector in this variant).
+            static_for<0, P - 1>([&](auto jc) __attribute__((always_inline)) {
+                constexpr int j = decltype(jc)::value;
+                constexpr int qj = j / LPS;                                 // the slot that holds pivot row j (in lane j % 16)
+                if constexpr (PFREC && j == GPV_PFREC_AT(P)) load_rec();    // pidx: the NEXT task's indices by now
+                // slots behind qj hold column j too: their writers of it go in front of the broadcast (dpp_row_bcast), and every
+                // DPP read of column j below depends on the broadcast through the reciprocal
+                double d1 = 0.0, d2 = 0.0;
+                if constexpr (qj + 1 < RPL) d1 = a[qj + 1][j];
+                if constexpr (qj + 2 < RPL) d2 = a[qj + 2][j];
+                const double pj = dpp_row_bcast<j % 16>(a[qj][j], d1, d2);   // pivot = Schur complement d_j^2
+                const double rinv = rcp_pivot_bounded(pj);
+                pivot_lane_keep<j % 16>(prinv[qj], rinv);
+                double nw[RPL];
+#pragma unroll
+                for (int q = qj; q < RPL; ++q) nw[q] = a[q][j] * -rinv;   // (slot qj after its last column: dead, removed)
+                static_for<j + 1, P>([&](auto cc) __attribute__((always_inline)) {
+                    constexpr int c = decltype(cc)::value;
+                    static_for<qj, RPL>([&](auto qc) __attribute__((always_inline)) {
+                        constexpr int q = decltype(qc)::value;
+                        if constexpr (c <= lik_maxcol<P>(q)) dpp_fmac<c % 16>(a[q][c], a[c / 16][j], nw[q]);
+                    });
+                });
+            });
+            vlast = set_bcast<LPS, (P - 1) % LPS>(a[(P - 1) / LPS][P - 1]);
+            negmu_z = set_bcast<LPS, P % LPS>(a[P / LPS][P - 1]);
+        } else if constexpr (G::DPP) {
             // the pivot row never leaves the registers: element c of pivot row j is a[j/16][c] of lane j%16, fetched by the DPP
             // row broadcast of each FMA (row pairs: column j of the bit-symmetric current matrix, see below)
             static_for<0, P - 1>([&](auto jc) __attribute__((always_inline)) {
@@ -1370,7 +1448,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                         // (the DPP source of column c + 2 is pinned to a VGPR HERE, two FMAs ahead of its read: under register
                         //  pressure -- three rows per lane at P = 41 -- hipcc parks matrix registers in AGPRs and fetches them back
                         //  with v_accvgpr_read right in front of their use, a VALU write the inline-asm DPP read would not wait
-                        //  for; tools/dpp_hazard_scan.py checks every built object for exactly that)
+                        //  for; python -m gpvecchia_amd.build --check-dpp (build.dpp_hazards) checks every built object for exactly that)
                         if constexpr (GPV_PIN_DPP_SRC(RPL) && c + 2 < P) asm volatile("" : "+v"(a[qj][c + 2]));
 #pragma unroll
                         for (int q = Q0; q < RPL; ++q)
@@ -1489,11 +1567,13 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         const bool fail = (__ballot(bad) & setmask) != 0ull;
         const double rs = rsqrt_pos(vlast);            // M[n0-1] = d_k = 1/R[n0-1][n0-1]
         const double dlast = vlast * rs;               // R[n0-1][n0-1] = sqrt(v)
-        double x[RPL];
+        double x[RPL] = {};                            // the set's row of U (LIK: not formed, nothing below reads it)
+        if constexpr (!LIK) {
 #pragma unroll
-        for (int q = 0; q < RPL; ++q) {
-            x[q] = (row[q] == P - 1) ? rs : -(a[q][P - 1] * prinv[q]) * rs;
-            if (!valid[q] || fail) x[q] = 0.0;
+            for (int q = 0; q < RPL; ++q) {
+                x[q] = (row[q] == P - 1) ? rs : -(a[q][P - 1] * prinv[q]) * rs;
+                if (!valid[q] || fail) x[q] = 0.0;
+            }
         }
 
         // ---- outputs -------------------------------------------------------------------
@@ -1509,7 +1589,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         const int32_t *const rowid = A.rowid;
         double *const aout = A.aout;
 #endif
-        if (A.flags & 1) {
+        if (!LIK && (A.flags & 1)) {
             const int n0 = P - nmiss;
             const int64_t kout = set_on ? (int64_t)(want_row ? row_out : rowid[k]) : 0;   // row of Lentries this stored set belongs to
 #pragma unroll
@@ -1520,7 +1600,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                 }
             }
         }
-        const bool fused = (A.flags & kFlagFused) != 0;
+        const bool fused = !LIK && (A.flags & kFlagFused) != 0;
         typedef double v2d_out __attribute__((ext_vector_type(2)));
         typedef __attribute__((address_space(1))) v2d_out gl_v2d;
         gl_v2d *Cout = nullptr;
@@ -1566,7 +1646,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                 // a vector (the compaction launch and the 'zy' mean, whose t IS a, read that); never both: the vector's entry
                 // is an 8-byte store to a line of its own per set
                 const bool a_to_vec = !fused || (A.flags & kFlagBoth) != 0;
-                if (aout != nullptr && a_to_vec && set_on && i == IO) aout[want_row ? row_out : rowid[k]] = fail ? 0.0 : negmu * rs;
+                if (!LIK && aout != nullptr && a_to_vec && set_on && i == IO) aout[want_row ? row_out : rowid[k]] = fail ? 0.0 : negmu * rs;
                 if (fused && set_on && i == IO) Cout[cb] = v2d_out{fail ? 0.0 : negmu * rs, 0.0};
                 if (A.flags & 2) {
                     const double tv = tau + vlast;
@@ -1629,6 +1709,39 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
 #endif
 }
 
+// Likelihood-only launches of row length P (k_lik<P>()): the LIK kernels are compiled in a translation unit of their own
+// (gpv_sets_inst.hip with GPV_INST_LIK, which instantiates this) so that they do not lengthen the longest compile
+template <int P>
+hipError_t launch_sets_lik(const SetArgs &a, int grid, hipStream_t stream);
+#ifdef GPV_INST_LIK
+template <int P>
+hipError_t launch_sets_lik(const SetArgs &a, int grid, hipStream_t stream)
+{
+    static_assert(k_lik<P>(), "LIK translation unit for a row length without the lower-triangle sweep");
+    auto go = [&](auto dc, auto cc) -> hipError_t {
+        constexpr int D = decltype(dc)::value, COV = decltype(cc)::value;
+        hipLaunchKernelGGL((gpv_sets_kernel<P, D, COV, true>), dim3(grid), dim3(wpb<P, D, COV>() * 64), 0, stream, a);
+        return hipGetLastError();
+    };
+    auto per_dim = [&](auto dc) -> hipError_t {
+        switch (a.cov) {
+            case COV_MATERN05: return go(dc, std::integral_constant<int, COV_MATERN05>{});
+            case COV_MATERN15: return go(dc, std::integral_constant<int, COV_MATERN15>{});
+            case COV_MATERN25: return go(dc, std::integral_constant<int, COV_MATERN25>{});
+            case COV_ESQE: return go(dc, std::integral_constant<int, COV_ESQE>{});
+            case COV_MATERN_GEN: return go(dc, std::integral_constant<int, COV_MATERN_GEN>{});
+            default: return hipErrorInvalidValue;
+        }
+    };
+    switch (a.dim) {
+        case 1: return per_dim(std::integral_constant<int, 1>{});
+        case 2: return per_dim(std::integral_constant<int, 2>{});
+        case 3: return per_dim(std::integral_constant<int, 3>{});
+        default: return per_dim(std::integral_constant<int, 0>{});
+    }
+}
+#endif
+
 template <int P, int D, int COV>
 hipError_t launch_sets_PDC(const SetArgs &a_in, int cus, int *grid_out, hipStream_t stream)
 {
@@ -1667,6 +1780,11 @@ hipError_t launch_sets_PDC(const SetArgs &a_in, int cus, int *grid_out, hipStrea
         a.share_young = two_one ? 1 : 2;
         if (shares_env) (void)sscanf(shares_env, "%d,%d", &a.share_old, &a.share_young);
         if (a.share_old > 16 || a.share_young < 1 || a.share_young >= a.share_old) a.share_old = a.share_young = 0;
+    }
+    // likelihood-only launches: no U row (GPV_WANT_U), no compact block, no a vector -- the lower-triangle sweep
+    // (same grid and task shares: the LIK kernel has the same geometry, LDS and occupancy)
+    if constexpr (k_lik<P>() && COV != COV_DENSE) {
+        if ((a.flags & (1 | kFlagFused)) == 0 && a.aout == nullptr) return launch_sets_lik<P>(a, grid, stream);
     }
     hipLaunchKernelGGL((gpv_sets_kernel<P, D, COV>), dim3(grid), dim3(W * 64), 0, stream, a);
     return hipGetLastError();

@@ -27,6 +27,9 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   done
   for P in $PLIST; do
     $HIPCC $CF "-DGPV_P_LIST(X)=$plx" -DGPV_INST_P=$P -c $CSRC/gpv_sets_inst.hip -o $B/sets_p$P.o & pids+=($!)
+    if [ $P -gt 16 ] && [ $P -lt 32 ]; then      # likelihood-only kernels: a unit of their own (gpvecchia_amd/build.py lik_p)
+      $HIPCC $CF "-DGPV_P_LIST(X)=$plx" -DGPV_INST_P=$P -DGPV_INST_LIK -c $CSRC/gpv_sets_inst.hip -o $B/sets_p${P}_lik.o & pids+=($!)
+    fi
   done
   $HIPCC $CF -x c++ -c $CSRC/gpv_order.cpp -o $B/order.o & pids+=($!)
   $HIPCC $CF -c $ROOT/tests/sanitize/mock_hip_runtime.cpp -o $B/mock.o & pids+=($!)
