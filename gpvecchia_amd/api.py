@@ -174,6 +174,33 @@ class Plan:
         L.check(L.lib().gpv_plan_get_posterior_mean(self._h, L.dptr(out)), "gpv_plan_get_posterior_mean")
         return out
 
+    def factor_stamp(self):
+        """0 while the plan holds no posterior factor, else a number that changes with every evaluation that writes one."""
+        st = C.c_int64(0)
+        L.check(L.lib().gpv_plan_factor_stamp(self._h, C.byref(st)), "gpv_plan_factor_stamp")
+        return int(st.value)
+
+    def lincomb(self, H_ord, cov_mat=False):
+        """Var(H y | z) (or, with cov_mat, Cov) for the rows of H_ord, a scipy.sparse or dense matrix with Nlocs columns in
+        the plan's ORDERED latent index, from the factor of the latest evaluation with GPV_WANT_DENOM / GPV_WANT_MEAN /
+        GPV_WANT_MEAN_B (gpv_plan_lincomb: one batched triangular solve on the device, nothing is factorised again)."""
+        import scipy.sparse as sp
+        H = H_ord.tocsr() if sp.issparse(H_ord) else sp.csr_matrix(np.atleast_2d(np.asarray(H_ord, dtype=np.float64)))
+        if H.shape[1] != self.Nlocs:
+            raise ValueError("H_ord must have one column per ordered location of the plan")
+        H.sum_duplicates()
+        nrows = int(H.shape[0])
+        hptr = np.ascontiguousarray(H.indptr, dtype=np.int64)
+        hidx = np.ascontiguousarray(H.indices, dtype=np.int32)
+        hval = np.ascontiguousarray(H.data, dtype=np.float64)
+        vars_ = np.zeros(max(nrows, 1))
+        cov = np.zeros((nrows, nrows)) if cov_mat else None
+        st = L.lib().gpv_plan_lincomb(self._h, nrows, hptr.ctypes.data_as(C.POINTER(C.c_int64)),
+                                      hidx.ctypes.data_as(C.POINTER(C.c_int32)), L.dptr(hval), L.dptr(vars_),
+                                      L.dptr(cov) if cov_mat else None)
+        L.check(st, "gpv_plan_lincomb")
+        return cov if cov_mat else vars_[:nrows]
+
     kernel_timing = True
 
     def set_kernel_timing(self, on):
@@ -849,14 +876,16 @@ class _TriFactor:
         return spla.spsolve_triangular(self.V.T.tocsr(), y, lower=False)
 
 
-def vecchia_mean_host(z, U_obj):
-    """R/vecchia_prediction.R:118-126 on the host: mu.ord = -W^{-1} z2 (ordered layout, one entry per latent variable)."""
+def vecchia_mean_host(z, U_obj, lu=None):
+    """R/vecchia_prediction.R:118-126 on the host: mu.ord = -W^{-1} z2 (ordered layout, one entry per latent variable).
+    lu: the factor object of U2V(U_obj) when the caller has it already."""
     U = U_obj["U"].tocsr()
     latent = U_obj["latent"]
     zord = np.asarray(z, dtype=np.float64)[U_obj["ord_z"] - 1]
     z1 = U[np.where(~latent)[0], :].T @ zord
     z2 = U[np.where(latent)[0], :] @ z1
-    lu = U2V(U_obj)
+    if lu is None:
+        lu = U2V(U_obj)
     return -(lu.solve(z2[::-1]))[::-1]
 
 

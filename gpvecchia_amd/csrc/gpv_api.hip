@@ -378,6 +378,13 @@ struct gpv_plan {
     int mean_head_levels = 0;                        // leading levels of the mean sweep run by one workgroup
     double *d_u = nullptr, *d_mu = nullptr;
     bool have_mean = false;
+    // linear combinations (gpv_plan_lincomb): everything is allocated on first use
+    bool have_factor = false;                        // C holds the factor of an evaluation with a posterior pass
+    int64_t factor_stamp = 0;                        // counts those evaluations
+    int2 *d_lc_rec = nullptr;                        // LincombArgs::lrec, rebuilt after gpv_plan_build_posterior
+    bool lc_ready = false;
+    double *d_lc_X = nullptr, *d_lc_part = nullptr, *d_lc_vars = nullptr, *d_lc_gpart = nullptr, *d_lc_gram = nullptr;
+    hipGraphExec_t lc_graph = nullptr;               // the sweep (levels, top block, column sums) as a captured graph
     double nug_scalar = 0.0;
     bool nug_is_scalar = true;
     uint8_t *d_cond = nullptr;
@@ -452,9 +459,11 @@ int gpv_plan_destroy(gpv_plan *pl)
                     pl->d_C, pl->d_cboff, pl->d_cdel, pl->d_ccol, pl->d_avec_base, pl->d_tvec, pl->d_rdiag, pl->d_post_part, pl->d_zuser,
                     pl->d_order2, pl->d_levptr2, pl->d_toppart, pl->d_u, pl->d_mu, pl->d_tp, pl->d_nug_post, pl->d_mt2[0], pl->d_mt2[1],
                     pl->d_vl_z, pl->d_vl_pm, pl->d_vl_y[0], pl->d_vl_y[1], pl->d_vl_out, pl->d_vl_flags, pl->d_ticket,
-                    pl->d_vl_y0, pl->d_vl_part, pl->d_user_ord, pl->d_meanrec, pl->d_obs, pl->d_topinfo, pl->d_toprows, pl->d_rr0, pl->d_nug_masked};
+                    pl->d_vl_y0, pl->d_vl_part, pl->d_user_ord, pl->d_meanrec, pl->d_obs, pl->d_topinfo, pl->d_toprows, pl->d_rr0, pl->d_nug_masked,
+                    pl->d_lc_rec, pl->d_lc_X, pl->d_lc_part, pl->d_lc_vars, pl->d_lc_gpart, pl->d_lc_gram};
     for (auto &g : pl->pgraph)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
+    if (pl->lc_graph) (void)hipGraphExecDestroy(pl->lc_graph);
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (int t = 0; t < 2; ++t) {
@@ -974,6 +983,7 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
         }
     }
     if (flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B)) {
+        pl->have_factor = false;                                         // C is being rewritten: true again once the pass is enqueued
         // (constant nugget: the set kernel above left it in d_nug_post[0]; vector: d_nug_user, a fixed address as well)
         PostArgs pa;
         pa.colptr = pl->d_colptr; pa.crow = pl->d_crow;
@@ -1055,6 +1065,8 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
             }
         }
         if (!launched) GPV_HIP(enqueue());                               // inside someone else's capture, or graphs off
+        pl->have_factor = true;                                          // (gpv_plan_lincomb reads C as this pass leaves it)
+        ++pl->factor_stamp;
         if (want_mean || mean_b) pl->have_mean = true;
     }
     pl->evaluated = true;
@@ -1191,6 +1203,9 @@ static int build_posterior_impl(gpv_plan *pl, const int *revNN, const int *revCo
     // a rebuild that fails half way must not leave the old schedule's graphs and flag over new tables: the plan has no
     // posterior structure from here until the last line of this function
     pl->have_post = false;
+    pl->have_factor = false;
+    pl->lc_ready = false;
+    if (pl->lc_graph) { (void)hipGraphExecDestroy(pl->lc_graph); pl->lc_graph = nullptr; }
     if (pl->last_stream) { GPV_HIP(hipSetDevice(pl->device)); GPV_HIP(hipStreamSynchronize(pl->last_stream)); }
     for (auto &g : pl->pgraph)
         if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
@@ -1883,6 +1898,170 @@ int gpv_plan_posterior_levels(gpv_plan *pl, int *n_levels)
     if (!pl || !n_levels) return GPV_ERR_BAD_ARG;
     if (!pl->have_post) return GPV_ERR_STATE;
     *n_levels = (int)pl->levptr.size() - 1;
+    return GPV_OK;
+}
+
+int gpv_lincomb_batch(void) { return kLincombNB; }
+
+int gpv_plan_factor_stamp(gpv_plan *pl, int64_t *stamp)
+{
+    if (!pl || !stamp) return GPV_ERR_BAD_ARG;
+    *stamp = (pl->have_post && pl->have_factor) ? pl->factor_stamp : 0;
+    return GPV_OK;
+}
+
+// LincombArgs::lrec from the plan's structure as it lives on the device (built on the first gpv_plan_lincomb after a
+// gpv_plan_build_posterior: plans that never ask for variances pay nothing).  The row lists are rebuilt exactly as
+// build_posterior_impl lays them out (columns ascending, the column itself first), so that the positions the column records
+// name are these.
+static int lincomb_prepare(gpv_plan *pl)
+{
+    const int64_t n = pl->Nlocs;
+    const size_t nnz = (size_t)pl->post_nnz;
+    std::vector<int32_t> colptr((size_t)n + 1), crow(nnz), cboff((size_t)n);
+    std::vector<int2> topinfo((size_t)pl->top_K);
+    GPV_HIP(hipMemcpy(colptr.data(), pl->d_colptr, colptr.size() * 4, hipMemcpyDeviceToHost));
+    if (nnz) GPV_HIP(hipMemcpy(crow.data(), pl->d_crow, nnz * 4, hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(cboff.data(), pl->d_cboff, cboff.size() * 4, hipMemcpyDeviceToHost));
+    if (pl->top_K > 0) GPV_HIP(hipMemcpy(topinfo.data(), pl->d_topinfo, topinfo.size() * sizeof(int2), hipMemcpyDeviceToHost));
+    if ((size_t)colptr[(size_t)n] != nnz) return GPV_ERR_STATE;
+    std::vector<uint8_t> in_top((size_t)n, 0);
+    for (const int2 &t : topinfo) {
+        if (t.x < 0 || t.x >= n) return GPV_ERR_STATE;
+        in_top[(size_t)t.x] = 1;
+    }
+    std::vector<int32_t> fill((size_t)n + 1, 0);
+    for (size_t e = 0; e < nnz; ++e) {
+        if (crow[e] < 0 || crow[e] >= n) return GPV_ERR_STATE;
+        fill[(size_t)crow[e] + 1]++;
+    }
+    for (int64_t i = 0; i < n; ++i) fill[(size_t)i + 1] += fill[(size_t)i];
+    std::vector<int2> lrec(nnz ? nnz : 1);
+    for (int64_t c = 0; c < n; ++c)
+        for (int32_t e = colptr[(size_t)c]; e < colptr[(size_t)c + 1]; ++e) {
+            const int32_t i = crow[(size_t)e];
+            lrec[(size_t)fill[(size_t)i]++] = make_int2(in_top[(size_t)c] ? ~(int32_t)c : (int32_t)c,
+                                                        cboff[(size_t)c] + 1 + (e - colptr[(size_t)c]));
+        }
+    if (pl->d_lc_rec) { (void)hipFree(pl->d_lc_rec); pl->d_lc_rec = nullptr; }
+    GPV_HIP(hipMalloc((void **)&pl->d_lc_rec, lrec.size() * sizeof(int2)));
+    GPV_HIP(hipMemcpy(pl->d_lc_rec, lrec.data(), lrec.size() * sizeof(int2), hipMemcpyHostToDevice));
+    if (!pl->d_lc_X) GPV_HIP(hipMalloc((void **)&pl->d_lc_X, sizeof(double) * (size_t)n * kLincombNB));
+    if (!pl->d_lc_part) GPV_HIP(hipMalloc((void **)&pl->d_lc_part, sizeof(double) * (size_t)kLincombBlocks * kLincombNB));
+    if (!pl->d_lc_vars) GPV_HIP(hipMalloc((void **)&pl->d_lc_vars, sizeof(double) * kLincombNB));
+    pl->lc_ready = true;
+    return GPV_OK;
+}
+
+int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int32_t *hidx, const double *hval, double *vars,
+                     double *cov)
+{
+    constexpr int NB = kLincombNB;
+    if (!pl || nrows < 0 || !hptr || !vars) return GPV_ERR_BAD_ARG;
+    if (cov && nrows > NB) return GPV_ERR_BAD_ARG;
+    if (hptr[0] < 0) return GPV_ERR_BAD_ARG;
+    for (int64_t r = 0; r < nrows; ++r)
+        if (hptr[r + 1] < hptr[r]) return GPV_ERR_BAD_ARG;
+    const int64_t h0 = hptr[0], hnnz = hptr[nrows] - h0;
+    if (hnnz > 0 && (!hidx || !hval)) return GPV_ERR_BAD_ARG;
+    // per batch: the longest row, and whether some row repeats an index (rows that ascend strictly cannot)
+    const int64_t nbatch = (nrows + NB - 1) / NB;
+    std::vector<int64_t> bmax((size_t)nbatch, 0);
+    std::vector<uint8_t> bserial((size_t)nbatch, 0);
+    for (int64_t r = 0; r < nrows; ++r) {
+        bool ascending = true;
+        for (int64_t q = hptr[r]; q < hptr[r + 1]; ++q) {
+            if (hidx[q] < 0 || (int64_t)hidx[q] >= pl->Nlocs) return GPV_ERR_INDEX;
+            if (q > hptr[r] && hidx[q] <= hidx[q - 1]) ascending = false;
+        }
+        if (!ascending) {                                    // no repeat after all?  (sorted copy of the row)
+            std::vector<int32_t> tmp(hidx + hptr[r], hidx + hptr[r + 1]);
+            std::sort(tmp.begin(), tmp.end());
+            if (std::adjacent_find(tmp.begin(), tmp.end()) != tmp.end()) bserial[(size_t)(r / NB)] = 1;
+        }
+        bmax[(size_t)(r / NB)] = std::max(bmax[(size_t)(r / NB)], hptr[r + 1] - hptr[r]);
+    }
+    if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
+    if (nrows == 0) return GPV_OK;
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (!pl->lc_ready) {
+        const int rc = lincomb_prepare(pl);
+        if (rc != GPV_OK) return rc;
+    }
+    hipStream_t st = pl->stream;
+    int64_t *d_hptr = nullptr;
+    int32_t *d_hidx = nullptr;
+    double *d_hval = nullptr;
+    auto release = [&]() {
+        if (d_hptr) (void)hipFree(d_hptr);
+        if (d_hidx) (void)hipFree(d_hidx);
+        if (d_hval) (void)hipFree(d_hval);
+    };
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); release(); return rc; };
+    std::vector<int64_t> hp((size_t)nrows + 1);
+    for (int64_t r = 0; r <= nrows; ++r) hp[(size_t)r] = hptr[r] - h0;        // offsets into the uploaded slice
+    if (GPV_HIP_FAILED(hipMalloc((void **)&d_hptr, hp.size() * sizeof(int64_t))) ||
+        GPV_HIP_FAILED(hipMalloc((void **)&d_hidx, (size_t)(hnnz ? hnnz : 1) * sizeof(int32_t))) ||
+        GPV_HIP_FAILED(hipMalloc((void **)&d_hval, (size_t)(hnnz ? hnnz : 1) * sizeof(double))))
+        return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpy(d_hptr, hp.data(), hp.size() * sizeof(int64_t), hipMemcpyHostToDevice))) return fail(GPV_ERR_HIP);
+    if (hnnz && (GPV_HIP_FAILED(hipMemcpy(d_hidx, hidx + h0, (size_t)hnnz * sizeof(int32_t), hipMemcpyHostToDevice)) ||
+                 GPV_HIP_FAILED(hipMemcpy(d_hval, hval + h0, (size_t)hnnz * sizeof(double), hipMemcpyHostToDevice))))
+        return fail(GPV_ERR_HIP);
+    if (cov) {
+        if (!pl->d_lc_gpart && GPV_HIP_FAILED(hipMalloc((void **)&pl->d_lc_gpart, sizeof(double) * (size_t)kLincombBlocks * NB * NB)))
+            return fail(GPV_ERR_HIP);
+        if (!pl->d_lc_gram && GPV_HIP_FAILED(hipMalloc((void **)&pl->d_lc_gram, sizeof(double) * NB * NB))) return fail(GPV_ERR_HIP);
+    }
+    LincombArgs la;
+    la.colrec = pl->d_colrec; la.lrec = pl->d_lc_rec; la.C = pl->d_C; la.X = pl->d_lc_X;
+    // the sweep: the factor pass's levels, leaves first, then the dense top block, then the column sums
+    auto enqueue = [&]() -> hipError_t {
+        hipError_t e = hipSuccess;
+        for (size_t lv = 0; e == hipSuccess && lv + 1 < pl->levptr.size(); ++lv)
+            e = launch_lincomb_level(la, pl->levptr[lv], pl->levptr[lv + 1] - pl->levptr[lv], lv == 0, st);
+        if (e == hipSuccess && pl->top_K > 0)
+            e = launch_lincomb_top(la, (int)(pl->Nlocs - pl->top_K), pl->top_K, pl->d_topinfo, pl->d_toprows, st);
+        if (e == hipSuccess) e = launch_lincomb_vars(pl->d_lc_X, pl->Nlocs, pl->d_lc_part, pl->d_lc_vars, st);
+        return e;
+    };
+    static const bool no_graph = getenv("GPV_NO_GRAPH") != nullptr;
+    if (!no_graph && !pl->lc_graph) {
+        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            const hipError_t e = enqueue();
+            hipGraph_t graph = nullptr;
+            const hipError_t e2 = hipStreamEndCapture(st, &graph);
+            if (!(e == hipSuccess && e2 == hipSuccess && graph && hipGraphInstantiate(&pl->lc_graph, graph, nullptr, nullptr, 0) == hipSuccess))
+                pl->lc_graph = nullptr;
+            if (graph) (void)hipGraphDestroy(graph);
+            (void)hipGetLastError();
+        }
+    }
+    std::vector<double> vb((size_t)NB), gb(cov ? (size_t)NB * NB : 0);
+    for (int64_t b = 0; b < nbatch; ++b) {
+        const int64_t row0 = b * NB;
+        const int nb = (int)std::min<int64_t>(NB, nrows - row0);
+        if (GPV_HIP_FAILED(launch_lincomb_init(pl->d_lc_X, pl->Nlocs, d_hptr, d_hidx, d_hval, row0, nb, bmax[(size_t)b],
+                                               bserial[(size_t)b] != 0, st)))
+            return fail(GPV_ERR_HIP);
+        if (!no_graph && pl->lc_graph) {
+            if (GPV_HIP_FAILED(hipGraphLaunch(pl->lc_graph, st))) return fail(GPV_ERR_HIP);
+        } else if (GPV_HIP_FAILED(enqueue())) {
+            return fail(GPV_ERR_HIP);
+        }
+        if (cov && GPV_HIP_FAILED(launch_lincomb_gram(pl->d_lc_X, pl->Nlocs, pl->d_lc_gpart, pl->d_lc_gram, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipMemcpyAsync(vb.data(), pl->d_lc_vars, sizeof(double) * NB, hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+        if (cov && GPV_HIP_FAILED(hipMemcpyAsync(gb.data(), pl->d_lc_gram, sizeof(double) * NB * NB, hipMemcpyDeviceToHost, st)))
+            return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+        for (int j = 0; j < nb; ++j) vars[row0 + j] = vb[(size_t)j];
+        if (cov)
+            for (int i = 0; i < nb; ++i)
+                for (int j = 0; j < nb; ++j) cov[(int64_t)i * nrows + j] = gb[(size_t)i * NB + j];
+    }
+    pl->last_stream = st;
+    release();
     return GPV_OK;
 }
 

@@ -162,4 +162,27 @@ hipError_t launch_negate(const double *src, double *dst, int64_t n, hipStream_t 
 hipError_t launch_sum_pair(const double *x, const double *y, int64_t n, double *partials, double *sums, double *sums_copy,
                            hipStream_t s);
 
+// ---- linear combinations (gpv_lincomb.hip): R x = h for kLincombNB right-hand sides at once, on the finished factor -------
+#ifndef GPV_LINCOMB_NB
+#define GPV_LINCOMB_NB 32
+#endif
+constexpr int kLincombNB = GPV_LINCOMB_NB;            // right-hand sides per batch: X[Nlocs][kLincombNB]
+constexpr int kLincombWide16 = 512, kLincombWide8 = 2048;   // levels up to this many columns: 16 / 8 waves share a column
+constexpr int kLincombBlocks = 1024;                  // block partials of the reductions
+struct LincombArgs {
+    const int4 *colrec;      // PostArgs::colrec
+    const int2 *lrec;        // [nnz] by row-list position (the positions colrec names): {column c (~c: c is in the top block),
+                             //       index in C of the pair (R_kc in its .y)}
+    const double2 *C;
+    double *X;               // [Nlocs][kLincombNB]
+};
+// X <- 0, then the CSR rows [row0, row0 + nb) of H (device copies) into the columns 0 .. nb-1 of X; serial: some row repeats
+// an index (its entries are then added one by one in the order given); max_row_nnz: longest of the rows
+hipError_t launch_lincomb_init(double *X, int64_t n, const int64_t *hptr, const int32_t *hidx, const double *hval, int64_t row0,
+                               int nb, int64_t max_row_nnz, bool serial, hipStream_t s);
+hipError_t launch_lincomb_level(const LincombArgs &a, int first, int count, bool leaves, hipStream_t s);
+// vars[kLincombNB] = column sums of X^2 (partials: kLincombBlocks * kLincombNB); gram[NB][NB] = X^T X (partials: kLincombBlocks * NB * NB)
+hipError_t launch_lincomb_vars(const double *X, int64_t n, double *partials, double *vars, hipStream_t s);
+hipError_t launch_lincomb_gram(const double *X, int64_t n, double *partials, double *gram, hipStream_t s);
+
 }  // namespace gpv

@@ -1,0 +1,248 @@
+// gpv_lincomb.hip — Var(H y | z) = || R^-1 h ||^2 for many right-hand sides at once (R/vecchia_prediction.R:164-178,
+// vecchia_lincomb; :223-244, the var.exact path of vecchia_var).
+//
+// W = R R^T with R upper triangular on the pattern of the latent block (gpv_posterior.hip), so h' W^-1 h = |x|^2 with
+// R x = h: the solve the factor pass performs for ONE right-hand side while it factorises, here on its own, after the factor
+// is complete, for kLincombNB right-hand sides interleaved as X[Nlocs][NB]:
+//     x_k[j] = (h_k[j] - sum_{c > k, k in col c} R_kc x_c[j]) / R_kk ,      R_kc = C[cb_c + 1 + e_k].y .
+// Same level schedule as the factor pass (column k waits for every column c > k that contains row k), one launch per level.
+// A gathered x_c is a contiguous run of NB doubles used in full (the scalar sweeps use 8 or 16 bytes of every 128-byte line),
+// and one pass over the records and the R values serves NB solves.
+//
+// One wavefront per column: the 64 lanes first fetch 64 row-list records and their R_kc in one coalesced trip each, then the
+// lanes (NB right-hand sides x 64/NB slices of the chunk) walk the chunk with the record and the value broadcast from the
+// lane that fetched them.  Every partial sum has a fixed order (slice: ascending entries; slices and waves: fixed trees) =>
+// bitwise reproducible.  No floating-point atomics.
+#include "gpv_internal.h"
+#include "gpv_posterior_ext.h"
+#include <atomic>
+
+namespace gpv {
+
+constexpr int NB = kLincombNB, kLcS = 64 / NB;          // right-hand sides per batch, slices of a chunk
+static_assert(NB == 16 || NB == 32, "batch width");
+
+// X <- 0, then X[idx][j] (+)= val over the CSR rows [row0, row0 + nb) of H: row j of the batch is column j of X
+__global__ void __launch_bounds__(256) gpv_lincomb_zero_kernel(double *X, int64_t total)
+{
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) X[i] = 0.0;
+}
+// rows without a repeated index: one store per entry, blockIdx.y = row of the batch
+__global__ void __launch_bounds__(256) gpv_lincomb_scatter_kernel(double *X, const int64_t *hptr, const int32_t *hidx,
+                                                                  const double *hval, int64_t row0)
+{
+    const int j = blockIdx.y;
+    const int64_t b = hptr[row0 + j], e = hptr[row0 + j + 1];
+    for (int64_t q = b + (int64_t)blockIdx.x * 256 + threadIdx.x; q < e; q += (int64_t)gridDim.x * 256)
+        X[(int64_t)hidx[q] * NB + j] = hval[q];
+}
+// any rows: one thread per row walks its entries in the order given (duplicates add in that order)
+__global__ void __launch_bounds__(64) gpv_lincomb_scatter_serial_kernel(double *X, const int64_t *hptr, const int32_t *hidx,
+                                                                        const double *hval, int64_t row0, int nb)
+{
+    const int j = threadIdx.x;
+    if (j >= nb) return;
+    for (int64_t q = hptr[row0 + j]; q < hptr[row0 + j + 1]; ++q) X[(int64_t)hidx[q] * NB + j] += hval[q];
+}
+hipError_t launch_lincomb_init(double *X, int64_t n, const int64_t *hptr, const int32_t *hidx, const double *hval, int64_t row0,
+                               int nb, int64_t max_row_nnz, bool serial, hipStream_t s)
+{
+    if (n <= 0 || nb <= 0 || nb > NB) return hipErrorInvalidValue;
+    const int64_t total = n * NB;
+    const int zg = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
+    hipLaunchKernelGGL(gpv_lincomb_zero_kernel, dim3(zg), dim3(256), 0, s, X, total);
+    if (serial) {
+        hipLaunchKernelGGL(gpv_lincomb_scatter_serial_kernel, dim3(1), dim3(64), 0, s, X, hptr, hidx, hval, row0, nb);
+    } else if (max_row_nnz > 0) {
+        const int gx = (int)((max_row_nnz + 255) / 256 < 256 ? (max_row_nnz + 255) / 256 : 256);
+        hipLaunchKernelGGL(gpv_lincomb_scatter_kernel, dim3(gx, nb), dim3(256), 0, s, X, hptr, hidx, hval, row0);
+    }
+    return hipGetLastError();
+}
+
+__device__ __forceinline__ double lc_shfl(const double v, const int l)
+{
+    const int lo = __builtin_amdgcn_ds_bpermute(l << 2, __double2loint(v));
+    const int hi = __builtin_amdgcn_ds_bpermute(l << 2, __double2hiint(v));
+    return __hiloint2double(hi, lo);
+}
+
+// One column of the solve.  WPC = waves that share the column (hub rows with row lists of hundreds to thousands of entries
+// in the narrow late levels: the 64-entry chunks are dealt round-robin to the waves, the partial sums meet in LDS in wave
+// order).  MODE 1 (the columns of the dense top block): the row-list entries whose column is in the block (record .x < 0)
+// are left to gpv_lincomb_top_kernel, and X_k <- h_k - (the other terms), undivided.
+template <int WPC, int MODE>
+__global__ void __launch_bounds__(WPC == 1 ? 256 : 64 * WPC) gpv_lincomb_level_kernel(const LincombArgs A, const int first,
+                                                                                     const int count)
+{
+    const int lane = threadIdx.x & 63, wib = threadIdx.x >> 6;
+    const int w = (WPC == 1) ? (int)(blockIdx.x * (blockDim.x >> 6)) + wib : (int)blockIdx.x;
+    if (w >= count) return;                                   // (WPC > 1: never, the grid is the level)
+    const int4 c0 = A.colrec[2 * (size_t)(first + w)];
+    const int4 c1 = A.colrec[2 * (size_t)(first + w) + 1];
+    const int k = c0.x, cnt = c0.z;
+    const int qb = c0.w + 1, qe = c1.x;                       // row list of k without its first pair, the column itself
+    const int j = lane & (NB - 1), sl = lane / NB;
+    // the epilogue's operands leave with the first chunk's records
+    const double hk = A.X[(size_t)k * NB + j];
+    const double rkk = A.C[(size_t)c0.y + cnt].y;             // the diagonal: last entry of the column's block
+    double acc = 0.0;
+    for (int base = qb + ((WPC == 1) ? 0 : 64 * wib); base < qe; base += 64 * WPC) {
+        const int q = base + lane;
+        int cc = k;                                           // (a lane without a pair points at the column itself: a valid row)
+        double rv = 0.0;
+        if (q < qe) {
+            const int2 r = A.lrec[q];
+            const double v = A.C[r.y].y;
+            if (MODE == 1 && r.x < 0) { cc = k; rv = 0.0; }
+            else { cc = r.x; rv = v; }
+        }
+        const int m = (qe - base < 64) ? qe - base : 64;      // pairs of this chunk (wave uniform)
+        for (int t = 0; t < m; t += 4 * kLcS) {
+            double x[4], r[4];
+            bool on[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int e = t + u * kLcS + sl;
+                const int ee = e < 64 ? e : 63;
+                on[u] = e < m;
+                const int c = __builtin_amdgcn_ds_bpermute(ee << 2, cc);
+                r[u] = lc_shfl(rv, ee);
+                x[u] = A.X[(size_t)c * NB + j];
+            }
+#pragma unroll
+            for (int u = 0; u < 4; ++u) acc = on[u] ? __builtin_fma(r[u], x[u], acc) : acc;
+        }
+    }
+    if constexpr (WPC > 1) {
+        __shared__ double part[WPC][64];
+        part[wib][lane] = acc;
+        __syncthreads();
+        if (wib != 0) return;
+        acc = 0.0;
+#pragma unroll
+        for (int v = 0; v < WPC; ++v) acc += part[v][lane];
+    }
+    // the slices of a right-hand side: butterflies (a + b == b + a: every lane of a right-hand side ends with the same bits)
+#pragma unroll
+    for (int off = NB; off < 64; off <<= 1) acc += lc_shfl(acc, lane ^ off);
+    if (lane < NB) A.X[(size_t)k * NB + j] = (MODE == 1) ? hk - acc : (hk - acc) / rkk;
+}
+
+hipError_t launch_lincomb_level(const LincombArgs &a, int first, int count, bool leaves, hipStream_t s)
+{
+    if (count <= 0) return hipSuccess;
+    if (!leaves && count <= kLincombWide16) {
+        hipLaunchKernelGGL((gpv_lincomb_level_kernel<16, 0>), dim3(count), dim3(1024), 0, s, a, first, count);
+    } else if (!leaves && count <= kLincombWide8) {
+        hipLaunchKernelGGL((gpv_lincomb_level_kernel<8, 0>), dim3(count), dim3(512), 0, s, a, first, count);
+    } else {
+        hipLaunchKernelGGL((gpv_lincomb_level_kernel<1, 0>), dim3((count + 3) / 4), dim3(256), 0, s, a, first, count);
+    }
+    return hipGetLastError();
+}
+
+// The dense top block (gpv_posterior_ext.h): K <= 128 columns that wait for everything and for each other.  After
+// gpv_lincomb_level_kernel<16, 1> has taken the terms of the columns outside the block, ONE workgroup solves
+// R_TT x_T = rhs_T by back substitution, last column first: R_TT in LDS (zero off the pattern), thread (g, j) keeps the
+// right-hand side j of the rows g, g + G, .. in registers; per step the owner of row c publishes x_c[j] and every thread
+// subtracts R_rc x_c[j] from its rows r < c.  A fixed order per entry => reproducible.
+constexpr int kLcTop = kTopMax, kLcTopLd = kLcTop + 1;
+constexpr int kLcTopG = 1024 / NB, kLcTopRows = kLcTop / kLcTopG;          // row groups, rows per thread
+constexpr size_t kLcTopSmem = ((size_t)kLcTop * kLcTopLd + 2 * NB) * sizeof(double);
+__global__ void __launch_bounds__(1024) gpv_lincomb_top_kernel(const LincombArgs A, const int K, const int2 *topinfo,
+                                                              const uint8_t *toprows)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char lctop_smem[];
+    double *Rl = reinterpret_cast<double *>(lctop_smem);       // [row][column], rows kLcTopLd apart
+    double *xc = Rl + (size_t)kLcTop * kLcTopLd;               // [2][NB]: x_c of the step, double buffered
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < kLcTop * kLcTopLd; i += 1024) Rl[i] = 0.0;
+    __syncthreads();
+    if (tid < kLcTop && tid >= K) Rl[tid * kLcTopLd + tid] = 1.0;
+    for (int kk = wave; kk < K; kk += 16) {                    // column kk of the block: entry e (lane) sits in row toprows[kk][e]
+        const int r = (int)toprows[kTopBlock * kk + lane];
+        if (r != 0xFF) Rl[r * kLcTopLd + kk] = A.C[(size_t)topinfo[kk].y + 1 + lane].y;
+    }
+    const int j = tid & (NB - 1), g = tid / NB;
+    double reg[kLcTopRows];
+    int kcol[kLcTopRows];
+#pragma unroll
+    for (int r = 0; r < kLcTopRows; ++r) {
+        const int row = g + r * kLcTopG;
+        kcol[r] = row < K ? topinfo[row].x : -1;
+        reg[r] = row < K ? A.X[(size_t)kcol[r] * NB + j] : 0.0;
+    }
+    __syncthreads();
+    for (int c = K - 1; c >= 0; --c) {
+        double *xb = xc + (c & 1) * NB;
+        if (g == c % kLcTopG) {
+            const double d = Rl[c * kLcTopLd + c];
+#pragma unroll
+            for (int r = 0; r < kLcTopRows; ++r)
+                if (r == c / kLcTopG) { reg[r] = reg[r] / d; xb[j] = reg[r]; }
+        }
+        __syncthreads();
+        const double xv = xb[j];
+#pragma unroll
+        for (int r = 0; r < kLcTopRows; ++r) {
+            const int row = g + r * kLcTopG;
+            if (row < c) reg[r] = __builtin_fma(-Rl[row * kLcTopLd + c], xv, reg[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kLcTopRows; ++r)
+        if (kcol[r] >= 0) A.X[(size_t)kcol[r] * NB + j] = reg[r];
+}
+
+hipError_t launch_lincomb_top(const LincombArgs &a, int first, int K, const int2 *topinfo, const uint8_t *toprows, hipStream_t s)
+{
+    if (K <= 0) return hipSuccess;
+    if (K > kLcTop) return hipErrorInvalidValue;
+    static std::atomic<unsigned long long> done{0ull};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(done.load(std::memory_order_relaxed) & bit)) {
+        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(&gpv_lincomb_top_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLcTopSmem);
+        if (e1 != hipSuccess) return e1;
+        done.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL((gpv_lincomb_level_kernel<16, 1>), dim3(K), dim3(1024), 0, s, a, first, K);
+    hipLaunchKernelGGL(gpv_lincomb_top_kernel, dim3(1), dim3(1024), kLcTopSmem, s, a, K, topinfo, toprows);
+    return hipGetLastError();
+}
+
+// ---- deterministic reductions: vars[j] = sum_k X[k][j]^2, G[i][j] = sum_k X[k][i] X[k][j] -------------------------------
+// Fixed block partials (block b takes the rows b, b + kLincombBlocks, ..), then their sum in block order.  GRAM = false is
+// the diagonal of GRAM = true computed by the same operations in the same order: diag(G) == vars bit for bit.
+template <bool GRAM>
+__global__ void __launch_bounds__(GRAM ? NB * NB : NB) gpv_lincomb_sq_stage1(const double *X, int64_t n, double *partials)
+{
+    const int j = threadIdx.x & (NB - 1), i = GRAM ? (int)(threadIdx.x / NB) : j;
+    double acc = 0.0;
+    for (int64_t k = blockIdx.x; k < n; k += gridDim.x) acc = __builtin_fma(X[k * NB + i], X[k * NB + j], acc);
+    partials[(size_t)blockIdx.x * blockDim.x + threadIdx.x] = acc;
+}
+template <bool GRAM>
+__global__ void __launch_bounds__(GRAM ? NB * NB : NB) gpv_lincomb_sq_stage2(const double *partials, int nb, double *out)
+{
+    double acc = 0.0;
+    for (int b = 0; b < nb; ++b) acc += partials[(size_t)b * blockDim.x + threadIdx.x];
+    out[threadIdx.x] = acc;
+}
+hipError_t launch_lincomb_vars(const double *X, int64_t n, double *partials, double *vars, hipStream_t s)
+{
+    hipLaunchKernelGGL((gpv_lincomb_sq_stage1<false>), dim3(kLincombBlocks), dim3(NB), 0, s, X, n, partials);
+    hipLaunchKernelGGL((gpv_lincomb_sq_stage2<false>), dim3(1), dim3(NB), 0, s, (const double *)partials, kLincombBlocks, vars);
+    return hipGetLastError();
+}
+hipError_t launch_lincomb_gram(const double *X, int64_t n, double *partials, double *gram, hipStream_t s)
+{
+    hipLaunchKernelGGL((gpv_lincomb_sq_stage1<true>), dim3(kLincombBlocks), dim3(NB * NB), 0, s, X, n, partials);
+    hipLaunchKernelGGL((gpv_lincomb_sq_stage2<true>), dim3(1), dim3(NB * NB), 0, s, (const double *)partials, kLincombBlocks, gram);
+    return hipGetLastError();
+}
+
+}  // namespace gpv

@@ -22,4 +22,7 @@ hipError_t launch_posterior_top(const PostArgs &a, int first, int K, double *tpa
                                 int64_t rr0_off, hipStream_t s);
 // Mean sweep, the columns of T: the plan's ascending schedule (order2 / levptr2 / meanrec) holds the OTHER columns only
 hipError_t launch_mean_top(const PostArgs &a, double *u, int K, const int2 *topinfo, const uint8_t *toprows, hipStream_t s);
+// Linear combinations (gpv_lincomb.hip), the columns of T, after every level: their row-list terms outside T, then the dense
+// back substitution R_TT x_T = rhs_T in one workgroup
+hipError_t launch_lincomb_top(const LincombArgs &a, int first, int K, const int2 *topinfo, const uint8_t *toprows, hipStream_t s);
 }  // namespace gpv

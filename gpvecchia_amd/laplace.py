@@ -1,7 +1,7 @@
 """Vecchia-Laplace approximation for non-Gaussian data — host-side mirror of
 R/vecchia_laplace_NR.R (calculate_posterior_VL :31-155, likelihood families :213-322,
 vecchia_laplace_likelihood :361-416) and of the mean part of vecchia_prediction
-(R/vecchia_prediction.R:17-56,118-142).
+(R/vecchia_prediction.R:17-56,118-142, with the exact variances of :203-247 through lincomb.py).
 
 Every Newton-Raphson step is one vecchia_prediction(..., return.values='meanmat') with
 per-observation pseudo-nuggets: on the GPU that is one conditioning-set launch (the hot path,
@@ -63,14 +63,44 @@ def _families(model, likparms):
 # ---------------------------------------------------------------------------
 # posterior mean — R/vecchia_prediction.R:17-56 (mean part), :118-142
 # ---------------------------------------------------------------------------
-def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", return_values="mean", device=0):
+_RETURN_VALUES = ("mean", "meanvar", "meanmat", "all")
+
+
+def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", return_values="mean", device=0, var_exact=None):
     """Posterior mean of the latent field at the observed (mu.obs) and prediction (mu.pred) locations, each in the
-    caller's order.  Fully observed 'SGV'/'z' plans: set kernel + posterior pass + mean sweeps on the GPU; plans with
-    prediction locations or 'zy' conditioning: U on the GPU, V and the two triangular solves on the host like the
-    reference's Matrix calls (R/vecchia_prediction.R:62-142).  Variances (SelInv) are not built."""
+    caller's order, and on request its variances (R/vecchia_prediction.R:17-56).  Fully observed 'SGV'/'z' plans, 'zy' plans
+    and prediction plans with latent conditioning whose structure the device accepts: set kernel + posterior pass + mean
+    sweeps on the GPU; otherwise U on the GPU, V and the two triangular solves on the host like the reference's Matrix calls
+    (R/vecchia_prediction.R:62-142).
+
+    return_values: 'mean' (the default: means only, var_obs = var_pred = None), 'meanvar' (also var_obs / var_pred),
+    'meanmat' (also `factor`, the opaque handle vecchia_lincomb takes: on the device routes the plan and a stamp of this
+    evaluation, on the host route (U_obj, lu)) or 'all' (both).
+
+    Variances are EXACT for the factor in use: diag(W^-1) through unit-vector rows of vecchia_lincomb (the reference's
+    var.exact = TRUE path, :223-244), zeros for zero-nugget observations (:210-212).  var_exact=None stands for the
+    reference's rule sum(!obs) < 4e4 (:46) and var_exact=False for its SelInv approximation; there is no selected inverse
+    here, so the same exact values are computed either way.  For an exact fill-closed factor (SGV, the obs-pred branch, the
+    filled 'y' structure) that IS the diagonal SelInv returns; for 'zy' and ic0 it differs from the reference's
+    var.exact = FALSE approximation."""
+    from . import lincomb as LC
+    if return_values not in _RETURN_VALUES:
+        raise ValueError(f"return_values must be one of {_RETURN_VALUES}")
+    want_var = return_values in ("meanvar", "all")
+    want_mat = return_values in ("meanmat", "all")
     va = vecchia_approx
     z, nug = A._removeNAs(z, nuggets)
     n = int(np.sum(va["obs"]))
+
+    def finish_device(out, plan, ord_, obs, offset):
+        # (the factor handle first: the variance solves below only read the factor, the stamp stays)
+        if want_mat:
+            out["factor"] = LC._device_factor(plan, ord_, obs, offset)
+        if want_var:
+            var_ord = LC.exact_variances_device(plan, len(ord_), offset)
+            out["var_obs"], out["var_pred"] = A.split_mean(var_ord, dict(ord=ord_, obs=obs))
+        return out
+
     plain = (n == va["locsord"].shape[0]) and va["cond_yz"] in ("SGV", "z", "false")
     # (the device posterior pass takes any m as long as no conditioning set has more than 64 latent entries)
     if plain and isinstance(covmodel, str) and not np.any(nug == 0) and A._plan_for(va, device).ensure_posterior():
@@ -79,7 +109,10 @@ def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
         plan.eval(covmodel, covparms, A._device_nuggets(va, nug), GPV_WANT_MEAN)
         mu = np.empty(n)
         mu[va["ord"] - 1] = plan.posterior_mean()                         # orig.order = order(U.obj$ord), :135-136
-        return dict(mu_obs=mu, mu_pred=np.empty(0), var_obs=None, var_pred=None)
+        out = dict(mu_obs=mu, mu_pred=np.empty(0), var_obs=None, var_pred=None)
+        if want_var or want_mat:
+            finish_device(out, plan, va["ord"], np.ones(n, dtype=bool), 0)
+        return out
     if (va["cond_yz"] == "zy" and isinstance(covmodel, str) and not np.any(nug == 0)
             and A._plan_for(va, device).ensure_posterior()):
         # the reference's default with prediction locations in two or more dimensions (R/vecchia_specify.R:92-96).  V.ord is
@@ -96,7 +129,10 @@ def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
         mu_ord = plan.posterior_mean()[n:]                               # without the dummy latent variables (R/createU.R:166-171)
         obs = np.delete(np.asarray(va["obs"], dtype=bool), np.arange(n, 2 * n))
         mu_obs, mu_pred = A.split_mean(mu_ord, dict(ord=va["ord"], obs=obs))
-        return dict(mu_obs=mu_obs, mu_pred=mu_pred, var_obs=None, var_pred=None)
+        out = dict(mu_obs=mu_obs, mu_pred=mu_pred, var_obs=None, var_pred=None)
+        if want_var or want_mat:
+            finish_device(out, plan, va["ord"], obs, n)                  # the factor IS B: the dummies' rows stay zero
+        return out
     nrows = va["locsord"].shape[0]
     if (n < nrows and va["cond_yz"] in ("SGV", "SGVT", "y") and isinstance(covmodel, str) and not np.any(nug == 0)
             and not va.get("ic0", False) and nug.size in (1, n)):
@@ -120,9 +156,13 @@ def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
             nug_all_ord, _, _ = A._ordered_nuggets(va, nug, n)             # 0 at the unobserved locations (R/createU.R:75-77)
             plan.eval(covmodel, covparms, nug_all_ord, GPV_WANT_MEAN)
             mu_obs, mu_pred = A.split_mean(plan.posterior_mean(), dict(ord=va["ord"], obs=va["obs"]))
-            return dict(mu_obs=mu_obs, mu_pred=mu_pred, var_obs=None, var_pred=None, route="device")
+            out = dict(mu_obs=mu_obs, mu_pred=mu_pred, var_obs=None, var_pred=None, route="device")
+            if want_var or want_mat:
+                finish_device(out, plan, va["ord"], np.asarray(va["obs"], dtype=bool), 0)
+            return out
     U_obj = A.createU(va, covparms, nug, covmodel, device=device)
-    mu_ord = A.vecchia_mean_host(z, U_obj)
+    lu = A.U2V(U_obj) if (want_var or want_mat) else None
+    mu_ord = A.vecchia_mean_host(z, U_obj, lu)
     if U_obj["zero_nugg"]:
         # for zero nugget, observations are posterior means (R/vecchia_prediction.R:129-132); createU has moved those
         # locations to the end of ord / obs (R/createU.R:190-191)
@@ -130,7 +170,13 @@ def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
         zord = np.asarray(z, dtype=np.float64)[U_obj["ord_z"] - 1]
         mu_ord = np.concatenate([mu_ord, zord[U_obj["zero_nugg"]["inds_z"] - 1]])
     mu_obs, mu_pred = A.split_mean(mu_ord, U_obj)
-    return dict(mu_obs=mu_obs, mu_pred=mu_pred, var_obs=None, var_pred=None)
+    out = dict(mu_obs=mu_obs, mu_pred=mu_pred, var_obs=None, var_pred=None)
+    if want_mat:
+        out["factor"] = LC._host_factor(U_obj, lu)
+        out["U_obj"] = U_obj
+    if want_var:
+        out["var_obs"], out["var_pred"] = LC.host_variances(U_obj, lu)    # zeros for zero-nugget observations, :210-212
+    return out
 
 
 def vecchia_laplace_prediction(vl_posterior, vecchia_approx, covparms, pred_mean=0.0, covmodel="matern", device=0):

@@ -164,15 +164,15 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
 
 
 def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, **specify_args):
-    """R/vecchia_wrappers.R:134-161, means only (prediction variances are not built): spatial prediction at new locations
-    from the result of vecchia_estimate.  With prediction locations in two or more dimensions vecchia_specify defaults to
+    """R/vecchia_wrappers.R:134-161: spatial prediction at new locations from the result of vecchia_estimate, with the
+    exact prediction variances of the latent field (vecchia_prediction(..., return_values='meanvar')).  With prediction locations in two or more dimensions vecchia_specify defaults to
     cond.yz='zy' (R/vecchia_specify.R:92-96), whose posterior mean is one triangular solve on the GPU."""
     import warnings
     from .laplace import vecchia_prediction
     va = A.vecchia_specify(vecchia_est["locs"], m, locs_pred=np.asarray(locs_pred, dtype=np.float64), **specify_args)   # :137
     theta_hat = np.asarray(vecchia_est["theta_hat"], dtype=np.float64)                               # :140-143
     preds = vecchia_prediction(vecchia_est["z"], va, theta_hat[:-1], theta_hat[-1],
-                               covmodel=vecchia_est.get("covmodel", "matern"), device=device)
+                               covmodel=vecchia_est.get("covmodel", "matern"), return_values="meanvar", device=device)
     if X_pred is not None:                                                                           # :146-147
         mu_pred = preds["mu_pred"] + np.asarray(X_pred, dtype=np.float64) @ vecchia_est["beta_hat"]
     elif vecchia_est["trend"] == "none":                                                             # :148-149
@@ -182,4 +182,4 @@ def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, **specify_
     else:                                                                                            # :152-156
         mu_pred = preds["mu_pred"]
         warnings.warn("X.pred was not specified, so no trend was added back to the predictions")
-    return dict(mean_pred=mu_pred, var_pred=None)                                                    # :159
+    return dict(mean_pred=mu_pred, var_pred=preds["var_pred"])                                                    # :159

@@ -210,6 +210,23 @@ int gpv_plan_posterior_levels(gpv_plan *plan, int *n_levels);
 /* blocking: mu.ord (length Nlocs, ordered layout) after an eval with GPV_WANT_MEAN */
 int gpv_plan_get_posterior_mean(gpv_plan *plan, double *mu_ord);
 
+/* Var(H y | z) for nrows linear combinations of the latent field (R/vecchia_prediction.R:164-178, vecchia_lincomb), after an
+ * eval of this plan with GPV_WANT_DENOM, GPV_WANT_MEAN or GPV_WANT_MEAN_B (the factor of THAT evaluation is used; it is only
+ * read, nothing is factorised again).  With W = R R^T the variance of row h is |x|^2, R x = h: one level-scheduled triangular
+ * solve for gpv_lincomb_batch() rows at a time.  H in CSR over the plan's ORDERED latent index (hptr: nrows + 1 offsets, hidx
+ * in [0, Nlocs), repeated indices within a row add in the order given).  Unit rows give the exact posterior variances
+ * (the var.exact path of vecchia_var, :223-244; for a fill-closed factor also the diagonal SelInv returns).
+ * vars: nrows out.  cov: NULL, or nrows x nrows (row-major) out -- only for nrows <= gpv_lincomb_batch(), else GPV_ERR_BAD_ARG;
+ * its diagonal equals vars bit for bit.  Blocking.  Results are bitwise reproducible from call to call.
+ * GPV_ERR_STATE: no posterior structure / no such evaluation yet / a communicator is attached; GPV_ERR_INDEX: an index
+ * outside [0, Nlocs).  Arguments are validated before the device is touched. */
+int gpv_plan_lincomb(gpv_plan *plan, int64_t nrows, const int64_t *hptr, const int32_t *hidx, const double *hval,
+                     double *vars, double *cov);
+int gpv_lincomb_batch(void);   /* right-hand sides per sweep (32) */
+/* stamp: 0 when the plan holds no factor, else a number that changes with every evaluation that writes one (callers that keep
+ * a result of gpv_plan_lincomb's inputs around can tell whether the factor is still the one they mean) */
+int gpv_plan_factor_stamp(gpv_plan *plan, int64_t *stamp);
+
 /* Vecchia-Laplace Newton-Raphson with the state on the device: calculate_posterior_VL of R/vecchia_laplace_NR.R:31-155
  * for fully observed data.  model: position in the reference's family list (:32): 0 gaussian, 1 logistic, 2 poisson,
  * 3 gamma, 4 beta, 5 gamma_alt.  likparms = {alpha, sigma} (:33), for beta {alpha, sigma, beta}.

@@ -1,0 +1,97 @@
+"""Cost of gpv_plan_lincomb (gpv_lincomb.hip): ms per batch of NB solves, beside
+  (a) ONE mean sweep of the same plan (GPV_WANT_MEAN minus GPV_WANT_DENOM evaluation time: the same level structure for one
+      right-hand side), and
+  (b) scipy's spsolve_triangular for the same NB right-hand sides on the oracle's V on the host (--host; n <= 1e5).
+
+    python tools/lincomb_timing.py [--n 1000000] [--m 30] [--batches 8] [--host] [--pred]
+
+Times are wall clock around the blocking calls after a clock warm-up of evaluations (as bench.py does); the lincomb call is
+timed with 1 and with 1 + batches batches and the difference divided, so that the upload of H and the call's fixed cost drop out.
+--pred: also vecchia_prediction(..., 'meanvar') at 4e4 + 1e4 locations.  Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: F401,E402  (first: see tests/conftest.py)
+import gpvecchia_amd as G  # noqa: E402
+from gpvecchia_amd import _lib as L  # noqa: E402
+
+
+def med(f, reps):
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        f()
+        ts.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(ts))
+
+
+def main():
+    import scipy.sparse as sp
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--m", type=int, default=30)
+    ap.add_argument("--batches", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--host", action="store_true")
+    ap.add_argument("--pred", action="store_true")
+    a = ap.parse_args()
+    NB = L.lib().gpv_lincomb_batch()
+    n, m = a.n, a.m
+    locs = np.random.default_rng(0).random((n, 2))
+    z = np.random.default_rng(1).standard_normal(n)
+    cp, tau = [1.0, 0.02 if n >= 500_000 else 0.05, 1.5], 0.1
+    va = G.vecchia_specify(locs, m, ordering="maxmin", cond_yz="SGV", nn_backend="gpu")
+    plan = G.api._plan_for(va, 0)
+    assert plan.ensure_posterior()
+    plan.set_data(z[va["ord_z"] - 1])
+    nug = np.array([tau])
+
+    def ev(flags):
+        plan.eval("matern", cp, nug, flags)
+        plan.sums()
+    for _ in range(30):                                               # clock warm-up
+        ev(G.GPV_WANT_MEAN)
+    t_mean, t_den = med(lambda: ev(G.GPV_WANT_MEAN), 15), med(lambda: ev(G.GPV_WANT_DENOM), 15)
+    ev(G.GPV_WANT_MEAN)
+    rng = np.random.default_rng(2)
+
+    def H(nb):
+        rows = nb * NB
+        idx = rng.choice(n, rows, replace=False)
+        return sp.csr_matrix((np.ones(rows), idx, np.arange(rows + 1)), shape=(rows, n))
+    H1, Hk = H(1), H(1 + a.batches)
+    plan.lincomb(H1)                                                  # first use: records, X, graph
+    t1, tk = med(lambda: plan.lincomb(H1), a.reps), med(lambda: plan.lincomb(Hk), a.reps)
+    per_batch = (tk - t1) / a.batches
+    out = dict(n=n, m=m, NB=NB, levels=plan.posterior_levels(), eval_mean_ms=t_mean, eval_denom_ms=t_den,
+               one_mean_sweep_ms=t_mean - t_den, lincomb_first_batch_call_ms=t1, lincomb_ms_per_batch=per_batch,
+               lincomb_ms_per_solve=per_batch / NB, batch_over_single_sweep=per_batch / max(t_mean - t_den, 1e-9),
+               X_bytes=n * NB * 8)
+    if a.host:
+        import scipy.sparse.linalg as spla
+        from oracle import r_side as R
+        sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+        from test_gpu_lincomb import _to_oracle_va
+        V = sp.csr_matrix(R.U2V_sparse(R.createU_sparse(_to_oracle_va(va), cp, tau)))
+        B = np.asarray(H1[:, (va["ord"] - 1)[::-1]].T.todense())
+        out["host_spsolve_triangular_ms_per_batch"] = med(lambda: spla.spsolve_triangular(V, B, lower=True), 3)
+    if a.pred:
+        r2 = np.random.default_rng(11)
+        lo, lp = r2.random((40_000, 2)), r2.random((10_000, 2))
+        z2 = r2.standard_normal(40_000)
+        t2 = 0.05 + 0.1 * r2.random(40_000)
+        va2 = G.vecchia_specify(lo, 15, ordering="maxmin", cond_yz="SGV", locs_pred=lp, ordering_pred="obspred")
+        G.vecchia_prediction(z2, va2, [1.0, 0.05, 1.5], t2, return_values="meanvar")
+        out["prediction_meanvar_4e4_1e4_ms"] = med(lambda: G.vecchia_prediction(z2, va2, [1.0, 0.05, 1.5], t2, return_values="meanvar"), 3)
+        out["prediction_mean_4e4_1e4_ms"] = med(lambda: G.vecchia_prediction(z2, va2, [1.0, 0.05, 1.5], t2), 3)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

@@ -22,7 +22,7 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   local CF="--offload-host-only -O1 -g -std=c++17 -fPIC -fno-omit-frame-pointer $san -DGPV_DEVELOPER -Wno-unused-variable"
   local plx=""; for P in $PLIST; do plx="$plx X($P)"; done
   local pids=()
-  for f in gpv_api gpv_aux_kernels gpv_posterior gpv_laplace gpv_sets_generic gpv_nn; do
+  for f in gpv_api gpv_aux_kernels gpv_posterior gpv_lincomb gpv_laplace gpv_sets_generic gpv_nn; do
     $HIPCC $CF "-DGPV_P_LIST(X)=$plx" -c $CSRC/$f.hip -o $B/$f.o & pids+=($!)
   done
   for P in $PLIST; do
