@@ -165,6 +165,24 @@ __host__ __device__ constexpr bool k_lik()
 {
     return Geo<P>::DPP && !Geo<P>::DPP2 && Geo<P>::RPL >= 2 && Geo<P>::ZROW && P <= GPV_LIK_MAXP;
 }
+// Which instantiations keep the covariance rounds' staging addresses (RPL * P/2 absolute LDS byte addresses, 30 at P = 31) in
+// registers across the task loop instead of deriving each one per pair (compare, select, add: three issue slots of a kernel
+// bound by VALU issue).  Decided by register room: the likelihood-only kernels have it (P = 31, 2-D, Matern 1.5: 195 VGPRs
+// of the 256 that two wavefronts per SIMD allow); the Gauss-Jordan kernels of the same row lengths (231 at P = 31) do not,
+// and general nu, whose rounds hold two rounds of table rows, has it up to P = 21 only (P = 26, 31: with the table hipcc
+// spills VGPRs to scratch).  Per instantiation with its register count: DESIGN.md section 4.
+#ifndef GPV_OPT_COVTAB
+#define GPV_OPT_COVTAB 1
+#endif
+#ifndef GPV_COVTAB_GEN_MAXP
+#define GPV_COVTAB_GEN_MAXP 21
+#endif
+template <int P, int D, int COV, bool LIK>
+__host__ __device__ constexpr bool k_cov_addr_table()
+{
+    return GPV_OPT_COVTAB != 0 && LIK && k_lik<P>() && D != 0 && COV != COV_DENSE &&
+           (COV != COV_MATERN_GEN || P <= GPV_COVTAB_GEN_MAXP);
+}
 // the last column a row of slot q can own on or left of its diagonal (the data row ends at column P - 1)
 template <int P>
 __host__ __device__ constexpr int lik_maxcol(int q)
@@ -186,9 +204,16 @@ __device__ __forceinline__ void static_for(F &&f)
 
 // x of lane N of the caller's 16-lane DPP row, in every lane of that row.  The two wait states cover a VALU write of
 // the source by the preceding instruction (inline asm is invisible to hipcc's hazard recogniser: a VALU result needs
-// two wait states before a DPP read).  dep0/dep1 are not read: naming them orders every writer of the column the sweep
-// is about to read through DPP in front of this statement, and all those reads sit behind the reciprocal chain that
-// starts here, so no DPP read can follow its producer by less than two instructions.
+// two wait states before a DPP read).  dep0 .. dep3 are not read: naming them orders every writer of COLUMN j of the
+// pivot in front of this statement.  That covers the sweeps whose DPP operand is column j (the lower-triangle sweep of
+// the likelihood-only kernels, the row-pair geometry): all those reads sit behind the reciprocal chain that starts here,
+// so none can follow its producer by less than two instructions.  It does NOT cover the 16-lane Gauss-Jordan sweep
+// (LPS = 16, GPV_OPT_PIVROW), whose operand is element c of the pivot ROW, register a[qj][c] of lane j % 16: its last
+// writers are the previous pivot's DPP FMAs on the columns behind j, which no operand here names.  There the distance is
+// kept by the order of the updates (the slot of the pivot row goes last, and a pivot's broadcast, reciprocal and
+// multipliers lie between its last FMA and the next pivot's first read), by the pins where matrix rows get parked in
+// AGPRs (GPV_PIN_DPP_SRC), and it is CHECKED, not guaranteed: gpvecchia_amd.build.dpp_hazards disassembles every built
+// object and a CPU test keeps its count at 0.
 template <int N>
 __device__ __forceinline__ double dpp_row_bcast(double x, double dep0 = 0.0, double dep1 = 0.0, double dep2 = 0.0, double dep3 = 0.0)
 {
@@ -955,6 +980,28 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         if (want_cb) pcb = cboff_pf[prow];                   // prow: the NEXT task's output row by now (or this one's, in the prologue)
     };
     if constexpr (PFREC) load_rec();
+    // Covariance staging addresses (k_cov_addr_table): where the closed-form rounds store the pair (row slot q, round s) in the
+    // packed triangle depends on the lane's row, its set slice and compile-time constants only, so the RPL * P/2 absolute LDS
+    // byte addresses are worked out here, once per wavefront, from i_const (NOT from the per-task copy of the row index below)
+    // and stay in 32-bit registers through the task loop.  The empty asm makes each entry opaque: the compiler can neither
+    // re-derive it per task nor keep the (row < P - s) compares as lane masks in SGPRs.
+    constexpr bool COVTAB = k_cov_addr_table<P, D, COV, LIK>();
+    unsigned ctab[COVTAB ? RPL : 1][COVTAB ? P / 2 : 1];
+    if constexpr (COVTAB) {
+        const unsigned tr0 = lds_addr(&L.tri[sub][0]);
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const unsigned r = (lane_on && i_const + q * LPS < P) ? (unsigned)(i_const + q * LPS) : 0u;   // as rq[q] of the rounds
+            const unsigned rt8 = tr0 + __umul24(r, r + 1) * 4;
+#pragma unroll
+            for (int s = 1; s <= P / 2; ++s) {
+                // pair (r, r+s): r+s < P: slot rt + r (s+1) + s(s+1)/2; wrapped (j = r+s-P < r): slot rt + j
+                unsigned at = (r < (unsigned)(P - s)) ? rt8 + 8 * (r * (s + 1) + s * (s + 1) / 2) : rt8 + 8 * (r + s - P);
+                asm volatile("" : "+v"(at));
+                ctab[q][s - 1] = at;
+            }
+        }
+    }
     int task_layer = 0;
     for (int64_t task = task_lo + vfirst, task_next; task < task_hi; task = task_next) {
         task_next = task + step_from(task_layer);
@@ -1142,6 +1189,16 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                 trA[q] = rt8 + 2 * rq8[q];                              // s = 1
                 trB[q] = rt8 + rq8[q] - 8 * P;
             }
+            // the pair (slot q, round s) goes to its triangle slot: from the wavefront's address table where the instantiation
+            // keeps one (then rq8 / trA / trB above are dead code), else one select and two adds per pair
+            auto stage = [&](int q, int s, double v) {
+                if constexpr (COVTAB) {
+                    *lds_wptr(ctab[q][s - 1]) = v;
+                } else {
+                    *lds_wptr(((rq[q] < P - s) ? trA[q] : trB[q]) + 8 * s) = v;
+                    trA[q] += rq8[q] + 8 * s;                            // to round s + 1
+                }
+            };
             auto fetch = [&](int q, int s, double (&dst)[DD]) {
                 const lds_cdouble *xj = Lds::XYEXT ? lds_ptr(xoA[q] + s * Lds::XS_ROW * 8)
                                                    : lds_ptr(((rq[q] < P - s) ? xoA[q] : xoB[q]) + s * Lds::XS_ROW * 8);
@@ -1203,8 +1260,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                         double v = matern_table_value(rc[q], sgc[q]);
                         if constexpr (!(R2MIN && GPV_OPT_GEN_NOLIVE != 0)) v = livec[q] ? v : sig0;   // src/Matern.cpp:76 (else: matern_gen_fixup)
                         if constexpr (MASKED) v = usedc[q] ? v : 0.0;
-                        *lds_wptr(((rq[q] < P - s) ? trA[q] : trB[q]) + 8 * s) = v;
-                        trA[q] += rq8[q] + 8 * s;                    // to round s + 1
+                        stage(q, s, v);
                     }
                 }
             } else
@@ -1247,10 +1303,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                     if constexpr (MASKED) v[q] = used ? v[q] : 0.0;
                 }
 #pragma unroll
-                for (int q = 0; q < RPL; ++q) {
-                    *lds_wptr(((rq[q] < P - s) ? trA[q] : trB[q]) + 8 * s) = v[q];
-                    trA[q] += rq8[q] + 8 * s;                        // to round s + 1
-                }
+                for (int q = 0; q < RPL; ++q) stage(q, s, v[q]);
             }
             if constexpr (COV == COV_MATERN_GEN) {
                 // the flagged pairs again, exactly (matern_gen_fixup: a real function call, so that the quadrature, its loop and
