@@ -201,6 +201,20 @@ class Plan:
         L.check(st, "gpv_plan_lincomb")
         return cov if cov_mat else vars_[:nrows]
 
+    def solve_t(self, E_ord):
+        """R^T x = e for every row e of E_ord, (ncols, Nlocs) or (Nlocs,) float64 in the plan's ORDERED latent layout, with
+        the factor lincomb reads (gpv_plan_solve_t: batched, level scheduled, on the device).  For e ~ N(0, I) the rows of the
+        result have covariance W^-1: posterior_mean() + x is a posterior draw.  Returns an array of the same shape."""
+        E = np.asarray(E_ord, dtype=np.float64)
+        if E.ndim not in (1, 2) or E.shape[-1] != self.Nlocs:
+            raise ValueError("E_ord must have one entry per ordered location of the plan in its last dimension")
+        E2 = np.ascontiguousarray(np.atleast_2d(E))
+        X = np.empty_like(E2)
+        ncols = int(E2.shape[0])
+        st = L.lib().gpv_plan_solve_t(self._h, ncols, L.dptr(E2), self.Nlocs, L.dptr(X), self.Nlocs)
+        L.check(st, "gpv_plan_solve_t")
+        return X.reshape(E.shape)
+
     kernel_timing = True
 
     def set_kernel_timing(self, on):

@@ -385,6 +385,8 @@ struct gpv_plan {
     bool lc_ready = false;
     double *d_lc_X = nullptr, *d_lc_part = nullptr, *d_lc_vars = nullptr, *d_lc_gpart = nullptr, *d_lc_gram = nullptr;
     hipGraphExec_t lc_graph = nullptr;               // the sweep (levels, top block, column sums) as a captured graph
+    double *d_st_E = nullptr;                        // gpv_plan_solve_t: one batch of dense columns, [kLincombNB][Nlocs]
+    hipGraphExec_t st_graph = nullptr;               // the transposed sweep (top block, levels) as a captured graph
     double nug_scalar = 0.0;
     bool nug_is_scalar = true;
     uint8_t *d_cond = nullptr;
@@ -460,10 +462,11 @@ int gpv_plan_destroy(gpv_plan *pl)
                     pl->d_order2, pl->d_levptr2, pl->d_toppart, pl->d_u, pl->d_mu, pl->d_tp, pl->d_nug_post, pl->d_mt2[0], pl->d_mt2[1],
                     pl->d_vl_z, pl->d_vl_pm, pl->d_vl_y[0], pl->d_vl_y[1], pl->d_vl_out, pl->d_vl_flags, pl->d_ticket,
                     pl->d_vl_y0, pl->d_vl_part, pl->d_user_ord, pl->d_meanrec, pl->d_obs, pl->d_topinfo, pl->d_toprows, pl->d_rr0, pl->d_nug_masked,
-                    pl->d_lc_rec, pl->d_lc_X, pl->d_lc_part, pl->d_lc_vars, pl->d_lc_gpart, pl->d_lc_gram};
+                    pl->d_lc_rec, pl->d_lc_X, pl->d_lc_part, pl->d_lc_vars, pl->d_lc_gpart, pl->d_lc_gram, pl->d_st_E};
     for (auto &g : pl->pgraph)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (pl->lc_graph) (void)hipGraphExecDestroy(pl->lc_graph);
+    if (pl->st_graph) (void)hipGraphExecDestroy(pl->st_graph);
     for (void *q : ptrs)
         if (q) (void)hipFree(q);
     for (int t = 0; t < 2; ++t) {
@@ -1206,6 +1209,7 @@ static int build_posterior_impl(gpv_plan *pl, const int *revNN, const int *revCo
     pl->have_factor = false;
     pl->lc_ready = false;
     if (pl->lc_graph) { (void)hipGraphExecDestroy(pl->lc_graph); pl->lc_graph = nullptr; }
+    if (pl->st_graph) { (void)hipGraphExecDestroy(pl->st_graph); pl->st_graph = nullptr; }
     if (pl->last_stream) { GPV_HIP(hipSetDevice(pl->device)); GPV_HIP(hipStreamSynchronize(pl->last_stream)); }
     for (auto &g : pl->pgraph)
         if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
@@ -2063,6 +2067,99 @@ int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int
     pl->last_stream = st;
     release();
     return GPV_OK;
+}
+
+// the transposed sweep on d_lc_X: the dense top block, then the mean sweep's levels in ascending order, one launch each
+static hipError_t solvet_enqueue(gpv_plan *pl, hipStream_t st)
+{
+    SolveTArgs sa;
+    sa.meanrec = pl->d_meanrec; sa.crow = pl->d_crow; sa.C = pl->d_C; sa.X = pl->d_lc_X;
+    hipError_t e = hipSuccess;
+    if (pl->top_K > 0) e = launch_solvet_top(sa, pl->top_K, pl->d_topinfo, pl->d_toprows, st);
+    for (size_t lv = 0; e == hipSuccess && lv + 1 < pl->levptr2.size(); ++lv)
+        e = launch_solvet_level(sa, pl->levptr2[lv], pl->levptr2[lv + 1] - pl->levptr2[lv], st);
+    return e;
+}
+// ... as the plan's captured graph (captured on first use; GPV_NO_GRAPH: launch by launch)
+static hipError_t solvet_sweep(gpv_plan *pl, hipStream_t st)
+{
+    static const bool no_graph = getenv("GPV_NO_GRAPH") != nullptr;
+    if (!no_graph && !pl->st_graph) {
+        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            const hipError_t e = solvet_enqueue(pl, st);
+            hipGraph_t graph = nullptr;
+            const hipError_t e2 = hipStreamEndCapture(st, &graph);
+            if (!(e == hipSuccess && e2 == hipSuccess && graph && hipGraphInstantiate(&pl->st_graph, graph, nullptr, nullptr, 0) == hipSuccess))
+                pl->st_graph = nullptr;
+            if (graph) (void)hipGraphDestroy(graph);
+            (void)hipGetLastError();
+        }
+    }
+    if (!no_graph && pl->st_graph) return hipGraphLaunch(pl->st_graph, st);
+    return solvet_enqueue(pl, st);
+}
+
+int gpv_plan_solve_t(gpv_plan *pl, int64_t ncols, const double *E, int64_t lde, double *X, int64_t ldx)
+{
+    constexpr int NB = kLincombNB;
+    if (!pl || ncols < 0 || !E || !X) return GPV_ERR_BAD_ARG;
+    const int64_t n = pl->Nlocs;
+    if (lde < n || ldx < n) return GPV_ERR_BAD_ARG;
+    if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
+    if (pl->post_ld > 64 || !pl->d_meanrec) return GPV_ERR_STATE;               // (no structure is built with longer columns)
+    if (ncols == 0) return GPV_OK;
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (!pl->d_lc_X) GPV_HIP(hipMalloc((void **)&pl->d_lc_X, sizeof(double) * (size_t)n * NB));
+    if (!pl->d_st_E) GPV_HIP(hipMalloc((void **)&pl->d_st_E, sizeof(double) * (size_t)n * NB));
+    hipStream_t st = pl->stream;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    const int64_t nbatch = (ncols + NB - 1) / NB;
+    for (int64_t b = 0; b < nbatch; ++b) {
+        const int64_t col0 = b * NB;
+        const int nb = (int)std::min<int64_t>(NB, ncols - col0);
+        for (int j = 0; j < nb; ++j)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_st_E + (size_t)j * n, E + (col0 + j) * lde, sizeof(double) * (size_t)n,
+                                              hipMemcpyHostToDevice, st)))
+                return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_solvet_pack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(solvet_sweep(pl, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_solvet_unpack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return fail(GPV_ERR_HIP);
+        for (int j = 0; j < nb; ++j)                                              // (X may be E: the batch was read before)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(X + (col0 + j) * ldx, pl->d_st_E + (size_t)j * n, sizeof(double) * (size_t)n,
+                                              hipMemcpyDeviceToHost, st)))
+                return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+    }
+    pl->last_stream = st;
+    return GPV_OK;
+}
+
+// developer aid (tools/lincomb_timing.py; not part of the public header): device time of `reps` transposed sweeps over a full
+// batch, each on a fresh copy of what the latest gpv_plan_solve_t left in the staging buffer (the time does not depend on the
+// values), by a pair of events around the sweep alone: no packing, no copies
+extern "C" int gpv_plan_debug_solve_t_ms(gpv_plan *pl, int reps, double *ms)
+{
+    if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
+    if (!pl->have_post || !pl->have_factor || pl->comm || !pl->d_lc_X || !pl->d_st_E) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    hipEvent_t a = nullptr, b = nullptr;
+    GPV_HIP(hipEventCreate(&a));
+    if (GPV_HIP_FAILED(hipEventCreate(&b))) { (void)hipEventDestroy(a); return GPV_ERR_HIP; }
+    int rc = GPV_OK;
+    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
+        float t = 0.f;
+        if (GPV_HIP_FAILED(launch_solvet_pack(pl->d_lc_X, pl->d_st_E, pl->Nlocs, pl->Nlocs, kLincombNB, st)) ||
+            GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(solvet_sweep(pl, st)) || GPV_HIP_FAILED(hipEventRecord(b, st)) ||
+            GPV_HIP_FAILED(hipStreamSynchronize(st)) || GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
+            rc = GPV_ERR_HIP;
+        ms[r] = (double)t;
+    }
+    (void)hipStreamSynchronize(st);
+    (void)hipEventDestroy(a);
+    (void)hipEventDestroy(b);
+    return rc;
 }
 
 int gpv_plan_get_sums(gpv_plan *pl, double *sums)

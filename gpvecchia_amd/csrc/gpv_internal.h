@@ -185,4 +185,17 @@ hipError_t launch_lincomb_level(const LincombArgs &a, int first, int count, bool
 hipError_t launch_lincomb_vars(const double *X, int64_t n, double *partials, double *vars, hipStream_t s);
 hipError_t launch_lincomb_gram(const double *X, int64_t n, double *partials, double *gram, hipStream_t s);
 
+// ---- the transposed solve (gpv_lincomb.hip): R^T X = E for kLincombNB right-hand sides, in place on X[Nlocs][kLincombNB] ------
+struct SolveTArgs {
+    const int4 *meanrec;     // PostArgs::meanrec: per column of the ascending schedule {k, block offset in C, entries, first entry in crow}
+    const int32_t *crow;     // PostArgs::crow: rows of the columns, ascending, the column itself last
+    const double2 *C;
+    double *X;               // [Nlocs][kLincombNB]
+};
+// E: nb dense columns of length n, ld apart (device) -> X[n][kLincombNB], the columns nb.. zero; and back
+hipError_t launch_solvet_pack(double *X, const double *E, int64_t n, int64_t ld, int nb, hipStream_t s);
+hipError_t launch_solvet_unpack(const double *X, double *E, int64_t n, int64_t ld, int nb, hipStream_t s);
+// the columns [first, first + count) of the mean sweep's schedule (one level), at most 64 entries per column
+hipError_t launch_solvet_level(const SolveTArgs &a, int first, int count, hipStream_t s);
+
 }  // namespace gpv

@@ -13,6 +13,8 @@
 // lanes (NB right-hand sides x 64/NB slices of the chunk) walk the chunk with the record and the value broadcast from the
 // lane that fetched them.  Every partial sum has a fixed order (slice: ascending entries; slices and waves: fixed trees) =>
 // bitwise reproducible.  No floating-point atomics.
+//
+// Further down: the TRANSPOSED solve R^T X = E on the same buffer and batching (posterior draws, gpv_plan_solve_t).
 #include "gpv_internal.h"
 #include "gpv_posterior_ext.h"
 #include <atomic>
@@ -242,6 +244,167 @@ hipError_t launch_lincomb_gram(const double *X, int64_t n, double *partials, dou
 {
     hipLaunchKernelGGL((gpv_lincomb_sq_stage1<true>), dim3(kLincombBlocks), dim3(NB * NB), 0, s, X, n, partials);
     hipLaunchKernelGGL((gpv_lincomb_sq_stage2<true>), dim3(1), dim3(NB * NB), 0, s, (const double *)partials, kLincombBlocks, gram);
+    return hipGetLastError();
+}
+
+// ---- the transposed solve R^T X = E (posterior draws: e ~ N(0, I) => x = R^-T e has covariance W^-1) ------------------------
+//     x_k[j] = (e_k[j] - sum_{c < k, c in col k} R_ck x_c[j]) / R_kk ,      R_ck = C[cb_k + 1 + l].y, l = position of c in col k.
+// The gather form of the sweep above: column k reads ITS OWN entries (the rows crow[..] of the column, the self entry last),
+// which is the recurrence of the scalar mean sweep (gpv_posterior.hip, gpv_mean_level_rec_kernel) for NB right-hand sides, on
+// that sweep's ascending schedule (meanrec / levptr2), one launch per level, the dense top block first.
+//
+// One wavefront per column.  A column has at most 64 entries, so the lanes fetch its rows and R values in ONE coalesced trip;
+// then the lanes (NB right-hand sides x kLcS slices) walk the entries, row and value broadcast from the lane that fetched
+// them; a gathered x_c[0..NB) is one contiguous run.  A slice adds its entries in ascending order, the slices meet in slice
+// order, every lane of a right-hand side executes the same operations whatever its j => bitwise reproducible, and a column
+// of E gives the same bits at every position of its batch.
+__global__ void __launch_bounds__(256) gpv_solvet_level_kernel(const SolveTArgs A, const int first, const int count)
+{
+    const int lane = threadIdx.x & 63;
+    const int w = (int)(blockIdx.x * 4) + (int)(threadIdx.x >> 6);
+    if (w >= count) return;
+    const int4 rec = A.meanrec[first + w];
+    const int k = rec.x, cnt = rec.z;
+    const int j = lane & (NB - 1), sl = lane / NB;
+    const double ek = A.X[(size_t)k * NB + j];
+    int cc = k;                                               // (a lane without an entry points at the column itself: a valid row)
+    double rv = 0.0;
+    if (lane < cnt) {
+        cc = A.crow[rec.w + lane];
+        rv = A.C[(size_t)rec.y + 1 + lane].y;
+    }
+    const double rkk = lc_shfl(rv, cnt - 1);                  // the diagonal: last entry of the column
+    const int m = cnt - 1;
+    double acc = 0.0;
+    for (int t = 0; t < m; t += 4 * kLcS) {
+        double x[4], r[4];
+        bool on[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int e = t + u * kLcS + sl;
+            const int ee = e < 64 ? e : 63;
+            on[u] = e < m;
+            const int c = __builtin_amdgcn_ds_bpermute(ee << 2, cc);
+            r[u] = lc_shfl(rv, ee);
+            x[u] = A.X[(size_t)c * NB + j];
+        }
+#pragma unroll
+        for (int u = 0; u < 4; ++u) acc = on[u] ? __builtin_fma(r[u], x[u], acc) : acc;
+    }
+    double tot = lc_shfl(acc, j);
+#pragma unroll
+    for (int s = 1; s < kLcS; ++s) tot += lc_shfl(acc, j + s * NB);
+    if (lane < NB) A.X[(size_t)k * NB + j] = (ek - tot) / rkk;
+}
+
+hipError_t launch_solvet_level(const SolveTArgs &a, int first, int count, hipStream_t s)
+{
+    if (count <= 0) return hipSuccess;
+    hipLaunchKernelGGL(gpv_solvet_level_kernel, dim3((count + 3) / 4), dim3(256), 0, s, a, first, count);
+    return hipGetLastError();
+}
+
+// The dense top block, FIRST here: the rows of a column of T are in T, so R_TT^T x_T = e_T is a forward substitution of its own.
+// The layout of gpv_lincomb_top_kernel (R_TT in LDS, thread (g, j) keeps the right-hand side j of the columns g, g + G, ..),
+// walked from the first column: the owner of column c publishes x_c[j], every thread subtracts R_c,cc x_c[j] from its columns
+// cc > c (row c of R: consecutive words for consecutive g).
+__global__ void __launch_bounds__(1024) gpv_solvet_top_kernel(const SolveTArgs A, const int K, const int2 *topinfo,
+                                                             const uint8_t *toprows)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char sttop_smem[];
+    double *Rl = reinterpret_cast<double *>(sttop_smem);       // [row][column], rows kLcTopLd apart
+    double *xc = Rl + (size_t)kLcTop * kLcTopLd;               // [2][NB]: x_c of the step, double buffered
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int i = tid; i < kLcTop * kLcTopLd; i += 1024) Rl[i] = 0.0;
+    __syncthreads();
+    if (tid < kLcTop && tid >= K) Rl[tid * kLcTopLd + tid] = 1.0;
+    for (int kk = wave; kk < K; kk += 16) {                    // column kk of the block: entry e (lane) sits in row toprows[kk][e]
+        const int r = (int)toprows[kTopBlock * kk + lane];
+        if (r != 0xFF) Rl[r * kLcTopLd + kk] = A.C[(size_t)topinfo[kk].y + 1 + lane].y;
+    }
+    const int j = tid & (NB - 1), g = tid / NB;
+    double reg[kLcTopRows];
+    int kcol[kLcTopRows];
+#pragma unroll
+    for (int r = 0; r < kLcTopRows; ++r) {
+        const int col = g + r * kLcTopG;
+        kcol[r] = col < K ? topinfo[col].x : -1;
+        reg[r] = col < K ? A.X[(size_t)kcol[r] * NB + j] : 0.0;
+    }
+    __syncthreads();
+    for (int c = 0; c < K; ++c) {
+        double *xb = xc + (c & 1) * NB;
+        if (g == c % kLcTopG) {
+            const double d = Rl[c * kLcTopLd + c];
+#pragma unroll
+            for (int r = 0; r < kLcTopRows; ++r)
+                if (r == c / kLcTopG) { reg[r] = reg[r] / d; xb[j] = reg[r]; }
+        }
+        __syncthreads();
+        const double xv = xb[j];
+#pragma unroll
+        for (int r = 0; r < kLcTopRows; ++r) {
+            const int col = g + r * kLcTopG;
+            if (col > c) reg[r] = __builtin_fma(-Rl[c * kLcTopLd + col], xv, reg[r]);
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < kLcTopRows; ++r)
+        if (kcol[r] >= 0) A.X[(size_t)kcol[r] * NB + j] = reg[r];
+}
+
+hipError_t launch_solvet_top(const SolveTArgs &a, int K, const int2 *topinfo, const uint8_t *toprows, hipStream_t s)
+{
+    if (K <= 0) return hipSuccess;
+    if (K > kLcTop) return hipErrorInvalidValue;
+    static std::atomic<unsigned long long> done{0ull};
+    int dev = 0;
+    (void)hipGetDevice(&dev);
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(done.load(std::memory_order_relaxed) & bit)) {
+        hipError_t e1 = hipFuncSetAttribute(reinterpret_cast<const void *>(&gpv_solvet_top_kernel),
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLcTopSmem);
+        if (e1 != hipSuccess) return e1;
+        done.fetch_or(bit, std::memory_order_relaxed);
+    }
+    hipLaunchKernelGGL(gpv_solvet_top_kernel, dim3(1), dim3(1024), kLcTopSmem, s, a, K, topinfo, toprows);
+    return hipGetLastError();
+}
+
+// nb dense columns of E (ld apart) <-> the interleaved X[n][NB], 64 locations per block through an LDS tile so that both sides
+// move whole lines; pack pads a short batch with zero columns
+__global__ void __launch_bounds__(256) gpv_solvet_pack_kernel(double *X, const double *E, int64_t n, int64_t ld, int nb)
+{
+    __shared__ double tile[NB][65];
+    const int64_t k0 = (int64_t)blockIdx.x * 64;
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int jj = ty; jj < NB; jj += 4) tile[jj][tx] = (jj < nb && k0 + tx < n) ? E[(int64_t)jj * ld + k0 + tx] : 0.0;
+    __syncthreads();
+    const int c = threadIdx.x & (NB - 1);
+    for (int r = threadIdx.x / NB; r < 64; r += 256 / NB)
+        if (k0 + r < n) X[(k0 + r) * NB + c] = tile[c][r];
+}
+__global__ void __launch_bounds__(256) gpv_solvet_unpack_kernel(const double *X, double *E, int64_t n, int64_t ld, int nb)
+{
+    __shared__ double tile[NB][65];
+    const int64_t k0 = (int64_t)blockIdx.x * 64;
+    const int c = threadIdx.x & (NB - 1);
+    for (int r = threadIdx.x / NB; r < 64; r += 256 / NB) tile[c][r] = (k0 + r < n) ? X[(k0 + r) * NB + c] : 0.0;
+    __syncthreads();
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int jj = ty; jj < nb; jj += 4)
+        if (k0 + tx < n) E[(int64_t)jj * ld + k0 + tx] = tile[jj][tx];
+}
+hipError_t launch_solvet_pack(double *X, const double *E, int64_t n, int64_t ld, int nb, hipStream_t s)
+{
+    if (n <= 0 || nb <= 0 || nb > NB || ld < n || (n + 63) / 64 > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gpv_solvet_pack_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, X, E, n, ld, nb);
+    return hipGetLastError();
+}
+hipError_t launch_solvet_unpack(const double *X, double *E, int64_t n, int64_t ld, int nb, hipStream_t s)
+{
+    if (n <= 0 || nb <= 0 || nb > NB || ld < n || (n + 63) / 64 > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gpv_solvet_unpack_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, X, E, n, ld, nb);
     return hipGetLastError();
 }
 

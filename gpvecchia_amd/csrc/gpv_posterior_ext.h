@@ -25,4 +25,7 @@ hipError_t launch_mean_top(const PostArgs &a, double *u, int K, const int2 *topi
 // Linear combinations (gpv_lincomb.hip), the columns of T, after every level: their row-list terms outside T, then the dense
 // back substitution R_TT x_T = rhs_T in one workgroup
 hipError_t launch_lincomb_top(const LincombArgs &a, int first, int K, const int2 *topinfo, const uint8_t *toprows, hipStream_t s);
+// The transposed solve (gpv_lincomb.hip), the columns of T, before every level (they wait for nothing outside T): the dense
+// forward substitution R_TT^T x_T = e_T in one workgroup
+hipError_t launch_solvet_top(const SolveTArgs &a, int K, const int2 *topinfo, const uint8_t *toprows, hipStream_t s);
 }  // namespace gpv

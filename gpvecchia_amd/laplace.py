@@ -179,22 +179,33 @@ def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
     return out
 
 
-def vecchia_laplace_prediction(vl_posterior, vecchia_approx, covparms, pred_mean=0.0, covmodel="matern", device=0):
-    """R/vecchia_laplace_NR.R:523-551, means only (variances are not built): vecchia_prediction with the pseudo-data and
-    pseudo-nuggets of a calculate_posterior_VL result, on a vecchia.approx that may carry prediction locations; the latent
-    means and their images under the family's link function."""
+def vecchia_laplace_prediction(vl_posterior, vecchia_approx, covparms, pred_mean=0.0, covmodel="matern", device=0,
+                               return_values="mean", var_exact=None):
+    """R/vecchia_laplace_NR.R:523-551: vecchia_prediction with the pseudo-data and pseudo-nuggets of a calculate_posterior_VL
+    result, on a vecchia.approx that may carry prediction locations; the latent means and their images under the family's
+    link function.  return_values / var_exact pass through to vecchia_prediction (the default 'mean': means only).  With
+    'meanvar' / 'all' also the data-scale 5% / 95% quantiles of :541-548; with 'meanmat' / 'all' the `factor` handle, so that
+    vecchia_posterior_sample draws the latent field of a Vecchia-Laplace posterior (data_link of a draw: the data scale)."""
     z_pseudo = np.asarray(vl_posterior["t"], dtype=np.float64) - vl_posterior["prior_mean"]          # :526
     nug_pseudo = np.asarray(vl_posterior["D"], dtype=np.float64)                                    # :527
     if nug_pseudo.size < z_pseudo.size:                                   # missing observations: D holds the observed entries
         full = np.full(z_pseudo.size, np.nan)
         full[~np.isnan(z_pseudo)] = nug_pseudo
         nug_pseudo = full
-    preds = vecchia_prediction(z_pseudo, vecchia_approx, covparms, nug_pseudo, covmodel, device=device)   # :530-531
+    preds = vecchia_prediction(z_pseudo, vecchia_approx, covparms, nug_pseudo, covmodel, return_values=return_values,
+                               device=device, var_exact=var_exact)        # :530-531
     preds["mu_pred"] = preds["mu_pred"] + pred_mean                       # :532
     preds["mu_obs"] = preds["mu_obs"] + vl_posterior["prior_mean"]        # :533
     link = vl_posterior["data_link"]
     preds["data_pred"] = link(preds["mu_pred"])                           # :537
     preds["data_obs"] = link(preds["mu_obs"])                             # :538
+    if return_values in ("meanvar", "all"):                               # :541-548
+        from scipy.stats import norm
+        for key, p, mu, var in (("data_pred_upper_quantile", .95, preds["mu_pred"], preds["var_pred"]),
+                                ("data_pred_lower_quantile", .05, preds["mu_pred"], preds["var_pred"]),
+                                ("data_obs_upper_quantiles", .95, preds["mu_obs"], preds["var_obs"]),
+                                ("data_obs_lower_quantiles", .05, preds["mu_obs"], preds["var_obs"])):
+            preds[key] = link(mu + np.sqrt(var) * norm.ppf(p))               # qnorm(p, mu, sd); sd = 0 gives mu, as in R
     return preds
 
 

@@ -7,6 +7,10 @@ that is gpv_plan_lincomb (gpv_lincomb.hip: one level-scheduled triangular solve 
 the prediction's evaluation left in the plan); on the host route the same quantity through the factor object of api.U2V.
 Unit-vector rows give diag(W^-1): the exact posterior variances, which for an exact fill-closed factor is also what the
 reference's SelInv returns.
+
+vecchia_posterior_sample reads the same factor the other way round: for e ~ N(0, I), x = R^-T e has covariance W^-1, so
+mu + x is a draw from the Vecchia posterior of the latent field at every observed and prediction location (conditional
+simulation).  Device routes: gpv_plan_solve_t (32 draws per sweep); host route: rev(x) = V^-T rev(e) with the factor of api.U2V.
 """
 from __future__ import annotations
 
@@ -116,3 +120,72 @@ def host_variances(U_obj, lu):
     if U_obj["zero_nugg"]:
         var_ord = np.concatenate([var_ord, np.zeros(len(U_obj["zero_nugg"]["inds_z"]))])
     return split_mean(var_ord, U_obj)
+
+
+def _host_solve_t(lu, Erev):
+    """V^-T e for the columns e of Erev (reversed ordered layout), V V^T = rev(W): the mirror of _host_quadform.  SuperLU
+    object of api.U2V: rev(W) = L D L^T (natural order, no pivoting), V = L sqrt(D), so V^-T e = L^-T (e / sqrt(diag U))."""
+    import scipy.sparse.linalg as spla
+    Erev = np.asarray(Erev, dtype=np.float64)
+    V = getattr(lu, "V", None)
+    if V is not None:                                                     # api._TriFactor
+        return spla.spsolve_triangular(V.T.tocsr(), Erev, lower=False)
+    nW = lu.shape[0]
+    if not (np.array_equal(lu.perm_r, np.arange(nW)) and np.array_equal(lu.perm_c, np.arange(nW))):
+        raise RuntimeError("vecchia_posterior_sample: the sparse factorisation pivoted (matrix not positive definite?)")
+    d = lu.U.diagonal()
+    return spla.spsolve_triangular(lu.L.T.tocsr(), Erev / np.sqrt(d)[:, None], lower=False)
+
+
+def _split_rows(X_ord, ord_, obs):
+    """api.split_mean for every row of X_ord (nsim x ordered latent variables): (nsim x n, nsim x n_p) in the caller's order."""
+    orig_order = np.argsort(np.asarray(ord_), kind="stable")
+    X = np.asarray(X_ord)[:, orig_order]
+    obs_orig = np.asarray(obs, dtype=bool)[orig_order]
+    return X[:, obs_orig], X[:, ~obs_orig]
+
+
+def vecchia_posterior_sample(preds, nsim=1, seed=None, eps=None):
+    """Draws from the Vecchia posterior of the latent field given the data (conditional simulation): mu + R^-T eps with
+    W = R R^T the posterior precision of vecchia_prediction (R/vecchia_prediction.R:62-126).  preds: the result of
+    vecchia_prediction(..., return_values='meanmat' | 'all') (or of vecchia_laplace_prediction with those values: the draws
+    are then of the latent field, and vl_posterior['data_link'] of them is the data-scale predictive).  eps: (nsim, number of
+    latent variables) standard normals in the ORDERED latent layout; absent, np.random.default_rng(seed).standard_normal.
+    Returns dict(y_obs (nsim x n), y_pred (nsim x n_p), eps), locations in the caller's order; zero-nugget observations
+    (host route) are their data in every draw (variance 0, :129-132, :210-212)."""
+    fac = preds.get("factor") if isinstance(preds, dict) else None
+    if fac is None:
+        raise ValueError("vecchia_posterior_sample needs the result of vecchia_prediction(..., return_values='meanmat' or 'all')")
+    if fac["kind"] == "device":
+        plan = _check_stamp(fac)
+        nlat, nzero = int(fac["ord"].size), 0
+        if fac["offset"] + nlat != plan.Nlocs:
+            raise ValueError("preds does not match the plan of this prediction")
+    else:
+        U_obj, lu = fac["U_obj"], fac["lu"]
+        nlat = int(np.sum(U_obj["latent"]))
+        nzero = len(U_obj["zero_nugg"]["inds_z"]) if U_obj["zero_nugg"] else 0
+    if eps is None:
+        nsim = int(nsim)
+        if nsim < 0:
+            raise ValueError("nsim must not be negative")
+        eps = np.random.default_rng(seed).standard_normal((nsim, nlat))
+    else:
+        eps = np.asarray(eps, dtype=np.float64)
+        if eps.ndim != 2 or eps.shape[1] != nlat:
+            raise ValueError(f"eps must be (nsim, {nlat}): one column per latent variable, ordered layout")
+        nsim = int(eps.shape[0])
+    if fac["kind"] == "device":
+        off = fac["offset"]
+        # (cond.yz = 'zy': the n dummy rows in front carry zeros, as the columns of H do in vecchia_lincomb)
+        E = np.hstack([np.zeros((nsim, off)), eps]) if off else eps
+        X = plan.solve_t(E)[:, off:] if nsim else np.zeros((0, nlat))
+        x_obs, x_pred = _split_rows(X, fac["ord"], fac["obs"])
+    else:
+        X = np.empty((nsim, nlat))
+        for b in range(0, nsim, _HOST_CHUNK):
+            X[b:b + _HOST_CHUNK] = _host_solve_t(lu, eps[b:b + _HOST_CHUNK, ::-1].T)[::-1].T
+        if nzero:
+            X = np.hstack([X, np.zeros((nsim, nzero))])
+        x_obs, x_pred = _split_rows(X, U_obj["ord"], U_obj["obs"])
+    return dict(y_obs=np.asarray(preds["mu_obs"])[None, :] + x_obs, y_pred=np.asarray(preds["mu_pred"])[None, :] + x_pred, eps=eps)

@@ -222,6 +222,17 @@ int gpv_plan_get_posterior_mean(gpv_plan *plan, double *mu_ord);
  * outside [0, Nlocs).  Arguments are validated before the device is touched. */
 int gpv_plan_lincomb(gpv_plan *plan, int64_t nrows, const int64_t *hptr, const int32_t *hidx, const double *hval,
                      double *vars, double *cov);
+/* The batched transposed solve R^T x_j = e_j, j < ncols, with the same factor (W = R R^T; for GPV_WANT_MEAN_B, R = B).  For
+ * e ~ N(0, I), x = R^-T e has covariance W^-1: mu.ord + x is a draw from the Vecchia posterior of the latent field at every
+ * location of the plan.  Column j of E is E + j * lde, length Nlocs, in the plan's ORDERED latent layout; X likewise with ldx,
+ * and X may be E itself (then with ldx == lde).  gpv_lincomb_batch() columns share one level-scheduled sweep (the schedule of
+ * the posterior mean's R^T u = t); a short last batch is padded with zeros.  The factor is only read and
+ * gpv_plan_factor_stamp does not change.  Blocking.  Results are bitwise reproducible from call to call and do not depend on
+ * a column's position among the ncols.  For cond.yz = 'zy' plans the n dummy rows in front are outside the contract: pass
+ * zeros there, as in H for gpv_plan_lincomb (x is then zero there as well).
+ * GPV_ERR_BAD_ARG: a null pointer, ncols < 0, lde or ldx < Nlocs; GPV_ERR_STATE: as for gpv_plan_lincomb; ncols == 0 is GPV_OK.
+ * Arguments are validated before the device is touched. */
+int gpv_plan_solve_t(gpv_plan *plan, int64_t ncols, const double *E, int64_t lde, double *X, int64_t ldx);
 int gpv_lincomb_batch(void);   /* right-hand sides per sweep (32) */
 /* stamp: 0 when the plan holds no factor, else a number that changes with every evaluation that writes one (callers that keep
  * a result of gpv_plan_lincomb's inputs around can tell whether the factor is still the one they mean) */

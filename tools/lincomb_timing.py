@@ -5,6 +5,12 @@
 
     python tools/lincomb_timing.py [--n 1000000] [--m 30] [--batches 8] [--host] [--pred]
 
+The transposed solve (gpv_plan_solve_t, posterior draws) is timed twice: the sweep alone on the device (a pair of events around
+the captured graph, gpv_plan_debug_solve_t_ms), which is what compares with one mean sweep and with one lincomb batch, and the
+whole call per batch, which at n = 1e6 is mostly the 2 x 256 MB of the batch crossing PCIe from and to pageable memory.  These
+legs are measured in --rounds alternating rounds (mean evaluation, denominator evaluation, lincomb, transposed sweep, ...) and
+reported as medians over the rounds.
+
 Times are wall clock around the blocking calls after a clock warm-up of evaluations (as bench.py does); the lincomb call is
 timed with 1 and with 1 + batches batches and the difference divided, so that the upload of H and the call's fixed cost drop out.
 --pred: also vecchia_prediction(..., 'meanvar') at 4e4 + 1e4 locations.  Prints one JSON line."""
@@ -38,6 +44,7 @@ def main():
     ap.add_argument("--m", type=int, default=30)
     ap.add_argument("--batches", type=int, default=8)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--pred", action="store_true")
     a = ap.parse_args()
@@ -73,6 +80,37 @@ def main():
                one_mean_sweep_ms=t_mean - t_den, lincomb_first_batch_call_ms=t1, lincomb_ms_per_batch=per_batch,
                lincomb_ms_per_solve=per_batch / NB, batch_over_single_sweep=per_batch / max(t_mean - t_den, 1e-9),
                X_bytes=n * NB * 8)
+    # the transposed sweep, in alternating rounds with what it is compared to
+    import ctypes as C
+    lib = L.lib()
+    lib.gpv_plan_debug_solve_t_ms.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_double)]
+    E1 = rng.standard_normal((NB, n))
+    Ek = np.ascontiguousarray(np.broadcast_to(E1, (3, NB, n)).reshape(3 * NB, n))
+    plan.solve_t(E1)                                                  # first use: staging buffers, graph
+    one = np.zeros(1)
+
+    def sweep_ms():
+        L.check(lib.gpv_plan_debug_solve_t_ms(plan._h, 1, L.dptr(one)), "gpv_plan_debug_solve_t_ms")
+        return float(one[0])
+    legs = dict(mean=[], denom=[], lc1=[], lck=[], st_sweep=[], st1=[], stk=[])
+    for _ in range(a.rounds):
+        legs["mean"].append(med(lambda: ev(G.GPV_WANT_MEAN), 1))
+        legs["denom"].append(med(lambda: ev(G.GPV_WANT_DENOM), 1))
+        ev(G.GPV_WANT_MEAN)
+        legs["lc1"].append(med(lambda: plan.lincomb(H1), 1))
+        legs["lck"].append(med(lambda: plan.lincomb(Hk), 1))
+        legs["st_sweep"].append(sweep_ms())
+        legs["st1"].append(med(lambda: plan.solve_t(E1), 1))
+        legs["stk"].append(med(lambda: plan.solve_t(Ek), 1))
+    m_ = {k: float(np.median(v)) for k, v in legs.items()}
+    r_sweep = m_["mean"] - m_["denom"]
+    r_lc = (m_["lck"] - m_["lc1"]) / a.batches
+    out.update(rounds=a.rounds, rounds_eval_mean_ms=m_["mean"], rounds_eval_denom_ms=m_["denom"], rounds_one_mean_sweep_ms=r_sweep,
+               rounds_lincomb_ms_per_batch=r_lc, solve_t_sweep_ms_per_batch=m_["st_sweep"],
+               solve_t_sweep_min_max_ms=[float(np.min(legs["st_sweep"])), float(np.max(legs["st_sweep"]))],
+               solve_t_sweep_ms_per_solve=m_["st_sweep"] / NB, solve_t_sweep_over_single_sweep=m_["st_sweep"] / max(r_sweep, 1e-9),
+               solve_t_sweep_over_lincomb_batch=m_["st_sweep"] / max(r_lc, 1e-9),
+               solve_t_call_ms_per_batch=(m_["stk"] - m_["st1"]) / 2, solve_t_first_batch_call_ms=m_["st1"])
     if a.host:
         import scipy.sparse.linalg as spla
         from oracle import r_side as R

@@ -46,6 +46,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run.log; then
     echo "== $tag: FAILED (rc $rc)"; return 1
   fi
+  # the same objects under the driver of gpv_plan_solve_t (a program of its own: tests/sanitize/solve_t_driver.cpp)
+  mkdir -p $B/solve_t
+  $HIPCC $CF -c $ROOT/tests/sanitize/solve_t_driver.cpp -o $B/solve_t/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/solve_t/driver.o -o $B/solve_t_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./solve_t_driver ) 2>&1 | tee $B/run_solve_t.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_solve_t.log; then
+    echo "== $tag: solve_t_driver FAILED (rc $rc)"; return 1
+  fi
   echo "== $tag: clean"
 }
 
