@@ -215,6 +215,40 @@ class Plan:
         L.check(st, "gpv_plan_solve_t")
         return X.reshape(E.shape)
 
+    def draws_normals(self, seed, ncols, col0=0, skip_front=0):
+        """The standard normals gpv_plan_draws_summary's device generator writes for the draws [col0, col0 + ncols) with this
+        seed, read back (gpv_plan_draws_normals): (ncols, Nlocs) in the plan's ORDERED latent layout, zeros in the first
+        skip_front columns.  A function of (seed, location, draw) alone: solve_t of these rows are the draws the summary sums."""
+        E = np.empty((int(ncols), self.Nlocs))
+        st = L.lib().gpv_plan_draws_normals(self._h, int(seed), int(skip_front), int(col0), int(ncols), L.dptr(E), self.Nlocs)
+        L.check(st, "gpv_plan_draws_normals")
+        return E
+
+    def draws_summary(self, ndraws, seed=0, skip_front=0, mu_ord=None, link=0, thresholds=None, mask=None, draw_stats=True):
+        """Monte-Carlo summaries of ndraws posterior draws y = mu_ord + R^-T e, reduced on the device (gpv_plan_draws_summary):
+        normals from the device generator, 32 draws per transposed sweep, sums folded after every sweep.  link 0 / 1 / 2 = g:
+        identity / exp / logistic.  Returns dict(mean, var (Nlocs each, of g(y)), exceed (len(thresholds) x Nlocs: the share of
+        draws with y > threshold, LATENT scale), draw_max, draw_mean (ndraws each: of g(y) over the locations of `mask`, a
+        boolean per ordered location, None = all behind skip_front; None with draw_stats=False)), ordered layout."""
+        n, ndraws = self.Nlocs, int(ndraws)
+        mu = None if mu_ord is None else np.ascontiguousarray(mu_ord, dtype=np.float64)
+        if mu is not None and mu.shape != (n,):
+            raise ValueError("mu_ord must have one entry per ordered location of the plan")
+        thr = np.ascontiguousarray([] if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+        mk = None if mask is None else np.ascontiguousarray(np.asarray(mask, dtype=bool), dtype=np.uint8)
+        if mk is not None and mk.shape != (n,):
+            raise ValueError("mask must have one entry per ordered location of the plan")
+        mean, var = np.empty(n), np.empty(n)
+        exceed = np.empty((thr.size, n))
+        dmax, dmean = (np.empty(max(ndraws, 0)), np.empty(max(ndraws, 0))) if draw_stats else (None, None)
+        st = L.lib().gpv_plan_draws_summary(
+            self._h, ndraws, int(seed), int(skip_front), None if mu is None else L.dptr(mu), int(link), int(thr.size),
+            L.dptr(thr) if thr.size else None, None if mk is None else mk.ctypes.data_as(C.POINTER(C.c_uint8)),
+            L.dptr(mean), L.dptr(var), L.dptr(exceed) if thr.size else None,
+            None if dmax is None else L.dptr(dmax), None if dmean is None else L.dptr(dmean))
+        L.check(st, "gpv_plan_draws_summary")
+        return dict(mean=mean, var=var, exceed=exceed, draw_max=dmax, draw_mean=dmean)
+
     kernel_timing = True
 
     def set_kernel_timing(self, on):

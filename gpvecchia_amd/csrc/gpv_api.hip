@@ -7,6 +7,7 @@
 #include "gpv_laplace.h"
 #include "gpv_generic.h"
 #include "gpv_posterior_ext.h"
+#include "gpv_philox.hpp"
 
 #include <dlfcn.h>
 
@@ -387,6 +388,12 @@ struct gpv_plan {
     hipGraphExec_t lc_graph = nullptr;               // the sweep (levels, top block, column sums) as a captured graph
     double *d_st_E = nullptr;                        // gpv_plan_solve_t: one batch of dense columns, [kLincombNB][Nlocs]
     hipGraphExec_t st_graph = nullptr;               // the transposed sweep (top block, levels) as a captured graph
+    // gpv_plan_draws_summary: mu, S1, S2, mean, var [Nlocs] each, exceed [8][Nlocs], the accumulation's block partials; counts
+    // [8][Nlocs]; mask [Nlocs]; draw_max, draw_mean [ds_draw_cap] each.  Allocated on first use.
+    double *d_ds = nullptr, *d_ds_draw = nullptr;
+    uint32_t *d_ds_cnt = nullptr;
+    uint8_t *d_ds_mask = nullptr;
+    int64_t ds_draw_cap = 0;
     double nug_scalar = 0.0;
     bool nug_is_scalar = true;
     uint8_t *d_cond = nullptr;
@@ -462,7 +469,8 @@ int gpv_plan_destroy(gpv_plan *pl)
                     pl->d_order2, pl->d_levptr2, pl->d_toppart, pl->d_u, pl->d_mu, pl->d_tp, pl->d_nug_post, pl->d_mt2[0], pl->d_mt2[1],
                     pl->d_vl_z, pl->d_vl_pm, pl->d_vl_y[0], pl->d_vl_y[1], pl->d_vl_out, pl->d_vl_flags, pl->d_ticket,
                     pl->d_vl_y0, pl->d_vl_part, pl->d_user_ord, pl->d_meanrec, pl->d_obs, pl->d_topinfo, pl->d_toprows, pl->d_rr0, pl->d_nug_masked,
-                    pl->d_lc_rec, pl->d_lc_X, pl->d_lc_part, pl->d_lc_vars, pl->d_lc_gpart, pl->d_lc_gram, pl->d_st_E};
+                    pl->d_lc_rec, pl->d_lc_X, pl->d_lc_part, pl->d_lc_vars, pl->d_lc_gpart, pl->d_lc_gram, pl->d_st_E,
+                    pl->d_ds, pl->d_ds_draw, pl->d_ds_cnt, pl->d_ds_mask};
     for (auto &g : pl->pgraph)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (pl->lc_graph) (void)hipGraphExecDestroy(pl->lc_graph);
@@ -2159,6 +2167,186 @@ extern "C" int gpv_plan_debug_solve_t_ms(gpv_plan *pl, int reps, double *ms)
     (void)hipStreamSynchronize(st);
     (void)hipEventDestroy(a);
     (void)hipEventDestroy(b);
+    return rc;
+}
+
+// ---- Monte-Carlo summaries of posterior draws: normals made on the device, the transposed sweep, fused sums ------------------
+int gpv_draws_normals_host(uint64_t seed, int64_t k0, int64_t nk, int64_t col0, int64_t ncols, double *E, int64_t lde)
+{
+    if (!E || k0 < 0 || nk < 0 || col0 < 0 || ncols < 0 || lde < nk) return GPV_ERR_BAD_ARG;
+    if (nk == 0 || ncols == 0) return GPV_OK;
+    const int64_t q0 = col0 / 2, q1 = (col0 + ncols - 1) / 2;
+    for (int64_t q = q0; q <= q1; ++q)
+        for (int64_t k = 0; k < nk; ++k) {
+            double z[2];
+            draws_normal_pair(seed, (uint64_t)(k0 + k), (uint64_t)q, z[0], z[1]);
+            for (int h = 0; h < 2; ++h) {
+                const int64_t j = 2 * q + h - col0;
+                if (j >= 0 && j < ncols) E[j * lde + k] = z[h];
+            }
+        }
+    return GPV_OK;
+}
+
+// the state every entry that sweeps with the factor asks for (gpv_plan_solve_t)
+static int draws_state(const gpv_plan *pl)
+{
+    if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
+    if (pl->post_ld > 64 || !pl->d_meanrec) return GPV_ERR_STATE;
+    return GPV_OK;
+}
+
+int gpv_plan_draws_normals(gpv_plan *pl, uint64_t seed, int64_t skip_front, int64_t col0, int64_t ncols, double *E, int64_t lde)
+{
+    constexpr int NB = kLincombNB;
+    if (!pl || !E || ncols < 0 || col0 < 0) return GPV_ERR_BAD_ARG;
+    const int64_t n = pl->Nlocs;
+    if (lde < n || skip_front < 0 || skip_front >= n) return GPV_ERR_BAD_ARG;
+    if (const int rc = draws_state(pl)) return rc;
+    if (ncols == 0) return GPV_OK;
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (!pl->d_lc_X) GPV_HIP(hipMalloc((void **)&pl->d_lc_X, sizeof(double) * (size_t)n * NB));
+    if (!pl->d_st_E) GPV_HIP(hipMalloc((void **)&pl->d_st_E, sizeof(double) * (size_t)n * NB));
+    hipStream_t st = pl->stream;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    const int64_t end = col0 + ncols;
+    for (int64_t b = col0 / NB; b * NB < end; ++b) {                       // the batches of gpv_plan_draws_summary that hold them
+        const int64_t base = b * NB;
+        const int nb = (int)std::min<int64_t>(NB, end - base);
+        if (GPV_HIP_FAILED(launch_draws_fill(pl->d_lc_X, n, seed, skip_front, base, nb, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_solvet_unpack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return fail(GPV_ERR_HIP);
+        for (int64_t j = std::max(base, col0); j < base + nb; ++j)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(E + (j - col0) * lde, pl->d_st_E + (size_t)(j - base) * n, sizeof(double) * (size_t)n,
+                                              hipMemcpyDeviceToHost, st)))
+                return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+    }
+    pl->last_stream = st;
+    return GPV_OK;
+}
+
+// the device buffers of the summaries, by their offsets in d_ds (doubles)
+struct DrawsBuf {
+    double *mu, *S1, *S2, *mean, *var, *exceed, *part;
+};
+static DrawsBuf draws_buf(const gpv_plan *pl)
+{
+    const size_t n = (size_t)pl->Nlocs;
+    double *b = pl->d_ds;
+    return DrawsBuf{b, b + n, b + 2 * n, b + 3 * n, b + 4 * n, b + 5 * n, b + (5 + kDrawsMaxThr) * n};
+}
+static int draws_alloc(gpv_plan *pl, int64_t ndraws)
+{
+    constexpr int NB = kLincombNB;
+    const size_t n = (size_t)pl->Nlocs;
+    if (!pl->d_lc_X) GPV_HIP(hipMalloc((void **)&pl->d_lc_X, sizeof(double) * n * NB));
+    if (!pl->d_ds) GPV_HIP(hipMalloc((void **)&pl->d_ds, sizeof(double) * ((5 + kDrawsMaxThr) * n + (size_t)kDrawsBlocks * 2 * NB)));
+    if (!pl->d_ds_cnt) GPV_HIP(hipMalloc((void **)&pl->d_ds_cnt, sizeof(uint32_t) * kDrawsMaxThr * n));
+    if (!pl->d_ds_mask) GPV_HIP(hipMalloc((void **)&pl->d_ds_mask, n));
+    if (pl->ds_draw_cap < ndraws) {
+        if (pl->d_ds_draw) { (void)hipFree(pl->d_ds_draw); pl->d_ds_draw = nullptr; pl->ds_draw_cap = 0; }
+        GPV_HIP(hipMalloc((void **)&pl->d_ds_draw, sizeof(double) * 2 * (size_t)ndraws));
+        pl->ds_draw_cap = ndraws;
+    }
+    return GPV_OK;
+}
+
+int gpv_plan_draws_summary(gpv_plan *pl, int64_t ndraws, uint64_t seed, int64_t skip_front, const double *mu_ord, int link, int nthr,
+                           const double *thr, const uint8_t *mask, double *mean, double *var, double *exceed, double *draw_max,
+                           double *draw_mean)
+{
+    constexpr int NB = kLincombNB;
+    if (!pl || !mean || !var || ndraws < 2 || nthr < 0 || nthr > kDrawsMaxThr || link < 0 || link > 2) return GPV_ERR_BAD_ARG;
+    if (nthr > 0 && (!thr || !exceed)) return GPV_ERR_BAD_ARG;
+    if ((draw_max == nullptr) != (draw_mean == nullptr)) return GPV_ERR_BAD_ARG;
+    const int64_t n = pl->Nlocs;
+    if (skip_front < 0 || skip_front >= n) return GPV_ERR_BAD_ARG;
+    const bool want_draw = draw_max != nullptr;
+    int64_t nsel = n - skip_front;
+    if (mask) {
+        nsel = 0;
+        for (int64_t k = skip_front; k < n; ++k) nsel += mask[k] != 0;
+        if (nsel == 0) return GPV_ERR_BAD_ARG;
+    }
+    if (const int rc = draws_state(pl)) return rc;
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (const int rc = draws_alloc(pl, ndraws)) return rc;
+    hipStream_t st = pl->stream;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    const DrawsBuf B = draws_buf(pl);
+    DrawsArgs a{};
+    a.X = pl->d_lc_X; a.mu = B.mu; a.mask = (mask && want_draw) ? pl->d_ds_mask : nullptr;
+    a.S1 = B.S1; a.S2 = B.S2; a.cnt = pl->d_ds_cnt; a.part = B.part;
+    a.n = n; a.skip_front = skip_front; a.nthr = nthr; a.want_draw = want_draw ? 1 : 0;
+    for (int t = 0; t < nthr; ++t) a.thr[t] = thr[t];
+    const size_t nbytes = sizeof(double) * (size_t)n;
+    if (mu_ord ? GPV_HIP_FAILED(hipMemcpyAsync(B.mu, mu_ord, nbytes, hipMemcpyHostToDevice, st))
+               : GPV_HIP_FAILED(hipMemsetAsync(B.mu, 0, nbytes, st)))
+        return fail(GPV_ERR_HIP);
+    if (a.mask && GPV_HIP_FAILED(hipMemcpyAsync(pl->d_ds_mask, mask, (size_t)n, hipMemcpyHostToDevice, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemsetAsync(B.S1, 0, 2 * nbytes, st))) return fail(GPV_ERR_HIP);                  // S1 and S2
+    if (nthr > 0 && GPV_HIP_FAILED(hipMemsetAsync(pl->d_ds_cnt, 0, sizeof(uint32_t) * (size_t)nthr * (size_t)n, st)))
+        return fail(GPV_ERR_HIP);
+    double *d_max = pl->d_ds_draw, *d_mean = pl->d_ds_draw + ndraws;
+    for (int64_t draw0 = 0; draw0 < ndraws; draw0 += NB) {
+        const int nb = (int)std::min<int64_t>(NB, ndraws - draw0);
+        if (GPV_HIP_FAILED(launch_draws_fill(pl->d_lc_X, n, seed, skip_front, draw0, nb, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(solvet_sweep(pl, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_draws_accum(a, link, nb, draw0, (double)nsel, want_draw ? d_max : nullptr,
+                                              want_draw ? d_mean : nullptr, st)))
+            return fail(GPV_ERR_HIP);
+    }
+    if (GPV_HIP_FAILED(launch_draws_finish(a, link, ndraws, B.mean, B.var, B.exceed, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(mean, B.mean, nbytes, hipMemcpyDeviceToHost, st)) ||
+        GPV_HIP_FAILED(hipMemcpyAsync(var, B.var, nbytes, hipMemcpyDeviceToHost, st)))
+        return fail(GPV_ERR_HIP);
+    if (nthr > 0 && GPV_HIP_FAILED(hipMemcpyAsync(exceed, B.exceed, nbytes * (size_t)nthr, hipMemcpyDeviceToHost, st)))
+        return fail(GPV_ERR_HIP);
+    if (want_draw && (GPV_HIP_FAILED(hipMemcpyAsync(draw_max, d_max, sizeof(double) * (size_t)ndraws, hipMemcpyDeviceToHost, st)) ||
+                      GPV_HIP_FAILED(hipMemcpyAsync(draw_mean, d_mean, sizeof(double) * (size_t)ndraws, hipMemcpyDeviceToHost, st))))
+        return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+    pl->last_stream = st;
+    return GPV_OK;
+}
+
+// developer aid (tools/lincomb_timing.py --summary; not part of the public header): device times of ONE full batch of
+// gpv_plan_draws_summary by events between its three parts, ms[0..3) = fill, sweep, accumulation (link 0, no thresholds, the
+// per-draw functionals over every location).  The sums it leaves in the plan's buffers belong to no call.
+extern "C" int gpv_plan_debug_draws_ms(gpv_plan *pl, uint64_t seed, double *ms)
+{
+    if (!pl || !ms) return GPV_ERR_BAD_ARG;
+    if (const int rc = draws_state(pl)) return rc;
+    if (!pl->d_lc_X || !pl->d_ds || pl->ds_draw_cap < kLincombNB) return GPV_ERR_STATE;   // (after a gpv_plan_draws_summary)
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    hipStream_t st = pl->stream;
+    const DrawsBuf B = draws_buf(pl);
+    DrawsArgs a{};
+    a.X = pl->d_lc_X; a.mu = B.mu; a.S1 = B.S1; a.S2 = B.S2; a.cnt = pl->d_ds_cnt; a.part = B.part;
+    a.n = pl->Nlocs; a.want_draw = 1;
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    int rc = GPV_OK;
+    for (auto &e : ev)
+        if (rc == GPV_OK && GPV_HIP_FAILED(hipEventCreate(&e))) rc = GPV_ERR_HIP;
+    if (rc == GPV_OK &&
+        (GPV_HIP_FAILED(hipEventRecord(ev[0], st)) || GPV_HIP_FAILED(launch_draws_fill(pl->d_lc_X, a.n, seed, 0, 0, kLincombNB, st)) ||
+         GPV_HIP_FAILED(hipEventRecord(ev[1], st)) || GPV_HIP_FAILED(solvet_sweep(pl, st)) ||
+         GPV_HIP_FAILED(hipEventRecord(ev[2], st)) ||
+         GPV_HIP_FAILED(launch_draws_accum(a, 0, kLincombNB, 0, (double)a.n, pl->d_ds_draw, pl->d_ds_draw + pl->ds_draw_cap, st)) ||
+         GPV_HIP_FAILED(hipEventRecord(ev[3], st)) || GPV_HIP_FAILED(hipStreamSynchronize(st))))
+        rc = GPV_ERR_HIP;
+    for (int i = 0; i < 3 && rc == GPV_OK; ++i) {
+        float t = 0.f;
+        if (GPV_HIP_FAILED(hipEventElapsedTime(&t, ev[i], ev[i + 1]))) rc = GPV_ERR_HIP;
+        ms[i] = (double)t;
+    }
+    (void)hipStreamSynchronize(st);
+    pl->last_stream = st;
+    for (auto &e : ev)
+        if (e) (void)hipEventDestroy(e);
     return rc;
 }
 

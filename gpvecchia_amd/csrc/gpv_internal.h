@@ -198,4 +198,27 @@ hipError_t launch_solvet_unpack(const double *X, double *E, int64_t n, int64_t l
 // the columns [first, first + count) of the mean sweep's schedule (one level), at most 64 entries per column
 hipError_t launch_solvet_level(const SolveTArgs &a, int first, int count, hipStream_t s);
 
+// ---- Monte-Carlo summaries of posterior draws (gpv_lincomb.hip): device normals, the sweep above, fused sums ------------------
+constexpr int kDrawsMaxThr = 8;                       // thresholds per call
+constexpr int kDrawsBlocks = 512;                     // workgroups of the accumulation at most (their partials: 2 * kLincombNB each)
+struct DrawsArgs {
+    const double *X;         // [n][kLincombNB]: the batch after the transposed sweep
+    const double *mu;        // [n] ordered latent mean
+    const uint8_t *mask;     // [n] locations of the per-draw functionals, or null: every k >= skip_front
+    double *S1, *S2;         // [n] running sums of d = g(mu + x) - g(mu) and of d^2
+    uint32_t *cnt;           // [nthr][n] running counts of mu + x > thr
+    double *part;            // [workgroups][2][kLincombNB]: per-draw {max, sum} of g(mu + x) over the selected locations
+    int64_t n, skip_front;
+    int nthr, want_draw;
+    double thr[kDrawsMaxThr];
+};
+// columns 0 .. nb-1 of X <- the standard normals of the draws draw0 .. (draw0 even), zeros in the rows k < skip_front and in the
+// columns nb ..
+hipError_t launch_draws_fill(double *X, int64_t n, uint64_t seed, int64_t skip_front, int64_t draw0, int nb, hipStream_t s);
+int draws_accum_blocks(int64_t n);
+// one batch into the running sums; with a.want_draw also draw_max / draw_mean[draw0 .. draw0 + nb) (nsel: selected locations)
+hipError_t launch_draws_accum(const DrawsArgs &a, int link, int nb, int64_t draw0, double nsel, double *draw_max, double *draw_mean,
+                              hipStream_t s);
+hipError_t launch_draws_finish(const DrawsArgs &a, int link, int64_t ndraws, double *mean, double *var, double *exceed, hipStream_t s);
+
 }  // namespace gpv

@@ -14,9 +14,11 @@
 // lane that fetched them.  Every partial sum has a fixed order (slice: ascending entries; slices and waves: fixed trees) =>
 // bitwise reproducible.  No floating-point atomics.
 //
-// Further down: the TRANSPOSED solve R^T X = E on the same buffer and batching (posterior draws, gpv_plan_solve_t).
+// Further down: the TRANSPOSED solve R^T X = E on the same buffer and batching (posterior draws, gpv_plan_solve_t), and the
+// Monte-Carlo summaries of such draws with normals made on the device (gpv_plan_draws_summary).
 #include "gpv_internal.h"
 #include "gpv_posterior_ext.h"
+#include "gpv_philox.hpp"
 #include <atomic>
 
 namespace gpv {
@@ -405,6 +407,181 @@ hipError_t launch_solvet_unpack(const double *X, double *E, int64_t n, int64_t l
 {
     if (n <= 0 || nb <= 0 || nb > NB || ld < n || (n + 63) / 64 > 0x7FFFFFFF) return hipErrorInvalidValue;
     hipLaunchKernelGGL(gpv_solvet_unpack_kernel, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, s, X, E, n, ld, nb);
+    return hipGetLastError();
+}
+
+// ---- Monte-Carlo summaries of posterior draws (gpv_plan_draws_summary): normals made on the device, sums kept on the device --
+// Per batch: gpv_draws_fill_kernel writes E ~ N(0, I) straight into X[Nlocs][NB] (gpv_philox.hpp: a function of seed, location
+// and draw alone), the transposed sweep above turns it into X = R^-T E in place, and gpv_draws_accum_kernel folds
+// y = mu + x into per-location sums, threshold counts and per-draw functionals.  After the last batch gpv_draws_finish_kernel
+// turns the sums into mean, variance and exceedance probabilities.  Every sum has one fixed order; no floating-point atomics.
+
+// One thread per (location, draw pair): a Box-Muller pair is two adjacent columns, stored as one 16-byte word, so a wavefront
+// writes 64 / (NB / 2) whole rows.  draw0: the draw in column 0 (even).  Rows in front of skip_front and columns >= nb: zeros.
+__global__ void __launch_bounds__(256) gpv_draws_fill_kernel(double *X, int64_t n, uint64_t seed, int64_t skip_front,
+                                                             int64_t draw0, int nb)
+{
+    constexpr int PAIRS = NB / 2;
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t k = t / PAIRS;
+    const int p = (int)(t % PAIRS);
+    if (k >= n) return;
+    double2 v = make_double2(0.0, 0.0);
+    if (k >= skip_front && 2 * p < nb) {
+        draws_normal_pair(seed, (uint64_t)k, (uint64_t)(draw0 / 2 + p), v.x, v.y);
+        if (2 * p + 1 >= nb) v.y = 0.0;
+    }
+    *reinterpret_cast<double2 *>(X + k * NB + 2 * p) = v;
+}
+hipError_t launch_draws_fill(double *X, int64_t n, uint64_t seed, int64_t skip_front, int64_t draw0, int nb, hipStream_t s)
+{
+    const int64_t blocks = (n * (NB / 2) + 255) / 256;
+    if (n <= 0 || nb <= 0 || nb > NB || skip_front < 0 || draw0 < 0 || (draw0 & 1) || blocks > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gpv_draws_fill_kernel, dim3((unsigned)blocks), dim3(256), 0, s, X, n, seed, skip_front, draw0, nb);
+    return hipGetLastError();
+}
+
+template <int LINK>
+__device__ __forceinline__ double draws_link(const double y)
+{
+    if constexpr (LINK == 1) return exp(y);
+    else if constexpr (LINK == 2) return 1.0 / (1.0 + exp(-y));
+    else return y;
+}
+
+// A workgroup walks tiles of 64 locations (tile = blockIdx.x, blockIdx.x + gridDim.x, ..).  Thread t keeps the column
+// c = t % NB and the rows t / NB, t / NB + 256 / NB, .. of the tile: the NB columns of a location sit in NB adjacent lanes, so
+// a count is one ballot and a popcount of the location's part of the mask.  d = g(y) - g(mu) goes through an LDS tile, and
+// thread r < 64 adds row r's columns in ascending order before it adds the result into S1 / S2: one fixed order over all
+// draws.  The per-draw maximum and sum over the selected locations stay in registers across the tiles, meet in LDS in
+// row-group order, and leave as this workgroup's partial {max[NB], sum[NB]} (gpv_draws_stage2_kernel adds them in block order).
+template <int LINK>
+__global__ void __launch_bounds__(256) gpv_draws_accum_kernel(const DrawsArgs A, const int nb)
+{
+    constexpr int RPP = 256 / NB, PASSES = 64 / RPP;         // rows per pass, passes per tile
+    __shared__ double dt[64][NB + 1];
+    __shared__ double mu_s[64], gmu_s[64];
+    __shared__ uint32_t ct[kDrawsMaxThr][64];
+    __shared__ double pmax[RPP][NB], psum[RPP][NB];
+    const int tid = threadIdx.x, c = tid & (NB - 1), g = tid / NB, lane = tid & 63;
+    const bool colive = c < nb;
+    const int64_t ntiles = (A.n + 63) / 64;
+    double dmax = -INFINITY, dsum = 0.0;
+    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+        const int64_t k0 = tile * 64;
+        if (tid < 64) {
+            const int64_t k = k0 + tid;
+            const double m = (k < A.n) ? A.mu[k] : 0.0;
+            mu_s[tid] = m;
+            gmu_s[tid] = draws_link<LINK>(m);
+        }
+        __syncthreads();
+        double x[PASSES];
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            const int64_t k = k0 + g + i * RPP;
+            x[i] = (k < A.n) ? A.X[k * NB + c] : 0.0;
+        }
+#pragma unroll
+        for (int i = 0; i < PASSES; ++i) {
+            const int r = g + i * RPP;
+            const int64_t k = k0 + r;
+            const bool live = colive && k < A.n && k >= A.skip_front;
+            const double y = mu_s[r] + x[i];
+            const double gy = draws_link<LINK>(y);
+            dt[r][c] = live ? gy - gmu_s[r] : 0.0;
+            for (int th = 0; th < A.nthr; ++th) {
+                const unsigned long long m = __ballot(live && y > A.thr[th]);
+                if (c == 0) ct[th][r] = (uint32_t)__popcll((m >> (lane & ~(NB - 1))) & ((1ull << NB) - 1ull));
+            }
+            if (A.want_draw && live && (A.mask == nullptr || A.mask[k] != 0)) {
+                dmax = fmax(dmax, gy);
+                dsum += gy;
+            }
+        }
+        __syncthreads();
+        if (tid < 64) {
+            const int64_t k = k0 + tid;
+            if (k < A.n && k >= A.skip_front) {
+                double s1 = 0.0, s2 = 0.0;
+#pragma unroll
+                for (int cc = 0; cc < NB; ++cc) {
+                    const double d = dt[tid][cc];
+                    s1 += d;
+                    s2 += d * d;
+                }
+                A.S1[k] += s1;
+                A.S2[k] += s2;
+                for (int th = 0; th < A.nthr; ++th) A.cnt[(int64_t)th * A.n + k] += ct[th][tid];
+            }
+        }
+        __syncthreads();
+    }
+    if (!A.want_draw) return;
+    pmax[g][c] = dmax;
+    psum[g][c] = dsum;
+    __syncthreads();
+    if (tid < NB) {
+        double mx = pmax[0][tid], sm = psum[0][tid];
+#pragma unroll
+        for (int gg = 1; gg < RPP; ++gg) { mx = fmax(mx, pmax[gg][tid]); sm += psum[gg][tid]; }
+        A.part[((size_t)blockIdx.x * 2) * NB + tid] = mx;
+        A.part[((size_t)blockIdx.x * 2 + 1) * NB + tid] = sm;
+    }
+}
+// the workgroups' partials in block order: draw_max / draw_mean of the draws draw0 .. draw0 + nb - 1
+__global__ void __launch_bounds__(NB) gpv_draws_stage2_kernel(const double *part, int nblocks, int nb, double nsel, double *draw_max,
+                                                              double *draw_mean, int64_t draw0)
+{
+    const int c = threadIdx.x;
+    if (c >= nb) return;
+    double mx = -INFINITY, sm = 0.0;
+    for (int b = 0; b < nblocks; ++b) {
+        mx = fmax(mx, part[((size_t)b * 2) * NB + c]);
+        sm += part[((size_t)b * 2 + 1) * NB + c];
+    }
+    draw_max[draw0 + c] = mx;
+    draw_mean[draw0 + c] = sm / nsel;
+}
+int draws_accum_blocks(int64_t n)
+{
+    const int64_t ntiles = (n + 63) / 64;
+    return (int)(ntiles < kDrawsBlocks ? ntiles : kDrawsBlocks);
+}
+hipError_t launch_draws_accum(const DrawsArgs &a, int link, int nb, int64_t draw0, double nsel, double *draw_max, double *draw_mean,
+                              hipStream_t s)
+{
+    if (a.n <= 0 || nb <= 0 || nb > NB || a.nthr < 0 || a.nthr > kDrawsMaxThr || link < 0 || link > 2) return hipErrorInvalidValue;
+    if (a.want_draw && (!draw_max || !draw_mean || !(nsel > 0.0))) return hipErrorInvalidValue;
+    const int blocks = draws_accum_blocks(a.n);
+    if (link == 0) hipLaunchKernelGGL(gpv_draws_accum_kernel<0>, dim3(blocks), dim3(256), 0, s, a, nb);
+    else if (link == 1) hipLaunchKernelGGL(gpv_draws_accum_kernel<1>, dim3(blocks), dim3(256), 0, s, a, nb);
+    else hipLaunchKernelGGL(gpv_draws_accum_kernel<2>, dim3(blocks), dim3(256), 0, s, a, nb);
+    if (a.want_draw)
+        hipLaunchKernelGGL(gpv_draws_stage2_kernel, dim3(1), dim3(NB), 0, s, (const double *)a.part, blocks, nb, nsel, draw_max,
+                           draw_mean, draw0);
+    return hipGetLastError();
+}
+
+// mean = g(mu) + S1 / N, var = (S2 - S1^2 / N) / (N - 1) clamped at 0, exceed = cnt / N; zeros in front of skip_front
+__global__ void __launch_bounds__(256) gpv_draws_finish_kernel(const DrawsArgs A, const int link, const double N, double *mean,
+                                                               double *var, double *exceed)
+{
+    const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (k >= A.n) return;
+    const bool live = k >= A.skip_front;
+    const double m = A.mu[k], s1 = A.S1[k], s2 = A.S2[k];
+    const double gm = link == 1 ? draws_link<1>(m) : link == 2 ? draws_link<2>(m) : m;
+    const double v = (s2 - s1 * s1 / N) / (N - 1.0);
+    mean[k] = live ? gm + s1 / N : 0.0;
+    var[k] = (live && v > 0.0) ? v : 0.0;
+    for (int th = 0; th < A.nthr; ++th) exceed[(int64_t)th * A.n + k] = live ? (double)A.cnt[(int64_t)th * A.n + k] / N : 0.0;
+}
+hipError_t launch_draws_finish(const DrawsArgs &a, int link, int64_t ndraws, double *mean, double *var, double *exceed, hipStream_t s)
+{
+    if (a.n <= 0 || ndraws < 2 || (a.n + 255) / 256 > 0x7FFFFFFF) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gpv_draws_finish_kernel, dim3((unsigned)((a.n + 255) / 256)), dim3(256), 0, s, a, link, (double)ndraws, mean,
+                       var, exceed);
     return hipGetLastError();
 }
 

@@ -185,7 +185,9 @@ def vecchia_laplace_prediction(vl_posterior, vecchia_approx, covparms, pred_mean
     result, on a vecchia.approx that may carry prediction locations; the latent means and their images under the family's
     link function.  return_values / var_exact pass through to vecchia_prediction (the default 'mean': means only).  With
     'meanvar' / 'all' also the data-scale 5% / 95% quantiles of :541-548; with 'meanmat' / 'all' the `factor` handle, so that
-    vecchia_posterior_sample draws the latent field of a Vecchia-Laplace posterior (data_link of a draw: the data scale)."""
+    vecchia_posterior_sample draws the latent field of a Vecchia-Laplace posterior (data_link of a draw: the data scale), and
+    vecchia_posterior_summary(preds, nsim, link='exp' | 'logistic') gives Monte-Carlo moments on the data scale for the
+    families with those links (Poisson / gamma rates: 'exp'; logistic probabilities: 'logistic')."""
     z_pseudo = np.asarray(vl_posterior["t"], dtype=np.float64) - vl_posterior["prior_mean"]          # :526
     nug_pseudo = np.asarray(vl_posterior["D"], dtype=np.float64)                                    # :527
     if nug_pseudo.size < z_pseudo.size:                                   # missing observations: D holds the observed entries

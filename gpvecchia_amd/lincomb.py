@@ -189,3 +189,136 @@ def vecchia_posterior_sample(preds, nsim=1, seed=None, eps=None):
             X = np.hstack([X, np.zeros((nsim, nzero))])
         x_obs, x_pred = _split_rows(X, U_obj["ord"], U_obj["obs"])
     return dict(y_obs=np.asarray(preds["mu_obs"])[None, :] + x_obs, y_pred=np.asarray(preds["mu_pred"])[None, :] + x_pred, eps=eps)
+
+
+_LINKS = {None: 0, "identity": 0, "exp": 1, "logistic": 2}
+
+
+def _link_fun(code):
+    if code == 1:
+        return np.exp
+    if code == 2:
+        return lambda y: 1.0 / (1.0 + np.exp(-y))
+    return lambda y: y
+
+
+def _join_ord(a_obs, a_pred, ord_, obs):
+    """The inverse of api.split_mean: values at the observed and the prediction locations in the caller's order -> one vector
+    in the ordered latent layout."""
+    orig_order = np.argsort(np.asarray(ord_), kind="stable")
+    obs_orig = np.asarray(obs, dtype=bool)[orig_order]
+    a_obs, a_pred = np.asarray(a_obs), np.asarray(a_pred)
+    if a_obs.shape != (int(obs_orig.sum()),) or a_pred.shape != (int((~obs_orig).sum()),):
+        raise ValueError("one entry per observed location and one per prediction location is needed")
+    caller = np.empty(obs_orig.size, dtype=np.result_type(a_obs, a_pred))
+    caller[obs_orig] = a_obs
+    caller[~obs_orig] = a_pred
+    out = np.empty_like(caller)
+    out[orig_order] = caller
+    return out
+
+
+def draws_normals_host(seed, k0, nk, col0, ncols):
+    """gpv_draws_normals_host: the generator's standard normals of the ordered locations [k0, k0 + nk) and the draws
+    [col0, col0 + ncols), computed on the host: (ncols, nk).  No device is needed.  Exported from the package: a caller who wants
+    the draws behind a vecchia_posterior_summary passes these rows (k0 = the plan's rows in front, 0 or n for 'zy') as eps to
+    vecchia_posterior_sample."""
+    from . import _lib as L
+    E = np.empty((int(ncols), int(nk)))
+    L.check(L.lib().gpv_draws_normals_host(int(seed), int(k0), int(nk), int(col0), int(ncols), L.dptr(E), int(nk)),
+            "gpv_draws_normals_host")
+    return E
+
+
+def _host_summary(lu, k0, nzero, mu_ord, nsim, seed, code, thr, mask):
+    """What gpv_plan_draws_summary computes, on the host factor, with the same generator: chunks of draws through
+    _host_solve_t, the same sums.  mu_ord / mask cover the nlat latent variables and the nzero zero-nugget observations behind
+    them (those are their data in every draw)."""
+    g = _link_fun(code)
+    nlat = mu_ord.size - nzero
+    gmu = g(mu_ord)
+    S1, S2 = np.zeros(mu_ord.size), np.zeros(mu_ord.size)
+    cnt = np.zeros((thr.size, mu_ord.size))
+    draw_max, draw_mean = np.empty(nsim), np.empty(nsim)
+    for b in range(0, nsim, _HOST_CHUNK):
+        nb = min(_HOST_CHUNK, nsim - b)
+        E = draws_normals_host(seed, k0, nlat, b, nb)
+        X = _host_solve_t(lu, E[:, ::-1].T)[::-1].T
+        if nzero:
+            X = np.hstack([X, np.zeros((nb, nzero))])
+        Y = mu_ord[None, :] + X
+        GY = g(Y)
+        D = GY - gmu[None, :]
+        S1 += D.sum(axis=0)
+        S2 += (D * D).sum(axis=0)
+        for t in range(thr.size):
+            cnt[t] += (Y > thr[t]).sum(axis=0)
+        draw_max[b:b + nb] = GY[:, mask].max(axis=1)
+        draw_mean[b:b + nb] = GY[:, mask].mean(axis=1)
+    N = float(nsim)
+    return dict(mean=gmu + S1 / N, var=np.maximum((S2 - S1 * S1 / N) / (N - 1.0), 0.0), exceed=cnt / N,
+                draw_max=draw_max, draw_mean=draw_mean)
+
+
+def vecchia_posterior_summary(preds, nsim, seed=0, thresholds=None, link=None, mask_obs=None, mask_pred=None):
+    """Monte-Carlo summaries of nsim draws from the Vecchia posterior (the draws of vecchia_posterior_sample, never brought to
+    the host): pointwise mean and variance, exceedance probabilities, and for every draw the maximum and the mean over a region.
+    preds: as for vecchia_posterior_sample.  The standard normals come from the library's counter-based generator (Philox4x32-10,
+    a function of seed, ordered location and draw alone), on the device routes made on the device (gpv_plan_draws_summary: 32
+    draws per sweep, sums folded on the device); the host route computes the same quantities from the same generator.
+
+    link: None / 'identity', 'exp' or 'logistic': mean, var, draw_max and draw_mean are those of link(y), e.g. the data scale of
+    a vecchia_laplace_prediction result.  thresholds (at most 8) are on the LATENT scale: exceed[t] = share of draws with
+    y > thresholds[t].  mask_obs / mask_pred: booleans per observed / prediction location (caller's order) selecting the region
+    of draw_max / draw_mean; both None: every location; one None: no location of that group.
+
+    Returns dict(mean_obs, mean_pred, var_obs, var_pred, exceed_obs (len(thresholds) x n), exceed_pred, draw_max, draw_mean
+    (nsim each)).  Zero-nugget observations (host route) have variance 0 and their data as mean."""
+    fac = preds.get("factor") if isinstance(preds, dict) else None
+    if fac is None:
+        raise ValueError("vecchia_posterior_summary needs the result of vecchia_prediction(..., return_values='meanmat' or 'all')")
+    if link not in _LINKS:
+        raise ValueError("link must be None, 'identity', 'exp' or 'logistic'")
+    code, nsim = _LINKS[link], int(nsim)
+    if nsim < 2:
+        raise ValueError("nsim must be at least 2")
+    thr = np.asarray([] if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+    if thr.size > 8:
+        raise ValueError("at most 8 thresholds")
+    if fac["kind"] == "device":
+        plan = _check_stamp(fac)
+        ord_, obs, off = fac["ord"], fac["obs"], fac["offset"]
+        if off + int(ord_.size) != plan.Nlocs:
+            raise ValueError("preds does not match the plan of this prediction")
+    else:
+        U_obj, lu = fac["U_obj"], fac["lu"]
+        ord_, obs = np.asarray(U_obj["ord"]), np.asarray(U_obj["obs"], dtype=bool)
+        nzero = len(U_obj["zero_nugg"]["inds_z"]) if U_obj["zero_nugg"] else 0
+        off = int(np.sum(obs)) if U_obj.get("cond_yz") == "zy" else 0      # the device layout's dummy rows: the same normals
+    mu_ord = _join_ord(np.asarray(preds["mu_obs"], dtype=np.float64), np.asarray(preds["mu_pred"], dtype=np.float64), ord_, obs)
+    n_obs = int(np.sum(obs))
+    if mask_obs is None and mask_pred is None:
+        mask = np.ones(mu_ord.size, dtype=bool)
+    else:
+        mask = _join_ord(np.zeros(n_obs, dtype=bool) if mask_obs is None else np.asarray(mask_obs, dtype=bool),
+                         np.zeros(mu_ord.size - n_obs, dtype=bool) if mask_pred is None else np.asarray(mask_pred, dtype=bool),
+                         ord_, obs)
+        if not mask.any():
+            raise ValueError("the masks select no location")
+    if fac["kind"] == "device":
+        pad = lambda a, fill: np.concatenate([np.full(off, fill, dtype=a.dtype), a]) if off else a
+        res = plan.draws_summary(nsim, seed=seed, skip_front=off, mu_ord=pad(mu_ord, 0.0), link=code, thresholds=thr,
+                                 mask=None if (mask_obs is None and mask_pred is None) else pad(mask, False))
+        res = dict(mean=res["mean"][off:], var=res["var"][off:], exceed=res["exceed"][:, off:], draw_max=res["draw_max"],
+                   draw_mean=res["draw_mean"])
+    else:
+        res = _host_summary(lu, off, nzero, mu_ord, nsim, seed, code, thr, mask)
+    from .api import split_mean
+    so = dict(ord=ord_, obs=obs)
+    out = dict(draw_max=res["draw_max"], draw_mean=res["draw_mean"])
+    out["mean_obs"], out["mean_pred"] = split_mean(res["mean"], so)
+    out["var_obs"], out["var_pred"] = split_mean(res["var"], so)
+    ex = [split_mean(res["exceed"][t], so) for t in range(thr.size)]
+    out["exceed_obs"] = np.array([e[0] for e in ex]).reshape(thr.size, n_obs)
+    out["exceed_pred"] = np.array([e[1] for e in ex]).reshape(thr.size, mu_ord.size - n_obs)
+    return out

@@ -233,6 +233,34 @@ int gpv_plan_lincomb(gpv_plan *plan, int64_t nrows, const int64_t *hptr, const i
  * GPV_ERR_BAD_ARG: a null pointer, ncols < 0, lde or ldx < Nlocs; GPV_ERR_STATE: as for gpv_plan_lincomb; ncols == 0 is GPV_OK.
  * Arguments are validated before the device is touched. */
 int gpv_plan_solve_t(gpv_plan *plan, int64_t ncols, const double *E, int64_t lde, double *X, int64_t ldx);
+/* Monte-Carlo summaries of posterior draws, reduced on the device.  The standard normal of (ordered location k, draw j) is a
+ * function of (seed, k, j) alone: Philox4x32-10 with key (seed low, seed high) and counter (k low, k high, q low, q high),
+ * q = j / 2; its four words give two uniforms with 52 random bits in (0, 1), and Box-Muller in FP64 gives draw 2q (cosine) and
+ * draw 2q + 1 (sine).  It does not depend on Nlocs, on the batch or on how many draws are asked for.
+ *
+ * gpv_draws_normals_host: host only, no device needed: the normals of the locations [k0, k0 + nk) and the draws
+ * [col0, col0 + ncols); column j at E + j * lde (lde >= nk).  The device's values differ by a few ulp of log / sqrt / sincos.
+ * gpv_plan_draws_normals: what the device writes for the draws [col0, col0 + ncols) of a summary with this seed and skip_front,
+ * read back: column j at E + j * lde in the plan's ORDERED latent layout (lde >= Nlocs), zeros in the rows k < skip_front.
+ *
+ * gpv_plan_draws_summary: ndraws draws y = mu_ord + R^-T e (the draws of gpv_plan_solve_t with those normals),
+ * gpv_lincomb_batch() per sweep, folded after every sweep; only the results leave the device.  With g the link (0: identity,
+ * 1: exp, 2: logistic 1 / (1 + exp(-y))) and d = g(y) - g(mu):
+ *   mean[k] = g(mu_k) + sum d / ndraws,  var[k] = (sum d^2 - (sum d)^2 / ndraws) / (ndraws - 1), clamped at 0;
+ *   exceed[t * Nlocs + k] = #{draws: y_k > thr[t]} / ndraws, thresholds on the LATENT scale, nthr <= 8;
+ *   draw_max[j], draw_mean[j]: maximum and mean of g(y) over the locations k >= skip_front with mask[k] != 0 (mask NULL: all
+ *   of them) in draw j; pass both or neither.
+ * skip_front: the rows in front that carry no latent variable (the n dummy rows of cond.yz = 'zy'): their normals are zero and
+ * their results are zeros.  mu_ord NULL stands for zeros; exceed may be NULL when nthr == 0.
+ * State, stream handling and blocking as gpv_plan_solve_t; the factor is only read and gpv_plan_factor_stamp does not change.
+ * Results are bitwise reproducible from call to call.  GPV_ERR_BAD_ARG: ndraws < 2, nthr outside [0, 8], link outside {0, 1, 2},
+ * skip_front outside [0, Nlocs), a mask that selects nothing, a required pointer NULL, one of draw_max / draw_mean NULL.
+ * Arguments are validated before the device is touched. */
+int gpv_draws_normals_host(uint64_t seed, int64_t k0, int64_t nk, int64_t col0, int64_t ncols, double *E, int64_t lde);
+int gpv_plan_draws_normals(gpv_plan *plan, uint64_t seed, int64_t skip_front, int64_t col0, int64_t ncols, double *E, int64_t lde);
+int gpv_plan_draws_summary(gpv_plan *plan, int64_t ndraws, uint64_t seed, int64_t skip_front, const double *mu_ord, int link,
+                           int nthr, const double *thr, const uint8_t *mask, double *mean, double *var, double *exceed,
+                           double *draw_max, double *draw_mean);
 int gpv_lincomb_batch(void);   /* right-hand sides per sweep (32) */
 /* stamp: 0 when the plan holds no factor, else a number that changes with every evaluation that writes one (callers that keep
  * a result of gpv_plan_lincomb's inputs around can tell whether the factor is still the one they mean) */

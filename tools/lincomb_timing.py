@@ -3,13 +3,18 @@
       right-hand side), and
   (b) scipy's spsolve_triangular for the same NB right-hand sides on the oracle's V on the host (--host; n <= 1e5).
 
-    python tools/lincomb_timing.py [--n 1000000] [--m 30] [--batches 8] [--host] [--pred]
+    python tools/lincomb_timing.py [--n 1000000] [--m 30] [--batches 8] [--host] [--pred] [--summary]
 
 The transposed solve (gpv_plan_solve_t, posterior draws) is timed twice: the sweep alone on the device (a pair of events around
 the captured graph, gpv_plan_debug_solve_t_ms), which is what compares with one mean sweep and with one lincomb batch, and the
 whole call per batch, which at n = 1e6 is mostly the 2 x 256 MB of the batch crossing PCIe from and to pageable memory.  These
 legs are measured in --rounds alternating rounds (mean evaluation, denominator evaluation, lincomb, transposed sweep, ...) and
 reported as medians over the rounds.
+
+--summary: the Monte-Carlo summaries (gpv_plan_draws_summary: normals made on the device, the same sweep, sums folded on the
+device) in alternating rounds of their own with the parent route they replace: (i) the device time per batch of fill, sweep
+and accumulation between events (gpv_plan_debug_draws_ms), (ii) the wall time per batch of the call (96 draws minus 32 draws,
+halved), beside the sweep alone and gpv_plan_solve_t per batch from the same rounds.
 
 Times are wall clock around the blocking calls after a clock warm-up of evaluations (as bench.py does); the lincomb call is
 timed with 1 and with 1 + batches batches and the difference divided, so that the upload of H and the call's fixed cost drop out.
@@ -47,6 +52,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--host", action="store_true")
     ap.add_argument("--pred", action="store_true")
+    ap.add_argument("--summary", action="store_true")
     a = ap.parse_args()
     NB = L.lib().gpv_lincomb_batch()
     n, m = a.n, a.m
@@ -111,6 +117,32 @@ def main():
                solve_t_sweep_ms_per_solve=m_["st_sweep"] / NB, solve_t_sweep_over_single_sweep=m_["st_sweep"] / max(r_sweep, 1e-9),
                solve_t_sweep_over_lincomb_batch=m_["st_sweep"] / max(r_lc, 1e-9),
                solve_t_call_ms_per_batch=(m_["stk"] - m_["st1"]) / 2, solve_t_first_batch_call_ms=m_["st1"])
+    if a.summary:
+        lib.gpv_plan_debug_draws_ms.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_double)]
+        mu = plan.posterior_mean()
+        kw = dict(seed=1, mu_ord=mu, link=0, thresholds=[-0.5, 0.0, 0.5])
+        plan.draws_summary(3 * NB, **kw)                                  # first use: buffers
+        three = np.zeros(3)
+
+        def parts_ms():
+            L.check(lib.gpv_plan_debug_draws_ms(plan._h, 1, L.dptr(three)), "gpv_plan_debug_draws_ms")
+            return three.copy()
+        sl = dict(st_sweep=[], st1=[], stk=[], parts=[], ds1=[], dsk=[])
+        for _ in range(a.rounds):
+            sl["st_sweep"].append(sweep_ms())
+            sl["st1"].append(med(lambda: plan.solve_t(E1), 1))
+            sl["stk"].append(med(lambda: plan.solve_t(Ek), 1))
+            sl["parts"].append(parts_ms())
+            sl["ds1"].append(med(lambda: plan.draws_summary(NB, **kw), 1))
+            sl["dsk"].append(med(lambda: plan.draws_summary(3 * NB, **kw), 1))
+        parts = np.median(np.array(sl["parts"]), axis=0)
+        s_ = {k: float(np.median(v)) for k, v in sl.items() if k != "parts"}
+        out.update(summary_rounds=a.rounds, summary_fill_ms_per_batch=float(parts[0]), summary_sweep_ms_per_batch=float(parts[1]),
+                   summary_accum_ms_per_batch=float(parts[2]), summary_device_ms_per_batch=float(parts.sum()),
+                   summary_call_ms_per_batch=(s_["dsk"] - s_["ds1"]) / 2, summary_first_batch_call_ms=s_["ds1"],
+                   summary_rounds_solve_t_sweep_ms_per_batch=s_["st_sweep"],
+                   summary_rounds_solve_t_call_ms_per_batch=(s_["stk"] - s_["st1"]) / 2,
+                   summary_call_below_solve_t_call=bool((s_["dsk"] - s_["ds1"]) < (s_["stk"] - s_["st1"])))
     if a.host:
         import scipy.sparse.linalg as spla
         from oracle import r_side as R

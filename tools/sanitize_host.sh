@@ -56,6 +56,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_solve_t.log; then
     echo "== $tag: solve_t_driver FAILED (rc $rc)"; return 1
   fi
+  # ... and under the driver of the draws summaries (tests/sanitize/draws_summary_driver.cpp)
+  mkdir -p $B/draws_summary
+  $HIPCC $CF -c $ROOT/tests/sanitize/draws_summary_driver.cpp -o $B/draws_summary/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/draws_summary/driver.o -o $B/draws_summary_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./draws_summary_driver ) 2>&1 | tee $B/run_draws_summary.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_draws_summary.log; then
+    echo "== $tag: draws_summary_driver FAILED (rc $rc)"; return 1
+  fi
   echo "== $tag: clean"
 }
 
