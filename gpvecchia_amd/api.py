@@ -180,6 +180,22 @@ class Plan:
         L.check(L.lib().gpv_plan_factor_stamp(self._h, C.byref(st)), "gpv_plan_factor_stamp")
         return int(st.value)
 
+    def loglik_grad(self, covmodel, covparms, nugget, row_terms=False):
+        """Value and analytic gradient of the cond.yz='z' log-likelihood of the plan's data (gpv_plan_loglik_grad): returns
+        (loglik, grad, n_failed) and, with row_terms, a fourth array (Nlocs, len(covparms) + 2) of {l_k, its derivatives} per
+        ordered row.  grad = d/d covparms, then d/d nugget; the smoothness entry of 'matern' is NaN (not differentiated).
+        The plan's last evaluation (sums, Lentries, factor stamp) is left as it was."""
+        cp = np.ascontiguousarray(covparms, dtype=np.float64)
+        ll, nf = C.c_double(0.0), C.c_int64(0)
+        grad = np.zeros(cp.size + 1)
+        rt = np.zeros((self.Nlocs, cp.size + 2)) if row_terms else None
+        st = L.lib().gpv_plan_loglik_grad(self._h, covmodel.encode() if isinstance(covmodel, str) else bytes(covmodel),
+                                          L.dptr(cp), int(cp.size), float(nugget), C.byref(ll), L.dptr(grad), C.byref(nf),
+                                          L.dptr(rt) if row_terms else None)
+        L.check(st, "gpv_plan_loglik_grad")
+        out = (float(ll.value), grad, int(nf.value))
+        return out + (rt,) if row_terms else out
+
     def lincomb(self, H_ord, cov_mat=False):
         """Var(H y | z) (or, with cov_mat, Cov) for the rows of H_ord, a scipy.sparse or dense matrix with Nlocs columns in
         the plan's ORDERED latent index, from the factor of the latest evaluation with GPV_WANT_DENOM / GPV_WANT_MEAN /
@@ -1006,3 +1022,28 @@ def vecchia_likelihood(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
             return loglik_from_sums(plan.sums(), n)
     U_obj = createU(va, covparms, nug, covmodel, device=device)
     return vecchia_likelihood_U(z, U_obj)
+
+
+def vecchia_likelihood_grad(z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+    """(loglik, grad) of the cond.yz='z' Vecchia log-likelihood, both on the GPU in one pass over the conditioning sets
+    (Plan.loglik_grad): grad = d loglik / d covparms, then d / d nugget; for 'matern' the smoothness (0.5, 1.5 or 2.5) is not
+    differentiated and its entry is NaN.  Only what has an exact, cheap gradient is accepted: cond.yz = 'z' (or m = 0), one
+    constant nugget > 0, complete data, no prediction locations, a named covariance family."""
+    va = vecchia_approx
+    if va["cond_yz"] not in ("z", "false"):
+        raise ValueError("vecchia_likelihood_grad needs cond_yz='z' (the gradient of the other modes goes through the "
+                         "posterior factor)")
+    if not isinstance(covmodel, str):
+        raise ValueError("vecchia_likelihood_grad needs a named covariance family ('matern' or 'esqe'), not a function or matrix")
+    nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
+    if nug.size != 1:
+        raise ValueError("vecchia_likelihood_grad takes one constant nugget")
+    z = np.asarray(z, dtype=np.float64)
+    if np.isnan(z.sum()):
+        raise ValueError("vecchia_likelihood_grad needs complete data (no NaN)")
+    if int(np.sum(va["obs"])) != va["locsord"].shape[0]:
+        raise ValueError("vecchia_likelihood_grad does not take plans with prediction locations")
+    plan = _plan_for(va, device)
+    plan.set_user_data(z, va["ord_z"])
+    ll, grad, _ = plan.loglik_grad(covmodel, covparms, float(nug[0]))
+    return ll, grad

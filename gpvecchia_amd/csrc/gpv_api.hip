@@ -8,6 +8,7 @@
 #include "gpv_generic.h"
 #include "gpv_posterior_ext.h"
 #include "gpv_philox.hpp"
+#include "gpv_grad.h"
 
 #include <dlfcn.h>
 
@@ -399,6 +400,10 @@ struct gpv_plan {
     uint8_t *d_cond = nullptr;
     std::vector<int32_t> h_newpos;  // host copy of d_newpos (shared with the sibling plans of a gpv_mplan)
     bool generic = false;          // row length > 64 or dimension > 8: workgroup-per-set kernel (gpv_sets_generic.hip)
+    bool latent_nb = false;        // some NEIGHBOUR (not a row's own point) is conditioned on as latent y: not a cond.yz='z' plan
+    // gpv_plan_loglik_grad (gpv_grad.hip), allocated on first use: per-workgroup partials, their totals, per-row terms
+    double *d_gr_part = nullptr, *d_gr_tot = nullptr, *d_gr_rows = nullptr;
+    int gr_grid = 0;
     // Vecchia-Laplace state (gpv_plan_vl_begin): data z, prior mean, two latent-mean buffers (current / next), flags + max
     double *d_vl_z = nullptr, *d_vl_pm = nullptr, *d_vl_y[2] = {nullptr, nullptr}, *d_vl_out = nullptr;
     double *d_vl_y0 = nullptr;                       // the start value, kept so that a restart needs no upload
@@ -470,7 +475,7 @@ int gpv_plan_destroy(gpv_plan *pl)
                     pl->d_vl_z, pl->d_vl_pm, pl->d_vl_y[0], pl->d_vl_y[1], pl->d_vl_out, pl->d_vl_flags, pl->d_ticket,
                     pl->d_vl_y0, pl->d_vl_part, pl->d_user_ord, pl->d_meanrec, pl->d_obs, pl->d_topinfo, pl->d_toprows, pl->d_rr0, pl->d_nug_masked,
                     pl->d_lc_rec, pl->d_lc_X, pl->d_lc_part, pl->d_lc_vars, pl->d_lc_gpart, pl->d_lc_gram, pl->d_st_E,
-                    pl->d_ds, pl->d_ds_draw, pl->d_ds_cnt, pl->d_ds_mask};
+                    pl->d_ds, pl->d_ds_draw, pl->d_ds_cnt, pl->d_ds_mask, pl->d_gr_part, pl->d_gr_tot, pl->d_gr_rows};
     for (auto &g : pl->pgraph)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (pl->lc_graph) (void)hipGraphExecDestroy(pl->lc_graph);
@@ -609,6 +614,8 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
     std::vector<uint8_t> cd((size_t)(rows > 0 ? rows : 1) * P, 1);
     std::vector<int> err_flag(1, GPV_OK);
     int *errp = err_flag.data();
+    std::atomic<int> latent_nb{0};                     // a neighbour conditioned on as latent y (gpv_plan_loglik_grad refuses)
+    std::atomic<int> *latp = &latent_nb;
     // stored set s <- conditioning set (row) rowsrc[s]: rows sorted by the Morton position of the point they belong
     // to (the last entry of the row, R/U_sparsity.R:32), so that sets processed together share neighbours in L2
     std::vector<int32_t> rowsrc((size_t)(rows > 0 ? rows : 1), 0);
@@ -644,6 +651,7 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
                     if (c == INT_MIN) { *errp = GPV_ERR_BAD_ARG; c = 1; }
                 }
                 cr[P - n0 + t] = (uint8_t)(c != 0);
+                if (c != 0 && t < n0 - 1) latp->store(1, std::memory_order_relaxed);
             }
         }
     });
@@ -652,6 +660,7 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
         delete pl;
         return e;
     }
+    pl->latent_nb = latent_nb.load() != 0;
     tm.lap("plan: index re-layout");
     std::vector<double> lr((size_t)Nlocs * pl->locs_ld, 0.0);
     if (locs) {
@@ -1919,6 +1928,71 @@ int gpv_plan_factor_stamp(gpv_plan *pl, int64_t *stamp)
 {
     if (!pl || !stamp) return GPV_ERR_BAD_ARG;
     *stamp = (pl->have_post && pl->have_factor) ? pl->factor_stamp : 0;
+    return GPV_OK;
+}
+
+// Value and gradient of the cond.yz='z' log-likelihood (gpv_grad.hip).  Reads the plan's records and index arrays only and
+// writes buffers of its own, so the sums, the U entries and the factor of the plan's last evaluation stay what they were.
+int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                         double *grad, int64_t *n_failed, double *row_terms)
+{
+    if (!pl || !covType || !covparms || !loglik || !grad || !n_failed) return GPV_ERR_BAD_ARG;
+    const bool matern = std::strcmp(covType, "matern") == 0;
+    if (!matern && std::strcmp(covType, "esqe") != 0) return GPV_ERR_COVTYPE;
+    if (ncovparms != (matern ? 3 : 4)) return GPV_ERR_BAD_ARG;
+    if (!(nugget > 0.0) || !std::isfinite(nugget)) return GPV_ERR_BAD_ARG;
+    CovSetup cs;
+    const int rc = cov_setup(covType, covparms, ncovparms, cs);
+    if (rc != GPV_OK) return rc;
+    if (cs.cov == COV_MATERN_GEN) return GPV_ERR_UNSUPPORTED_NU;    // the reference's Matern is discontinuous in nu at the closed forms
+    if (pl->p > kGradMaxP) return GPV_ERR_UNSUPPORTED_M;
+    if (!pl->has_z || pl->comm || pl->rows != pl->Nlocs || pl->d_obs || pl->latent_nb) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    const int grid = grad_grid(pl->rows, pl->cus);
+    if (pl->d_gr_part && pl->gr_grid < grid) { GPV_HIP(hipFree(pl->d_gr_part)); pl->d_gr_part = nullptr; }
+    if (!pl->d_gr_part) {
+        GPV_HIP(hipMalloc((void **)&pl->d_gr_part, sizeof(double) * kGradNV * (size_t)grid));
+        pl->gr_grid = grid;
+    }
+    if (!pl->d_gr_tot) GPV_HIP(hipMalloc((void **)&pl->d_gr_tot, sizeof(double) * kGradNV));
+    if (row_terms && !pl->d_gr_rows) GPV_HIP(hipMalloc((void **)&pl->d_gr_rows, sizeof(double) * kGradRowLd * (size_t)pl->rows));
+    GradArgs a;
+    a.rec = pl->d_locs; a.locs = pl->d_locs; a.z = pl->d_z;
+    a.nn = pl->d_nn; a.rowid = pl->d_rowid;
+    a.row_terms = row_terms ? pl->d_gr_rows : nullptr;
+    a.block_part = pl->d_gr_part; a.totals = pl->d_gr_tot;
+    a.rows = pl->rows; a.P = pl->P; a.dim = pl->dim; a.locs_ld = pl->locs_ld; a.cov = cs.cov;
+    a.sA = cs.sA; a.cA = cs.cA; a.irA = 1.0 / covparms[1];
+    a.sB = cs.sB; a.cB = cs.cB; a.irB = matern ? 0.0 : 1.0 / covparms[3];
+    a.nug = nugget;
+    hipStream_t st = pl->stream;
+    double tot[kGradNV];
+    GPV_HIP(launch_grad(pl->p, a, grid, st));
+    GPV_HIP(hipMemcpyAsync(tot, pl->d_gr_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    GPV_HIP(hipStreamSynchronize(st));
+    // kernel parameters -> covparms: matern {variance, range, -, nugget}, esqe {variance 1, range 1, variance 2, range 2, nugget}
+    const int nk = matern ? 3 : 5;                                   // derivatives the kernel produced
+    auto spread = [&](const double *src, double *dst) {              // src: {derivatives}, dst: ncovparms + 1
+        if (matern) { dst[0] = src[0]; dst[1] = src[1]; dst[2] = NAN; dst[3] = src[2]; }
+        else for (int t = 0; t < nk; ++t) dst[t] = src[t];
+    };
+    *n_failed = (int64_t)tot[6];
+    if (tot[6] > 0.0) {
+        *loglik = -INFINITY;
+        for (int t = 0; t <= ncovparms; ++t) grad[t] = NAN;
+    } else {
+        *loglik = tot[0];
+        spread(tot + 1, grad);
+    }
+    if (row_terms) {
+        std::vector<double> h((size_t)pl->rows * kGradRowLd);
+        GPV_HIP(hipMemcpy(h.data(), pl->d_gr_rows, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        const int ld = ncovparms + 2;
+        for (int64_t k = 0; k < pl->rows; ++k) {
+            row_terms[k * ld] = h[(size_t)k * kGradRowLd];
+            spread(&h[(size_t)k * kGradRowLd + 1], row_terms + k * ld + 1);
+        }
+    }
     return GPV_OK;
 }
 

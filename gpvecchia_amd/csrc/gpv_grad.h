@@ -1,0 +1,43 @@
+// gpv_grad.h — launcher of the value-and-gradient kernel of the cond.yz='z' log-likelihood (gpv_grad.hip).  Not installed.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace gpv {
+
+constexpr int kGradMaxP = 64;          // longest row (m + 1) the kernel takes: one lane per row of the block
+constexpr int kGradNV = 8;             // values per row / partial: {l, d/d(kernel parameter 0..4), failed, rows}
+constexpr int kGradRowLd = 6;          // doubles per row of GradArgs::row_terms: {l_k, its derivatives}
+// kernel parameters, in this order (the smoothness of "matern" is not one of them):
+//   matern: variance, range, nugget                      esqe: variance 1, range 1, variance 2, range 2, nugget
+constexpr int kGradWavesPerBlock = 4;
+// Grid cap: 4 workgroups of 4 wavefronts per CU, 4096 wavefronts on the 256 CUs of an MI355X.  At n = 40 000 every wavefront
+// then takes 9 or 10 conditioning sets; the per-workgroup partials (kGradNV doubles each) stay a few KB.
+constexpr int kGradBlocksPerCU = 4;
+
+struct GradArgs {
+    const double *rec;       // SetArgs::rec   (dim <= 3: {c0, c1, c2, datum})
+    const double *locs;      // SetArgs::locs  (dim > 3)
+    const double *z;         // SetArgs::z     (dim > 3)
+    const int32_t *nn;       // [rows][P], valid entries right-aligned (gpv_plan_create compacts them), -1 = missing
+    const int32_t *rowid;    // [rows] output row of each stored set
+    double *row_terms;       // [rows][kGradRowLd] by OUTPUT row, or nullptr; NaN in a row whose block was not positive definite
+    double *block_part;      // [grid][kGradNV] per-workgroup partials
+    double *totals;          // [kGradNV] their sum in workgroup order (second launch)
+    int64_t rows;
+    int P;                   // row stride of nn (the plan's compiled row length; may be shorter than the bucket)
+    int dim, locs_ld;
+    int cov;                 // CovKind: COV_MATERN05 / 15 / 25 / COV_ESQE
+    double sA, cA, irA;      // matern: sigma^2, sqrt(2 nu)/range, 1/range        esqe: s1, 1/r1, 1/r1
+    double sB, cB, irB;      // esqe: s2, 1/r2^2, 1/r2
+    double nug;
+};
+
+// row-length bucket of a row of p entries (16, 32 or 64), 0: too long
+inline int grad_bucket(int p) { return p <= 16 ? 16 : (p <= 32 ? 32 : (p <= kGradMaxP ? 64 : 0)); }
+// workgroups of the launch for `rows` sets on a device of `cus` compute units
+int grad_grid(int64_t rows, int cus);
+// both launches (the set pass, then the fixed-order sum of its partials) on `stream`; p: entries per row (m + 1)
+hipError_t launch_grad(int p, const GradArgs &a, int grid, hipStream_t stream);
+
+}  // namespace gpv

@@ -109,7 +109,24 @@ def _nelder_mead_nash(fn, x0, reltol, maxit, abstol=-np.inf, alpha=1.0, beta=0.5
 
 
 def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini=None, output_level=1,
-                     reltol=np.sqrt(np.finfo(float).eps), seed=0, maxit=300, **specify_args):
+                     reltol=np.sqrt(np.finfo(float).eps), seed=0, maxit=300, smoothness=None, method="Nelder-Mead",
+                     **specify_args):
+    """smoothness: a value fixes the Matern smoothness and takes it out of the search (theta_ini then holds variance, range,
+    nugget).  method: "Nelder-Mead" (the reference's search) or "L-BFGS-B", which minimises over the log-parameters with the
+    analytic gradient of the GPU (vecchia_likelihood_grad; d/d log theta = theta d/d theta) and needs cond_yz='z' and, for
+    'matern', smoothness in {0.5, 1.5, 2.5}.  n_evals counts likelihood (or value + gradient) evaluations."""
+    if method not in ("Nelder-Mead", "L-BFGS-B"):
+        raise ValueError(f"method='{method}' not defined")
+    fix_nu = smoothness is not None
+    if fix_nu and covmodel != "matern":
+        raise ValueError("smoothness applies to covmodel='matern' only")
+    if method == "L-BFGS-B":
+        if specify_args.get("cond_yz") != "z":
+            raise ValueError("method='L-BFGS-B' needs cond_yz='z' (the likelihood whose gradient the GPU returns)")
+        if not isinstance(covmodel, str):
+            raise ValueError("method='L-BFGS-B' needs a named covariance family")
+        if covmodel == "matern" and (not fix_nu or float(smoothness) not in (0.5, 1.5, 2.5)):
+            raise ValueError("method='L-BFGS-B' with covmodel='matern' needs smoothness in {0.5, 1.5, 2.5}")
     data = np.asarray(data, dtype=np.float64)
     locs = np.asarray(locs, dtype=np.float64)
     if isinstance(X, str) and X == "missing":                        # :32-37 constant trend
@@ -133,23 +150,46 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         sub = locs[idx]
         dm = np.sqrt(((sub[:, None, :] - sub[None, :, :]) ** 2).sum(-1))
         theta_ini = np.array([.9 * var_res, dm.mean() / 4, .8, .1 * var_res])        # var, range, smooth, nugget
+        if fix_nu:
+            theta_ini = np.delete(theta_ini, 2)
     theta_ini = np.asarray(theta_ini, dtype=np.float64)
+
+    def full(th):                                                    # searched parameters -> (covparms, nugget)
+        cp = np.concatenate([th[:2], [float(smoothness)], th[2:-1]]) if fix_nu else th[:-1]
+        return cp, th[-1]
     n_par = len(theta_ini)
     evals = [0]
 
     def negloglik(lg):                                               # :72-78
-        if covmodel == "matern" and np.exp(lg[2]) > 10:
+        if covmodel == "matern" and not fix_nu and np.exp(lg[2]) > 10:
             raise RuntimeError("The default optimization routine to find parameters did not converge. "
                                "Try writing your own optimization.")
         evals[0] += 1
         th = np.exp(lg)
-        return -A.vecchia_likelihood(z, va, th[:-1], th[-1], covmodel=covmodel)
+        cp, nug = full(th)
+        return -A.vecchia_likelihood(z, va, cp, nug, covmodel=covmodel)
+
+    def negloglik_grad(lg):                                          # value and gradient in the log-parameters
+        evals[0] += 1
+        th = np.exp(lg)
+        cp, nug = full(th)
+        ll, g = A.vecchia_likelihood_grad(z, va, cp, nug, covmodel=covmodel)
+        g = np.delete(g, 2) if covmodel == "matern" else g           # the smoothness is fixed
+        if not np.isfinite(ll):
+            return _BIG, np.zeros_like(lg)
+        return -ll, -g * th
 
     parscale = np.ones(n_par)                                        # :83-85 (entries with theta.ini == 1 stay 1; the
     non1 = theta_ini != 1                                            #  reference's rep(1, length(n.par)) leaves them NA)
     parscale[non1] = np.log(theta_ini[non1])
     x0 = np.log(theta_ini) / parscale                                # optim works on par / parscale
-    xbest, fbest, _, conv = _nelder_mead_nash(lambda x: negloglik(x * parscale), x0, reltol=reltol, maxit=maxit)   # :87-93
+    if method == "L-BFGS-B":
+        from scipy.optimize import minimize
+        r = minimize(negloglik_grad, np.log(theta_ini), jac=True, method="L-BFGS-B",
+                     options=dict(maxiter=maxit, ftol=1e-3 * reltol, gtol=1e-5))   # (relative decrease per iteration; gradient in log-parameters)
+        xbest, fbest, conv, parscale = r.x, float(r.fun), (0 if r.success else 1), np.ones(n_par)
+    else:
+        xbest, fbest, _, conv = _nelder_mead_nash(lambda x: negloglik(x * parscale), x0, reltol=reltol, maxit=maxit)   # :87-93
 
     class _Res:
         x, fun = xbest, fbest
@@ -158,7 +198,7 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     if output_level > 0:                                             # :98-101
         print("estimated trend coefficients:\n", beta_hat)
         print("estimated covariance parameters:\n",
-              dict(zip(("variance", "range", "smoothness", "nugget"), theta_hat)))
+              dict(zip(("variance", "range", "nugget") if fix_nu else ("variance", "range", "smoothness", "nugget"), theta_hat)))
     return dict(z=z, beta_hat=beta_hat, theta_hat=theta_hat, trend=trend, locs=locs, covmodel=covmodel,
                 n_evals=evals[0], neg_loglik=float(res.fun), convergence=conv)
 

@@ -37,7 +37,8 @@ enum {
     GPV_ERR_COVTYPE = 3,        /* covType not "matern"/"esqe" (src/U_NZentries.cpp:27-29) */
     GPV_ERR_UNSUPPORTED_NU = 4, /* Matern smoothness not in (0, 60] or not finite                */
     GPV_ERR_UNSUPPORTED_M = 5,  /* m+1 > 192 (m+1 <= 64: unrolled register kernels; up to 192 and any dimension: a slow
-                                   workgroup-per-set kernel); m+1 > 64 for gpv_plan_build_posterior */
+                                   workgroup-per-set kernel); m+1 > 64 for gpv_plan_build_posterior and for
+                                   gpv_plan_loglik_grad */
     GPV_ERR_HIP = 6,            /* HIP runtime failure (alloc, copy, launch)         */
     GPV_ERR_STATE = 7,          /* call order: result requested before an eval, no data set */
     GPV_ERR_INDEX = 8           /* neighbour index outside [0, Nlocs]                */
@@ -265,6 +266,29 @@ int gpv_lincomb_batch(void);   /* right-hand sides per sweep (32) */
 /* stamp: 0 when the plan holds no factor, else a number that changes with every evaluation that writes one (callers that keep
  * a result of gpv_plan_lincomb's inputs around can tell whether the factor is still the one they mean) */
 int gpv_plan_factor_stamp(gpv_plan *plan, int64_t *stamp);
+
+/* Value and analytic gradient of the cond.yz='z' log-likelihood of the plan's data (the density the sums [2], [3] of a
+ * GPV_WANT_LOGLIK_Z evaluation describe, R/vecchia_likelihood.R:63-99 with a diagonal W), for gradient-based estimation.
+ * Per conditioning set with valid entries J (own point last), S' = C(J, J) + nugget I, u = S'^-1 e_last, w = S'^-1 z_J, q = u'z_J:
+ *   l_k = 1/2 log u_last - 1/2 q^2 / u_last - 1/2 log 2 pi,
+ *   dl_k/dtheta = -1/2 a / u_last + q b / u_last - 1/2 q^2 a / u_last^2 with a = u'D u, b = w'D u, D = dS'/dtheta elementwise.
+ * covType "matern" (covparms = variance, range, smoothness in {0.5, 1.5, 2.5}) or "esqe" (4 covparms); nugget: one constant > 0.
+ *   loglik     out: sum of l_k
+ *   grad       out, ncovparms + 1: d/d covparms[i], then d/d nugget.  The smoothness entry of "matern" is NaN: the reference's
+ *              Matern is discontinuous in nu at the closed-form branches, so it is not differentiated.
+ *   n_failed   out: rows whose block was not positive definite (pivot <= 0 or NaN, e.g. a NaN coordinate); they contribute
+ *              nothing, and with n_failed > 0 loglik is -Inf (like gpv_loglik_z_from_sums) and every grad entry NaN
+ *   row_terms  NULL, or out: Nlocs x (ncovparms + 2) row-major, row k = {l_k, the same derivatives} in the plan's ORDERED row
+ *              numbering (NaN in a failed row)
+ * Blocking, on the plan's own stream.  Results are bitwise reproducible from call to call.  The plan's last evaluation stays
+ * intact: gpv_plan_get_sums, gpv_plan_get_Lentries and gpv_plan_factor_stamp return what they returned before.
+ * Arguments are validated before the device is touched.  GPV_ERR_BAD_ARG: a null plan or pointer, ncovparms not 3 / 4, nugget
+ * not finite or <= 0; GPV_ERR_COVTYPE; GPV_ERR_UNSUPPORTED_NU: a smoothness other than 0.5, 1.5, 2.5; GPV_ERR_UNSUPPORTED_M:
+ * m + 1 > 64; GPV_ERR_STATE: no data set, a communicator attached, a row shard, unobserved locations (gpv_plan_set_observed), or
+ * a plan in which some neighbour is conditioned on as latent y (cond.yz other than 'z'). */
+int gpv_plan_loglik_grad(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
+                         double *loglik, double *grad /* ncovparms + 1 */, int64_t *n_failed,
+                         double *row_terms /* NULL, or Nlocs x (ncovparms + 2), row-major */);
 
 /* Vecchia-Laplace Newton-Raphson with the state on the device: calculate_posterior_VL of R/vecchia_laplace_NR.R:31-155
  * for fully observed data.  model: position in the reference's family list (:32): 0 gaussian, 1 logistic, 2 poisson,

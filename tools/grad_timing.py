@@ -1,0 +1,73 @@
+"""Cost of one gpv_plan_loglik_grad call (gpv_grad.hip) beside one likelihood-only evaluation of the same plan:
+
+    python tools/grad_timing.py [--n 1000000] [--m 30] [--nu 1.5] [--rounds 9] [--reps 7]
+
+One process, one plan (d = 2, cond.yz = 'z', maxmin ordering).  After a clock warm-up of likelihood evaluations (as bench.py
+does) the two legs run in alternating rounds -- `reps` gradient calls, `reps` plan.eval(GPV_WANT_LOGLIK_Z) + sums() -- and each
+is reported as the median over the rounds of the round's median, wall clock around the blocking calls.  The second leg is the
+code the benchmark measures and is the yardstick; central differences over the 3 parameters would cost 2 * 3 + 1 = 7 of them.
+Prints one JSON line."""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: F401,E402  (first: see tests/conftest.py)
+import gpvecchia_amd as G  # noqa: E402
+
+
+def med(f, reps):
+    ts = []
+    for _ in range(reps):
+        t0 = time.perf_counter()
+        f()
+        ts.append(time.perf_counter() - t0)
+    return 1e3 * float(np.median(ts))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--n", type=int, default=1_000_000)
+    ap.add_argument("--m", type=int, default=30)
+    ap.add_argument("--nu", type=float, default=1.5)
+    ap.add_argument("--rounds", type=int, default=9)
+    ap.add_argument("--reps", type=int, default=7)
+    a = ap.parse_args()
+    n, m = a.n, a.m
+    locs = np.random.default_rng(0).random((n, 2))
+    z = np.random.default_rng(1).standard_normal(n)
+    cp, tau = [1.0, 0.02 if n >= 500_000 else 0.05, a.nu], 0.1
+    va = G.vecchia_specify(locs, m, ordering="maxmin", cond_yz="z", nn_backend="gpu")
+    plan = G.api._plan_for(va, 0)
+    plan.set_data(z[va["ord_z"] - 1])
+    nug = np.array([tau])
+
+    def lik():
+        plan.eval("matern", cp, nug, G.GPV_WANT_LOGLIK_Z)
+        return plan.sums()
+
+    def grad():
+        return plan.loglik_grad("matern", cp, tau)
+    for _ in range(30):                                               # clock warm-up
+        lik()
+    ll, g, nfail = grad()                                             # first use: buffers
+    ll_ref = G.loglik_z_from_sums(lik(), n)
+    t_grad, t_lik = [], []
+    for _ in range(a.rounds):
+        t_grad.append(med(grad, a.reps))
+        t_lik.append(med(lik, a.reps))
+    out = dict(n=n, m=m, nu=a.nu, rounds=a.rounds, reps=a.reps, loglik_grad_ms=float(np.median(t_grad)),
+               loglik_only_ms=float(np.median(t_lik)), loglik_grad_ms_rounds=[round(t, 4) for t in t_grad],
+               loglik_only_ms_rounds=[round(t, 4) for t in t_lik], n_failed=nfail,
+               value_rel_diff=abs(ll - ll_ref) / abs(ll_ref))
+    out["ratio"] = out["loglik_grad_ms"] / out["loglik_only_ms"]
+    out["central_difference_break_even"] = 7
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

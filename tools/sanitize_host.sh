@@ -25,6 +25,10 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   for f in gpv_api gpv_aux_kernels gpv_posterior gpv_lincomb gpv_laplace gpv_sets_generic gpv_nn; do
     $HIPCC $CF "-DGPV_P_LIST(X)=$plx" -c $CSRC/$f.hip -o $B/$f.o & pids+=($!)
   done
+  for pb in 16 32 64; do                         # value + gradient kernel: one unit per row-length bucket, then its dispatcher
+    $HIPCC $CF -DGPV_GRAD_PB=$pb -c $CSRC/gpv_grad.hip -o $B/grad_pb$pb.o & pids+=($!)
+  done
+  $HIPCC $CF -c $CSRC/gpv_grad.hip -o $B/grad.o & pids+=($!)
   for P in $PLIST; do
     $HIPCC $CF "-DGPV_P_LIST(X)=$plx" -DGPV_INST_P=$P -c $CSRC/gpv_sets_inst.hip -o $B/sets_p$P.o & pids+=($!)
     if [ $P -gt 16 ] && [ $P -lt 32 ]; then      # likelihood-only kernels: a unit of their own (gpvecchia_amd/build.py lik_p)
@@ -65,6 +69,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   rc=${PIPESTATUS[0]}
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_draws_summary.log; then
     echo "== $tag: draws_summary_driver FAILED (rc $rc)"; return 1
+  fi
+  # ... and under the driver of the value-and-gradient entry (tests/sanitize/loglik_grad_driver.cpp)
+  mkdir -p $B/loglik_grad
+  $HIPCC $CF -c $ROOT/tests/sanitize/loglik_grad_driver.cpp -o $B/loglik_grad/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/loglik_grad/driver.o -o $B/loglik_grad_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./loglik_grad_driver ) 2>&1 | tee $B/run_loglik_grad.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_loglik_grad.log; then
+    echo "== $tag: loglik_grad_driver FAILED (rc $rc)"; return 1
   fi
   echo "== $tag: clean"
 }
