@@ -276,6 +276,10 @@ class Plan:
         L.check(L.lib().gpv_plan_last_kernel_ms(self._h, C.byref(ms)), "gpv_plan_last_kernel_ms")
         return float(ms.value)
 
+    def last_set_kernel(self):
+        """Bit flags of the conditioning-set kernel the last eval ran: 1 = likelihood-only sweep, 2 = its lean variant."""
+        return int(L.lib().gpv_plan_last_set_kernel(self._h))
+
     def set_comm(self, comm):
         """Attach (or, with None, detach) a Comm: every eval() then all-reduces its 8 sums over the ranks, inside the library."""
         L.check(L.lib().gpv_plan_set_comm(self._h, comm._h if comm is not None else None), "gpv_plan_set_comm")

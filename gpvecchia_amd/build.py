@@ -31,6 +31,12 @@ def lik_p(P):
     return 16 < P < 32
 
 
+def lean_p(P):
+    """Row lengths with the lean likelihood-only kernels: m = 20, 25, 30; a TU of their own.  The same list is k_lean<P>() in
+    gpv_sets_kernel.hpp, which decides what the launcher asks for: keep them equal (a mismatch is a link error)."""
+    return P in (21, 26, 31)
+
+
 def plist():
     txt = open(os.path.join(CSRC, "gpv_plist.h")).read()
     line = [l for l in txt.splitlines() if l.startswith("#define GPV_P_LIST")][0]
@@ -88,6 +94,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
             work.append((inst, os.path.join(BUILD, f"sets_p{P}.o"), [f"-DGPV_INST_P={P}"] + extra_flags, kern, force))
         if lik_p(P):
             work.append((inst, os.path.join(BUILD, f"sets_p{P}_lik.o"), [f"-DGPV_INST_P={P}", "-DGPV_INST_LIK"] + extra_flags,
+                         kern, force))
+        if lean_p(P):
+            work.append((inst, os.path.join(BUILD, f"sets_p{P}_lean.o"), [f"-DGPV_INST_P={P}", "-DGPV_INST_LEAN"] + extra_flags,
                          kern, force))
     work.append((os.path.join(CSRC, "gpv_aux_kernels.hip"), os.path.join(BUILD, "aux.o"), list(extra_flags),
                  kern + H("gpv_plist.h"), force))

@@ -397,6 +397,14 @@ struct gpv_plan {
     int64_t ds_draw_cap = 0;
     double nug_scalar = 0.0;
     bool nug_is_scalar = true;
+    // Facts the lean likelihood-only kernel relies on (gpv_sets_kernel.hpp, k_lean), fixed when the plan is built ...
+    bool coords_finite = false;    // no NaN / Inf among the location coordinates
+    double bbox_diam = INFINITY;   // diagonal of the locations' bounding box: no pair of the plan is farther apart
+    bool idx32 = false;            // rows * P < 2^31: 32-bit products address nn / cond
+    uint8_t *d_task_pad = nullptr; // [tasks, padded to a multiple of 4] SetArgs::task_pad (instantiations with a lean kernel)
+    // ... or when the nugget vector is uploaded (a scalar nugget is tested per call)
+    bool nug_vec_ok = false;       // d_nuggets holds finite values <= 2^990 only
+    int last_set_kernel = 0;       // kSetKernel* of the latest evaluation (gpv_plan_last_set_kernel)
     uint8_t *d_cond = nullptr;
     std::vector<int32_t> h_newpos;  // host copy of d_newpos (shared with the sibling plans of a gpv_mplan)
     bool generic = false;          // row length > 64 or dimension > 8: workgroup-per-set kernel (gpv_sets_generic.hip)
@@ -475,7 +483,7 @@ int gpv_plan_destroy(gpv_plan *pl)
                     pl->d_vl_z, pl->d_vl_pm, pl->d_vl_y[0], pl->d_vl_y[1], pl->d_vl_out, pl->d_vl_flags, pl->d_ticket,
                     pl->d_vl_y0, pl->d_vl_part, pl->d_user_ord, pl->d_meanrec, pl->d_obs, pl->d_topinfo, pl->d_toprows, pl->d_rr0, pl->d_nug_masked,
                     pl->d_lc_rec, pl->d_lc_X, pl->d_lc_part, pl->d_lc_vars, pl->d_lc_gpart, pl->d_lc_gram, pl->d_st_E,
-                    pl->d_ds, pl->d_ds_draw, pl->d_ds_cnt, pl->d_ds_mask, pl->d_gr_part, pl->d_gr_tot, pl->d_gr_rows};
+                    pl->d_ds, pl->d_ds_draw, pl->d_ds_cnt, pl->d_ds_mask, pl->d_gr_part, pl->d_gr_tot, pl->d_gr_rows, pl->d_task_pad};
     for (auto &g : pl->pgraph)
         if (g.exec) (void)hipGraphExecDestroy(g.exec);
     if (pl->lc_graph) (void)hipGraphExecDestroy(pl->lc_graph);
@@ -665,12 +673,25 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
     std::vector<double> lr((size_t)Nlocs * pl->locs_ld, 0.0);
     if (locs) {
         const int ld = pl->locs_ld;
-        double mabs = 0.0;
-        for (int64_t i = 0; i < Nlocs * (int64_t)dim; ++i) {
-            const double v = std::fabs(locs[i]);
-            if (v > mabs && v <= 1.79e308) mabs = v;
+        // one pass over the coordinates: the largest finite |coordinate|, and for the lean kernel whether all of them are
+        // finite and how far apart two locations can be at most (the bounding box's diagonal)
+        double mabs = 0.0, diam2 = 0.0;
+        bool fin = true;
+        for (int t = 0; t < dim; ++t) {
+            double mn = INFINITY, mx = -INFINITY;
+            const double *c = locs + (int64_t)t * Nlocs;
+            for (int64_t i = 0; i < Nlocs; ++i) {
+                const double v = std::fabs(c[i]);
+                if (v > mabs && v <= 1.79e308) mabs = v;
+                fin = fin && std::isfinite(v);
+                mn = c[i] < mn ? c[i] : mn;
+                mx = c[i] > mx ? c[i] : mx;
+            }
+            diam2 += (mx - mn) * (mx - mn);
         }
         pl->coord_maxabs = mabs;
+        pl->coords_finite = fin;
+        pl->bbox_diam = fin ? std::sqrt(diam2) : INFINITY;
         parallel_for(Nlocs, [=, &lr](int64_t b, int64_t e) {
             for (int64_t i = b; i < e; ++i)
                 for (int t = 0; t < dim; ++t) lr[(size_t)np_[i] * ld + t] = locs[i + (int64_t)t * Nlocs];
@@ -758,6 +779,25 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
     if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_stage, sizeof(double) * (size_t)Nlocs))) return fail(GPV_ERR_HIP);
     if (GPV_HIP_FAILED(hipMemcpy(pl->d_newpos, newpos.data(), sizeof(int32_t) * (size_t)Nlocs, hipMemcpyHostToDevice)))
         return fail(GPV_ERR_HIP);
+    // lean kernel: one byte per task of SPW sets (internal set order): does the task hold a missing neighbour or a set beyond
+    // `rows`.  This plan's rows are fixed (a shard is a plan of its own), so the bytes are too.
+    pl->idx32 = rows * (int64_t)P < ((int64_t)1 << 31);
+    const int spw = generic ? 0 : sets_per_task(P);
+    if (spw > 0 && rows > 0) {
+        const int64_t ntasks = (rows + spw - 1) / spw;
+        std::vector<uint8_t> pad((size_t)((ntasks + 3) & ~(int64_t)3) + 4, 1);
+        const int32_t *nnp = nn.data();
+        parallel_for(ntasks, [=, &pad](int64_t b, int64_t e) {
+            for (int64_t t = b; t < e; ++t) {
+                bool any = (t + 1) * spw > rows;
+                for (int64_t sset = t * spw; sset < (t + 1) * spw && !any; ++sset)
+                    for (int j = 0; j < P; ++j) any = any || nnp[sset * P + j] < 0;
+                pad[(size_t)t] = any ? 1 : 0;
+            }
+        });
+        if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_task_pad, pad.size()))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipMemcpy(pl->d_task_pad, pad.data(), pad.size(), hipMemcpyHostToDevice))) return fail(GPV_ERR_HIP);
+    }
     tm.lap("plan: alloc + H2D");
     pl->h_newpos.swap(newpos);
     *out = pl;
@@ -839,8 +879,19 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
             pl->nug_scalar = nuggets[0];
         } else if (n_nuggets == -1 && pl->d_nug_user) {
             pl->nug_is_scalar = false;                                        // per-location nuggets already in HBM (VL step)
+            pl->nug_vec_ok = false;                                           // (written on the device: not inspected)
         } else if (n_nuggets == pl->Nlocs) {
             pl->nug_is_scalar = false;
+            {
+                std::atomic<int> okv{1};
+                std::atomic<int> *okp = &okv;
+                parallel_for(pl->Nlocs, [=](int64_t b, int64_t e) {
+                    bool ok = true;
+                    for (int64_t i = b; i < e; ++i) ok = ok && std::isfinite(nuggets[i]) && nuggets[i] <= 0x1p990;
+                    if (!ok) okp->store(0, std::memory_order_relaxed);
+                });
+                pl->nug_vec_ok = okv.load() != 0;
+            }
             if (!pl->d_nug_user)
                 GPV_HIP(hipMalloc((void **)&pl->d_nug_user, sizeof(double) * (size_t)pl->Nlocs));
             GPV_HIP(hipMemcpyAsync(pl->d_nug_user, nuggets, sizeof(double) * (size_t)pl->Nlocs,
@@ -917,6 +968,23 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
     // Same outcome here, through the diagonal.  (nu = 0.5 gives exact zeros there instead, an independent model: not mirrored.)
     if (cs.cov != COV_DENSE && cs.cov != COV_ESQE && !(std::fabs(cs.cA) * pl->coord_maxabs < 1e300)) a.sig0 = NAN;
     a.mt = nullptr; a.mt_base = 0; a.mt_nseg = 0; a.mt_full = 0; a.mt_win = 0;
+    // The lean likelihood-only kernel leaves out what these facts make a no-op (the launcher checks family, dimension and
+    // row length, sets_args_lean):
+    //   coordinates finite, nuggets finite and <= 2^990, sigma^2 finite and small against 2^990: no NaN to inject into a
+    //     diagonal, none above the 2^990 clamp;
+    //   t_bounded: parameters finite and cA * (bounding-box diagonal) <= 500: no pair's scaled distance reaches the clamp at
+    //     1000 (500 leaves the rounding of this product and of the kernel's own sum of squares a wide margin);
+    //   idx32; flags exactly GPV_WANT_LOGLIK_Z.
+    // GPV_NO_LEAN=1: always the general likelihood-only kernel (tests and A/B runs).
+    {
+        static const bool no_lean = getenv("GPV_NO_LEAN") != nullptr;
+        const bool nug_ok = pl->nug_is_scalar ? (std::isfinite(pl->nug_scalar) && pl->nug_scalar <= 0x1p990) : pl->nug_vec_ok;
+        const bool parms_ok = std::isfinite(a.sig0) && std::fabs(a.sig0) <= 0x1p930 && std::isfinite(a.sA) && std::isfinite(a.cA);
+        const bool t_bounded = parms_ok && std::fabs(a.cA) * pl->bbox_diam <= 500.0;
+        const bool only_z = a.flags == GPV_WANT_LOGLIK_Z;
+        a.task_pad = pl->d_task_pad;
+        a.lean_ok = (!no_lean && pl->d_task_pad && pl->coords_finite && nug_ok && pl->idx32 && t_bounded && only_z) ? 1 : 0;
+    }
     if (cs.cov == COV_MATERN_GEN) {
         static const bool no_tab = getenv("GPV_NO_MATERN_TABLE") != nullptr;
         if (!no_tab && pl->dist_min > 0.0 && pl->dist_max >= pl->dist_min) {
@@ -978,6 +1046,7 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
         }
     }
     if (pl->timing) GPV_HIP(hipEventRecord(pl->ev0, st));
+    pl->last_set_kernel = pl->generic ? 0 : sets_kernel_kind(pl->P, a);
     if (pl->generic) GPV_HIP(launch_sets_generic(pl->P, a, pl->cus, &pl->grid, st));
     else GPV_HIP(launch_sets(pl->P, a, pl->cus, &pl->grid, st));
     if (pl->timing) GPV_HIP(hipEventRecord(pl->ev1, st));   // ev0..ev1 brackets the conditioning-set kernel alone
@@ -2576,6 +2645,11 @@ int gpv_plan_last_kernel_ms(gpv_plan *pl, double *ms)
     GPV_HIP(hipEventElapsedTime(&f, pl->ev0, pl->ev1));
     *ms = (double)f;
     return GPV_OK;
+}
+
+int gpv_plan_last_set_kernel(gpv_plan *pl)
+{
+    return (pl && pl->evaluated) ? pl->last_set_kernel : 0;
 }
 
 int gpv_plan_set_kernel_timing(gpv_plan *pl, int on)

@@ -43,6 +43,31 @@ int sets_mt_window_rows(int P, int dim)
             return 0;
     }
 }
+int sets_kernel_kind(int P, const SetArgs &a)
+{
+    if (a.cov == COV_DENSE || !sets_args_lik(a)) return 0;
+    switch (P) {
+#define GPV_CASE(P) \
+    case P:         \
+        return !k_lik<P>() ? 0 : ((k_lean<P>() && sets_args_lean(a)) ? (kSetKernelLik | kSetKernelLean) : kSetKernelLik);
+        GPV_P_LIST(GPV_CASE)
+#undef GPV_CASE
+        default:
+            return 0;
+    }
+}
+int sets_per_task(int P)
+{
+    switch (P) {
+#define GPV_CASE(P) \
+    case P:         \
+        return Geo<P>::SPW;
+        GPV_P_LIST(GPV_CASE)
+#undef GPV_CASE
+        default:
+            return 0;
+    }
+}
 hipError_t launch_sets(int P, const SetArgs &a, int cus, int *grid_out, hipStream_t stream)
 {
     switch (P) {

@@ -72,7 +72,17 @@ struct SetArgs {
     int mt_win;              //   first table row of the window the workgroups keep in LDS (where the distances concentrate)
     int share_old, share_young;   // set by the launcher (0, 0 = equal shares): task slots per round of a wavefront of the workgroups
                                   // dispatched first / second when there is exactly one workgroup per resident slot (gpv_sets_kernel.hpp)
+    // the lean likelihood-only kernel (gpv_sets_kernel.hpp, k_lean):
+    const uint8_t *task_pad; // [tasks of Geo<P>::SPW sets, padded to a multiple of 4] 1: a set of the task has a missing neighbour or
+                             //          lies beyond `rows`; plan-resident, in the plan's internal set order; or nullptr
+    int lean_ok;             // 1: the host established every fact the lean kernel relies on for THIS launch (gpv_api.hip, lean_facts)
 };
+// bit flags of the set kernel a launch takes (gpv_plan_last_set_kernel)
+constexpr int kSetKernelLik = 1, kSetKernelLean = 2;
+// which kernel launch_sets(P, a, ...) runs
+int sets_kernel_kind(int P, const SetArgs &a);
+// conditioning sets per task of the instantiation for row length P (0: no such instantiation)
+int sets_per_task(int P);
 
 // launch the conditioning-set kernel compiled for row length P (one of gpv_plist.h); the grid is chosen from
 // the instantiation's LDS footprint and the device's CU count and returned through grid_out (<= kMaxGrid)

@@ -2,7 +2,8 @@
 // Long rows (the fully unrolled sweep of P >= 41 takes minutes per instantiation) are split further, one TU per
 // spatial dimension:  -DGPV_INST_P=61 -DGPV_INST_DIM=1|2|3|0  (0 = run-time dimension > 3 and the dense-covariance
 // variant of U_NZentries_mat) plus  -DGPV_INST_P=61 -DGPV_INST_DISPATCH  for the function that picks among them.
-// Row lengths with the likelihood-only kernels (k_lik) compile those apart:  -DGPV_INST_P=31 -DGPV_INST_LIK.
+// Row lengths with the likelihood-only kernels (k_lik) compile those apart:  -DGPV_INST_P=31 -DGPV_INST_LIK,
+// and their lean variants (k_lean) apart again:  -DGPV_INST_P=31 -DGPV_INST_LEAN.
 #include "gpv_sets_kernel.hpp"
 #ifndef GPV_INST_P
 #error "compile with -DGPV_INST_P=<row length>"
@@ -13,6 +14,8 @@
 namespace gpv {
 #if defined(GPV_INST_LIK)
 template hipError_t launch_sets_lik<GPV_INST_P>(const SetArgs &, int, hipStream_t);
+#elif defined(GPV_INST_LEAN)
+template hipError_t launch_sets_lean<GPV_INST_P>(const SetArgs &, int, hipStream_t);
 #elif defined(GPV_INST_DISPATCH)
 hipError_t GPV_PART(0)(const SetArgs &, int, int *, hipStream_t);
 hipError_t GPV_PART(1)(const SetArgs &, int, int *, hipStream_t);

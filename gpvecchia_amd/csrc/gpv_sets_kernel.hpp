@@ -183,6 +183,22 @@ __host__ __device__ constexpr bool k_cov_addr_table()
     return GPV_OPT_COVTAB != 0 && LIK && k_lik<P>() && D != 0 && COV != COV_DENSE &&
            (COV != COV_MATERN_GEN || P <= GPV_COVTAB_GEN_MAXP);
 }
+// The LEAN variant of the likelihood-only kernel: the same sweep for launches whose plan and parameters make the per-task
+// safety work a no-op (SetArgs::lean_ok, set by the host; gpv_api.hip says how each fact is established).  Built for the
+// closed-form Matern families in 1 to 3 dimensions at the row lengths of m = 20, 25, 30, in translation units of their own.
+// (The same three row lengths are listed in lean_p() of build.py, which decides which sets_p*_lean.o exist: keep them equal.)
+template <int P>
+__host__ __device__ constexpr bool k_lean()
+{
+    return k_lik<P>() && (P == 21 || P == 26 || P == 31);
+}
+// likelihood-only launch: no U row (GPV_WANT_U), no compact block, no a vector
+inline bool sets_args_lik(const SetArgs &a) { return (a.flags & (1 | kFlagFused)) == 0 && a.aout == nullptr; }
+inline bool sets_args_lean(const SetArgs &a)
+{
+    return a.lean_ok != 0 && a.task_pad != nullptr && sets_args_lik(a) && a.dim >= 1 && a.dim <= 3 &&
+           (a.cov == COV_MATERN05 || a.cov == COV_MATERN15 || a.cov == COV_MATERN25);
+}
 // the last column a row of slot q can own on or left of its diagonal (the data row ends at column P - 1)
 template <int P>
 __host__ __device__ constexpr int lik_maxcol(int q)
@@ -703,7 +719,7 @@ __device__ __forceinline__ double matern_table_value(const double (&r)[MaternTab
 // normcon s^nu K_nu(s) by the quadrature of gpv_bessel.hpp (src/Matern.cpp:72-84), written over the value the lane staged
 // in the packed triangle.  A real call (never inlined): rare, divergent, and large.
 // xy0 / tr0: LDS byte addresses of the set's staged coordinates and triangle; xs_row / xs_dim: the coordinates' strides.
-static __device__ __attribute__((noinline)) void matern_gen_fixup(unsigned long long need, int rq, int P_, int H_, int dim, unsigned xy0,
+static __device__ __attribute__((noinline, unused)) void matern_gen_fixup(unsigned long long need, int rq, int P_, int H_, int dim, unsigned xy0,
                                                                   int xs_row, int xs_dim, unsigned tr0, double x0, double x1, double x2,
                                                                   double r2init, double cmul, double normcon, double nu, double sig0)
 {
@@ -776,7 +792,8 @@ __device__ __forceinline__ bool gen_fetch(double r2, double cA, const SetArgs &A
 // (t = c*1.5e-154 vanishes against 1 for any range above 1e-150; NaN coordinates are handled by `poison`)
 // SCALED: the coordinates were multiplied by cA (= sqrt(2 nu)/range) when they were gathered, sqrt(r2) is t itself;
 // R2MIN: r2 was accumulated from the smallest normal number (coincident points give exactly that), no clamp needed
-template <int COV, int MTW = 0, bool SCALED = false, bool R2MIN = false>
+// CLAMP = false (lean kernel): the caller guarantees t <= 1000 and no NaN, where the clamp is the identity
+template <int COV, int MTW = 0, bool SCALED = false, bool R2MIN = false, bool CLAMP = true>
 __device__ __forceinline__ double cov_closed(double r2, double sig0, double sA, double cA, double sB, double cB,
                                              const SetArgs &A, const ExpScaled &E, const double *mt_lds,
                                              unsigned long long &need, const int bit, const bool pair_used = true)
@@ -794,13 +811,15 @@ __device__ __forceinline__ double cov_closed(double r2, double sig0, double sA, 
     // this point is Inf * 0 out of the square root of an overflowed squared distance (NaN / Inf coordinates and a NaN range
     // were turned into a NaN diagonal), where the covariance of the reference is exp(-Inf) = 0 like the clamped value's
     if constexpr (COV == COV_MATERN15) {
-        const double t = __builtin_fmin(SCALED ? dist : dist * cA, 1000.0);
+        const double t0 = SCALED ? dist : dist * cA;
+        const double t = CLAMP ? __builtin_fmin(t0, 1000.0) : t0;
         const double e = exp_neg_scaled<false>(t, E);       // sigma^2 exp(-t)
         return __builtin_fma(t, e, e);
     } else if constexpr (COV == COV_MATERN05) {
-        return exp_neg_scaled<true>(SCALED ? dist : dist * cA, E);
+        return exp_neg_scaled<CLAMP>(SCALED ? dist : dist * cA, E);
     } else if constexpr (COV == COV_MATERN25) {
-        const double t = __builtin_fmin(SCALED ? dist : dist * cA, 1000.0);
+        const double t0 = SCALED ? dist : dist * cA;
+        const double t = CLAMP ? __builtin_fmin(t0, 1000.0) : t0;
         return exp_neg_scaled<false>(t, E) * __builtin_fma(t, __builtin_fma(t, 1.0 / 3.0, 1.0), 1.0);
     } else {
         return __builtin_fma(sA, exp_neg(dist * cA), sB * exp_neg(r2 * cB));
@@ -808,9 +827,24 @@ __device__ __forceinline__ double cov_closed(double r2, double sig0, double sA, 
 }
 
 // LIK: the likelihood-only variant (k_lik): lower-triangle sweep, no U row, no compact block, no a vector
-template <int P, int D, int COV, bool LIK = false>
-__global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_sets_kernel(const SetArgs A)
+// LEAN: LIK for launches with SetArgs::lean_ok (k_lean): finite coordinates and nuggets, bounded scaled distances, rows * P
+//       below 2^31, flags == GPV_WANT_LOGLIK_Z, padding known per task from SetArgs::task_pad
+//       (each thing it leaves out was switched off on its own once: profiles/r09_lean_ab.txt).
+//       It is NOT a template parameter of its own: a fifth parameter, defaulted or not, renames every existing kernel
+//       (gpv_sets_kernel<31, 2, 1, true, false>), and the profiles on record, the tools that read them and the register tests
+//       find the kernels by their four-argument names; a wrapper around a shared body, the other way to keep those names,
+//       changed the existing kernels' code (other inlining order: the padded rounds of <31, 2, 1, true> came out 71 VALU
+//       instructions longer).  So the lean kernels are the instantiations gpv_sets_kernel<P, D, COV | kCovLean, true>: the
+//       bit rides in the covariance argument and is taken off first thing (in a profile: <31, 2, 17, true>, 17 = 1 | 16).
+constexpr int kCovLean = 16;
+template <int P, int D, int COVX, bool LIK = false>
+__global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), Geo<P>::MINW) gpv_sets_kernel(const SetArgs A)
 {
+    constexpr int COV = COVX & (kCovLean - 1);
+    constexpr bool LEAN = (COVX & kCovLean) != 0;
+    static_assert(!LEAN || (LIK && k_lean<P>() && D >= 1 && D <= 3 &&
+                            (COV == COV_MATERN05 || COV == COV_MATERN15 || COV == COV_MATERN25)),
+                  "the lean variant: closed-form Matern, 1 to 3 dimensions, likelihood-only");
     using G = Geo<P>;
     constexpr int RPL = G::RPL, LPS = G::LPS, SPW = G::SPW, W = wpb<P, D, COV>();
     constexpr bool ZROW = G::ZROW;
@@ -889,9 +923,20 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         cboff_pf = reinterpret_cast<gl_ci32_t *>(((gl_cu64_t *)A.aout - 4)[1]);
     }
     int prow = 0, pcb = 0;
+    unsigned ppad = 1;                                       // lean: the next task's byte of task_pad (wave-uniform)
     auto load_ic = [&](const int64_t t) __attribute__((always_inline)) {
-        const int64_t kk = t * SPW + sub;
-        const bool on = lane_on && t < task_hi && kk < A.rows;
+        // lean: rows * P < 2^31 (and a task index past the wavefront's last one stays far below 2^31 / SPW): 32-bit products
+        using idx_t = std::conditional_t<LEAN, int, int64_t>;
+        const idx_t kk = (idx_t)t * SPW + sub;
+        const bool on = lane_on && t < task_hi && kk < (idx_t)A.rows;
+        if constexpr (LEAN) {
+            // one byte per task, read as the aligned 32-bit word that holds it: a scalar load (the array is padded to words)
+            typedef const __attribute__((address_space(4))) uint32_t k_cu32;
+            const int tu0 = __builtin_amdgcn_readfirstlane((int)t);
+            const int tu = tu0 < (int)task_hi ? tu0 : 0;
+            const uint32_t w = ((k_cu32 *)kargs_now()->task_pad)[tu >> 2];
+            ppad = (w >> ((tu & 3) * 8)) & 0xffu;
+        }
 #if GPV_OPT_KARGS
         KSetArgs *const Kg = kargs_now();
         if (want_row) prow = ((gl_ci32_t *)Kg->rowid)[on ? kk : 0];
@@ -908,7 +953,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         for (int q = 0; q < RPL; ++q) {                      // no branches: an idle slot reads entry 0 and is masked
             const int r = i_const + q * LPS;
             const bool ld = on && r < P;
-            const int64_t at = ld ? kk * P + r : 0;
+            const idx_t at = ld ? kk * P + r : 0;
             const int vi = nnp[at];
             const int vc = cdp[at];
             pidx[q] = ld ? vi : -1;
@@ -1007,12 +1052,13 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         task_next = task + step_from(task_layer);
         task_layer = (task_layer + 1 < my_layers) ? task_layer + 1 : 0;
         const int64_t k = task * SPW + sub;
-        const bool set_on = lane_on && (k < A.rows);
+        const bool set_on = lane_on && (LEAN ? ((int)task * SPW + sub < (int)A.rows) : (k < A.rows));
         // re-materialise the lane's row index per task: otherwise hipcc hoists all P (row == j) lane masks
         // out of the task loop (2P SGPRs -> SGPR spills through v_writelane/v_readlane inside the sweep)
         int i = i_const;
         asm volatile("" : "+v"(i));
         const int row_out = prow;                             // this task's output row / block offset (the loads below replace them)
+        const unsigned pad_now = ppad;
         int cb_pf = pcb;
 
         // ---- gather: indices, cond flags, coordinates, nugget, data -------------------
@@ -1063,10 +1109,12 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                 }
                 if (valid[q] && COV == COV_DENSE && A.z != nullptr) zi[q] = A.z[idx[q]];
             }
-            vmask[q] = __ballot(valid[q]);
+            if constexpr (!LEAN) vmask[q] = __ballot(valid[q]);
             if constexpr (D != 0) {
+                if constexpr (!LEAN) {
 #pragma unroll
-                for (int t = 0; t < D; ++t) poison[q] = poison[q] | ((xi[q][t] - xi[q][t]) != 0.0);   // NaN or +-Inf
+                    for (int t = 0; t < D; ++t) poison[q] = poison[q] | ((xi[q][t] - xi[q][t]) != 0.0);   // NaN or +-Inf
+                }
                 if constexpr (PRESCALE) {                        // t = sqrt(2 nu) dist / range = |c x_r - c x_j|: once per slot
 #pragma unroll
                     for (int t = 0; t < D; ++t) xi[q][t] *= cA;
@@ -1087,13 +1135,25 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         // wave-uniform: does any set of this task have padding (missing neighbours / rows beyond the data)?
         int nvalid = 0;
         bool all_valid = true;
+        if constexpr (LEAN) {
+            // the plan knows which tasks hold a missing neighbour or a set beyond `rows`; the lane masks of the masked rounds
+            // are formed on that (rare) path only
+            all_valid = pad_now == 0u;
 #pragma unroll
-        for (int q = 0; q < RPL; ++q) {
-            nvalid += __popcll(vmask[q] & setmask);
-            const unsigned long long want = __ballot(lane_on && row[q] < P);
-            all_valid = all_valid && (vmask[q] == want);
+            for (int q = 0; q < RPL; ++q) vmask[q] = 0ull;
+            if (!all_valid) {
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) vmask[q] = __ballot(valid[q]);
+            }
+        } else {
+#pragma unroll
+            for (int q = 0; q < RPL; ++q) {
+                nvalid += __popcll(vmask[q] & setmask);
+                const unsigned long long want = __ballot(lane_on && row[q] < P);
+                all_valid = all_valid && (vmask[q] == want);
+            }
         }
-        const int nmiss = P - nvalid;
+        const int nmiss = P - nvalid;                         // (read by the kernels that write U rows only)
         wave_sync();
 #ifdef GPV_TRACE_TIMES
         if (tr_t[1] == 0ull) tr_t[1] = wall_clock64();        // first task gathered (prologue + two trips to memory behind us)
@@ -1299,7 +1359,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                         }
                         used = vq[q] && jvalid;
                     }
-                    v[q] = cov_closed<COV, MTW, PRESCALE, R2MIN>(r2, sig0, sA, cA, sB, cB, A, expS, mt_lds, need[q], s - 1, used);
+                    v[q] = cov_closed<COV, MTW, PRESCALE, R2MIN, !LEAN>(r2, sig0, sA, cA, sB, cB, A, expS, mt_lds, need[q], s - 1, used);
                     if constexpr (MASKED) v[q] = used ? v[q] : 0.0;
                 }
 #pragma unroll
@@ -1335,10 +1395,13 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
             double diag;
             if constexpr (COV == COV_DENSE) diag = valid[q] ? A.covvals[(int64_t)idx[q] * A.nlocs + idx[q]] : 1.0;
             else diag = valid[q] ? (sig0 + nugraw[q] * (1.0 - (double)(cndraw[q] & 1))) : 1.0;   // src/U_NZentries.cpp:47,52
-            if (poison[q]) diag = __builtin_nan("");
             // an Inf (or absurdly large) nugget behaves like 2^990: its multipliers vanish below rounding either way, and
             // no pivot (a Schur complement, at most its diagonal entry) can then overflow the reciprocal; NaN stays NaN
-            diag = (diag > 0x1p990) ? 0x1p990 : diag;
+            // (lean: coordinates, parameters and nuggets are finite and sigma^2 + nugget <= 2^990, checked on the host)
+            if constexpr (!LEAN) {
+                if (poison[q]) diag = __builtin_nan("");
+                diag = (diag > 0x1p990) ? 0x1p990 : diag;
+            }
             if (lane_on && row[q] < P) {
                 L.tri[sub][(int)(__umul24(row[q], row[q] + 1) >> 1) + row[q]] = diag;
                 // data row: z_j of the neighbours conditioned on as observations (R/vecchia_likelihood.R:74)
@@ -1386,6 +1449,14 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         for (int q = 0; q < RPL; ++q) prinv[q] = 1.0;
         double vlast;                                  // Schur complement of the point itself (row P-1)
         double negmu_z = 0.0;                          // data row after the sweep: -mu_k (ZROW geometries)
+        // lean: the running "minimum" of the set's pivot reciprocals, kept as the OR of their high words (the pivot is broadcast
+        // over the set's 16 lanes: uniform over them).  Only its sign is read: set exactly when some reciprocal is negative,
+        // which is all min(...) > 0 would tell -- a reciprocal is never 0 (pivots stay below 2^991), and a NaN one (pivot 0, NaN
+        // or subnormal), which v_min_f64 would drop as well, is in the multipliers of row P - 1 for that pivot and so in vlast,
+        // which fails vlast > 0.  An integer OR instead of v_min_f64: hipcc puts a canonicalising v_max_f64 in front of every
+        // minimum whose operand crosses a basic block (45 instructions for the 30 pivots).  One v_or_b32 per pivot, as inline
+        // asm: from a plain `|=` hipcc keeps all 30 reciprocals alive to the end of the sweep and ORs both of their halves there.
+        int psign = 0;
         if constexpr (LIK) {
             // Lower-triangle LDL^T sweep (dpotf2's outer-product form) over pivots 0..P-2.  Row r keeps its cells c <= r; pivot j
             // takes the multiplier nw = -a_rj / p_j from its own register and updates a_rc += nw a_cj for j < c <= r, where a_cj is
@@ -1404,7 +1475,8 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                 if constexpr (qj + 2 < RPL) d2 = a[qj + 2][j];
                 const double pj = dpp_row_bcast<j % 16>(a[qj][j], d1, d2);   // pivot = Schur complement d_j^2
                 const double rinv = rcp_pivot_bounded(pj);
-                pivot_lane_keep<j % 16>(prinv[qj], rinv);
+                if constexpr (LEAN) asm("v_or_b32 %0, %0, %1" : "+v"(psign) : "v"(__double2hiint(rinv)));
+                else pivot_lane_keep<j % 16>(prinv[qj], rinv);
                 double nw[RPL];
 #pragma unroll
                 for (int q = qj; q < RPL; ++q) nw[q] = a[q][j] * -rinv;   // (slot qj after its last column: dead, removed)
@@ -1614,11 +1686,12 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
         for (int q = 0; q < RPL; ++q) {
             // LAPACK dpotrf: a pivot <= 0 or NaN -> not positive definite (src/U_NZentries.cpp:60-66); the sign / NaN-ness
             // of a pivot survives in its reciprocal, the last pivot is tested directly
-            const bool okp = (row[q] == P - 1) ? (vlast > 0.0) : (prinv[q] > 0.0);
+            const bool okp = LEAN ? (psign >= 0 && vlast > 0.0) : ((row[q] == P - 1) ? (vlast > 0.0) : (prinv[q] > 0.0));
             bad = bad | (lane_on && row[q] < P && !okp);
         }
         const bool fail = (__ballot(bad) & setmask) != 0ull;
-        const double rs = rsqrt_pos(vlast);            // M[n0-1] = d_k = 1/R[n0-1][n0-1]
+        // (lean, flags == GPV_WANT_LOGLIK_Z: neither is read)
+        const double rs = LEAN ? 0.0 : rsqrt_pos(vlast);   // M[n0-1] = d_k = 1/R[n0-1][n0-1]
         const double dlast = vlast * rs;               // R[n0-1][n0-1] = sqrt(v)
         double x[RPL] = {};                            // the set's row of U (LIK: not formed, nothing below reads it)
         if constexpr (!LIK) {
@@ -1675,7 +1748,7 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                 if (set_on && row[q] < P && valid[q] && (cndraw[q] >> 1) != 0)     // (1 + position in the block; 0: not latent)
                     Cout[cb + (cndraw[q] >> 1)] = v2d_out{x[q], both ? x[q] : 0.0};
         }
-        if (A.flags & 6) {
+        if (LEAN || (A.flags & 6)) {
             double negmu;                              // -mu_k = -sum_j b_j z_j over observed-conditioned neighbours
             if constexpr (ZROW) {
                 negmu = negmu_z;
@@ -1701,14 +1774,14 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
                 const bool a_to_vec = !fused || (A.flags & kFlagBoth) != 0;
                 if (!LIK && aout != nullptr && a_to_vec && set_on && i == IO) aout[want_row ? row_out : rowid[k]] = fail ? 0.0 : negmu * rs;
                 if (fused && set_on && i == IO) Cout[cb] = v2d_out{fail ? 0.0 : negmu * rs, 0.0};
-                if (A.flags & 2) {
+                if (LEAN || (A.flags & 2)) {
                     const double tv = tau + vlast;
                     const double rz = zk + negmu;                    // z_k - mu_k
                     lg_tv.mul(tv, good);
                     const double t3 = rz * rz * rcp_safe(tv);
                     acc_rz += good ? t3 : 0.0;
                 }
-                if (A.flags & 4) {
+                if (!LEAN && (A.flags & 4)) {
                     const double ak = negmu * rs;                    // a_k = -mu_k d_k
                     lg_d.mul(rs, good);
                     lg_tau.mul(tau, good);
@@ -1726,12 +1799,12 @@ __global__ void __launch_bounds__((wpb<P, D, COV>() * 64), Geo<P>::MINW) gpv_set
 #endif
     if (lane_on && i_const == IO) {
         double *ac = L.acc[sub];
-        ac[0] = (A.flags & 4) ? lg_d.value() : 0.0;
+        ac[0] = (!LEAN && (A.flags & 4)) ? lg_d.value() : 0.0;
         ac[1] = acc_a2;
-        ac[2] = (A.flags & 2) ? lg_tv.value() : 0.0;
+        ac[2] = (LEAN || (A.flags & 2)) ? lg_tv.value() : 0.0;
         ac[3] = acc_rz;
         ac[4] = acc_z2;
-        ac[5] = (A.flags & 4) ? lg_tau.value() : 0.0;
+        ac[5] = (!LEAN && (A.flags & 4)) ? lg_tau.value() : 0.0;
         ac[6] = (double)acc_fail;
         ac[7] = (double)acc_rows;
     }
@@ -1795,6 +1868,36 @@ hipError_t launch_sets_lik(const SetArgs &a, int grid, hipStream_t stream)
 }
 #endif
 
+// ... and the lean ones apart again (gpv_sets_inst.hip with GPV_INST_LEAN): the caller has checked sets_args_lean(a)
+template <int P>
+hipError_t launch_sets_lean(const SetArgs &a, int grid, hipStream_t stream);
+#ifdef GPV_INST_LEAN
+template <int P>
+hipError_t launch_sets_lean(const SetArgs &a, int grid, hipStream_t stream)
+{
+    static_assert(k_lean<P>(), "lean translation unit for a row length without the lean kernel");
+    auto go = [&](auto dc, auto cc) -> hipError_t {
+        constexpr int D = decltype(dc)::value, COV = decltype(cc)::value;
+        hipLaunchKernelGGL((gpv_sets_kernel<P, D, COV | kCovLean, true>), dim3(grid), dim3(wpb<P, D, COV>() * 64), 0, stream, a);
+        return hipGetLastError();
+    };
+    auto per_dim = [&](auto dc) -> hipError_t {
+        switch (a.cov) {
+            case COV_MATERN05: return go(dc, std::integral_constant<int, COV_MATERN05>{});
+            case COV_MATERN15: return go(dc, std::integral_constant<int, COV_MATERN15>{});
+            case COV_MATERN25: return go(dc, std::integral_constant<int, COV_MATERN25>{});
+            default: return hipErrorInvalidValue;
+        }
+    };
+    switch (a.dim) {
+        case 1: return per_dim(std::integral_constant<int, 1>{});
+        case 2: return per_dim(std::integral_constant<int, 2>{});
+        case 3: return per_dim(std::integral_constant<int, 3>{});
+        default: return hipErrorInvalidValue;
+    }
+}
+#endif
+
 template <int P, int D, int COV>
 hipError_t launch_sets_PDC(const SetArgs &a_in, int cus, int *grid_out, hipStream_t stream)
 {
@@ -1837,7 +1940,12 @@ hipError_t launch_sets_PDC(const SetArgs &a_in, int cus, int *grid_out, hipStrea
     // likelihood-only launches: no U row (GPV_WANT_U), no compact block, no a vector -- the lower-triangle sweep
     // (same grid and task shares: the LIK kernel has the same geometry, LDS and occupancy)
     if constexpr (k_lik<P>() && COV != COV_DENSE) {
-        if ((a.flags & (1 | kFlagFused)) == 0 && a.aout == nullptr) return launch_sets_lik<P>(a, grid, stream);
+        if (sets_args_lik(a)) {
+            if constexpr (k_lean<P>()) {
+                if (sets_args_lean(a)) return launch_sets_lean<P>(a, grid, stream);
+            }
+            return launch_sets_lik<P>(a, grid, stream);
+        }
     }
     hipLaunchKernelGGL((gpv_sets_kernel<P, D, COV>), dim3(grid), dim3(W * 64), 0, stream, a);
     return hipGetLastError();

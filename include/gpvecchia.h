@@ -339,6 +339,10 @@ int gpv_plan_rows(gpv_plan *plan, int64_t *row_begin, int64_t *row_end);
 int gpv_plan_dims(gpv_plan *plan, int64_t *Nlocs, int *dim, int *ncolNN);
 /* milliseconds the last eval's conditioning-set kernel took on the device (hipEvent pair around that launch) */
 int gpv_plan_last_kernel_ms(gpv_plan *plan, double *ms);
+/* which conditioning-set kernel the last eval ran, as bit flags: bit 0 = the likelihood-only (lower-triangle) sweep, bit 1 = its
+ * lean variant (plan and parameters let it skip the per-task safety work; GPV_NO_LEAN=1 in the environment never selects it).
+ * 0 before the first eval.  The results do not depend on it bit for bit; tests and tuning runs read it. */
+int gpv_plan_last_set_kernel(gpv_plan *plan);
 /* on = 0: evaluations no longer record that event pair (two queue packets per evaluation; they matter only when an
  * evaluation is a fraction of a millisecond, e.g. one rank's shard of an 8-GPU job) and gpv_plan_last_kernel_ms returns
  * GPV_ERR_STATE; default on */
