@@ -100,7 +100,9 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
                          kern, force))
     work.append((os.path.join(CSRC, "gpv_aux_kernels.hip"), os.path.join(BUILD, "aux.o"), list(extra_flags),
                  kern + H("gpv_plist.h"), force))
-    work.append((os.path.join(CSRC, "gpv_api.hip"), os.path.join(BUILD, "api.o"), list(extra_flags), internal + [pub] + H("gpv_laplace.h", "gpv_generic.h", "gpv_posterior_ext.h", "gpv_philox.hpp", "gpv_grad.h"), force))
+    work.append((os.path.join(CSRC, "gpv_api.hip"), os.path.join(BUILD, "api.o"), list(extra_flags),
+                 internal + [pub] + H("gpv_laplace.h", "gpv_generic.h", "gpv_posterior_ext.h", "gpv_philox.hpp", "gpv_grad.h",
+                                      "gpv_hip_raii.hpp"), force))
     work.append((os.path.join(CSRC, "gpv_posterior.hip"), os.path.join(BUILD, "posterior.o"), list(extra_flags),
                  internal + H("gpv_posterior_ext.h"), force))
     work.append((os.path.join(CSRC, "gpv_lincomb.hip"), os.path.join(BUILD, "lincomb.o"), list(extra_flags),

@@ -9,15 +9,13 @@
 #include "gpv_posterior_ext.h"
 #include "gpv_philox.hpp"
 #include "gpv_grad.h"
+#include "gpv_hip_raii.hpp"
 
 #include <dlfcn.h>
 
-#include <cstdio>
 #include <chrono>
 #include <climits>
-#include <cstdio>
 #include <cmath>
-#include <cstdlib>
 #include <cstring>
 #include <algorithm>
 #include <atomic>
@@ -28,28 +26,6 @@
 #include <vector>
 
 using namespace gpv;
-
-// Every HIP failure is remembered (per host thread) with the call that produced it, so that a caller that gets
-// GPV_ERR_HIP can tell out-of-memory from a bad stream from a failed launch: gpv_last_hip_error().
-namespace {
-thread_local int g_hip_code = 0;
-thread_local char g_hip_text[256] = "";
-inline int note_hip(hipError_t e, const char *what, int line)
-{
-    g_hip_code = (int)e;
-    (void)hipGetLastError();          // HIP keeps a failure until it is read: the launch wrappers' hipGetLastError() would report it again
-    std::snprintf(g_hip_text, sizeof(g_hip_text), "%s: %s [%s, gpv_api.hip:%d]", hipGetErrorName(e), hipGetErrorString(e),
-                  what, line);
-    return GPV_ERR_HIP;
-}
-}  // namespace
-#define GPV_HIP(expr)                                                   \
-    do {                                                                \
-        hipError_t e_ = (expr);                                         \
-        if (e_ != hipSuccess) return note_hip(e_, #expr, __LINE__);     \
-    } while (0)
-// the same for code that cleans up before it returns: evaluates to true on failure
-#define GPV_HIP_FAILED(expr) ([&]() { hipError_t e_ = (expr); if (e_ != hipSuccess) { note_hip(e_, #expr, __LINE__); return true; } return false; }())
 
 // RCCL is bound at run time (dlopen), never at link time: the library must load in an R session on a one-GPU machine that has
 // no RCCL at all.  Only five entry points are used; their C ABI (rccl.h: 128-byte ncclUniqueId by value, ncclDouble = 8,
@@ -310,25 +286,27 @@ Hash128 hash_bytes(const void *ptr, size_t bytes, uint64_t seed, unsigned max_th
 }  // namespace
 
 struct gpv_plan {
+    // Every device resource is a member that releases itself (gpv_hip_raii.hpp); gpv_plan_destroy holds no list of them.
+    // Members are destroyed in REVERSE order of declaration and the release order is graphs, buffers, events, stream: so the
+    // stream comes first here, then the events, the buffers follow, and the graphs stand at the very end.
+    Stream stream;
+    Event ev0, ev1;
+    Event stage_ev[2], mt_ev[2];                     // guards of h_stage / of the general-nu table copies (h_mt2, d_mt2)
     int device = 0, cus = 0;
     int64_t Nlocs = 0, row_begin = 0, row_end = 0, rows = 0;
     int dim = 0, p = 0, P = 0, locs_ld = 0, grid = 1;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     // d_locs: dim <= 3: packed records [Nlocs][4] = {c0,c1,c2,data} in the plan's INTERNAL (Morton) order;
     //         dim  > 3: coordinates [Nlocs][dim] in internal order, data in d_z
     // d_nuggets: internal order (gathered by the kernel); d_nug_user: caller's ordered layout (Zentries)
-    double *d_locs = nullptr, *d_nuggets = nullptr, *d_nug_user = nullptr, *d_z = nullptr, *d_L = nullptr,
-           *d_block = nullptr, *d_sums = nullptr, *d_Z = nullptr, *d_tmp = nullptr, *d_covvals = nullptr,
-           *d_stage = nullptr;
-    int32_t *d_nn = nullptr, *d_newpos = nullptr, *d_rowid = nullptr;
-    unsigned *d_ticket = nullptr;                    // arrival counter of the set kernel's workgroups (gpv_reduce_tail.hpp)
+    DevBuf<double> d_locs, d_nuggets, d_nug_user, d_z, d_L, d_block, d_sums, d_Z, d_tmp, d_covvals, d_stage;
+    DevBuf<int32_t> d_nn, d_newpos, d_rowid;
+    DevBuf<unsigned> d_ticket;                       // arrival counter of the set kernel's workgroups (gpv_reduce_tail.hpp)
     bool ticket_dirty = false;                       // an evaluation failed after its launch may have started: reset before the next
     // pinned host mirror of the totals: when the caller names no device mirror, the kernels write the totals straight into
     // host memory and gpv_plan_get_sums needs no copy command, only the stream's completion
-    void *h_stage[2] = {nullptr, nullptr};           // pinned staging of gpv_plan_get_Lentries (32 MB each, on first use)
-    hipEvent_t stage_ev[2] = {nullptr, nullptr};
-    double *h_sums = nullptr, *h_sums_dev = nullptr;
+    PinnedBuf<char> h_stage[2];                      // pinned staging of gpv_plan_get_Lentries (32 MB each, on first use)
+    PinnedBuf<double> h_sums;
+    double *h_sums_dev = nullptr;                    // the device's address of h_sums
     bool sums_on_host = false;
     // hand-off of the totals by memory: h_sums holds 8 totals and, behind them, 8 sequence numbers the producing kernel
     // stores after the totals (gpv_reduce_tail.hpp, publish_seq); gpv_plan_get_sums spins on them
@@ -337,63 +315,56 @@ struct gpv_plan {
     gpv_comm *comm = nullptr;                        // attached communicator: every evaluation all-reduces its 8 sums (gpv_plan_set_comm)
     // posterior ("U2V") pass, built on request (gpv_plan_build_posterior)
     bool have_post = false;
-    int32_t *d_colptr = nullptr, *d_crow = nullptr;
-    int32_t *d_ccol = nullptr;
-    int4 *d_colrec = nullptr, *d_rowrec = nullptr;
-    int4 *d_rr0 = nullptr;                           // first-round row-list records in schedule order (PostArgs::rr0)
+    DevBuf<int32_t> d_colptr, d_crow, d_ccol;
+    DevBuf<int4> d_colrec, d_rowrec;
+    DevBuf<int4> d_rr0;                              // first-round row-list records in schedule order (PostArgs::rr0)
     std::vector<int64_t> lev_rr0;                    // [level] where its records start in d_rr0
     int64_t top_rr0 = 0;                             // the dense top block's
-    uint8_t *d_tp = nullptr;
-    double2 *d_C = nullptr;
-    int32_t *d_cboff = nullptr, *d_cdel = nullptr;   // block offsets in d_C (Morton order of the locations), and cboff - colptr
+    DevBuf<uint8_t> d_tp;
+    DevBuf<double2> d_C;
+    DevBuf<int32_t> d_cboff, d_cdel;                 // block offsets in d_C (Morton order of the locations), and cboff - colptr
     int64_t post_nnz = 0;
     bool post_fused = false;                         // the set kernel writes the compact blocks itself (block positions in d_cond)
     int post_ld = 0;                                 // bound of the entries per column of the posterior structure (>= P; more with fill)
-    uint8_t *d_cslot = nullptr;
-    double *d_avec_base = nullptr;                   // allocation of d_avec: 64 bytes of header, then the n values
-    double *d_avec = nullptr, *d_tvec = nullptr, *d_rdiag = nullptr, *d_post_part = nullptr,
-           *d_zuser = nullptr;
-    uint8_t *d_obs = nullptr;                        // [Nlocs] ordered layout: 1 = the location carries an observation; nullptr: all do
-    double *d_nug_masked = nullptr;                  // [Nlocs] the evaluation's nuggets with +Inf where d_obs == 0 (PostArgs::nuggets)
+    DevBuf<uint8_t> d_cslot;
+    DevBuf<double> d_avec_base;                      // allocation of d_avec: 64 bytes of header, then the n values
+    double *d_avec = nullptr;                        // = d_avec_base + 8
+    DevBuf<double> d_tvec, d_rdiag, d_post_part, d_zuser;
+    DevBuf<uint8_t> d_obs;                           // [Nlocs] ordered layout: 1 = the location carries an observation; nullptr: all do
+    DevBuf<double> d_nug_masked;                     // [Nlocs] the evaluation's nuggets with +Inf where d_obs == 0 (PostArgs::nuggets)
     std::vector<int32_t> levptr, levptr2;
     std::vector<int> lev_lpc;                        // lanes per column of every level's kernel (16 / 32 / 64), from its row lists
-    // the posterior pass as a captured HIP graph (one per {denominator, denominator + mean}): ~140 (280) launches of a few
-    // microseconds each, which the host cannot enqueue as fast as the device retires them in the narrow tail levels
-    struct PostGraph { hipGraphExec_t exec = nullptr; double *sums_out = nullptr; };
-    PostGraph pgraph[8];                             // index = want_mean + 2 * (nuggets are a vector) + 4 * (mean from B: 'zy')
-    double *d_nug_post = nullptr;                    // ONE double: the constant nugget of the evaluation (PostArgs::nug_cell)
+    DevBuf<double> d_nug_post;                       // ONE double: the constant nugget of the evaluation (PostArgs::nug_cell)
     // general-nu Matern: range of pair distances of the plan (parameter independent) and the per-evaluation table
     double coord_maxabs = 0.0;                       // largest finite |coordinate| (guards the kernel's pre-scaled coordinates)
     double dist_min = 0.0, dist_max = 0.0;
     // distances of ALL pairs inside a sample of the conditioning sets, by quarter octave (index = floor(4 log2 d) + 4400):
     // where the set kernel's LDS window of the general-nu table goes
     std::vector<int64_t> dist_hist;
-    double *h_mt2[2] = {nullptr, nullptr}, *d_mt2[2] = {nullptr, nullptr};   // pinned staging / device copies, used alternately
-    hipEvent_t mt_ev[2] = {nullptr, nullptr};
+    PinnedBuf<double> h_mt2[2];                      // pinned staging / device copies, used alternately
+    DevBuf<double> d_mt2[2];
     int mt_slot = 0, mt_pending = -1;
-    int32_t *d_order2 = nullptr, *d_levptr2 = nullptr;
-    int4 *d_meanrec = nullptr;                       // mean sweep: one record per column in schedule order
-    double *d_toppart = nullptr;                     // [top_K][66] partial sums of the top block's columns
-    int2 *d_topinfo = nullptr;                       // [top_K] {column, offset of its block in C}
-    uint8_t *d_toprows = nullptr;                    // [top_K][64] index inside the block of each entry's row
+    DevBuf<int32_t> d_order2, d_levptr2;
+    DevBuf<int4> d_meanrec;                          // mean sweep: one record per column in schedule order
+    DevBuf<double> d_toppart;                        // [top_K][66] partial sums of the top block's columns
+    DevBuf<int2> d_topinfo;                          // [top_K] {column, offset of its block in C}
+    DevBuf<uint8_t> d_toprows;                       // [top_K][64] index inside the block of each entry's row
     int top_K = 0;                                   // columns 0 .. top_K-1 are kept out of the schedule (gpv_posterior_ext.h)
     int mean_head_levels = 0;                        // leading levels of the mean sweep run by one workgroup
-    double *d_u = nullptr, *d_mu = nullptr;
+    DevBuf<double> d_u, d_mu;
     bool have_mean = false;
     // linear combinations (gpv_plan_lincomb): everything is allocated on first use
     bool have_factor = false;                        // C holds the factor of an evaluation with a posterior pass
     int64_t factor_stamp = 0;                        // counts those evaluations
-    int2 *d_lc_rec = nullptr;                        // LincombArgs::lrec, rebuilt after gpv_plan_build_posterior
+    DevBuf<int2> d_lc_rec;                           // LincombArgs::lrec, rebuilt after gpv_plan_build_posterior
     bool lc_ready = false;
-    double *d_lc_X = nullptr, *d_lc_part = nullptr, *d_lc_vars = nullptr, *d_lc_gpart = nullptr, *d_lc_gram = nullptr;
-    hipGraphExec_t lc_graph = nullptr;               // the sweep (levels, top block, column sums) as a captured graph
-    double *d_st_E = nullptr;                        // gpv_plan_solve_t: one batch of dense columns, [kLincombNB][Nlocs]
-    hipGraphExec_t st_graph = nullptr;               // the transposed sweep (top block, levels) as a captured graph
+    DevBuf<double> d_lc_X, d_lc_part, d_lc_vars, d_lc_gpart, d_lc_gram;
+    DevBuf<double> d_st_E;                           // gpv_plan_solve_t: one batch of dense columns, [kLincombNB][Nlocs]
     // gpv_plan_draws_summary: mu, S1, S2, mean, var [Nlocs] each, exceed [8][Nlocs], the accumulation's block partials; counts
     // [8][Nlocs]; mask [Nlocs]; draw_max, draw_mean [ds_draw_cap] each.  Allocated on first use.
-    double *d_ds = nullptr, *d_ds_draw = nullptr;
-    uint32_t *d_ds_cnt = nullptr;
-    uint8_t *d_ds_mask = nullptr;
+    DevBuf<double> d_ds, d_ds_draw;
+    DevBuf<uint32_t> d_ds_cnt;
+    DevBuf<uint8_t> d_ds_mask;
     int64_t ds_draw_cap = 0;
     double nug_scalar = 0.0;
     bool nug_is_scalar = true;
@@ -401,30 +372,43 @@ struct gpv_plan {
     bool coords_finite = false;    // no NaN / Inf among the location coordinates
     double bbox_diam = INFINITY;   // diagonal of the locations' bounding box: no pair of the plan is farther apart
     bool idx32 = false;            // rows * P < 2^31: 32-bit products address nn / cond
-    uint8_t *d_task_pad = nullptr; // [tasks, padded to a multiple of 4] SetArgs::task_pad (instantiations with a lean kernel)
+    DevBuf<uint8_t> d_task_pad;    // [tasks, padded to a multiple of 4] SetArgs::task_pad (instantiations with a lean kernel)
     // ... or when the nugget vector is uploaded (a scalar nugget is tested per call)
     bool nug_vec_ok = false;       // d_nuggets holds finite values <= 2^990 only
     int last_set_kernel = 0;       // kSetKernel* of the latest evaluation (gpv_plan_last_set_kernel)
-    uint8_t *d_cond = nullptr;
+    DevBuf<uint8_t> d_cond;
     std::vector<int32_t> h_newpos;  // host copy of d_newpos (shared with the sibling plans of a gpv_mplan)
     bool generic = false;          // row length > 64 or dimension > 8: workgroup-per-set kernel (gpv_sets_generic.hip)
     bool latent_nb = false;        // some NEIGHBOUR (not a row's own point) is conditioned on as latent y: not a cond.yz='z' plan
     // gpv_plan_loglik_grad (gpv_grad.hip), allocated on first use: per-workgroup partials, their totals, per-row terms
-    double *d_gr_part = nullptr, *d_gr_tot = nullptr, *d_gr_rows = nullptr;
+    DevBuf<double> d_gr_part, d_gr_tot, d_gr_rows;
     int gr_grid = 0;
     // Vecchia-Laplace state (gpv_plan_vl_begin): data z, prior mean, two latent-mean buffers (current / next), flags + max
-    double *d_vl_z = nullptr, *d_vl_pm = nullptr, *d_vl_y[2] = {nullptr, nullptr}, *d_vl_out = nullptr;
-    double *d_vl_y0 = nullptr;                       // the start value, kept so that a restart needs no upload
-    double *d_vl_part = nullptr;                     // scratch of the missing-data and likelihood-term reductions
-    int32_t *d_user_ord = nullptr;                   // ord.z (1-based): caller's layout <-> ordered layout on the device
-    int *d_vl_flags = nullptr;
+    DevBuf<double> d_vl_z, d_vl_pm, d_vl_y[2], d_vl_out;
+    DevBuf<double> d_vl_y0;                          // the start value, kept so that a restart needs no upload
+    DevBuf<double> d_vl_part;                        // scratch of the missing-data and likelihood-term reductions
+    DevBuf<int32_t> d_user_ord;                      // ord.z (1-based): caller's layout <-> ordered layout on the device
+    DevBuf<int> d_vl_flags;
     int vl_model = -1, vl_cur = 0;
     bool vl_missing = false;                         // some z is NaN: the substitutes of removeNAs are computed every step
-    double *h_vl = nullptr, *h_vl_dev = nullptr;     // pinned: {max|dy|, flags (as a double)} of the step, written by the kernels
+    PinnedBuf<double> h_vl;                          // pinned: {max|dy|, flags (as a double)} of the step, written by the kernels
+    double *h_vl_dev = nullptr;                      // the device's address of h_vl
     double vl_alpha = 2.0, vl_sigma = 0.0, vl_beta = 0.5;
     bool has_z = false, evaluated = false, have_U = false;
     bool timing = true, timed = false;               // hipEvent pair around the set kernel (gpv_plan_set_kernel_timing)
-    hipStream_t last_stream = nullptr;
+    hipStream_t last_stream = nullptr;               // not owned: the plan's stream or the caller's
+    // the posterior pass as a captured HIP graph (one per {denominator, denominator + mean}): ~140 (280) launches of a few
+    // microseconds each, which the host cannot enqueue as fast as the device retires them in the narrow tail levels
+    struct PostGraph { GraphExec exec; double *sums_out = nullptr; };
+    PostGraph pgraph[8];                             // index = want_mean + 2 * (nuggets are a vector) + 4 * (mean from B: 'zy')
+    GraphExec lc_graph;                              // gpv_plan_lincomb's sweep (levels, top block, column sums)
+    GraphExec st_graph;                              // the transposed sweep (top block, levels)
+    void drop_graphs()                               // they hold addresses and a schedule that are about to change
+    {
+        for (auto &g : pgraph) g.exec.reset();
+        lc_graph.reset();
+        st_graph.reset();
+    }
 };
 
 extern "C" {
@@ -475,35 +459,7 @@ int gpv_plan_destroy(gpv_plan *pl)
     if (!pl) return GPV_OK;
     (void)hipSetDevice(pl->device);
     if (pl->stream) (void)hipStreamSynchronize(pl->stream);
-    void *ptrs[] = {pl->d_locs, pl->d_nuggets, pl->d_nug_user, pl->d_z, pl->d_L, pl->d_block, pl->d_sums,
-                    pl->d_Z, pl->d_tmp, pl->d_covvals, pl->d_stage, pl->d_nn, pl->d_newpos, pl->d_rowid, pl->d_cond,
-                    pl->d_colptr, pl->d_crow, pl->d_colrec, pl->d_rowrec, pl->d_cslot,
-                    pl->d_C, pl->d_cboff, pl->d_cdel, pl->d_ccol, pl->d_avec_base, pl->d_tvec, pl->d_rdiag, pl->d_post_part, pl->d_zuser,
-                    pl->d_order2, pl->d_levptr2, pl->d_toppart, pl->d_u, pl->d_mu, pl->d_tp, pl->d_nug_post, pl->d_mt2[0], pl->d_mt2[1],
-                    pl->d_vl_z, pl->d_vl_pm, pl->d_vl_y[0], pl->d_vl_y[1], pl->d_vl_out, pl->d_vl_flags, pl->d_ticket,
-                    pl->d_vl_y0, pl->d_vl_part, pl->d_user_ord, pl->d_meanrec, pl->d_obs, pl->d_topinfo, pl->d_toprows, pl->d_rr0, pl->d_nug_masked,
-                    pl->d_lc_rec, pl->d_lc_X, pl->d_lc_part, pl->d_lc_vars, pl->d_lc_gpart, pl->d_lc_gram, pl->d_st_E,
-                    pl->d_ds, pl->d_ds_draw, pl->d_ds_cnt, pl->d_ds_mask, pl->d_gr_part, pl->d_gr_tot, pl->d_gr_rows, pl->d_task_pad};
-    for (auto &g : pl->pgraph)
-        if (g.exec) (void)hipGraphExecDestroy(g.exec);
-    if (pl->lc_graph) (void)hipGraphExecDestroy(pl->lc_graph);
-    if (pl->st_graph) (void)hipGraphExecDestroy(pl->st_graph);
-    for (void *q : ptrs)
-        if (q) (void)hipFree(q);
-    for (int t = 0; t < 2; ++t) {
-        if (pl->h_mt2[t]) (void)hipHostFree(pl->h_mt2[t]);
-        if (pl->mt_ev[t]) (void)hipEventDestroy(pl->mt_ev[t]);
-    }
-    for (int b = 0; b < 2; ++b) {
-        if (pl->h_stage[b]) (void)hipHostFree(pl->h_stage[b]);
-        if (pl->stage_ev[b]) (void)hipEventDestroy(pl->stage_ev[b]);
-    }
-    if (pl->h_sums) (void)hipHostFree(pl->h_sums);
-    if (pl->h_vl) (void)hipHostFree(pl->h_vl);
-    if (pl->ev0) (void)hipEventDestroy(pl->ev0);
-    if (pl->ev1) (void)hipEventDestroy(pl->ev1);
-    if (pl->stream) (void)hipStreamDestroy(pl->stream);
-    delete pl;
+    delete pl;                        // every resource goes with its member (an attached communicator is its creator's)
     return GPV_OK;
 }
 
@@ -533,11 +489,13 @@ int gpv_plan_create(gpv_plan **out, int device, int64_t Nlocs, int dim, int ncol
     return plan_create_impl(out, device, Nlocs, dim, ncolNN, locs, revNN, revCond, row_begin, row_end, nullptr);
 }
 
+static int plan_fill(gpv_plan *pl, int device, int64_t Nlocs, int dim, int ncolNN, const double *locs, const int *revNN,
+                     const int *revCond, int64_t row_begin, int64_t row_end, const int32_t *shared_newpos);
+
 static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, int ncolNN, const double *locs,
                             const int *revNN, const int *revCond, int64_t row_begin, int64_t row_end,
                             const int32_t *shared_newpos)
 {
-    PhaseTimer tm;
     if (!out) return GPV_ERR_BAD_ARG;
     *out = nullptr;
     if (Nlocs <= 0 || Nlocs >= ((int64_t)1 << 31) || dim < 1 || dim > 4096 || ncolNN < 1 || !revNN)
@@ -546,6 +504,20 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
     int ndev = 0;
     if (gpv_device_count(&ndev) != GPV_OK) return GPV_ERR_NO_DEVICE;
     if (device < 0 || device >= ndev) return GPV_ERR_NO_DEVICE;
+    gpv_plan *pl = new gpv_plan();
+    const int rc = plan_fill(pl, device, Nlocs, dim, ncolNN, locs, revNN, revCond, row_begin, row_end, shared_newpos);
+    if (rc != GPV_OK) {                                   // the one failure path: whatever the plan holds so far goes with it
+        gpv_plan_destroy(pl);
+        return rc;
+    }
+    *out = pl;
+    return GPV_OK;
+}
+
+static int plan_fill(gpv_plan *pl, int device, int64_t Nlocs, int dim, int ncolNN, const double *locs, const int *revNN,
+                     const int *revCond, int64_t row_begin, int64_t row_end, const int32_t *shared_newpos)
+{
+    PhaseTimer tm;
     int P = pick_P(ncolNN);
     bool generic = false;
     if (P == 0 || dim > kMaxDimGeneric) {          // shapes without an unrolled instantiation: the slow generic kernel
@@ -554,8 +526,6 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
         generic = true;
     }
     if (GPV_HIP_FAILED(hipSetDevice(device))) return GPV_ERR_NO_DEVICE;
-
-    gpv_plan *pl = new gpv_plan();
     pl->device = device;
     pl->Nlocs = Nlocs;
     pl->row_begin = row_begin;
@@ -567,10 +537,7 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
     pl->generic = generic;
     pl->locs_ld = (dim <= 3) ? 4 : dim;
     hipDeviceProp_t prop;
-    if (GPV_HIP_FAILED(hipGetDeviceProperties(&prop, device))) {
-        delete pl;
-        return GPV_ERR_NO_DEVICE;
-    }
+    if (GPV_HIP_FAILED(hipGetDeviceProperties(&prop, device))) return GPV_ERR_NO_DEVICE;
     pl->cus = prop.multiProcessorCount;
     pl->grid = 1;
 
@@ -663,11 +630,7 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
             }
         }
     });
-    if (err_flag[0] != GPV_OK) {
-        int e = err_flag[0];
-        delete pl;
-        return e;
-    }
+    if (err_flag[0] != GPV_OK) return err_flag[0];
     pl->latent_nb = latent_nb.load() != 0;
     tm.lap("plan: index re-layout");
     std::vector<double> lr((size_t)Nlocs * pl->locs_ld, 0.0);
@@ -750,35 +713,23 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
         pl->dist_max = gmax;
     }
     tm.lap("plan: location records");
-    auto fail = [&](int code) {
-        gpv_plan_destroy(pl);
-        return code;
-    };
-    if (GPV_HIP_FAILED(hipStreamCreateWithFlags(&pl->stream, hipStreamNonBlocking))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipEventCreate(&pl->ev0)) || GPV_HIP_FAILED(hipEventCreate(&pl->ev1))) return fail(GPV_ERR_HIP);
-    const size_t nnb = nn.size() * sizeof(int32_t), cdb = cd.size(), lrb = lr.size() * sizeof(double);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_nn, nnb))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_cond, cdb))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_locs, lrb))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_nuggets, sizeof(double) * (size_t)Nlocs))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_block, sizeof(double) * kNSums * (size_t)kMaxGrid))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_sums, sizeof(double) * kNSums))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_ticket, 64)) || GPV_HIP_FAILED(hipMemset(pl->d_ticket, 0, 64)))
-        return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipHostMalloc((void **)&pl->h_sums, sizeof(double) * 2 * kNSums, hipHostMallocDefault)) ||
-        GPV_HIP_FAILED(hipHostGetDevicePointer((void **)&pl->h_sums_dev, pl->h_sums, 0)))
-        return fail(GPV_ERR_HIP);
+    GPV_HIP(hipStreamCreateWithFlags(pl->stream.put(), hipStreamNonBlocking));
+    GPV_HIP(hipEventCreate(pl->ev0.put()));
+    GPV_HIP(hipEventCreate(pl->ev1.put()));
+    GPV_BUF(pl->d_nn, upload(nn.data(), nn.size()));
+    GPV_BUF(pl->d_cond, upload(cd.data(), cd.size()));
+    GPV_BUF(pl->d_locs, upload(lr.data(), lr.size()));
+    GPV_BUF(pl->d_nuggets, resize((size_t)Nlocs));
+    GPV_BUF(pl->d_block, resize(kNSums * (size_t)kMaxGrid));
+    GPV_BUF(pl->d_sums, resize(kNSums));
+    GPV_BUF(pl->d_ticket, resize(16));
+    GPV_HIP(hipMemset(pl->d_ticket, 0, 64));
+    GPV_BUF(pl->h_sums, resize(2 * kNSums));
+    GPV_HIP(hipHostGetDevicePointer((void **)&pl->h_sums_dev, pl->h_sums, 0));
     std::memset(pl->h_sums, 0, sizeof(double) * 2 * kNSums);
-    if (GPV_HIP_FAILED(hipMemcpy(pl->d_nn, nn.data(), nnb, hipMemcpyHostToDevice))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemcpy(pl->d_cond, cd.data(), cdb, hipMemcpyHostToDevice))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemcpy(pl->d_locs, lr.data(), lrb, hipMemcpyHostToDevice))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_rowid, sizeof(int32_t) * rowsrc.size()))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemcpy(pl->d_rowid, rowsrc.data(), sizeof(int32_t) * rowsrc.size(), hipMemcpyHostToDevice)))
-        return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_newpos, sizeof(int32_t) * (size_t)Nlocs))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_stage, sizeof(double) * (size_t)Nlocs))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemcpy(pl->d_newpos, newpos.data(), sizeof(int32_t) * (size_t)Nlocs, hipMemcpyHostToDevice)))
-        return fail(GPV_ERR_HIP);
+    GPV_BUF(pl->d_rowid, upload(rowsrc.data(), rowsrc.size()));
+    GPV_BUF(pl->d_newpos, upload(newpos.data(), (size_t)Nlocs));
+    GPV_BUF(pl->d_stage, resize((size_t)Nlocs));
     // lean kernel: one byte per task of SPW sets (internal set order): does the task hold a missing neighbour or a set beyond
     // `rows`.  This plan's rows are fixed (a shard is a plan of its own), so the bytes are too.
     pl->idx32 = rows * (int64_t)P < ((int64_t)1 << 31);
@@ -795,12 +746,10 @@ static int plan_create_impl(gpv_plan **out, int device, int64_t Nlocs, int dim, 
                 pad[(size_t)t] = any ? 1 : 0;
             }
         });
-        if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_task_pad, pad.size()))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipMemcpy(pl->d_task_pad, pad.data(), pad.size(), hipMemcpyHostToDevice))) return fail(GPV_ERR_HIP);
+        GPV_BUF(pl->d_task_pad, upload(pad.data(), pad.size()));
     }
     tm.lap("plan: alloc + H2D");
     pl->h_newpos.swap(newpos);
-    *out = pl;
     return GPV_OK;
 }
 
@@ -814,10 +763,10 @@ int gpv_plan_set_data(gpv_plan *pl, const double *z_ord)
     if (pl->dim <= 3) {
         GPV_HIP(launch_scatter(pl->d_stage, pl->d_newpos, pl->Nlocs, pl->d_locs, 4, 3, pl->stream));   // rec[.][3] = datum
     } else {
-        if (!pl->d_z) GPV_HIP(hipMalloc((void **)&pl->d_z, sizeof(double) * (size_t)pl->Nlocs));
+        GPV_BUF(pl->d_z, ensure((size_t)pl->Nlocs));
         GPV_HIP(launch_scatter(pl->d_stage, pl->d_newpos, pl->Nlocs, pl->d_z, 1, 0, pl->stream));
     }
-    if (!pl->d_zuser) GPV_HIP(hipMalloc((void **)&pl->d_zuser, sizeof(double) * (size_t)pl->Nlocs));
+    GPV_BUF(pl->d_zuser, ensure((size_t)pl->Nlocs));
     GPV_HIP(hipMemcpyAsync(pl->d_zuser, pl->d_stage, sizeof(double) * (size_t)pl->Nlocs, hipMemcpyDeviceToDevice, pl->stream));
     GPV_HIP(hipStreamSynchronize(pl->stream));
     pl->has_z = true;
@@ -829,90 +778,69 @@ int gpv_plan_set_observed(gpv_plan *pl, const int *obs_ord)
     if (!pl) return GPV_ERR_BAD_ARG;
     GPV_HIP(hipSetDevice(pl->device));
     if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
-    for (auto &g : pl->pgraph)                        // the captured passes hold the address of the nuggets they read
-        if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-    if (!obs_ord) {                                   // back to "every location is observed"
-        if (pl->d_obs) { GPV_HIP(hipFree(pl->d_obs)); pl->d_obs = nullptr; }
-        return GPV_OK;
-    }
+    for (auto &g : pl->pgraph) g.exec.reset();        // the captured passes hold the address of the nuggets they read
     std::vector<uint8_t> h((size_t)pl->Nlocs);
     bool all = true;
-    for (int64_t i = 0; i < pl->Nlocs; ++i) { h[(size_t)i] = obs_ord[i] != 0 ? 1 : 0; all = all && h[(size_t)i]; }
-    if (all) {
-        if (pl->d_obs) { GPV_HIP(hipFree(pl->d_obs)); pl->d_obs = nullptr; }
+    for (int64_t i = 0; obs_ord && i < pl->Nlocs; ++i) { h[(size_t)i] = obs_ord[i] != 0 ? 1 : 0; all = all && h[(size_t)i]; }
+    if (all) {                                        // (or no list at all: back to "every location is observed")
+        GPV_HIP(pl->d_obs.reset());
         return GPV_OK;
     }
-    if (!pl->d_obs) GPV_HIP(hipMalloc((void **)&pl->d_obs, (size_t)pl->Nlocs));
+    GPV_BUF(pl->d_obs, ensure((size_t)pl->Nlocs));
     GPV_HIP(hipMemcpy(pl->d_obs, h.data(), (size_t)pl->Nlocs, hipMemcpyHostToDevice));
     return GPV_OK;
 }
 
-static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nuggets, int64_t n_nuggets, int flags,
-                          void *stream_v, double *d_sums_out)
+// ---- one evaluation of a plan, phase by phase (plan_eval_impl below is their sequence) ----------------------------------------
+constexpr int kPostFlags = GPV_WANT_DENOM | GPV_WANT_MEAN_B;          // the evaluation runs a posterior pass
+
+// the evaluation's nuggets: a constant, the caller's vector (inspected for the lean kernel, uploaded, scattered into the internal
+// order) or what a Vecchia-Laplace step left in HBM; with unobserved locations also the masked copy the posterior pass reads
+static int eval_nuggets(gpv_plan *pl, const double *nuggets, int64_t n_nuggets, int flags, hipStream_t st)
 {
-    flags &= 63;                                                  // (the bits above are the kernels' own)
-    if (flags & GPV_WANT_MEAN) flags |= GPV_WANT_DENOM;
-    const bool mean_b = (flags & GPV_WANT_MEAN_B) != 0;
-    if (mean_b && (flags & GPV_WANT_DENOM)) return GPV_ERR_BAD_ARG;      // one posterior pass per evaluation
-    if (flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B)) {
-        if (!pl->have_post) return GPV_ERR_STATE;
-        flags |= GPV_WANT_NUMERATOR;
-        if (!pl->post_fused) flags |= GPV_WANT_U;                 // (fused: the set kernel fills the compact blocks itself)
+    if (!nuggets && n_nuggets != -1) return GPV_ERR_BAD_ARG;
+    if (n_nuggets == 1) {
+        pl->nug_is_scalar = true;                                         // R/createU.R:74
+        pl->nug_scalar = nuggets[0];
+    } else if (n_nuggets == -1 && pl->d_nug_user) {
+        pl->nug_is_scalar = false;                                        // per-location nuggets already in HBM (VL step)
+        pl->nug_vec_ok = false;                                           // (written on the device: not inspected)
+    } else if (n_nuggets == pl->Nlocs) {
+        pl->nug_is_scalar = false;
+        std::atomic<int> okv{1};
+        std::atomic<int> *okp = &okv;
+        parallel_for(pl->Nlocs, [=](int64_t b, int64_t e) {
+            bool ok = true;
+            for (int64_t i = b; i < e; ++i) ok = ok && std::isfinite(nuggets[i]) && nuggets[i] <= 0x1p990;
+            if (!ok) okp->store(0, std::memory_order_relaxed);
+        });
+        pl->nug_vec_ok = okv.load() != 0;
+        GPV_BUF(pl->d_nug_user, ensure((size_t)pl->Nlocs));
+        GPV_HIP(hipMemcpyAsync(pl->d_nug_user, nuggets, sizeof(double) * (size_t)pl->Nlocs, hipMemcpyHostToDevice, st));
+        GPV_HIP(launch_scatter(pl->d_nug_user, pl->d_newpos, pl->Nlocs, pl->d_nuggets, 1, 0, st));
+    } else {
+        return GPV_ERR_BAD_ARG;
     }
-    if ((flags & (GPV_WANT_LOGLIK_Z | GPV_WANT_NUMERATOR)) && !pl->has_z) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    hipStream_t st = stream_v ? (hipStream_t)stream_v : pl->stream;
-    // the plan's buffers (nuggets, partial sums, U entries, posterior blocks) are reused by every evaluation: one that
-    // moves to ANOTHER stream first waits for the previous stream, evaluations on one stream are ordered by it
-    // (not while `st` is being captured into a graph: a host wait is illegal there, and the caller who captures owns the
-    // ordering against the plan's earlier evaluations)
-    hipStreamCaptureStatus cap0 = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cap0) != hipSuccess) { (void)hipGetLastError(); cap0 = hipStreamCaptureStatusNone; }
-    if (pl->last_stream && pl->last_stream != st && cap0 == hipStreamCaptureStatusNone) GPV_HIP(hipStreamSynchronize(pl->last_stream));
-    if ((flags & GPV_WANT_U) && !pl->d_L) {
-        GPV_HIP(hipMalloc((void **)&pl->d_L, sizeof(double) * (size_t)(pl->rows > 0 ? pl->rows : 1) * pl->P));
+    // locations without an observation (prediction locations): the set kernel keeps the caller's value (0 in the
+    // reference's nuggets.all.ord, R/createU.R:75-77; such a location is only ever conditioned on as latent, where the
+    // nugget drops out), the posterior pass reads +Inf there: no 1/tau on the diagonal of W = U_y U_y^T, no z/tau in z2.
+    // The masked values go to a buffer of their own that only the pass reads: Zentries, D_ord and the Vecchia-Laplace
+    // step keep seeing the caller's nuggets, and evaluations without a pass do not touch it.
+    if (pl->d_obs && !pl->nug_is_scalar && (flags & kPostFlags)) {
+        GPV_BUF(pl->d_nug_masked, ensure((size_t)pl->Nlocs));
+        GPV_HIP(launch_mask_unobserved(pl->d_nug_user, pl->d_nug_masked, pl->d_obs, pl->Nlocs, st));
     }
-    if (cs.cov != COV_DENSE) {
-        if (!nuggets && n_nuggets != -1) return GPV_ERR_BAD_ARG;
-        if (n_nuggets == 1) {
-            pl->nug_is_scalar = true;                                         // R/createU.R:74
-            pl->nug_scalar = nuggets[0];
-        } else if (n_nuggets == -1 && pl->d_nug_user) {
-            pl->nug_is_scalar = false;                                        // per-location nuggets already in HBM (VL step)
-            pl->nug_vec_ok = false;                                           // (written on the device: not inspected)
-        } else if (n_nuggets == pl->Nlocs) {
-            pl->nug_is_scalar = false;
-            {
-                std::atomic<int> okv{1};
-                std::atomic<int> *okp = &okv;
-                parallel_for(pl->Nlocs, [=](int64_t b, int64_t e) {
-                    bool ok = true;
-                    for (int64_t i = b; i < e; ++i) ok = ok && std::isfinite(nuggets[i]) && nuggets[i] <= 0x1p990;
-                    if (!ok) okp->store(0, std::memory_order_relaxed);
-                });
-                pl->nug_vec_ok = okv.load() != 0;
-            }
-            if (!pl->d_nug_user)
-                GPV_HIP(hipMalloc((void **)&pl->d_nug_user, sizeof(double) * (size_t)pl->Nlocs));
-            GPV_HIP(hipMemcpyAsync(pl->d_nug_user, nuggets, sizeof(double) * (size_t)pl->Nlocs,
-                                   hipMemcpyHostToDevice, st));
-            GPV_HIP(launch_scatter(pl->d_nug_user, pl->d_newpos, pl->Nlocs, pl->d_nuggets, 1, 0, st));
-        } else {
-            return GPV_ERR_BAD_ARG;
-        }
-        // locations without an observation (prediction locations): the set kernel keeps the caller's value (0 in the
-        // reference's nuggets.all.ord, R/createU.R:75-77; such a location is only ever conditioned on as latent, where the
-        // nugget drops out), the posterior pass reads +Inf there: no 1/tau on the diagonal of W = U_y U_y^T, no z/tau in z2.
-        // The masked values go to a buffer of their own that only the pass reads: Zentries, D_ord and the Vecchia-Laplace
-        // step keep seeing the caller's nuggets, and evaluations without a pass do not touch it.
-        if (pl->d_obs && !pl->nug_is_scalar && (flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B))) {
-            if (!pl->d_nug_masked) GPV_HIP(hipMalloc((void **)&pl->d_nug_masked, sizeof(double) * (size_t)pl->Nlocs));
-            GPV_HIP(launch_mask_unobserved(pl->d_nug_user, pl->d_nug_masked, pl->d_obs, pl->Nlocs, st));
-        }
-        // with unobserved locations the posterior pass needs the per-location form (a constant cannot say "none here")
-        if (pl->d_obs && (flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B)) && pl->nug_is_scalar) return GPV_ERR_BAD_ARG;
-    }
-    SetArgs a;
+    // with unobserved locations the posterior pass needs the per-location form (a constant cannot say "none here")
+    if (pl->d_obs && (flags & kPostFlags) && pl->nug_is_scalar) return GPV_ERR_BAD_ARG;
+    return GPV_OK;
+}
+
+// the hand-off of the totals by memory: the 8 sequence numbers behind the 8 totals of h_sums (gpv_reduce_tail.hpp, publish_seq)
+static unsigned long long *seq_cells_of(gpv_plan *pl) { return reinterpret_cast<unsigned long long *>(pl->h_sums_dev + kNSums); }
+
+// the launch arguments that do not depend on the covariance family's extras, and where this evaluation's totals go
+static int eval_set_args(gpv_plan *pl, const CovSetup &cs, int flags, hipStream_t st, double *d_sums_out, SetArgs &a)
+{
     a.rec = pl->d_locs;
     a.locs = pl->d_locs;
     a.nn = pl->d_nn;
@@ -923,44 +851,40 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
     a.z = (flags & (GPV_WANT_LOGLIK_Z | GPV_WANT_NUMERATOR)) ? pl->d_z : nullptr;
     a.covvals = pl->d_covvals;
     a.Lentries = (flags & GPV_WANT_U) ? pl->d_L : nullptr;
-    a.aout = (flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B)) ? pl->d_avec : nullptr;
-    const bool fused = (flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B)) && pl->post_fused;
-
+    a.aout = (flags & kPostFlags) ? pl->d_avec : nullptr;
+    const bool fused = (flags & kPostFlags) && pl->post_fused;
     a.block_sums = pl->d_block;
     a.sums = pl->d_sums;
     // with a communicator attached the totals of THIS rank stay in d_sums, RCCL sums them over the ranks in place on the
     // same stream, and one 64-byte copy command hands them to the host (or to the caller's device buffer)
     gpv_comm *const cm = pl->comm;
-    if (cm && (flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B))) return GPV_ERR_STATE;   // the posterior pass does not shard
-    double *const mirror = cm ? nullptr : (d_sums_out ? d_sums_out : pl->h_sums_dev);
+    if (cm && (flags & kPostFlags)) return GPV_ERR_STATE;         // the posterior pass does not shard
     pl->sums_on_host = (d_sums_out == nullptr);
-    a.sums_copy = mirror;
+    a.sums_copy = cm ? nullptr : (d_sums_out ? d_sums_out : pl->h_sums_dev);
     a.ticket = pl->d_ticket;
     // the set kernel's totals are final (no posterior pass adds to them) and go to the plan's own host buffer: the kernel
     // appends the sequence number of this evaluation and gpv_plan_get_sums spins on it instead of waiting for the stream
     static const bool no_seq = dev_getenv("GPV_NO_SEQ_HANDOFF") != nullptr;
-    unsigned long long *const seq_cells = reinterpret_cast<unsigned long long *>(pl->h_sums_dev + kNSums);
     // inside somebody's stream capture the sequence number would be frozen into the graph (every replay would publish the
     // same one, and gpv_plan_get_sums would accept the previous replay's totals without waiting): wait for the stream there
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap) != hipSuccess) { (void)hipGetLastError(); cap = hipStreamCaptureStatusNone; }
-    const bool final_here = !(flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B)) && d_sums_out == nullptr && !no_seq &&
-                            cap == hipStreamCaptureStatusNone;
+    const bool final_here = !(flags & kPostFlags) && d_sums_out == nullptr && !no_seq && cap == hipStreamCaptureStatusNone;
     if (pl->ticket_dirty) {                        // the previous evaluation of this plan ended in an error: the arrival counter
         GPV_HIP(hipMemsetAsync(pl->d_ticket, 0, 64, st));   // of its kernel may be non-zero (no workgroup would ever be "last")
         pl->ticket_dirty = false;
     }
     pl->sums_by_seq = final_here;
     if (final_here) ++pl->seq;
-    a.seq_cells = (final_here && !cm) ? seq_cells : nullptr;
+    a.seq_cells = (final_here && !cm) ? seq_cells_of(pl) : nullptr;
     a.seq = pl->seq;
-    a.nug_cell = (flags & GPV_WANT_DENOM) ? pl->d_nug_post : nullptr;
+    a.nug_cell = (flags & GPV_WANT_DENOM) ? pl->d_nug_post.get() : nullptr;
     a.rows = pl->rows;
     a.nlocs = pl->Nlocs;
     a.locs_ld = pl->locs_ld;
     a.dim = pl->dim;
     a.cov = cs.cov;
-    a.flags = flags | (fused ? kFlagFused : 0) | ((fused && mean_b) ? kFlagBoth : 0);
+    a.flags = flags | (fused ? kFlagFused : 0) | ((fused && (flags & GPV_WANT_MEAN_B)) ? kFlagBoth : 0);
     a.sig0 = cs.sig0; a.sA = cs.sA; a.cA = cs.cA; a.sB = cs.sB; a.cB = cs.cB;
     // The Matern kernels multiply the coordinates by cA = sqrt(2 nu)/range once per row instead of the distance once per
     // pair.  Where c * |x| would overflow (range below 1e-300 of the coordinates' magnitude) the reference's own dist/range
@@ -968,83 +892,94 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
     // Same outcome here, through the diagonal.  (nu = 0.5 gives exact zeros there instead, an independent model: not mirrored.)
     if (cs.cov != COV_DENSE && cs.cov != COV_ESQE && !(std::fabs(cs.cA) * pl->coord_maxabs < 1e300)) a.sig0 = NAN;
     a.mt = nullptr; a.mt_base = 0; a.mt_nseg = 0; a.mt_full = 0; a.mt_win = 0;
-    // The lean likelihood-only kernel leaves out what these facts make a no-op (the launcher checks family, dimension and
-    // row length, sets_args_lean):
-    //   coordinates finite, nuggets finite and <= 2^990, sigma^2 finite and small against 2^990: no NaN to inject into a
-    //     diagonal, none above the 2^990 clamp;
-    //   t_bounded: parameters finite and cA * (bounding-box diagonal) <= 500: no pair's scaled distance reaches the clamp at
-    //     1000 (500 leaves the rounding of this product and of the kernel's own sum of squares a wide margin);
-    //   idx32; flags exactly GPV_WANT_LOGLIK_Z.
-    // GPV_NO_LEAN=1: always the general likelihood-only kernel (tests and A/B runs).
-    {
-        static const bool no_lean = getenv("GPV_NO_LEAN") != nullptr;
-        const bool nug_ok = pl->nug_is_scalar ? (std::isfinite(pl->nug_scalar) && pl->nug_scalar <= 0x1p990) : pl->nug_vec_ok;
-        const bool parms_ok = std::isfinite(a.sig0) && std::fabs(a.sig0) <= 0x1p930 && std::isfinite(a.sA) && std::isfinite(a.cA);
-        const bool t_bounded = parms_ok && std::fabs(a.cA) * pl->bbox_diam <= 500.0;
-        const bool only_z = a.flags == GPV_WANT_LOGLIK_Z;
-        a.task_pad = pl->d_task_pad;
-        a.lean_ok = (!no_lean && pl->d_task_pad && pl->coords_finite && nug_ok && pl->idx32 && t_bounded && only_z) ? 1 : 0;
+    return GPV_OK;
+}
+
+// The lean likelihood-only kernel leaves out what these facts make a no-op (the launcher checks family, dimension and
+// row length, sets_args_lean):
+//   coordinates finite, nuggets finite and <= 2^990, sigma^2 finite and small against 2^990: no NaN to inject into a
+//     diagonal, none above the 2^990 clamp;
+//   t_bounded: parameters finite and cA * (bounding-box diagonal) <= 500: no pair's scaled distance reaches the clamp at
+//     1000 (500 leaves the rounding of this product and of the kernel's own sum of squares a wide margin);
+//   idx32; flags exactly GPV_WANT_LOGLIK_Z.
+// GPV_NO_LEAN=1: always the general likelihood-only kernel (tests and A/B runs).
+static void lean_facts(const gpv_plan *pl, SetArgs &a)
+{
+    static const bool no_lean = getenv("GPV_NO_LEAN") != nullptr;
+    const bool nug_ok = pl->nug_is_scalar ? (std::isfinite(pl->nug_scalar) && pl->nug_scalar <= 0x1p990) : pl->nug_vec_ok;
+    const bool parms_ok = std::isfinite(a.sig0) && std::fabs(a.sig0) <= 0x1p930 && std::isfinite(a.sA) && std::isfinite(a.cA);
+    const bool t_bounded = parms_ok && std::fabs(a.cA) * pl->bbox_diam <= 500.0;
+    const bool only_z = a.flags == GPV_WANT_LOGLIK_Z;
+    a.task_pad = pl->d_task_pad;
+    a.lean_ok = (!no_lean && pl->d_task_pad && pl->coords_finite && nug_ok && pl->idx32 && t_bounded && only_z) ? 1 : 0;
+}
+
+// LDS window of the kernel (gpv_sets_kernel.hpp, mt_window_rows): of the table's `noct` octaves of s = dist/range, the first
+// of those `win_oct` consecutive ones that hold most of the pair distances inside the plan's conditioning sets.  dist_hist counts
+// distances by quarter octave, e_lo is the binary exponent of the table's first segment, sh = log2 |cA|.
+static int matern_window_octave(const std::vector<int64_t> &dist_hist, int e_lo, int noct, int win_oct, double sh)
+{
+    const int kHist = (int)dist_hist.size();
+    std::vector<double> H((size_t)noct, 0.0);
+    for (int ex = 0; ex < kHist; ++ex) {
+        if (!dist_hist[(size_t)ex]) continue;
+        const int o = (int)std::floor(((double)(ex - kHist / 2) + 0.5) * 0.25 + sh) - e_lo;   // the bin's centre
+        if (o >= 0 && o < noct) H[(size_t)o] += (double)dist_hist[(size_t)ex];
     }
-    if (cs.cov == COV_MATERN_GEN) {
-        static const bool no_tab = getenv("GPV_NO_MATERN_TABLE") != nullptr;
-        if (!no_tab && pl->dist_min > 0.0 && pl->dist_max >= pl->dist_min) {
-            constexpr int kMaxSeg = 80 * MaternTab::SPO;                   // 80 octaves
-            // two device copies of the table used alternately (and, for the host fit GPV_MATERN_TABLE_HOST=1 only, two pinned
-            // staging buffers guarded by an event each, so that filling one never waits for the stream: the previous
-            // evaluation may still be reading the other copy)
-            const size_t tabb = sizeof(double) * kMaxSeg * MaternTab::ROW;
-            const int sl = pl->mt_slot ^= 1;
-            if (!pl->h_mt2[sl]) {
-                GPV_HIP(hipHostMalloc((void **)&pl->h_mt2[sl], tabb, hipHostMallocDefault));
-                GPV_HIP(hipMalloc((void **)&pl->d_mt2[sl], tabb));
-                GPV_HIP(hipEventCreateWithFlags(&pl->mt_ev[sl], hipEventDisableTiming));
-            } else {
-                GPV_HIP(hipEventSynchronize(pl->mt_ev[sl]));              // two evaluations ago: long done in steady state
-            }
-            int full = 0, e_lo = 0;
-            static const bool host_fit = getenv("GPV_MATERN_TABLE_HOST") != nullptr;    // cross-check of the device fit
-            const double s_lo = 0.5 * pl->dist_min * cs.cA, s_hi = 4.0 * pl->dist_max * cs.cA;
-            if (host_fit) matern_tab_build(cs.sB, s_lo, s_hi, cs.sA, pl->h_mt2[sl], &a.mt_base, &a.mt_nseg, kMaxSeg, &full);
-            else (void)matern_tab_range(s_lo, s_hi, kMaxSeg, &e_lo, &a.mt_base, &a.mt_nseg, &full);
-            a.mt_full = (a.mt_nseg > 0 && full) ? 1 : 0;
-            // LDS window of the kernel (gpv_sets_kernel.hpp, mt_window_rows): the octaves of s = dist/range -- as many as the
-            // instantiation has room for -- that hold most of the pair distances inside the plan's conditioning sets
-            a.mt_win = 0;
-            const int win_oct = sets_mt_window_rows(pl->P, pl->dim) / MaternTab::SPO;
-            if (a.mt_nseg > 0 && win_oct > 0 && !pl->dist_hist.empty()) {
-                const int e_lo = (a.mt_base >> MaternTab::LSPO) - 1023;   // binary exponent of the table's first segment
-                const int noct = a.mt_nseg / MaternTab::SPO;
-                const double sh = std::log2(std::fabs(cs.cA));
-                const int kHist = (int)pl->dist_hist.size();
-                std::vector<double> H((size_t)noct, 0.0);
-                for (int ex = 0; ex < kHist; ++ex) {
-                    if (!pl->dist_hist[(size_t)ex]) continue;
-                    const int o = (int)std::floor(((double)(ex - kHist / 2) + 0.5) * 0.25 + sh) - e_lo;   // the bin's centre
-                    if (o >= 0 && o < noct) H[(size_t)o] += (double)pl->dist_hist[(size_t)ex];
-                }
-                double best = -1.0;
-                int bo = 0;
-                for (int o = 0; o + win_oct <= noct || o == 0; ++o) {
-                    double mw = 0.0;
-                    for (int t = 0; t < win_oct && o + t < noct; ++t) mw += H[(size_t)(o + t)];
-                    if (mw > best) { best = mw; bo = o; }
-                    if (o + win_oct > noct) break;
-                }
-                a.mt_win = MaternTab::SPO * bo;
-            }
-            if (a.mt_nseg > 0) {
-                // the fit runs on the evaluation's stream in front of the set kernel (~10 us; on the host it was 0.3 ms in
-                // series with every optimiser step); the stream orders it behind the previous evaluation's reads
-                if (host_fit)
-                    GPV_HIP(hipMemcpyAsync(pl->d_mt2[sl], pl->h_mt2[sl], sizeof(double) * (size_t)a.mt_nseg * MaternTab::ROW,
-                                           hipMemcpyHostToDevice, st));
-                else
-                    GPV_HIP(launch_matern_tab(cs.sB, e_lo, a.mt_nseg, cs.sA, pl->d_mt2[sl], st));
-                a.mt = pl->d_mt2[sl];
-            }
-            pl->mt_pending = sl;
-        }
+    double best = -1.0;
+    int bo = 0;
+    for (int o = 0; o + win_oct <= noct || o == 0; ++o) {
+        double mw = 0.0;
+        for (int t = 0; t < win_oct && o + t < noct; ++t) mw += H[(size_t)(o + t)];
+        if (mw > best) { best = mw; bo = o; }
+        if (o + win_oct > noct) break;
     }
+    return bo;
+}
+
+// general nu: the evaluation's table of normcon s^nu K_nu(s) e^s over the plan's range of pair distances, fitted on the
+// evaluation's stream in front of the set kernel.  GPV_NO_MATERN_TABLE=1: the kernel evaluates the Bessel function per pair.
+static int matern_table_prepare(gpv_plan *pl, const CovSetup &cs, hipStream_t st, SetArgs &a)
+{
+    static const bool no_tab = getenv("GPV_NO_MATERN_TABLE") != nullptr;
+    if (no_tab || !(pl->dist_min > 0.0) || !(pl->dist_max >= pl->dist_min)) return GPV_OK;
+    constexpr int kMaxSeg = 80 * MaternTab::SPO;                   // 80 octaves
+    // two device copies of the table used alternately (and, for the host fit GPV_MATERN_TABLE_HOST=1 only, two pinned
+    // staging buffers guarded by an event each, so that filling one never waits for the stream: the previous
+    // evaluation may still be reading the other copy)
+    const size_t tabn = (size_t)kMaxSeg * MaternTab::ROW;
+    const int sl = pl->mt_slot ^= 1;
+    GPV_BUF(pl->h_mt2[sl], ensure(tabn));
+    GPV_BUF(pl->d_mt2[sl], ensure(tabn));
+    if (!pl->mt_ev[sl]) GPV_HIP(hipEventCreateWithFlags(pl->mt_ev[sl].put(), hipEventDisableTiming));
+    else GPV_HIP(hipEventSynchronize(pl->mt_ev[sl]));             // two evaluations ago: long done in steady state
+    int full = 0, e_lo = 0;
+    static const bool host_fit = getenv("GPV_MATERN_TABLE_HOST") != nullptr;    // cross-check of the device fit
+    const double s_lo = 0.5 * pl->dist_min * cs.cA, s_hi = 4.0 * pl->dist_max * cs.cA;
+    if (host_fit) matern_tab_build(cs.sB, s_lo, s_hi, cs.sA, pl->h_mt2[sl], &a.mt_base, &a.mt_nseg, kMaxSeg, &full);
+    else (void)matern_tab_range(s_lo, s_hi, kMaxSeg, &e_lo, &a.mt_base, &a.mt_nseg, &full);
+    a.mt_full = (a.mt_nseg > 0 && full) ? 1 : 0;
+    const int win_oct = sets_mt_window_rows(pl->P, pl->dim) / MaternTab::SPO;   // as many octaves as the instantiation has room for
+    if (a.mt_nseg > 0 && win_oct > 0 && !pl->dist_hist.empty())
+        a.mt_win = MaternTab::SPO * matern_window_octave(pl->dist_hist, (a.mt_base >> MaternTab::LSPO) - 1023,
+                                                         a.mt_nseg / MaternTab::SPO, win_oct, std::log2(std::fabs(cs.cA)));
+    if (a.mt_nseg > 0) {
+        // the fit runs on the evaluation's stream in front of the set kernel (~10 us; on the host it was 0.3 ms in
+        // series with every optimiser step); the stream orders it behind the previous evaluation's reads
+        if (host_fit)
+            GPV_HIP(hipMemcpyAsync(pl->d_mt2[sl], pl->h_mt2[sl], sizeof(double) * (size_t)a.mt_nseg * MaternTab::ROW,
+                                   hipMemcpyHostToDevice, st));
+        else
+            GPV_HIP(launch_matern_tab(cs.sB, e_lo, a.mt_nseg, cs.sA, pl->d_mt2[sl], st));
+        a.mt = pl->d_mt2[sl];
+    }
+    pl->mt_pending = sl;
+    return GPV_OK;
+}
+
+// the conditioning-set kernel between the timing events; the partial sums are totalled by its last workgroup (no reduction launch)
+static int eval_launch_sets(gpv_plan *pl, const SetArgs &a, hipStream_t st)
+{
     if (pl->timing) GPV_HIP(hipEventRecord(pl->ev0, st));
     pl->last_set_kernel = pl->generic ? 0 : sets_kernel_kind(pl->P, a);
     if (pl->generic) GPV_HIP(launch_sets_generic(pl->P, a, pl->cus, &pl->grid, st));
@@ -1055,109 +990,117 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
         GPV_HIP(hipEventRecord(pl->mt_ev[pl->mt_pending], st));
         pl->mt_pending = -1;
     }
-    // (the partial sums are totalled by the set kernel's last workgroup: no reduction launch)
-    if (cm) {
-        const RcclApi *R = rccl_api();
-        if (!R) return GPV_ERR_STATE;
-        const int rr = R->AllReduce(pl->d_sums, pl->d_sums, (size_t)kNSums, /*ncclDouble*/ 8, /*ncclSum*/ 0, cm->comm, st);
-        if (rr != 0) return note_rccl(rr, "ncclAllReduce");
-        // to the host by a 64-thread kernel that stores into pinned memory, not by a copy command: an event behind a 64-byte
-        // hipMemcpyAsync took ~100 us longer to turn ready under hipEventQuery (measured, tools/comm_diag.py)
-        if (d_sums_out) {
-            GPV_HIP(hipMemcpyAsync(d_sums_out, pl->d_sums, sizeof(double) * kNSums, hipMemcpyDeviceToDevice, st));
-        } else if (pl->sums_by_seq) {
-            GPV_HIP(launch_publish_sums(pl->d_sums, pl->h_sums_dev, seq_cells, pl->seq, st));
-        } else {
-            GPV_HIP(hipMemcpyAsync(pl->h_sums, pl->d_sums, sizeof(double) * kNSums, hipMemcpyDeviceToHost, st));
-        }
+    return GPV_OK;
+}
+
+// with a communicator: this rank's totals summed over the ranks in place, then handed to the host or the caller's buffer
+static int eval_allreduce(gpv_plan *pl, hipStream_t st, double *d_sums_out)
+{
+    const RcclApi *R = rccl_api();
+    if (!R) return GPV_ERR_STATE;
+    const int rr = R->AllReduce(pl->d_sums, pl->d_sums, (size_t)kNSums, /*ncclDouble*/ 8, /*ncclSum*/ 0, pl->comm->comm, st);
+    if (rr != 0) return note_rccl(rr, "ncclAllReduce");
+    // to the host by a 64-thread kernel that stores into pinned memory, not by a copy command: an event behind a 64-byte
+    // hipMemcpyAsync took ~100 us longer to turn ready under hipEventQuery (measured, tools/comm_diag.py)
+    if (d_sums_out) GPV_HIP(hipMemcpyAsync(d_sums_out, pl->d_sums, sizeof(double) * kNSums, hipMemcpyDeviceToDevice, st));
+    else if (pl->sums_by_seq) GPV_HIP(launch_publish_sums(pl->d_sums, pl->h_sums_dev, seq_cells_of(pl), pl->seq, st));
+    else GPV_HIP(hipMemcpyAsync(pl->h_sums, pl->d_sums, sizeof(double) * kNSums, hipMemcpyDeviceToHost, st));
+    return GPV_OK;
+}
+
+// the mean sweep R^T u = t, mu = -u: the dense top block, the head levels in one workgroup, then one launch per level
+static hipError_t mean_sweep_enqueue(gpv_plan *pl, const PostArgs &pa, hipStream_t st)
+{
+    hipError_t e = hipSuccess;
+    if (pl->top_K > 0) e = launch_mean_top(pa, pl->d_u, pl->top_K, pl->d_topinfo, pl->d_toprows, st);
+    if (e == hipSuccess) e = launch_mean_head(pa, pl->d_order2, pl->d_u, pl->d_levptr2, pl->mean_head_levels, st);
+    for (size_t lv = (size_t)pl->mean_head_levels; e == hipSuccess && lv + 1 < pl->levptr2.size(); ++lv)
+        e = launch_mean_level(pa, pl->d_order2, pl->d_u, pl->levptr2[lv], pl->levptr2[lv + 1] - pl->levptr2[lv], st);
+    if (e == hipSuccess) e = launch_negate(pl->d_u, pl->d_mu, pl->Nlocs, st);
+    return e;
+}
+
+// the posterior pass behind the set kernel: compaction (unless fused), the factor's levels and top block, the two sums into
+// `mirror` and the mean sweep; replayed from the plan's captured graph of that combination
+static int posterior_pass_enqueue(gpv_plan *pl, int flags, double *mirror, hipStream_t st)
+{
+    const bool want_mean = (flags & GPV_WANT_MEAN) != 0, mean_b = (flags & GPV_WANT_MEAN_B) != 0, fused = pl->post_fused;
+    pl->have_factor = false;                                         // C is being rewritten: true again once the pass is enqueued
+    // (constant nugget: the set kernel above left it in d_nug_post[0]; vector: d_nug_user, a fixed address as well)
+    PostArgs pa;
+    pa.colptr = pl->d_colptr; pa.crow = pl->d_crow;
+    pa.colrec = pl->d_colrec; pa.rowrec = pl->d_rowrec; pa.tp = pl->d_tp;
+    pa.C = pl->d_C; pa.cboff = pl->d_cboff; pa.z = pl->d_zuser;
+    pa.nuggets = pl->nug_is_scalar ? nullptr : (pl->d_obs ? pl->d_nug_masked : pl->d_nug_user);
+    pa.nug_cell = pl->d_nug_post;
+    pa.tvec = pl->d_tvec; pa.rdiag = pl->d_rdiag; pa.ld = pl->post_ld;
+    pa.meanrec = pl->d_meanrec;
+    pa.rr0 = pl->d_rr0;
+    // cond.yz = 'zy' (R/vecchia_prediction.R:68-70,118-126): V.ord is the reversed latent block B of U itself, no
+    // factorisation.  After createU's removal of the dummy latent variables (R/createU.R:166-171) no latent row has an
+    // entry in an observed column, so z2 = U[latent,] z1 = B a with a = z1[latent columns] = the a_k the set kernel
+    // already produces, and mu = -B^-T B^-1 z2 = -B^-T a: ONE lower-triangular solve, the level-scheduled mean sweep
+    // with R := B (the compaction writes B into both halves) and t := a.
+    if (mean_b) pa.tvec = pl->d_avec;
+    auto enqueue = [&]() -> hipError_t {
+        hipError_t e = fused ? hipSuccess
+                             : launch_posterior_compact(pl->d_L, pl->P, pl->d_avec, pl->d_colptr, pl->d_ccol, pl->d_cslot,
+                                                        pl->d_cdel, pl->Nlocs, pl->post_nnz, pl->d_C, mean_b, st);
+        if (mean_b) return e == hipSuccess ? mean_sweep_enqueue(pl, pa, st) : e;
+        for (size_t lv = 0; e == hipSuccess && lv + 1 < pl->levptr.size(); ++lv)
+            e = launch_posterior_level(pa, pl->levptr[lv], pl->levptr[lv + 1] - pl->levptr[lv], lv == 0,
+                                       lv < pl->lev_lpc.size() ? pl->lev_lpc[lv] : 64, pl->lev_rr0[lv], st);
+        if (e == hipSuccess && pl->top_K > 0)
+            e = launch_posterior_top(pa, (int)(pl->Nlocs - pl->top_K), pl->top_K, pl->d_toppart, pl->d_topinfo, pl->d_toprows,
+                                     pl->top_rr0, st);
+        if (e == hipSuccess)
+            e = launch_sum_pair(pl->d_rdiag, pl->d_tvec, pl->Nlocs, pl->d_post_part, pl->d_sums, mirror, st);
+        if (e == hipSuccess && want_mean) e = mean_sweep_enqueue(pl, pa, st);
+        return e;
+    };
+    static const bool post_skip = dev_getenv("GPV_POST_SKIP") != nullptr;   // developer aid (timing only, results are WRONG): the set
+    if (post_skip) return GPV_OK;                                           // kernel of mode S without its pass
+    gpv_plan::PostGraph &g = pl->pgraph[(want_mean ? 1 : 0) + (pl->nug_is_scalar ? 0 : 2) + (mean_b ? 4 : 0)];
+    bool captured = false;
+    GPV_HIP(graph_replay(g.exec, st, enqueue, /*stale: another mirror address*/ g.sums_out != mirror, &captured));
+    if (captured) g.sums_out = mirror;
+    pl->have_factor = true;                                          // (gpv_plan_lincomb reads C as this pass leaves it)
+    ++pl->factor_stamp;
+    if (want_mean || mean_b) pl->have_mean = true;
+    return GPV_OK;
+}
+
+static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nuggets, int64_t n_nuggets, int flags,
+                          void *stream_v, double *d_sums_out)
+{
+    flags &= 63;                                                  // (the bits above are the kernels' own)
+    if (flags & GPV_WANT_MEAN) flags |= GPV_WANT_DENOM;
+    if ((flags & GPV_WANT_MEAN_B) && (flags & GPV_WANT_DENOM)) return GPV_ERR_BAD_ARG;      // one posterior pass per evaluation
+    if (flags & kPostFlags) {
+        if (!pl->have_post) return GPV_ERR_STATE;
+        flags |= GPV_WANT_NUMERATOR;
+        if (!pl->post_fused) flags |= GPV_WANT_U;                 // (fused: the set kernel fills the compact blocks itself)
     }
-    if (flags & (GPV_WANT_DENOM | GPV_WANT_MEAN_B)) {
-        pl->have_factor = false;                                         // C is being rewritten: true again once the pass is enqueued
-        // (constant nugget: the set kernel above left it in d_nug_post[0]; vector: d_nug_user, a fixed address as well)
-        PostArgs pa;
-        pa.colptr = pl->d_colptr; pa.crow = pl->d_crow;
-        pa.colrec = pl->d_colrec; pa.rowrec = pl->d_rowrec; pa.tp = pl->d_tp;
-        pa.C = pl->d_C; pa.cboff = pl->d_cboff; pa.z = pl->d_zuser;
-        pa.nuggets = pl->nug_is_scalar ? nullptr : (pl->d_obs ? pl->d_nug_masked : pl->d_nug_user);
-        pa.nug_cell = pl->d_nug_post;
-        pa.tvec = pl->d_tvec; pa.rdiag = pl->d_rdiag; pa.ld = pl->post_ld;
-        pa.meanrec = pl->d_meanrec;
-        pa.rr0 = pl->d_rr0;
-        const bool want_mean = (flags & GPV_WANT_MEAN) != 0;
-        // cond.yz = 'zy' (R/vecchia_prediction.R:68-70,118-126): V.ord is the reversed latent block B of U itself, no
-        // factorisation.  After createU's removal of the dummy latent variables (R/createU.R:166-171) no latent row has an
-        // entry in an observed column, so z2 = U[latent,] z1 = B a with a = z1[latent columns] = the a_k the set kernel
-        // already produces, and mu = -B^-T B^-1 z2 = -B^-T a: ONE lower-triangular solve, the level-scheduled mean sweep
-        // with R := B (the compaction writes B into both halves) and t := a.
-        if (mean_b) pa.tvec = pl->d_avec;
-        auto enqueue = [&]() -> hipError_t {
-            hipError_t e = fused ? hipSuccess
-                                 : launch_posterior_compact(pl->d_L, pl->P, pl->d_avec, pl->d_colptr, pl->d_ccol, pl->d_cslot,
-                                                            pl->d_cdel, pl->Nlocs, pl->post_nnz, pl->d_C, mean_b, st);
-            if (mean_b) {
-                if (e == hipSuccess && pl->top_K > 0)
-                    e = launch_mean_top(pa, pl->d_u, pl->top_K, pl->d_topinfo, pl->d_toprows, st);
-                if (e == hipSuccess)
-                    e = launch_mean_head(pa, pl->d_order2, pl->d_u, pl->d_levptr2, pl->mean_head_levels, st);
-                for (size_t lv = (size_t)pl->mean_head_levels; e == hipSuccess && lv + 1 < pl->levptr2.size(); ++lv)
-                    e = launch_mean_level(pa, pl->d_order2, pl->d_u, pl->levptr2[lv],
-                                          pl->levptr2[lv + 1] - pl->levptr2[lv], st);
-                if (e == hipSuccess) e = launch_negate(pl->d_u, pl->d_mu, pl->Nlocs, st);
-                return e;
-            }
-            for (size_t lv = 0; e == hipSuccess && lv + 1 < pl->levptr.size(); ++lv)
-                e = launch_posterior_level(pa, pl->levptr[lv], pl->levptr[lv + 1] - pl->levptr[lv], lv == 0,
-                                           lv < pl->lev_lpc.size() ? pl->lev_lpc[lv] : 64, pl->lev_rr0[lv], st);
-            if (e == hipSuccess && pl->top_K > 0)
-                e = launch_posterior_top(pa, (int)(pl->Nlocs - pl->top_K), pl->top_K, pl->d_toppart, pl->d_topinfo, pl->d_toprows,
-                                         pl->top_rr0, st);
-            if (e == hipSuccess)
-                e = launch_sum_pair(pl->d_rdiag, pl->d_tvec, pl->Nlocs, pl->d_post_part, pl->d_sums, mirror, st);
-            if (want_mean) {
-                if (e == hipSuccess && pl->top_K > 0)
-                    e = launch_mean_top(pa, pl->d_u, pl->top_K, pl->d_topinfo, pl->d_toprows, st);
-                if (e == hipSuccess)
-                    e = launch_mean_head(pa, pl->d_order2, pl->d_u, pl->d_levptr2, pl->mean_head_levels, st);
-                for (size_t lv = (size_t)pl->mean_head_levels; e == hipSuccess && lv + 1 < pl->levptr2.size(); ++lv)
-                    e = launch_mean_level(pa, pl->d_order2, pl->d_u, pl->levptr2[lv],
-                                          pl->levptr2[lv + 1] - pl->levptr2[lv], st);
-                if (e == hipSuccess) e = launch_negate(pl->d_u, pl->d_mu, pl->Nlocs, st);
-            }
-            return e;
-        };
-        static const bool post_skip = dev_getenv("GPV_POST_SKIP") != nullptr;   // developer aid (timing only, results are WRONG): the set
-        if (post_skip) { pl->last_stream = st; pl->evaluated = true; return GPV_OK; }   // kernel of mode S without its pass
-        gpv_plan::PostGraph &g = pl->pgraph[(want_mean ? 1 : 0) + (pl->nug_is_scalar ? 0 : 2) + (mean_b ? 4 : 0)];
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        (void)hipStreamIsCapturing(st, &cap);
-        static const bool no_graph = getenv("GPV_NO_GRAPH") != nullptr;
-        bool launched = false;
-        if (!no_graph && cap == hipStreamCaptureStatusNone) {
-            if (!g.exec || g.sums_out != mirror) {                         // first use, or another mirror address
-                if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-                if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    const hipError_t e = enqueue();
-                    hipGraph_t graph = nullptr;
-                    const hipError_t e2 = hipStreamEndCapture(st, &graph);
-                    if (e == hipSuccess && e2 == hipSuccess && graph &&
-                        hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0) == hipSuccess)
-                        g.sums_out = mirror;
-                    else
-                        g.exec = nullptr;
-                    if (graph) (void)hipGraphDestroy(graph);
-                    (void)hipGetLastError();
-                }
-            }
-            if (g.exec) {
-                GPV_HIP(hipGraphLaunch(g.exec, st));
-                launched = true;
-            }
-        }
-        if (!launched) GPV_HIP(enqueue());                               // inside someone else's capture, or graphs off
-        pl->have_factor = true;                                          // (gpv_plan_lincomb reads C as this pass leaves it)
-        ++pl->factor_stamp;
-        if (want_mean || mean_b) pl->have_mean = true;
-    }
+    if ((flags & (GPV_WANT_LOGLIK_Z | GPV_WANT_NUMERATOR)) && !pl->has_z) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = stream_v ? (hipStream_t)stream_v : (hipStream_t)pl->stream;
+    // the plan's buffers (nuggets, partial sums, U entries, posterior blocks) are reused by every evaluation: one that
+    // moves to ANOTHER stream first waits for the previous stream, evaluations on one stream are ordered by it
+    // (not while `st` is being captured into a graph: a host wait is illegal there, and the caller who captures owns the
+    // ordering against the plan's earlier evaluations)
+    hipStreamCaptureStatus cap0 = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cap0) != hipSuccess) { (void)hipGetLastError(); cap0 = hipStreamCaptureStatusNone; }
+    if (pl->last_stream && pl->last_stream != st && cap0 == hipStreamCaptureStatusNone) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (flags & GPV_WANT_U) GPV_BUF(pl->d_L, ensure((size_t)(pl->rows > 0 ? pl->rows : 1) * pl->P));
+    int rc = cs.cov != COV_DENSE ? eval_nuggets(pl, nuggets, n_nuggets, flags, st) : GPV_OK;
+    SetArgs a;
+    if (rc == GPV_OK) rc = eval_set_args(pl, cs, flags, st, d_sums_out, a);
+    if (rc != GPV_OK) return rc;
+    lean_facts(pl, a);
+    if (cs.cov == COV_MATERN_GEN && (rc = matern_table_prepare(pl, cs, st, a)) != GPV_OK) return rc;
+    if ((rc = eval_launch_sets(pl, a, st)) != GPV_OK) return rc;
+    if (pl->comm && (rc = eval_allreduce(pl, st, d_sums_out)) != GPV_OK) return rc;
+    if ((flags & kPostFlags) && (rc = posterior_pass_enqueue(pl, flags, a.sums_copy, st)) != GPV_OK) return rc;
     pl->evaluated = true;
     pl->have_U = (flags & GPV_WANT_U) != 0;
     pl->last_stream = st;
@@ -1220,18 +1163,17 @@ int gpv_comm_create(gpv_comm **out, int device, int rank, int world, const void 
     // prove the communicator (and the hand-declared enum values) before any evaluation depends on it: all-reduce
     // (1, rank + 1) as doubles with "sum"; every rank must read (world, world (world + 1) / 2)
     {
-        double h[2] = {1.0, (double)(rank + 1)}, *d = nullptr;
-        hipStream_t ps = nullptr;
+        double h[2] = {1.0, (double)(rank + 1)};
+        DevBuf<double> d;
+        Stream ps;
         int bad = 0;
-        if (hipMalloc((void **)&d, sizeof(h)) != hipSuccess || hipStreamCreateWithFlags(&ps, hipStreamNonBlocking) != hipSuccess ||
-            hipMemcpy(d, h, sizeof(h), hipMemcpyHostToDevice) != hipSuccess)
-            bad = 1;
+        if (d.upload(h, 2) != hipSuccess || hipStreamCreateWithFlags(ps.put(), hipStreamNonBlocking) != hipSuccess) bad = 1;
         int ar = 0;
         if (!bad) ar = R->AllReduce(d, d, 2, /*ncclDouble*/ 8, /*ncclSum*/ 0, c, ps);
         if (!bad && ar == 0 && (hipStreamSynchronize(ps) != hipSuccess || hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost) != hipSuccess))
             bad = 1;
-        if (ps) (void)hipStreamDestroy(ps);
-        if (d) (void)hipFree(d);
+        ps.reset();
+        (void)d.reset();
         const double want0 = (double)world, want1 = 0.5 * (double)world * (double)(world + 1);
         if (bad || ar != 0 || h[0] != want0 || h[1] != want1) {
             (void)R->CommDestroy(c);
@@ -1294,11 +1236,8 @@ static int build_posterior_impl(gpv_plan *pl, const int *revNN, const int *revCo
     pl->have_post = false;
     pl->have_factor = false;
     pl->lc_ready = false;
-    if (pl->lc_graph) { (void)hipGraphExecDestroy(pl->lc_graph); pl->lc_graph = nullptr; }
-    if (pl->st_graph) { (void)hipGraphExecDestroy(pl->st_graph); pl->st_graph = nullptr; }
     if (pl->last_stream) { GPV_HIP(hipSetDevice(pl->device)); GPV_HIP(hipStreamSynchronize(pl->last_stream)); }
-    for (auto &g : pl->pgraph)
-        if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
+    pl->drop_graphs();
     if (pl->row_begin != 0 || pl->row_end != pl->Nlocs) return GPV_ERR_BAD_ARG;   // not shardable
     if (pl->Nlocs >= (int64_t)1 << 31) return GPV_ERR_BAD_ARG;
     const int64_t n = pl->Nlocs;
@@ -1677,64 +1616,51 @@ static int build_posterior_impl(gpv_plan *pl, const int *revNN, const int *revCo
         GPV_HIP(hipMemcpy(pl->d_cond, cdh.data(), cdh.size(), hipMemcpyHostToDevice));
         pl->post_fused = fuse;
     }
-    auto up = [&](void **dst, const void *src, size_t bytes) -> int {
-        if (*dst) { (void)hipFree(*dst); *dst = nullptr; }
-        if (GPV_HIP_FAILED(hipMalloc(dst, bytes ? bytes : 8))) return GPV_ERR_HIP;
-        if (bytes && GPV_HIP_FAILED(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice))) return GPV_ERR_HIP;
-        return GPV_OK;
-    };
-    int rc = GPV_OK;
-    if ((rc = up((void **)&pl->d_colptr, colptr.data(), colptr.size() * 4)) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_crow, crow.data(), nnz * 4)) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_cslot, cslot.data(), nnz)) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_colrec, colrec.data(), colrec.size() * sizeof(int4))) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_rowrec, rowrec.data(), rowrec.size() * sizeof(int4))) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_rr0, rr0.data(), rr0.size() * sizeof(int4))) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_tp, tp.data(), tp.size())) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_ccol, ccol.data(), nnz * 4)) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_cboff, cboff.data(), cboff.size() * 4)) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_cdel, cdel.data(), cdel.size() * 4)) != GPV_OK) return rc;
-    if (pl->d_C) { (void)hipFree(pl->d_C); pl->d_C = nullptr; }
-    GPV_HIP(hipMalloc((void **)&pl->d_C, sizeof(double2) * (size_t)c_entries));
+    GPV_BUF(pl->d_colptr, upload(colptr.data(), colptr.size()));
+    GPV_BUF(pl->d_crow, upload(crow.data(), nnz));
+    GPV_BUF(pl->d_cslot, upload(cslot.data(), nnz));
+    GPV_BUF(pl->d_colrec, upload(colrec.data(), colrec.size()));
+    GPV_BUF(pl->d_rowrec, upload(rowrec.data(), rowrec.size()));
+    GPV_BUF(pl->d_rr0, upload(rr0.data(), rr0.size()));
+    GPV_BUF(pl->d_tp, upload(tp.data(), tp.size()));
+    GPV_BUF(pl->d_ccol, upload(ccol.data(), nnz));
+    GPV_BUF(pl->d_cboff, upload(cboff.data(), cboff.size()));
+    GPV_BUF(pl->d_cdel, upload(cdel.data(), cdel.size()));
+    GPV_BUF(pl->d_C, resize((size_t)c_entries));
     pl->post_nnz = (int64_t)nnz;
-    if ((rc = up((void **)&pl->d_order2, order2.data(), order2.size() * 4)) != GPV_OK) return rc;
+    GPV_BUF(pl->d_order2, upload(order2.data(), order2.size()));
     {
         std::vector<int4> meanrec(order2.size());
         for (size_t i = 0; i < order2.size(); ++i) {
             const int32_t k = order2[i];
             meanrec[(size_t)i] = make_int4(k, cboff[(size_t)k], colptr[(size_t)k + 1] - colptr[(size_t)k], colptr[(size_t)k]);
         }
-        if ((rc = up((void **)&pl->d_meanrec, meanrec.data(), meanrec.size() * sizeof(int4))) != GPV_OK) return rc;
+        GPV_BUF(pl->d_meanrec, upload(meanrec.data(), meanrec.size()));
     }
-    if ((rc = up((void **)&pl->d_levptr2, pl->levptr2.data(), pl->levptr2.size() * 4)) != GPV_OK) return rc;
-    if (pl->d_toppart) { (void)hipFree(pl->d_toppart); pl->d_toppart = nullptr; }
-    if (pl->top_K > 0) GPV_HIP(hipMalloc((void **)&pl->d_toppart, sizeof(double) * 66 * (size_t)pl->top_K));
-    if ((rc = up((void **)&pl->d_topinfo, topinfo.data(), topinfo.size() * sizeof(int2))) != GPV_OK) return rc;
-    if ((rc = up((void **)&pl->d_toprows, toprows.data(), toprows.size())) != GPV_OK) return rc;
+    GPV_BUF(pl->d_levptr2, upload(pl->levptr2.data(), pl->levptr2.size()));
+    GPV_HIP(pl->d_toppart.reset());
+    if (pl->top_K > 0) GPV_BUF(pl->d_toppart, resize(66 * (size_t)pl->top_K));
+    GPV_BUF(pl->d_topinfo, upload(topinfo.data(), topinfo.size()));
+    GPV_BUF(pl->d_toprows, upload(toprows.data(), toprows.size()));
     pl->mean_head_levels = 0;
     static const bool no_head = dev_getenv("GPV_NO_MEAN_HEAD") != nullptr;
     while (!no_head && (size_t)pl->mean_head_levels + 1 < pl->levptr2.size() &&
            pl->levptr2[(size_t)pl->mean_head_levels + 1] - pl->levptr2[(size_t)pl->mean_head_levels] <= kMeanHeadMax)
         ++pl->mean_head_levels;
     if (pl->mean_head_levels < 4) pl->mean_head_levels = 0;            // not worth a launch of its own
-    const size_t nd = sizeof(double) * (size_t)n;
-    if (!pl->d_avec_base) {
-        GPV_HIP(hipMalloc((void **)&pl->d_avec_base, nd + 64));
-        pl->d_avec = pl->d_avec_base + 8;                              // 64 bytes of header in front (SetArgs::aout)
-    }
+    GPV_BUF(pl->d_avec_base, ensure((size_t)n + 8));
+    pl->d_avec = pl->d_avec_base + 8;                                  // 64 bytes of header in front (SetArgs::aout)
     {
-        const unsigned long long hdr[4] = {(unsigned long long)(uintptr_t)pl->d_C, (unsigned long long)(uintptr_t)pl->d_cboff, 0ull, 0ull};
+        const unsigned long long hdr[4] = {(unsigned long long)(uintptr_t)pl->d_C.get(), (unsigned long long)(uintptr_t)pl->d_cboff.get(), 0ull, 0ull};
         GPV_HIP(hipMemcpy(pl->d_avec - 4, hdr, sizeof(hdr), hipMemcpyHostToDevice));
     }
-    if (!pl->d_nug_post) GPV_HIP(hipMalloc((void **)&pl->d_nug_post, 64));
-    for (auto &g : pl->pgraph)                                         // the schedule may have changed
-        if (g.exec) { (void)hipGraphExecDestroy(g.exec); g.exec = nullptr; }
-    if (!pl->d_tvec) GPV_HIP(hipMalloc((void **)&pl->d_tvec, nd));
-    if (!pl->d_rdiag) GPV_HIP(hipMalloc((void **)&pl->d_rdiag, nd));
-    if (!pl->d_u) GPV_HIP(hipMalloc((void **)&pl->d_u, nd));
-    if (!pl->d_mu) GPV_HIP(hipMalloc((void **)&pl->d_mu, nd));
-    if (!pl->d_post_part) GPV_HIP(hipMalloc((void **)&pl->d_post_part, sizeof(double) * 2048));       // launch_sum_pair: 2 x 1024
-    if (!pl->d_L && !pl->post_fused) GPV_HIP(hipMalloc((void **)&pl->d_L, nd * pl->P));   // (fused: only when the caller wants U)
+    GPV_BUF(pl->d_nug_post, ensure(8));
+    GPV_BUF(pl->d_tvec, ensure((size_t)n));
+    GPV_BUF(pl->d_rdiag, ensure((size_t)n));
+    GPV_BUF(pl->d_u, ensure((size_t)n));
+    GPV_BUF(pl->d_mu, ensure((size_t)n));
+    GPV_BUF(pl->d_post_part, ensure(2048));                            // launch_sum_pair: 2 x 1024
+    if (!pl->post_fused) GPV_BUF(pl->d_L, ensure((size_t)n * pl->P));  // (fused: only when the caller wants U)
     pl->have_post = true;
     return GPV_OK;
 }
@@ -1760,15 +1686,14 @@ static int vl_begin_impl(gpv_plan *pl, int model, const double *likparms, const 
     GPV_HIP(hipSetDevice(pl->device));
     if (pl->last_stream && pl->last_stream != pl->stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
     const size_t nb = sizeof(double) * (size_t)pl->Nlocs;
-    double **bufs[] = {&pl->d_vl_z, &pl->d_vl_pm, &pl->d_vl_y[0], &pl->d_vl_y[1], &pl->d_vl_y0, &pl->d_nug_user, &pl->d_zuser};
-    for (double **b : bufs)
-        if (!*b) GPV_HIP(hipMalloc((void **)b, nb));
-    if (pl->dim > 3 && !pl->d_z) GPV_HIP(hipMalloc((void **)&pl->d_z, nb));
-    if (!pl->d_vl_out) GPV_HIP(hipMalloc((void **)&pl->d_vl_out, sizeof(double) * 4));
-    if (!pl->d_vl_flags) GPV_HIP(hipMalloc((void **)&pl->d_vl_flags, sizeof(int)));
-    if (!pl->d_vl_part) GPV_HIP(hipMalloc((void **)&pl->d_vl_part, sizeof(double) * 2048));
+    DevBuf<double> *bufs[] = {&pl->d_vl_z, &pl->d_vl_pm, &pl->d_vl_y[0], &pl->d_vl_y[1], &pl->d_vl_y0, &pl->d_nug_user, &pl->d_zuser};
+    for (DevBuf<double> *b : bufs) GPV_BUF(*b, ensure((size_t)pl->Nlocs));
+    if (pl->dim > 3) GPV_BUF(pl->d_z, ensure((size_t)pl->Nlocs));
+    GPV_BUF(pl->d_vl_out, ensure(4));
+    GPV_BUF(pl->d_vl_flags, ensure(1));
+    GPV_BUF(pl->d_vl_part, ensure(2048));
     if (!pl->h_vl) {
-        GPV_HIP(hipHostMalloc((void **)&pl->h_vl, sizeof(double) * 8, hipHostMallocDefault));
+        GPV_BUF(pl->h_vl, resize(8));
         GPV_HIP(hipHostGetDevicePointer((void **)&pl->h_vl_dev, pl->h_vl, 0));
     }
     {
@@ -1817,7 +1742,7 @@ int gpv_plan_set_user_order(gpv_plan *pl, const int *ord_z)
     for (int64_t i = 0; i < pl->Nlocs; ++i)
         if (ord_z[i] < 1 || (int64_t)ord_z[i] > pl->Nlocs) return GPV_ERR_INDEX;
     GPV_HIP(hipSetDevice(pl->device));
-    if (!pl->d_user_ord) GPV_HIP(hipMalloc((void **)&pl->d_user_ord, sizeof(int32_t) * (size_t)pl->Nlocs));
+    GPV_BUF(pl->d_user_ord, ensure((size_t)pl->Nlocs));
     GPV_HIP(hipMemcpy(pl->d_user_ord, ord_z, sizeof(int32_t) * (size_t)pl->Nlocs, hipMemcpyHostToDevice));
     return GPV_OK;
 }
@@ -2018,13 +1943,12 @@ int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covpar
     if (!pl->has_z || pl->comm || pl->rows != pl->Nlocs || pl->d_obs || pl->latent_nb) return GPV_ERR_STATE;
     GPV_HIP(hipSetDevice(pl->device));
     const int grid = grad_grid(pl->rows, pl->cus);
-    if (pl->d_gr_part && pl->gr_grid < grid) { GPV_HIP(hipFree(pl->d_gr_part)); pl->d_gr_part = nullptr; }
-    if (!pl->d_gr_part) {
-        GPV_HIP(hipMalloc((void **)&pl->d_gr_part, sizeof(double) * kGradNV * (size_t)grid));
+    if (!pl->d_gr_part || pl->gr_grid < grid) {
+        GPV_BUF(pl->d_gr_part, resize(kGradNV * (size_t)grid));
         pl->gr_grid = grid;
     }
-    if (!pl->d_gr_tot) GPV_HIP(hipMalloc((void **)&pl->d_gr_tot, sizeof(double) * kGradNV));
-    if (row_terms && !pl->d_gr_rows) GPV_HIP(hipMalloc((void **)&pl->d_gr_rows, sizeof(double) * kGradRowLd * (size_t)pl->rows));
+    GPV_BUF(pl->d_gr_tot, ensure(kGradNV));
+    if (row_terms) GPV_BUF(pl->d_gr_rows, ensure(kGradRowLd * (size_t)pl->rows));
     GradArgs a;
     a.rec = pl->d_locs; a.locs = pl->d_locs; a.z = pl->d_z;
     a.nn = pl->d_nn; a.rowid = pl->d_rowid;
@@ -2098,12 +2022,10 @@ static int lincomb_prepare(gpv_plan *pl)
             lrec[(size_t)fill[(size_t)i]++] = make_int2(in_top[(size_t)c] ? ~(int32_t)c : (int32_t)c,
                                                         cboff[(size_t)c] + 1 + (e - colptr[(size_t)c]));
         }
-    if (pl->d_lc_rec) { (void)hipFree(pl->d_lc_rec); pl->d_lc_rec = nullptr; }
-    GPV_HIP(hipMalloc((void **)&pl->d_lc_rec, lrec.size() * sizeof(int2)));
-    GPV_HIP(hipMemcpy(pl->d_lc_rec, lrec.data(), lrec.size() * sizeof(int2), hipMemcpyHostToDevice));
-    if (!pl->d_lc_X) GPV_HIP(hipMalloc((void **)&pl->d_lc_X, sizeof(double) * (size_t)n * kLincombNB));
-    if (!pl->d_lc_part) GPV_HIP(hipMalloc((void **)&pl->d_lc_part, sizeof(double) * (size_t)kLincombBlocks * kLincombNB));
-    if (!pl->d_lc_vars) GPV_HIP(hipMalloc((void **)&pl->d_lc_vars, sizeof(double) * kLincombNB));
+    GPV_BUF(pl->d_lc_rec, upload(lrec.data(), lrec.size()));
+    GPV_BUF(pl->d_lc_X, ensure((size_t)n * kLincombNB));
+    GPV_BUF(pl->d_lc_part, ensure((size_t)kLincombBlocks * kLincombNB));
+    GPV_BUF(pl->d_lc_vars, ensure(kLincombNB));
     pl->lc_ready = true;
     return GPV_OK;
 }
@@ -2145,30 +2067,17 @@ int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int
         if (rc != GPV_OK) return rc;
     }
     hipStream_t st = pl->stream;
-    int64_t *d_hptr = nullptr;
-    int32_t *d_hidx = nullptr;
-    double *d_hval = nullptr;
-    auto release = [&]() {
-        if (d_hptr) (void)hipFree(d_hptr);
-        if (d_hidx) (void)hipFree(d_hidx);
-        if (d_hval) (void)hipFree(d_hval);
-    };
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); release(); return rc; };
+    DevBuf<int64_t> d_hptr;                                                   // this call's rows (freed when it returns)
+    DevBuf<int32_t> d_hidx;
+    DevBuf<double> d_hval;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };   // nothing in flight reads them when they go
     std::vector<int64_t> hp((size_t)nrows + 1);
     for (int64_t r = 0; r <= nrows; ++r) hp[(size_t)r] = hptr[r] - h0;        // offsets into the uploaded slice
-    if (GPV_HIP_FAILED(hipMalloc((void **)&d_hptr, hp.size() * sizeof(int64_t))) ||
-        GPV_HIP_FAILED(hipMalloc((void **)&d_hidx, (size_t)(hnnz ? hnnz : 1) * sizeof(int32_t))) ||
-        GPV_HIP_FAILED(hipMalloc((void **)&d_hval, (size_t)(hnnz ? hnnz : 1) * sizeof(double))))
+    if (GPV_BUF_FAILED(d_hptr, upload(hp.data(), hp.size())) || GPV_BUF_FAILED(d_hidx, upload(hnnz ? hidx + h0 : nullptr, (size_t)hnnz)) ||
+        GPV_BUF_FAILED(d_hval, upload(hnnz ? hval + h0 : nullptr, (size_t)hnnz)))
         return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemcpy(d_hptr, hp.data(), hp.size() * sizeof(int64_t), hipMemcpyHostToDevice))) return fail(GPV_ERR_HIP);
-    if (hnnz && (GPV_HIP_FAILED(hipMemcpy(d_hidx, hidx + h0, (size_t)hnnz * sizeof(int32_t), hipMemcpyHostToDevice)) ||
-                 GPV_HIP_FAILED(hipMemcpy(d_hval, hval + h0, (size_t)hnnz * sizeof(double), hipMemcpyHostToDevice))))
+    if (cov && (GPV_BUF_FAILED(pl->d_lc_gpart, ensure((size_t)kLincombBlocks * NB * NB)) || GPV_BUF_FAILED(pl->d_lc_gram, ensure(NB * NB))))
         return fail(GPV_ERR_HIP);
-    if (cov) {
-        if (!pl->d_lc_gpart && GPV_HIP_FAILED(hipMalloc((void **)&pl->d_lc_gpart, sizeof(double) * (size_t)kLincombBlocks * NB * NB)))
-            return fail(GPV_ERR_HIP);
-        if (!pl->d_lc_gram && GPV_HIP_FAILED(hipMalloc((void **)&pl->d_lc_gram, sizeof(double) * NB * NB))) return fail(GPV_ERR_HIP);
-    }
     LincombArgs la;
     la.colrec = pl->d_colrec; la.lrec = pl->d_lc_rec; la.C = pl->d_C; la.X = pl->d_lc_X;
     // the sweep: the factor pass's levels, leaves first, then the dense top block, then the column sums
@@ -2181,18 +2090,6 @@ int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int
         if (e == hipSuccess) e = launch_lincomb_vars(pl->d_lc_X, pl->Nlocs, pl->d_lc_part, pl->d_lc_vars, st);
         return e;
     };
-    static const bool no_graph = getenv("GPV_NO_GRAPH") != nullptr;
-    if (!no_graph && !pl->lc_graph) {
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const hipError_t e = enqueue();
-            hipGraph_t graph = nullptr;
-            const hipError_t e2 = hipStreamEndCapture(st, &graph);
-            if (!(e == hipSuccess && e2 == hipSuccess && graph && hipGraphInstantiate(&pl->lc_graph, graph, nullptr, nullptr, 0) == hipSuccess))
-                pl->lc_graph = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
-            (void)hipGetLastError();
-        }
-    }
     std::vector<double> vb((size_t)NB), gb(cov ? (size_t)NB * NB : 0);
     for (int64_t b = 0; b < nbatch; ++b) {
         const int64_t row0 = b * NB;
@@ -2200,11 +2097,7 @@ int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int
         if (GPV_HIP_FAILED(launch_lincomb_init(pl->d_lc_X, pl->Nlocs, d_hptr, d_hidx, d_hval, row0, nb, bmax[(size_t)b],
                                                bserial[(size_t)b] != 0, st)))
             return fail(GPV_ERR_HIP);
-        if (!no_graph && pl->lc_graph) {
-            if (GPV_HIP_FAILED(hipGraphLaunch(pl->lc_graph, st))) return fail(GPV_ERR_HIP);
-        } else if (GPV_HIP_FAILED(enqueue())) {
-            return fail(GPV_ERR_HIP);
-        }
+        if (GPV_HIP_FAILED(graph_replay(pl->lc_graph, st, enqueue))) return fail(GPV_ERR_HIP);
         if (cov && GPV_HIP_FAILED(launch_lincomb_gram(pl->d_lc_X, pl->Nlocs, pl->d_lc_gpart, pl->d_lc_gram, st))) return fail(GPV_ERR_HIP);
         if (GPV_HIP_FAILED(hipMemcpyAsync(vb.data(), pl->d_lc_vars, sizeof(double) * NB, hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
         if (cov && GPV_HIP_FAILED(hipMemcpyAsync(gb.data(), pl->d_lc_gram, sizeof(double) * NB * NB, hipMemcpyDeviceToHost, st)))
@@ -2216,7 +2109,6 @@ int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int
                 for (int j = 0; j < nb; ++j) cov[(int64_t)i * nrows + j] = gb[(size_t)i * NB + j];
     }
     pl->last_stream = st;
-    release();
     return GPV_OK;
 }
 
@@ -2231,23 +2123,10 @@ static hipError_t solvet_enqueue(gpv_plan *pl, hipStream_t st)
         e = launch_solvet_level(sa, pl->levptr2[lv], pl->levptr2[lv + 1] - pl->levptr2[lv], st);
     return e;
 }
-// ... as the plan's captured graph (captured on first use; GPV_NO_GRAPH: launch by launch)
+// ... as the plan's captured graph
 static hipError_t solvet_sweep(gpv_plan *pl, hipStream_t st)
 {
-    static const bool no_graph = getenv("GPV_NO_GRAPH") != nullptr;
-    if (!no_graph && !pl->st_graph) {
-        if (hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-            const hipError_t e = solvet_enqueue(pl, st);
-            hipGraph_t graph = nullptr;
-            const hipError_t e2 = hipStreamEndCapture(st, &graph);
-            if (!(e == hipSuccess && e2 == hipSuccess && graph && hipGraphInstantiate(&pl->st_graph, graph, nullptr, nullptr, 0) == hipSuccess))
-                pl->st_graph = nullptr;
-            if (graph) (void)hipGraphDestroy(graph);
-            (void)hipGetLastError();
-        }
-    }
-    if (!no_graph && pl->st_graph) return hipGraphLaunch(pl->st_graph, st);
-    return solvet_enqueue(pl, st);
+    return graph_replay(pl->st_graph, st, [&] { return solvet_enqueue(pl, st); });
 }
 
 int gpv_plan_solve_t(gpv_plan *pl, int64_t ncols, const double *E, int64_t lde, double *X, int64_t ldx)
@@ -2261,8 +2140,8 @@ int gpv_plan_solve_t(gpv_plan *pl, int64_t ncols, const double *E, int64_t lde, 
     if (ncols == 0) return GPV_OK;
     GPV_HIP(hipSetDevice(pl->device));
     if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
-    if (!pl->d_lc_X) GPV_HIP(hipMalloc((void **)&pl->d_lc_X, sizeof(double) * (size_t)n * NB));
-    if (!pl->d_st_E) GPV_HIP(hipMalloc((void **)&pl->d_st_E, sizeof(double) * (size_t)n * NB));
+    GPV_BUF(pl->d_lc_X, ensure((size_t)n * NB));
+    GPV_BUF(pl->d_st_E, ensure((size_t)n * NB));
     hipStream_t st = pl->stream;
     auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     const int64_t nbatch = (ncols + NB - 1) / NB;
@@ -2295,9 +2174,9 @@ extern "C" int gpv_plan_debug_solve_t_ms(gpv_plan *pl, int reps, double *ms)
     if (!pl->have_post || !pl->have_factor || pl->comm || !pl->d_lc_X || !pl->d_st_E) return GPV_ERR_STATE;
     GPV_HIP(hipSetDevice(pl->device));
     hipStream_t st = pl->stream;
-    hipEvent_t a = nullptr, b = nullptr;
-    GPV_HIP(hipEventCreate(&a));
-    if (GPV_HIP_FAILED(hipEventCreate(&b))) { (void)hipEventDestroy(a); return GPV_ERR_HIP; }
+    Event a, b;
+    GPV_HIP(hipEventCreate(a.put()));
+    GPV_HIP(hipEventCreate(b.put()));
     int rc = GPV_OK;
     for (int r = 0; r < reps && rc == GPV_OK; ++r) {
         float t = 0.f;
@@ -2308,8 +2187,6 @@ extern "C" int gpv_plan_debug_solve_t_ms(gpv_plan *pl, int reps, double *ms)
         ms[r] = (double)t;
     }
     (void)hipStreamSynchronize(st);
-    (void)hipEventDestroy(a);
-    (void)hipEventDestroy(b);
     return rc;
 }
 
@@ -2349,8 +2226,8 @@ int gpv_plan_draws_normals(gpv_plan *pl, uint64_t seed, int64_t skip_front, int6
     if (ncols == 0) return GPV_OK;
     GPV_HIP(hipSetDevice(pl->device));
     if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
-    if (!pl->d_lc_X) GPV_HIP(hipMalloc((void **)&pl->d_lc_X, sizeof(double) * (size_t)n * NB));
-    if (!pl->d_st_E) GPV_HIP(hipMalloc((void **)&pl->d_st_E, sizeof(double) * (size_t)n * NB));
+    GPV_BUF(pl->d_lc_X, ensure((size_t)n * NB));
+    GPV_BUF(pl->d_st_E, ensure((size_t)n * NB));
     hipStream_t st = pl->stream;
     auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     const int64_t end = col0 + ncols;
@@ -2383,13 +2260,13 @@ static int draws_alloc(gpv_plan *pl, int64_t ndraws)
 {
     constexpr int NB = kLincombNB;
     const size_t n = (size_t)pl->Nlocs;
-    if (!pl->d_lc_X) GPV_HIP(hipMalloc((void **)&pl->d_lc_X, sizeof(double) * n * NB));
-    if (!pl->d_ds) GPV_HIP(hipMalloc((void **)&pl->d_ds, sizeof(double) * ((5 + kDrawsMaxThr) * n + (size_t)kDrawsBlocks * 2 * NB)));
-    if (!pl->d_ds_cnt) GPV_HIP(hipMalloc((void **)&pl->d_ds_cnt, sizeof(uint32_t) * kDrawsMaxThr * n));
-    if (!pl->d_ds_mask) GPV_HIP(hipMalloc((void **)&pl->d_ds_mask, n));
+    GPV_BUF(pl->d_lc_X, ensure(n * NB));
+    GPV_BUF(pl->d_ds, ensure((5 + kDrawsMaxThr) * n + (size_t)kDrawsBlocks * 2 * NB));
+    GPV_BUF(pl->d_ds_cnt, ensure(kDrawsMaxThr * n));
+    GPV_BUF(pl->d_ds_mask, ensure(n));
     if (pl->ds_draw_cap < ndraws) {
-        if (pl->d_ds_draw) { (void)hipFree(pl->d_ds_draw); pl->d_ds_draw = nullptr; pl->ds_draw_cap = 0; }
-        GPV_HIP(hipMalloc((void **)&pl->d_ds_draw, sizeof(double) * 2 * (size_t)ndraws));
+        pl->ds_draw_cap = 0;
+        GPV_BUF(pl->d_ds_draw, resize(2 * (size_t)ndraws));
         pl->ds_draw_cap = ndraws;
     }
     return GPV_OK;
@@ -2470,10 +2347,10 @@ extern "C" int gpv_plan_debug_draws_ms(gpv_plan *pl, uint64_t seed, double *ms)
     DrawsArgs a{};
     a.X = pl->d_lc_X; a.mu = B.mu; a.S1 = B.S1; a.S2 = B.S2; a.cnt = pl->d_ds_cnt; a.part = B.part;
     a.n = pl->Nlocs; a.want_draw = 1;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    Event ev[4];
     int rc = GPV_OK;
     for (auto &e : ev)
-        if (rc == GPV_OK && GPV_HIP_FAILED(hipEventCreate(&e))) rc = GPV_ERR_HIP;
+        if (rc == GPV_OK && GPV_HIP_FAILED(hipEventCreate(e.put()))) rc = GPV_ERR_HIP;
     if (rc == GPV_OK &&
         (GPV_HIP_FAILED(hipEventRecord(ev[0], st)) || GPV_HIP_FAILED(launch_draws_fill(pl->d_lc_X, a.n, seed, 0, 0, kLincombNB, st)) ||
          GPV_HIP_FAILED(hipEventRecord(ev[1], st)) || GPV_HIP_FAILED(solvet_sweep(pl, st)) ||
@@ -2488,8 +2365,6 @@ extern "C" int gpv_plan_debug_draws_ms(gpv_plan *pl, uint64_t seed, double *ms)
     }
     (void)hipStreamSynchronize(st);
     pl->last_stream = st;
-    for (auto &e : ev)
-        if (e) (void)hipEventDestroy(e);
     return rc;
 }
 
@@ -2553,7 +2428,7 @@ int gpv_plan_get_Lentries(gpv_plan *pl, double *Lentries)
     if (pl->rows == 0) return GPV_OK;
     GPV_HIP(hipSetDevice(pl->device));
     const size_t bytes = sizeof(double) * (size_t)pl->rows * pl->p;
-    if (!pl->d_tmp) GPV_HIP(hipMalloc((void **)&pl->d_tmp, bytes));
+    GPV_BUF(pl->d_tmp, ensure((size_t)pl->rows * pl->p));
     hipStream_t st = pl->last_stream;
     GPV_HIP(launch_rows_to_colmajor(pl->d_L, pl->P, pl->rows, pl->p, pl->d_tmp, st));
     static const bool no_stage = dev_getenv("GPV_NO_D2H_STAGING") != nullptr;
@@ -2567,11 +2442,11 @@ int gpv_plan_get_Lentries(gpv_plan *pl, double *Lentries)
     // ~27 GB/s through HIP's own staging.  Two pinned 32 MB buffers instead: chunk c travels by DMA while host threads
     // copy chunk c - 1 out of the other buffer into the caller's memory.
     for (int b = 0; b < 2; ++b) {
-        if (!pl->h_stage[b]) GPV_HIP(hipHostMalloc((void **)&pl->h_stage[b], kChunk, hipHostMallocDefault));
-        if (!pl->stage_ev[b]) GPV_HIP(hipEventCreateWithFlags(&pl->stage_ev[b], hipEventDisableTiming));
+        GPV_BUF(pl->h_stage[b], ensure(kChunk));
+        if (!pl->stage_ev[b]) GPV_HIP(hipEventCreateWithFlags(pl->stage_ev[b].put(), hipEventDisableTiming));
     }
     const size_t nchunk = (bytes + kChunk - 1) / kChunk;
-    const char *src = reinterpret_cast<const char *>(pl->d_tmp);
+    const char *src = reinterpret_cast<const char *>(pl->d_tmp.get());
     char *dst = reinterpret_cast<char *>(Lentries);
     auto issue = [&](size_t c) -> hipError_t {
         const size_t off = c * kChunk, len = (off + kChunk <= bytes) ? kChunk : bytes - off;
@@ -2584,7 +2459,7 @@ int gpv_plan_get_Lentries(gpv_plan *pl, double *Lentries)
     for (size_t c = 0; c < nchunk; ++c) {
         GPV_HIP(hipEventSynchronize(pl->stage_ev[c & 1]));
         const size_t off = c * kChunk, len = (off + kChunk <= bytes) ? kChunk : bytes - off;
-        const char *hs = reinterpret_cast<const char *>(pl->h_stage[c & 1]);
+        const char *hs = pl->h_stage[c & 1];
         parallel_for((int64_t)len, [=](int64_t b0, int64_t e0) { std::memcpy(dst + off + b0, hs + b0, (size_t)(e0 - b0)); }, 8);
         if (c + 2 < nchunk) GPV_HIP(issue(c + 2));
     }
@@ -2597,7 +2472,7 @@ int gpv_plan_get_Zentries(gpv_plan *pl, double *Z)
     if (!pl->evaluated) return GPV_ERR_STATE;
     if (pl->rows == 0) return GPV_OK;
     GPV_HIP(hipSetDevice(pl->device));
-    if (!pl->d_Z) GPV_HIP(hipMalloc((void **)&pl->d_Z, sizeof(double) * 2 * (size_t)pl->rows));
+    GPV_BUF(pl->d_Z, ensure(2 * (size_t)pl->rows));
     if (pl->nug_is_scalar) {
         GPV_HIP(launch_fill(pl->d_stage, pl->nug_scalar, pl->rows, pl->last_stream));
         GPV_HIP(launch_zentries(pl->d_stage, pl->rows, pl->d_Z, pl->last_stream));
@@ -2743,28 +2618,21 @@ static int zentries_host(gpv_plan *pl, const double *nuggets_obsord, int64_t n, 
     if (n <= 0) return GPV_OK;
     if (n <= pl->Nlocs && n <= pl->rows) {
         // the plan's own buffers: no allocation on the (cached) hot path of the drop-in
-        if (!pl->d_Z) GPV_HIP(hipMalloc((void **)&pl->d_Z, sizeof(double) * 2 * (size_t)pl->rows));
+        GPV_BUF(pl->d_Z, ensure(2 * (size_t)pl->rows));
         GPV_HIP(hipMemcpyAsync(pl->d_stage, nuggets_obsord, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, pl->stream));
         GPV_HIP(launch_zentries(pl->d_stage, n, pl->d_Z, pl->stream));
         GPV_HIP(hipMemcpyAsync(Zentries, pl->d_Z, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, pl->stream));
         GPV_HIP(hipStreamSynchronize(pl->stream));
         return GPV_OK;
     }
-    double *d_n = nullptr, *d_Z = nullptr;
-    GPV_HIP(hipMalloc((void **)&d_n, sizeof(double) * (size_t)n));
-    if (GPV_HIP_FAILED(hipMalloc((void **)&d_Z, sizeof(double) * 2 * (size_t)n))) {
-        (void)hipFree(d_n);
-        return GPV_ERR_HIP;
-    }
-    int rc = GPV_OK;
-    if (GPV_HIP_FAILED(hipMemcpyAsync(d_n, nuggets_obsord, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, pl->stream)) ||
-        GPV_HIP_FAILED(launch_zentries(d_n, n, d_Z, pl->stream)) ||
-        GPV_HIP_FAILED(hipMemcpyAsync(Zentries, d_Z, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, pl->stream)) ||
-        GPV_HIP_FAILED(hipStreamSynchronize(pl->stream)))
-        rc = GPV_ERR_HIP;
-    (void)hipFree(d_n);
-    (void)hipFree(d_Z);
-    return rc;
+    DevBuf<double> d_n, d_Z;
+    GPV_BUF(d_n, resize((size_t)n));
+    GPV_BUF(d_Z, resize(2 * (size_t)n));
+    GPV_HIP(hipMemcpyAsync(d_n, nuggets_obsord, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, pl->stream));
+    GPV_HIP(launch_zentries(d_n, n, d_Z, pl->stream));
+    GPV_HIP(hipMemcpyAsync(Zentries, d_Z, sizeof(double) * 2 * (size_t)n, hipMemcpyDeviceToHost, pl->stream));
+    GPV_HIP(hipStreamSynchronize(pl->stream));
+    return GPV_OK;
 }
 
 void gpv_U_NZentries(const int *Ncores, const int *n, const int *Nlocs, const int *dim, const int *ncolNN,
@@ -2888,9 +2756,7 @@ void gpv_U_NZentries_mat(const int *Ncores, const int *n, const int *Nlocs, cons
     gpv_plan *pl = nullptr;
     int rc = gpv_plan_create(&pl, 0, *Nlocs, 1, *ncolNN, nullptr, revNNarray, nullptr, 0, *Nlocs);
     if (rc != GPV_OK) { *status = rc; return; }
-    const size_t bytes = sizeof(double) * (size_t)(*Nlocs) * (size_t)(*Nlocs);
-    if (GPV_HIP_FAILED(hipMalloc((void **)&pl->d_covvals, bytes)) ||
-        GPV_HIP_FAILED(hipMemcpy(pl->d_covvals, covVals, bytes, hipMemcpyHostToDevice))) {
+    if (GPV_BUF_FAILED(pl->d_covvals, upload(covVals, (size_t)(*Nlocs) * (size_t)(*Nlocs)))) {
         gpv_plan_destroy(pl);
         *status = GPV_ERR_HIP;
         return;
@@ -2912,24 +2778,13 @@ static void covfun_host(const double *distmat, const int *nelem, const CovSetup 
     if (gpv_device_count(&ndev) != GPV_OK) { *status = GPV_ERR_NO_DEVICE; return; }
     const int64_t n = *nelem;
     if (n <= 0) { *status = GPV_OK; return; }
-    double *d_in = nullptr, *d_out = nullptr;
-    int rc = GPV_OK;
-    if (GPV_HIP_FAILED(hipSetDevice(0)) || GPV_HIP_FAILED(hipMalloc((void **)&d_in, sizeof(double) * (size_t)n))) {
-        *status = GPV_ERR_HIP;
-        return;
-    }
-    if (GPV_HIP_FAILED(hipMalloc((void **)&d_out, sizeof(double) * (size_t)n))) {
-        (void)hipFree(d_in);
-        *status = GPV_ERR_HIP;
-        return;
-    }
-    if (GPV_HIP_FAILED(hipMemcpy(d_in, distmat, sizeof(double) * (size_t)n, hipMemcpyHostToDevice)) ||
+    DevBuf<double> d_in, d_out;
+    *status = GPV_ERR_HIP;
+    if (GPV_HIP_FAILED(hipSetDevice(0)) || GPV_BUF_FAILED(d_in, upload(distmat, (size_t)n)) || GPV_BUF_FAILED(d_out, resize((size_t)n)) ||
         GPV_HIP_FAILED(launch_covfun(d_in, n, cs.cov, cs.sig0, cs.sA, cs.cA, cs.sB, cs.cB, d_out, nullptr)) ||
         GPV_HIP_FAILED(hipMemcpy(covmat, d_out, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost)))
-        rc = GPV_ERR_HIP;
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    *status = rc;
+        return;
+    *status = GPV_OK;
 }
 
 void gpv_MaternFun(const double *distmat, const int *nelem, const double *covparms, double *covmat, int *status)

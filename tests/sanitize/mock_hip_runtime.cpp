@@ -16,6 +16,7 @@
 
 namespace {
 std::atomic<long> g_launches{0}, g_allocs{0}, g_frees{0}, g_graph_launches{0};
+std::atomic<long> g_alloc_calls{0}, g_fail_at{-1};              // hipMalloc + hipHostMalloc calls so far; the call that fails (-1: none)
 std::mutex g_mu;
 std::unordered_map<void *, size_t> g_live;                      // device + pinned allocations still alive
 thread_local int t_capturing = 0;
@@ -25,6 +26,7 @@ thread_local hipStream_t t_stream = nullptr;
 struct Token { int kind; };
 void *track(size_t bytes)
 {
+    if (g_alloc_calls.fetch_add(1) == g_fail_at.load()) { g_fail_at = -1; return nullptr; }   // the armed failure, once
     void *p = calloc(bytes ? bytes : 1, 1);
     if (!p) return nullptr;
     std::lock_guard<std::mutex> g(g_mu);
@@ -51,6 +53,9 @@ extern "C" {
 long mockhip_launches(void) { return g_launches.load(); }
 long mockhip_graph_launches(void) { return g_graph_launches.load(); }
 long mockhip_live_allocations(void) { std::lock_guard<std::mutex> g(g_mu); return (long)g_live.size(); }
+long mockhip_allocs(void) { return g_alloc_calls.load(); }       // hipMalloc + hipHostMalloc calls so far, failed ones included
+// the k-th hipMalloc / hipHostMalloc from now on (k = 0: the next) returns hipErrorOutOfMemory, once; k < 0 disarms
+void mockhip_fail_alloc_at(long k) { g_fail_at = k < 0 ? -1 : g_alloc_calls.load() + k; }
 
 hipError_t hipGetDeviceCount(int *n) { *n = 1; return hipSuccess; }
 hipError_t hipSetDevice(int d) { return d == 0 ? hipSuccess : hipErrorInvalidDevice; }
@@ -117,7 +122,7 @@ hipError_t hipEventCreate(hipEvent_t *e) { *e = reinterpret_cast<hipEvent_t>(new
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned) { return hipEventCreate(e); }
 hipError_t hipEventDestroy(hipEvent_t e) { delete reinterpret_cast<Token *>(e); return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t, hipStream_t) { return hipSuccess; }
-hipError_t hipEventSynchronize(hipEvent_t) { return hipSuccess; }
+hipError_t hipEventSynchronize(hipEvent_t e) { return e ? hipSuccess : hipErrorInvalidResourceHandle; }   // (as the runtime does)
 hipError_t hipEventQuery(hipEvent_t) { return hipSuccess; }
 hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) { *ms = 0.125f; return hipSuccess; }
 
