@@ -196,6 +196,24 @@ class Plan:
         out = (float(ll.value), grad, int(nf.value))
         return out + (rt,) if row_terms else out
 
+    def loglik_fisher(self, covmodel, covparms, nugget, row_terms=False):
+        """Value, analytic gradient and expected Fisher information of the cond.yz='z' log-likelihood of the plan's data
+        (gpv_plan_loglik_fisher): returns (loglik, grad, info, n_failed) and, with row_terms, a fifth array
+        (Nlocs, len(covparms) + 2 + T), T = (len(covparms) + 1)(len(covparms) + 2) / 2, of {l_k, its derivatives, the upper triangle
+        of the row's information, row-major} per ordered row.  info is (len(covparms) + 1) square, symmetric, in the parameter
+        order of grad; for 'matern' the entries that involve the smoothness are NaN.  The plan's last evaluation is left as it was."""
+        cp = np.ascontiguousarray(covparms, dtype=np.float64)
+        ll, nf = C.c_double(0.0), C.c_int64(0)
+        npar = cp.size + 1
+        grad, info = np.zeros(npar), np.zeros((npar, npar))
+        rt = np.zeros((self.Nlocs, npar + 1 + npar * (npar + 1) // 2)) if row_terms else None
+        st = L.lib().gpv_plan_loglik_fisher(self._h, covmodel.encode() if isinstance(covmodel, str) else bytes(covmodel),
+                                            L.dptr(cp), int(cp.size), float(nugget), C.byref(ll), L.dptr(grad), L.dptr(info),
+                                            C.byref(nf), L.dptr(rt) if row_terms else None)
+        L.check(st, "gpv_plan_loglik_fisher")
+        out = (float(ll.value), grad, info, int(nf.value))
+        return out + (rt,) if row_terms else out
+
     def lincomb(self, H_ord, cov_mat=False):
         """Var(H y | z) (or, with cov_mat, Cov) for the rows of H_ord, a scipy.sparse or dense matrix with Nlocs columns in
         the plan's ORDERED latent index, from the factor of the latest evaluation with GPV_WANT_DENOM / GPV_WANT_MEAN /
@@ -1028,26 +1046,40 @@ def vecchia_likelihood(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
     return vecchia_likelihood_U(z, U_obj)
 
 
+def _grad_plan(name, z, va, nuggets, covmodel, device):
+    """The plan and the nugget of vecchia_likelihood_grad / vecchia_likelihood_fisher, after their common refusals."""
+    if va["cond_yz"] not in ("z", "false"):
+        raise ValueError(f"{name} needs cond_yz='z' (the gradient of the other modes goes through the "
+                         "posterior factor)")
+    if not isinstance(covmodel, str):
+        raise ValueError(f"{name} needs a named covariance family ('matern' or 'esqe'), not a function or matrix")
+    nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
+    if nug.size != 1:
+        raise ValueError(f"{name} takes one constant nugget")
+    z = np.asarray(z, dtype=np.float64)
+    if np.isnan(z.sum()):
+        raise ValueError(f"{name} needs complete data (no NaN)")
+    if int(np.sum(va["obs"])) != va["locsord"].shape[0]:
+        raise ValueError(f"{name} does not take plans with prediction locations")
+    plan = _plan_for(va, device)
+    plan.set_user_data(z, va["ord_z"])
+    return plan, float(nug[0])
+
+
 def vecchia_likelihood_grad(z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
     """(loglik, grad) of the cond.yz='z' Vecchia log-likelihood, both on the GPU in one pass over the conditioning sets
     (Plan.loglik_grad): grad = d loglik / d covparms, then d / d nugget; for 'matern' the smoothness (0.5, 1.5 or 2.5) is not
     differentiated and its entry is NaN.  Only what has an exact, cheap gradient is accepted: cond.yz = 'z' (or m = 0), one
     constant nugget > 0, complete data, no prediction locations, a named covariance family."""
-    va = vecchia_approx
-    if va["cond_yz"] not in ("z", "false"):
-        raise ValueError("vecchia_likelihood_grad needs cond_yz='z' (the gradient of the other modes goes through the "
-                         "posterior factor)")
-    if not isinstance(covmodel, str):
-        raise ValueError("vecchia_likelihood_grad needs a named covariance family ('matern' or 'esqe'), not a function or matrix")
-    nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
-    if nug.size != 1:
-        raise ValueError("vecchia_likelihood_grad takes one constant nugget")
-    z = np.asarray(z, dtype=np.float64)
-    if np.isnan(z.sum()):
-        raise ValueError("vecchia_likelihood_grad needs complete data (no NaN)")
-    if int(np.sum(va["obs"])) != va["locsord"].shape[0]:
-        raise ValueError("vecchia_likelihood_grad does not take plans with prediction locations")
-    plan = _plan_for(va, device)
-    plan.set_user_data(z, va["ord_z"])
-    ll, grad, _ = plan.loglik_grad(covmodel, covparms, float(nug[0]))
+    plan, nug = _grad_plan("vecchia_likelihood_grad", z, vecchia_approx, nuggets, covmodel, device)
+    ll, grad, _ = plan.loglik_grad(covmodel, covparms, nug)
     return ll, grad
+
+
+def vecchia_likelihood_fisher(z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+    """(loglik, grad, info): vecchia_likelihood_grad together with the expected Fisher information of the same likelihood
+    (Plan.loglik_fisher), a symmetric matrix over {covparms, nugget} whose inverse at the estimate approximates the covariance of
+    the estimator.  For 'matern' the row and column of the smoothness are NaN.  Accepts what vecchia_likelihood_grad accepts."""
+    plan, nug = _grad_plan("vecchia_likelihood_fisher", z, vecchia_approx, nuggets, covmodel, device)
+    ll, grad, info, _ = plan.loglik_fisher(covmodel, covparms, nug)
+    return ll, grad, info

@@ -110,11 +110,11 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
     work.append((os.path.join(CSRC, "gpv_laplace.hip"), os.path.join(BUILD, "laplace.o"), [], H("gpv_laplace.h"), force))
     work.append((os.path.join(CSRC, "gpv_sets_generic.hip"), os.path.join(BUILD, "generic.o"), list(extra_flags),
                  kern + H("gpv_generic.h"), force))
-    grad = os.path.join(CSRC, "gpv_grad.hip")                # value + gradient kernel: one object per row-length bucket
+    grad = os.path.join(CSRC, "gpv_grad.hip")                # value + gradient (+ information) kernels: one object per row-length bucket
     for pb in (64, 32, 16):
         work.append((grad, os.path.join(BUILD, f"grad_pb{pb}.o"), [f"-DGPV_GRAD_PB={pb}"] + extra_flags,
-                     internal + H("gpv_grad.h"), force))
-    work.append((grad, os.path.join(BUILD, "grad.o"), list(extra_flags), internal + H("gpv_grad.h"), force))
+                     internal + H("gpv_grad.h", "gpv_fisher_kernel.hpp"), force))
+    work.append((grad, os.path.join(BUILD, "grad.o"), list(extra_flags), internal + H("gpv_grad.h", "gpv_fisher_kernel.hpp"), force))
     work.append((os.path.join(CSRC, "gpv_order.cpp"), os.path.join(BUILD, "order.o"), ["-x", "c++"], [pub], force))
     work.append((os.path.join(CSRC, "gpv_nn.hip"), os.path.join(BUILD, "nn.o"), ["-ffp-contract=off"], internal + [pub], force))
     jobs = jobs or min(8, os.cpu_count() or 1)

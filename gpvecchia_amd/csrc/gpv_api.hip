@@ -383,6 +383,9 @@ struct gpv_plan {
     // gpv_plan_loglik_grad (gpv_grad.hip), allocated on first use: per-workgroup partials, their totals, per-row terms
     DevBuf<double> d_gr_part, d_gr_tot, d_gr_rows;
     int gr_grid = 0;
+    // the same for gpv_plan_loglik_fisher (gpv_fisher_kernel.hpp)
+    DevBuf<double> d_fi_part, d_fi_tot, d_fi_rows;
+    int fi_grid = 0;
     // Vecchia-Laplace state (gpv_plan_vl_begin): data z, prior mean, two latent-mean buffers (current / next), flags + max
     DevBuf<double> d_vl_z, d_vl_pm, d_vl_y[2], d_vl_out;
     DevBuf<double> d_vl_y0;                          // the start value, kept so that a restart needs no upload
@@ -1925,13 +1928,12 @@ int gpv_plan_factor_stamp(gpv_plan *pl, int64_t *stamp)
     return GPV_OK;
 }
 
-// Value and gradient of the cond.yz='z' log-likelihood (gpv_grad.hip).  Reads the plan's records and index arrays only and
-// writes buffers of its own, so the sums, the U entries and the factor of the plan's last evaluation stay what they were.
-int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
-                         double *grad, int64_t *n_failed, double *row_terms)
+// Argument and state checks shared by gpv_plan_loglik_grad and gpv_plan_loglik_fisher, before the device is touched; on GPV_OK
+// `a` holds everything but the output buffers.
+static int grad_args_checked(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool &matern,
+                             GradArgs &a)
 {
-    if (!pl || !covType || !covparms || !loglik || !grad || !n_failed) return GPV_ERR_BAD_ARG;
-    const bool matern = std::strcmp(covType, "matern") == 0;
+    matern = std::strcmp(covType, "matern") == 0;
     if (!matern && std::strcmp(covType, "esqe") != 0) return GPV_ERR_COVTYPE;
     if (ncovparms != (matern ? 3 : 4)) return GPV_ERR_BAD_ARG;
     if (!(nugget > 0.0) || !std::isfinite(nugget)) return GPV_ERR_BAD_ARG;
@@ -1941,6 +1943,26 @@ int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covpar
     if (cs.cov == COV_MATERN_GEN) return GPV_ERR_UNSUPPORTED_NU;    // the reference's Matern is discontinuous in nu at the closed forms
     if (pl->p > kGradMaxP) return GPV_ERR_UNSUPPORTED_M;
     if (!pl->has_z || pl->comm || pl->rows != pl->Nlocs || pl->d_obs || pl->latent_nb) return GPV_ERR_STATE;
+    a.rec = pl->d_locs; a.locs = pl->d_locs; a.z = pl->d_z;
+    a.nn = pl->d_nn; a.rowid = pl->d_rowid;
+    a.row_terms = nullptr; a.block_part = nullptr; a.totals = nullptr;
+    a.rows = pl->rows; a.P = pl->P; a.dim = pl->dim; a.locs_ld = pl->locs_ld; a.cov = cs.cov;
+    a.sA = cs.sA; a.cA = cs.cA; a.irA = 1.0 / covparms[1];
+    a.sB = cs.sB; a.cB = cs.cB; a.irB = matern ? 0.0 : 1.0 / covparms[3];
+    a.nug = nugget;
+    return GPV_OK;
+}
+
+// Value and gradient of the cond.yz='z' log-likelihood (gpv_grad.hip).  Reads the plan's records and index arrays only and
+// writes buffers of its own, so the sums, the U entries and the factor of the plan's last evaluation stay what they were.
+int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                         double *grad, int64_t *n_failed, double *row_terms)
+{
+    if (!pl || !covType || !covparms || !loglik || !grad || !n_failed) return GPV_ERR_BAD_ARG;
+    bool matern;
+    GradArgs a;
+    const int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, matern, a);
+    if (rc != GPV_OK) return rc;
     GPV_HIP(hipSetDevice(pl->device));
     const int grid = grad_grid(pl->rows, pl->cus);
     if (!pl->d_gr_part || pl->gr_grid < grid) {
@@ -1949,15 +1971,8 @@ int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covpar
     }
     GPV_BUF(pl->d_gr_tot, ensure(kGradNV));
     if (row_terms) GPV_BUF(pl->d_gr_rows, ensure(kGradRowLd * (size_t)pl->rows));
-    GradArgs a;
-    a.rec = pl->d_locs; a.locs = pl->d_locs; a.z = pl->d_z;
-    a.nn = pl->d_nn; a.rowid = pl->d_rowid;
     a.row_terms = row_terms ? pl->d_gr_rows : nullptr;
     a.block_part = pl->d_gr_part; a.totals = pl->d_gr_tot;
-    a.rows = pl->rows; a.P = pl->P; a.dim = pl->dim; a.locs_ld = pl->locs_ld; a.cov = cs.cov;
-    a.sA = cs.sA; a.cA = cs.cA; a.irA = 1.0 / covparms[1];
-    a.sB = cs.sB; a.cB = cs.cB; a.irB = matern ? 0.0 : 1.0 / covparms[3];
-    a.nug = nugget;
     hipStream_t st = pl->stream;
     double tot[kGradNV];
     GPV_HIP(launch_grad(pl->p, a, grid, st));
@@ -1984,6 +1999,70 @@ int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covpar
         for (int64_t k = 0; k < pl->rows; ++k) {
             row_terms[k * ld] = h[(size_t)k * kGradRowLd];
             spread(&h[(size_t)k * kGradRowLd + 1], row_terms + k * ld + 1);
+        }
+    }
+    return GPV_OK;
+}
+
+// Value, gradient and expected Fisher information of the same likelihood (gpv_fisher_kernel.hpp).  Like gpv_plan_loglik_grad it
+// writes buffers of its own only.
+int gpv_plan_loglik_fisher(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                           double *grad, double *fisher, int64_t *n_failed, double *row_terms)
+{
+    if (!pl || !covType || !covparms || !loglik || !grad || !fisher || !n_failed) return GPV_ERR_BAD_ARG;
+    bool matern;
+    GradArgs a;
+    const int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, matern, a);
+    if (rc != GPV_OK) return rc;
+    GPV_HIP(hipSetDevice(pl->device));
+    const int grid = grad_grid(pl->rows, pl->cus);
+    if (!pl->d_fi_part || pl->fi_grid < grid) {
+        GPV_BUF(pl->d_fi_part, resize(kFisherNV * (size_t)grid));
+        pl->fi_grid = grid;
+    }
+    GPV_BUF(pl->d_fi_tot, ensure(kFisherNV));
+    if (row_terms) GPV_BUF(pl->d_fi_rows, ensure(kFisherRowLd * (size_t)pl->rows));
+    a.row_terms = row_terms ? pl->d_fi_rows : nullptr;
+    a.block_part = pl->d_fi_part; a.totals = pl->d_fi_tot;
+    hipStream_t st = pl->stream;
+    double tot[kFisherNV];
+    GPV_HIP(launch_fisher(pl->p, a, grid, st));
+    GPV_HIP(hipMemcpyAsync(tot, pl->d_fi_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    GPV_HIP(hipStreamSynchronize(st));
+    // kernel parameters -> covparms as above; the triangle of the nk kernel parameters -> that of the np = ncovparms + 1 outputs
+    const int nk = matern ? 3 : 5, np = ncovparms + 1;
+    const int at[5] = {0, 1, matern ? 3 : 2, 3, 4};                  // output position of kernel parameter t
+    auto spread = [&](const double *src, double *dst) {
+        for (int t = 0; t < np; ++t) dst[t] = NAN;
+        for (int t = 0; t < nk; ++t) dst[at[t]] = src[t];
+    };
+    auto spread_tri = [&](const double *src, double *dst) {          // dst: np (np + 1) / 2, row-major with i <= j
+        for (int t = 0; t < np * (np + 1) / 2; ++t) dst[t] = NAN;
+        for (int i = 0, s = 0; i < nk; ++i)
+            for (int j = i; j < nk; ++j, ++s) dst[at[i] * np - at[i] * (at[i] - 1) / 2 + (at[j] - at[i])] = src[s];
+    };
+    *n_failed = (int64_t)tot[6];
+    if (tot[6] > 0.0) {
+        *loglik = -INFINITY;
+        for (int t = 0; t < np; ++t) grad[t] = NAN;
+        for (int t = 0; t < np * np; ++t) fisher[t] = NAN;
+    } else {
+        *loglik = tot[0];
+        spread(tot + 1, grad);
+        double tri[kFisherTri];
+        spread_tri(tot + kGradNV, tri);
+        for (int i = 0, s = 0; i < np; ++i)                          // mirrored here: exactly symmetric
+            for (int j = i; j < np; ++j, ++s) fisher[i * np + j] = fisher[j * np + i] = tri[s];
+    }
+    if (row_terms) {
+        std::vector<double> h((size_t)pl->rows * kFisherRowLd);
+        GPV_HIP(hipMemcpy(h.data(), pl->d_fi_rows, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        const int64_t ld = np + 1 + np * (np + 1) / 2;
+        for (int64_t k = 0; k < pl->rows; ++k) {
+            const double *src = &h[(size_t)k * kFisherRowLd];
+            row_terms[k * ld] = src[0];
+            spread(src + 1, row_terms + k * ld + 1);
+            spread_tri(src + kGradRowLd, row_terms + k * ld + 1 + np);
         }
     }
     return GPV_OK;

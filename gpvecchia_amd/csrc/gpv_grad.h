@@ -33,11 +33,20 @@ struct GradArgs {
     double nug;
 };
 
+// gpv_fisher_kernel (gpv_fisher_kernel.hpp) takes the same GradArgs with longer rows and partials: after {l_k, derivatives} comes
+// the upper triangle (row-major, i <= j) of the row's expected information over the kernel parameters, 6 entries for matern and
+// 15 for esqe, zeros behind them
+constexpr int kFisherTri = 15;
+constexpr int kFisherRowLd = kGradRowLd + kFisherTri;    // doubles per row of row_terms
+constexpr int kFisherNV = kGradNV + kFisherTri;          // values per partial: the kGradNV of the gradient, then the triangle
+
 // row-length bucket of a row of p entries (16, 32 or 64), 0: too long
 inline int grad_bucket(int p) { return p <= 16 ? 16 : (p <= 32 ? 32 : (p <= kGradMaxP ? 64 : 0)); }
 // workgroups of the launch for `rows` sets on a device of `cus` compute units
 int grad_grid(int64_t rows, int cus);
 // both launches (the set pass, then the fixed-order sum of its partials) on `stream`; p: entries per row (m + 1)
 hipError_t launch_grad(int p, const GradArgs &a, int grid, hipStream_t stream);
+// the same for value, gradient and information: row_terms [rows][kFisherRowLd], block_part [grid][kFisherNV], totals [kFisherNV]
+hipError_t launch_fisher(int p, const GradArgs &a, int grid, hipStream_t stream);
 
 }  // namespace gpv

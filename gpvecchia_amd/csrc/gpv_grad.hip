@@ -214,6 +214,8 @@ __global__ void __launch_bounds__(64 * kGradWavesPerBlock, (PB == 16 ? 3 : (PB =
     }
 }
 
+#include "gpv_fisher_kernel.hpp"
+
 }  // namespace
 
 #define GPV_GRAD_NAME2(pb) launch_grad_pb##pb
@@ -232,6 +234,22 @@ hipError_t GPV_GRAD_NAME(GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t s
     return hipGetLastError();
 }
 
+#define GPV_FISHER_NAME2(pb) launch_fisher_pb##pb
+#define GPV_FISHER_NAME(pb) GPV_FISHER_NAME2(pb)
+hipError_t GPV_FISHER_NAME(GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t stream)
+{
+    constexpr int PB = GPV_GRAD_PB;
+    const dim3 g((unsigned)grid), b(64 * kGradWavesPerBlock);
+    switch (a.cov) {
+        case COV_MATERN05: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN05>), g, b, 0, stream, a); break;
+        case COV_MATERN15: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN15>), g, b, 0, stream, a); break;
+        case COV_MATERN25: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN25>), g, b, 0, stream, a); break;
+        case COV_ESQE: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_ESQE>), g, b, 0, stream, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 #else  // the launcher that picks the bucket, and the second launch
 
 hipError_t launch_grad_pb16(const GradArgs &a, int grid, hipStream_t stream);
@@ -245,6 +263,21 @@ __global__ void __launch_bounds__(64) gpv_grad_total_kernel(const double *part, 
     if (threadIdx.x < kGradNV) {
         double s = 0.0;
         for (int b = 0; b < grid; ++b) s += part[(int64_t)b * kGradNV + threadIdx.x];
+        totals[threadIdx.x] = s;
+    }
+}
+}  // namespace
+
+hipError_t launch_fisher_pb16(const GradArgs &a, int grid, hipStream_t stream);
+hipError_t launch_fisher_pb32(const GradArgs &a, int grid, hipStream_t stream);
+hipError_t launch_fisher_pb64(const GradArgs &a, int grid, hipStream_t stream);
+
+namespace {
+__global__ void __launch_bounds__(64) gpv_fisher_total_kernel(const double *part, int grid, double *totals)
+{
+    if (threadIdx.x < kFisherNV) {
+        double s = 0.0;
+        for (int b = 0; b < grid; ++b) s += part[(int64_t)b * kFisherNV + threadIdx.x];
         totals[threadIdx.x] = s;
     }
 }
@@ -270,6 +303,21 @@ hipError_t launch_grad(int p, const GradArgs &a, int grid, hipStream_t stream)
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gpv_grad_total_kernel, dim3(1), dim3(64), 0, stream, a.block_part, grid, a.totals);
+    return hipGetLastError();
+}
+
+hipError_t launch_fisher(int p, const GradArgs &a, int grid, hipStream_t stream)
+{
+    if (grid < 1 || a.rows < 0) return hipErrorInvalidValue;
+    hipError_t e;
+    switch (grad_bucket(p)) {
+        case 16: e = launch_fisher_pb16(a, grid, stream); break;
+        case 32: e = launch_fisher_pb32(a, grid, stream); break;
+        case 64: e = launch_fisher_pb64(a, grid, stream); break;
+        default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gpv_fisher_total_kernel, dim3(1), dim3(64), 0, stream, a.block_part, grid, a.totals);
     return hipGetLastError();
 }
 

@@ -108,25 +108,67 @@ def _nelder_mead_nash(fn, x0, reltol, maxit, abstol=-np.inf, alpha=1.0, beta=0.5
     return V[lo].copy(), float(F[lo]), count, code
 
 
+def _fisher_scoring(fn, x0, reltol, maxit, max_step=1.0, max_halvings=10):
+    """Fisher scoring: maximises a log-likelihood from fn(x) -> (value, gradient, information), the information being the
+    expected one (positive definite where the model is identified).  The step s solves information s = gradient and is scaled
+    to norm max_step when longer; it is halved while the value at x + s is not finite or does not increase, and after
+    max_halvings halvings the search gives up.  It stops when gradient's <= reltol |value|: twice the gain the quadratic model
+    still promises.  Every call of fn counts.  Returns (x, value, gradient, information, n_evals, code): code 0 converged,
+    1 evaluation limit reached, step not found or information not positive definite."""
+    x = np.array(x0, dtype=np.float64)
+    f, g, info = fn(x)
+    if not np.isfinite(f):
+        raise RuntimeError("function cannot be evaluated at initial parameters")
+    count = 1
+    while True:
+        try:
+            s = np.linalg.solve(info, g)
+        except np.linalg.LinAlgError:
+            return x, float(f), g, info, count, 1
+        gain = float(g @ s)
+        if not np.isfinite(gain) or gain < 0.0:
+            return x, float(f), g, info, count, 1
+        if gain <= reltol * abs(f):
+            return x, float(f), g, info, count, 0
+        norm = float(np.sqrt(s @ s))
+        if norm > max_step:
+            s = s * (max_step / norm)
+        for _ in range(max_halvings + 1):
+            if count >= maxit:
+                return x, float(f), g, info, count, 1
+            xn = x + s
+            fn_, gn, infon = fn(xn)
+            count += 1
+            if np.isfinite(fn_) and fn_ > f:
+                break
+            s = 0.5 * s
+        else:
+            return x, float(f), g, info, count, 1
+        x, f, g, info = xn, fn_, gn, infon
+
+
 def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini=None, output_level=1,
                      reltol=np.sqrt(np.finfo(float).eps), seed=0, maxit=300, smoothness=None, method="Nelder-Mead",
                      **specify_args):
     """smoothness: a value fixes the Matern smoothness and takes it out of the search (theta_ini then holds variance, range,
     nugget).  method: "Nelder-Mead" (the reference's search) or "L-BFGS-B", which minimises over the log-parameters with the
     analytic gradient of the GPU (vecchia_likelihood_grad; d/d log theta = theta d/d theta) and needs cond_yz='z' and, for
-    'matern', smoothness in {0.5, 1.5, 2.5}.  n_evals counts likelihood (or value + gradient) evaluations."""
-    if method not in ("Nelder-Mead", "L-BFGS-B"):
+    'matern', smoothness in {0.5, 1.5, 2.5}; or "fisher", Fisher scoring over the log-parameters on the expected information of
+    the GPU (vecchia_likelihood_fisher, _fisher_scoring), with the preconditions of "L-BFGS-B".  n_evals counts likelihood (or
+    value + gradient [+ information]) evaluations.  For "fisher" the result also holds fisher_info (the information over the
+    searched parameters at theta_hat), theta_cov (its inverse) and theta_se (the square roots of that one's diagonal)."""
+    if method not in ("Nelder-Mead", "L-BFGS-B", "fisher"):
         raise ValueError(f"method='{method}' not defined")
     fix_nu = smoothness is not None
     if fix_nu and covmodel != "matern":
         raise ValueError("smoothness applies to covmodel='matern' only")
-    if method == "L-BFGS-B":
+    if method in ("L-BFGS-B", "fisher"):
         if specify_args.get("cond_yz") != "z":
-            raise ValueError("method='L-BFGS-B' needs cond_yz='z' (the likelihood whose gradient the GPU returns)")
+            raise ValueError(f"method='{method}' needs cond_yz='z' (the likelihood whose gradient the GPU returns)")
         if not isinstance(covmodel, str):
-            raise ValueError("method='L-BFGS-B' needs a named covariance family")
+            raise ValueError(f"method='{method}' needs a named covariance family")
         if covmodel == "matern" and (not fix_nu or float(smoothness) not in (0.5, 1.5, 2.5)):
-            raise ValueError("method='L-BFGS-B' with covmodel='matern' needs smoothness in {0.5, 1.5, 2.5}")
+            raise ValueError(f"method='{method}' with covmodel='matern' needs smoothness in {{0.5, 1.5, 2.5}}")
     data = np.asarray(data, dtype=np.float64)
     locs = np.asarray(locs, dtype=np.float64)
     if isinstance(X, str) and X == "missing":                        # :32-37 constant trend
@@ -179,6 +221,18 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
             return _BIG, np.zeros_like(lg)
         return -ll, -g * th
 
+    infos = {}                                                       # information over the searched parameters, by point
+
+    def loglik_fisher(lg):                                           # value, gradient and information in the log-parameters
+        evals[0] += 1
+        th = np.exp(lg)
+        cp, nug = full(th)
+        ll, g, info = A.vecchia_likelihood_fisher(z, va, cp, nug, covmodel=covmodel)
+        if covmodel == "matern":                                     # the smoothness is fixed
+            g, info = np.delete(g, 2), np.delete(np.delete(info, 2, axis=0), 2, axis=1)
+        infos[lg.tobytes()] = info
+        return ll, g * th, info * np.outer(th, th)
+
     parscale = np.ones(n_par)                                        # :83-85 (entries with theta.ini == 1 stay 1; the
     non1 = theta_ini != 1                                            #  reference's rep(1, length(n.par)) leaves them NA)
     parscale[non1] = np.log(theta_ini[non1])
@@ -188,6 +242,9 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         r = minimize(negloglik_grad, np.log(theta_ini), jac=True, method="L-BFGS-B",
                      options=dict(maxiter=maxit, ftol=1e-3 * reltol, gtol=1e-5))   # (relative decrease per iteration; gradient in log-parameters)
         xbest, fbest, conv, parscale = r.x, float(r.fun), (0 if r.success else 1), np.ones(n_par)
+    elif method == "fisher":
+        xbest, ll_best, _, _, _, conv = _fisher_scoring(loglik_fisher, np.log(theta_ini), reltol=reltol, maxit=maxit)
+        fbest, parscale = -ll_best, np.ones(n_par)
     else:
         xbest, fbest, _, conv = _nelder_mead_nash(lambda x: negloglik(x * parscale), x0, reltol=reltol, maxit=maxit)   # :87-93
 
@@ -199,8 +256,13 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         print("estimated trend coefficients:\n", beta_hat)
         print("estimated covariance parameters:\n",
               dict(zip(("variance", "range", "nugget") if fix_nu else ("variance", "range", "smoothness", "nugget"), theta_hat)))
-    return dict(z=z, beta_hat=beta_hat, theta_hat=theta_hat, trend=trend, locs=locs, covmodel=covmodel,
-                n_evals=evals[0], neg_loglik=float(res.fun), convergence=conv)
+    out = dict(z=z, beta_hat=beta_hat, theta_hat=theta_hat, trend=trend, locs=locs, covmodel=covmodel,
+               n_evals=evals[0], neg_loglik=float(res.fun), convergence=conv)
+    if method == "fisher":
+        out["fisher_info"] = infos[np.asarray(xbest).tobytes()]
+        out["theta_cov"] = np.linalg.inv(out["fisher_info"])
+        out["theta_se"] = np.sqrt(np.diag(out["theta_cov"]))
+    return out
 
 
 def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, **specify_args):

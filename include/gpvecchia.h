@@ -38,7 +38,7 @@ enum {
     GPV_ERR_UNSUPPORTED_NU = 4, /* Matern smoothness not in (0, 60] or not finite                */
     GPV_ERR_UNSUPPORTED_M = 5,  /* m+1 > 192 (m+1 <= 64: unrolled register kernels; up to 192 and any dimension: a slow
                                    workgroup-per-set kernel); m+1 > 64 for gpv_plan_build_posterior and for
-                                   gpv_plan_loglik_grad */
+                                   gpv_plan_loglik_grad and gpv_plan_loglik_fisher */
     GPV_ERR_HIP = 6,            /* HIP runtime failure (alloc, copy, launch)         */
     GPV_ERR_STATE = 7,          /* call order: result requested before an eval, no data set */
     GPV_ERR_INDEX = 8           /* neighbour index outside [0, Nlocs]                */
@@ -289,6 +289,25 @@ int gpv_plan_factor_stamp(gpv_plan *plan, int64_t *stamp);
 int gpv_plan_loglik_grad(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
                          double *loglik, double *grad /* ncovparms + 1 */, int64_t *n_failed,
                          double *row_terms /* NULL, or Nlocs x (ncovparms + 2), row-major */);
+
+/* The same value and gradient together with the expected Fisher information of that likelihood, for standard errors and Fisher
+ * scoring.  In the notation above, with t_i = D_i u (t = u for the nugget), a_i = u't_i and y_j = S'^-1 t_j, a row contributes
+ *   F_k[i][j] = t_i'y_j / u_last - 1/2 a_i a_j / u_last^2
+ *             = 1/2 tr(S'^-1 D_i S'^-1 D_j) - 1/2 tr(S'_c^-1 D_i,c S'_c^-1 D_j,c),   c: J without the row's own point,
+ * the expectation of -d2 l_k / dtheta_i dtheta_j (and of dl_k/dtheta_i dl_k/dtheta_j) under the exact process; the information
+ * is their sum.  It comes out of the pass that computes the gradient: the factorisation of each block is replayed on the
+ * ncovparms + 1 vectors t_i, nothing is factorised twice.
+ *   loglik, grad, n_failed   as for gpv_plan_loglik_grad
+ *   fisher     out, (ncovparms + 1)^2 row-major, parameters in the order of grad; exactly symmetric.  For "matern" every entry
+ *              that involves the smoothness is NaN.  With n_failed > 0 every entry is NaN.
+ *   row_terms  NULL, or out: Nlocs x (ncovparms + 2 + T) row-major with T = (ncovparms + 1)(ncovparms + 2) / 2, row k =
+ *              {l_k, its derivatives, the upper triangle of F_k row-major with i <= j} in the plan's ORDERED row numbering (NaN
+ *              in a failed row)
+ * Blocking, bitwise reproducible, leaves the plan's last evaluation intact, validates its arguments before the device is touched
+ * and returns the statuses of gpv_plan_loglik_grad for the same reasons (fisher NULL: GPV_ERR_BAD_ARG). */
+int gpv_plan_loglik_fisher(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
+                           double *loglik, double *grad /* ncovparms + 1 */, double *fisher /* (ncovparms + 1)^2, row-major */,
+                           int64_t *n_failed, double *row_terms /* NULL, or Nlocs x (ncovparms + 2 + T), row-major */);
 
 /* Vecchia-Laplace Newton-Raphson with the state on the device: calculate_posterior_VL of R/vecchia_laplace_NR.R:31-155
  * for fully observed data.  model: position in the reference's family list (:32): 0 gaussian, 1 logistic, 2 poisson,

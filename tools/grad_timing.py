@@ -1,11 +1,13 @@
 """Cost of one gpv_plan_loglik_grad call (gpv_grad.hip) beside one likelihood-only evaluation of the same plan:
 
-    python tools/grad_timing.py [--n 1000000] [--m 30] [--nu 1.5] [--rounds 9] [--reps 7]
+    python tools/grad_timing.py [--n 1000000] [--m 30] [--nu 1.5] [--rounds 9] [--reps 7] [--fisher]
 
 One process, one plan (d = 2, cond.yz = 'z', maxmin ordering).  After a clock warm-up of likelihood evaluations (as bench.py
 does) the two legs run in alternating rounds -- `reps` gradient calls, `reps` plan.eval(GPV_WANT_LOGLIK_Z) + sums() -- and each
 is reported as the median over the rounds of the round's median, wall clock around the blocking calls.  The second leg is the
 code the benchmark measures and is the yardstick; central differences over the 3 parameters would cost 2 * 3 + 1 = 7 of them.
+--fisher adds a third leg to every round, `reps` calls of gpv_plan_loglik_fisher (gpv_fisher_kernel.hpp), and
+reports it beside the gradient call of the same build, which is its yardstick (loglik_fisher_ms, fisher_over_grad).
 Prints one JSON line."""
 import argparse
 import json
@@ -36,6 +38,7 @@ def main():
     ap.add_argument("--nu", type=float, default=1.5)
     ap.add_argument("--rounds", type=int, default=9)
     ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--fisher", action="store_true", help="also time gpv_plan_loglik_fisher, in the same alternating rounds")
     a = ap.parse_args()
     n, m = a.n, a.m
     locs = np.random.default_rng(0).random((n, 2))
@@ -52,13 +55,20 @@ def main():
 
     def grad():
         return plan.loglik_grad("matern", cp, tau)
+
+    def fisher():
+        return plan.loglik_fisher("matern", cp, tau)
     for _ in range(30):                                               # clock warm-up
         lik()
     ll, g, nfail = grad()                                             # first use: buffers
     ll_ref = G.loglik_z_from_sums(lik(), n)
-    t_grad, t_lik = [], []
+    if a.fisher:
+        ll_f, g_f, info, nfail_f = fisher()                           # first use: buffers
+    t_grad, t_lik, t_fi = [], [], []
     for _ in range(a.rounds):
         t_grad.append(med(grad, a.reps))
+        if a.fisher:
+            t_fi.append(med(fisher, a.reps))
         t_lik.append(med(lik, a.reps))
     out = dict(n=n, m=m, nu=a.nu, rounds=a.rounds, reps=a.reps, loglik_grad_ms=float(np.median(t_grad)),
                loglik_only_ms=float(np.median(t_lik)), loglik_grad_ms_rounds=[round(t, 4) for t in t_grad],
@@ -66,6 +76,12 @@ def main():
                value_rel_diff=abs(ll - ll_ref) / abs(ll_ref))
     out["ratio"] = out["loglik_grad_ms"] / out["loglik_only_ms"]
     out["central_difference_break_even"] = 7
+    if a.fisher:
+        keep = ~np.isnan(g)
+        out.update(loglik_fisher_ms=float(np.median(t_fi)), loglik_fisher_ms_rounds=[round(t, 4) for t in t_fi],
+                   fisher_n_failed=nfail_f, fisher_value_rel_diff=abs(ll_f - ll) / abs(ll),
+                   fisher_grad_rel_diff=float((np.abs(g_f - g)[keep] / np.abs(g)[keep]).max()))
+        out["fisher_over_grad"] = out["loglik_fisher_ms"] / out["loglik_grad_ms"]
     print(json.dumps(out))
 
 
