@@ -24,6 +24,9 @@ from . import specify as S
 from ._lib import GPV_WANT_DENOM, GPV_WANT_LOGLIK_Z, GPV_WANT_NUMERATOR, GPV_WANT_U, NSUMS, GpvError
 
 
+WHITEN_MAX_COLS = 16                                  # gpv_whiten_max_cols(): columns per Plan.whiten call
+
+
 # ---------------------------------------------------------------------------
 # device plan
 # ---------------------------------------------------------------------------
@@ -213,6 +216,31 @@ class Plan:
         L.check(st, "gpv_plan_loglik_fisher")
         out = (float(ll.value), grad, info, int(nf.value))
         return out + (rt,) if row_terms else out
+
+    def whiten(self, B_ord, want_E=False):
+        """The whitening operator of the plan's latest evaluation (which must have asked for GPV_WANT_U) applied to the columns
+        of B_ord, (Nlocs, ncols) or (Nlocs,) in the plan's ORDERED row numbering, ncols <= 16 (gpv_plan_whiten): returns
+        (G, logdet, n_failed) and, with want_E, a fourth array E (Nlocs, ncols).  E[k] is the standardised conditional residual
+        of row k given its neighbours under C + tau I, G = E'E (exactly symmetric), logdet = sum_k log(tau_k + 1/d_k^2): for
+        the plan's data, G is sums[3] and logdet is sums[2].  With n_failed > 0 (blocks that were not positive definite) G and
+        logdet are NaN.  The plan's last evaluation (sums, Lentries, factor stamp) is left as it was."""
+        B = np.asarray(B_ord, dtype=np.float64)
+        if B.ndim == 1:
+            B = B[:, None]
+        if B.ndim != 2 or B.shape[0] != self.Nlocs:
+            raise ValueError("B_ord must have one row per ordered location of the plan")
+        ncols = int(B.shape[1])
+        if ncols < 1 or ncols > WHITEN_MAX_COLS:
+            raise ValueError(f"whiten takes 1 to {WHITEN_MAX_COLS} columns per call")
+        B = np.asfortranarray(B)
+        G = np.zeros((ncols, ncols))
+        E = np.zeros((self.Nlocs, ncols), order="F") if want_E else None
+        ld, nf = C.c_double(0.0), C.c_int64(0)
+        st = L.lib().gpv_plan_whiten(self._h, L.dptr(B), self.Nlocs, ncols, L.dptr(E) if want_E else None, self.Nlocs,
+                                     L.dptr(G), C.byref(ld), C.byref(nf))
+        L.check(st, "gpv_plan_whiten")
+        out = (G, float(ld.value), int(nf.value))
+        return out + (E,) if want_E else out
 
     def lincomb(self, H_ord, cov_mat=False):
         """Var(H y | z) (or, with cov_mat, Cov) for the rows of H_ord, a scipy.sparse or dense matrix with Nlocs columns in
@@ -1083,3 +1111,132 @@ def vecchia_likelihood_fisher(z, vecchia_approx, covparms, nuggets, covmodel="ma
     plan, nug = _grad_plan("vecchia_likelihood_fisher", z, vecchia_approx, nuggets, covmodel, device)
     ll, grad, info, _ = plan.loglik_fisher(covmodel, covparms, nug)
     return ll, grad, info
+
+
+# ---------------------------------------------------------------------------
+# whitening with the resident factor: GLS trend (profile likelihood), replicated data
+# ---------------------------------------------------------------------------
+def _whiten_plan(name, va, covparms, nuggets, covmodel, device):
+    """The plan of vecchia_whiten / vecchia_profile_likelihood / vecchia_likelihood_replicates after their common refusals,
+    evaluated with GPV_WANT_U at these parameters: the factor Plan.whiten reads is resident."""
+    if va["cond_yz"] not in ("z", "false"):
+        raise ValueError(f"{name} needs cond_yz='z' (the whitening of the other modes goes through the posterior factor)")
+    if not isinstance(covmodel, str):
+        raise ValueError(f"{name} needs a named covariance family ('matern' or 'esqe'), not a function or matrix")
+    n = va["locsord"].shape[0]
+    if int(np.sum(va["obs"])) != n:
+        raise ValueError(f"{name} does not take plans with prediction locations")
+    nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
+    if nug.size not in (1, n):
+        raise ValueError(f"{name}: nuggets must be one value or one per location")
+    plan = _plan_for(va, device)
+    plan.eval(covmodel, covparms, _device_nuggets(va, nug), GPV_WANT_U)
+    return plan
+
+
+def _user_columns(name, B, va):
+    B = np.asarray(B, dtype=np.float64)
+    if B.ndim == 1:
+        B = B[:, None]
+    if B.ndim != 2 or B.shape[0] != va["locsord"].shape[0]:
+        raise ValueError(f"{name}: the columns must have one row per location")
+    if not np.all(np.isfinite(B)):
+        raise ValueError(f"{name} needs complete, finite columns (no NaN)")
+    return B
+
+
+def vecchia_whiten(B, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+    """Whitens the columns of B (n x c, or a vector), given in the CALLER's order of the locations, with the Vecchia factor at
+    these parameters: one evaluation (GPV_WANT_U), then ceil(c / 16) Plan.whiten calls.  Returns (E, logdet): E (n x c) in the
+    ORDERED row numbering of the approximation, E[k] the standardised conditional residual of ordered row k, so that
+    E'E = B'(C + tau I)^-1 B under the approximation, and logdet = log det(C + tau I) under it."""
+    va = vecchia_approx
+    B = _user_columns("vecchia_whiten", B, va)
+    plan = _whiten_plan("vecchia_whiten", va, covparms, nuggets, covmodel, device)
+    Bord = B[va["ord_z"] - 1]
+    E = np.empty(Bord.shape)
+    logdet = np.nan
+    for c0 in range(0, Bord.shape[1], WHITEN_MAX_COLS):
+        _, logdet, _, Ec = plan.whiten(Bord[:, c0:c0 + WHITEN_MAX_COLS], want_E=True)
+        E[:, c0:c0 + WHITEN_MAX_COLS] = Ec
+    return E, logdet
+
+
+def profile_from_gram(G, logdet, n):
+    """The Gaussian profile likelihood of a linear trend from the Gram matrix of the whitened columns [X | z] (pure host
+    algebra): with A = X'QX = G[:q, :q], b = X'Qz = G[:q, q] and s = z'Qz = G[q, q] (Q the precision of the approximation),
+    beta_hat = A^-1 b, beta_cov = A^-1, quadform = s - b'beta_hat, loglik = -1/2 logdet - 1/2 quadform - 1/2 n log 2 pi.
+    ValueError when A is singular (collinear trend columns)."""
+    G = np.asarray(G, dtype=np.float64)
+    q = G.shape[0] - 1
+    if G.ndim != 2 or G.shape[1] != q + 1 or q < 1:
+        raise ValueError("G must be the square Gram matrix of at least one trend column and the data")
+    Amat, b, s = G[:q, :q], G[:q, q], float(G[q, q])
+    if not np.all(np.isfinite(G)):
+        raise ValueError("the Gram matrix is not finite")
+    try:
+        np.linalg.cholesky(Amat)
+        singular = np.linalg.cond(Amat) > 1.0 / np.finfo(float).eps
+    except np.linalg.LinAlgError:
+        singular = True
+    if singular:
+        raise ValueError("X'QX is singular: the trend columns are collinear")
+    beta_cov = np.linalg.inv(Amat)
+    beta_cov = 0.5 * (beta_cov + beta_cov.T)
+    beta_hat = np.linalg.solve(Amat, b)
+    quadform = s - float(b @ beta_hat)
+    loglik = -0.5 * float(logdet) - 0.5 * quadform - 0.5 * n * np.log(2.0 * np.pi)
+    return dict(beta_hat=beta_hat, beta_cov=beta_cov, quadform=quadform, logdet=float(logdet), loglik=loglik)
+
+
+def vecchia_profile_likelihood(data, X, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+    """Generalised least squares with the trend coefficients profiled out: data = X beta + field, beta_hat(theta) =
+    (X'QX)^-1 X'Qz under the Vecchia precision Q at (covparms, nuggets).  One evaluation (GPV_WANT_U) plus one Plan.whiten of
+    [X | data]; returns the dict of profile_from_gram (beta_hat, beta_cov, quadform, logdet, loglik).  X: n x q, q + 1 <= 16.
+    When some block is not positive definite at these parameters loglik is -Inf (as vecchia_likelihood) and the rest NaN."""
+    va = vecchia_approx
+    X = np.asarray(X, dtype=np.float64)
+    if X.ndim == 1:
+        X = X[:, None]
+    if X.ndim != 2 or X.shape[1] < 1:
+        raise ValueError("vecchia_profile_likelihood: X must be n x q with q >= 1")
+    if X.shape[1] + 1 > WHITEN_MAX_COLS:
+        raise ValueError(f"vecchia_profile_likelihood takes at most {WHITEN_MAX_COLS - 1} trend columns")
+    data = np.asarray(data, dtype=np.float64).reshape(-1)
+    if X.shape[0] != data.shape[0]:
+        raise ValueError("vecchia_profile_likelihood: X and data must have one row per location")
+    n, q = data.shape[0], X.shape[1]
+    if n != va["locsord"].shape[0]:
+        raise ValueError("vecchia_profile_likelihood: the columns must have one row per location")
+    o = va["ord_z"] - 1
+    Bord = np.empty((n, q + 1), order="F")               # [X | data] in ordered rows, gathered column by column: one pass each
+    for j in range(q):
+        np.take(X[:, j], o, out=Bord[:, j])
+    np.take(data, o, out=Bord[:, q])
+    if not np.isfinite(Bord).all():
+        raise ValueError("vecchia_profile_likelihood needs complete, finite columns (no NaN)")
+    plan = _whiten_plan("vecchia_profile_likelihood", va, covparms, nuggets, covmodel, device)
+    G, logdet, n_failed = plan.whiten(Bord)
+    if n_failed > 0:
+        return dict(beta_hat=np.full(q, np.nan), beta_cov=np.full((q, q), np.nan), quadform=np.nan, logdet=np.nan,
+                    loglik=-np.inf)
+    return profile_from_gram(G, logdet, n)
+
+
+def vecchia_likelihood_replicates(Z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+    """The log-likelihoods of R realisations over the same locations (the columns of Z, n x R, in the CALLER's order) under one
+    parameter value: ONE evaluation (the factor does not depend on the data), then ceil(R / 16) Plan.whiten calls.  Entry r
+    equals vecchia_likelihood(Z[:, r], ...)."""
+    va = vecchia_approx
+    Z = _user_columns("vecchia_likelihood_replicates", Z, va)
+    plan = _whiten_plan("vecchia_likelihood_replicates", va, covparms, nuggets, covmodel, device)
+    Zord = Z[va["ord_z"] - 1]
+    n, R = Zord.shape
+    out = np.empty(R)
+    for c0 in range(0, R, WHITEN_MAX_COLS):
+        G, logdet, n_failed = plan.whiten(Zord[:, c0:c0 + WHITEN_MAX_COLS])
+        if n_failed > 0:
+            out[c0:c0 + WHITEN_MAX_COLS] = -np.inf
+        else:
+            out[c0:c0 + WHITEN_MAX_COLS] = -0.5 * logdet - 0.5 * np.diag(G) - 0.5 * n * np.log(2.0 * np.pi)
+    return out

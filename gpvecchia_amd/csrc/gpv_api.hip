@@ -9,6 +9,8 @@
 #include "gpv_posterior_ext.h"
 #include "gpv_philox.hpp"
 #include "gpv_grad.h"
+#define GPV_WHITEN_LINKAGE __attribute__((weak))
+#include "gpv_whiten.h"
 #include "gpv_hip_raii.hpp"
 
 #include <dlfcn.h>
@@ -386,6 +388,15 @@ struct gpv_plan {
     // the same for gpv_plan_loglik_fisher (gpv_fisher_kernel.hpp)
     DevBuf<double> d_fi_part, d_fi_tot, d_fi_rows;
     int fi_grid = 0;
+    // gpv_plan_whiten (gpv_whiten.hip), allocated on first use and grown with the padded column count: the caller's columns as
+    // they arrive / E on its way back [cp][Nlocs], the columns by internal position [Nlocs][cp], E [Nlocs][cp], the partials of
+    // both passes and the totals
+    DevBuf<double> d_wh_in, d_wh_B, d_wh_E, d_wh_wpart, d_wh_gpart, d_wh_tot;
+    int wh_cp_cap = 0, wh_cp_last = 0, wh_wgrid = 0, wh_ggrid = 0;
+    // d_L and the nuggets on the device (d_nuggets / nug_scalar) belong to evaluation L_of_eval of the plan (evaluations are
+    // counted from 1; 0: to none).  Set at the end of an evaluation that materialised U, cleared before anything of the two is
+    // rewritten: an evaluation that starts, a Vecchia-Laplace step that writes its pseudo-nuggets, a rebuilt posterior structure.
+    int64_t eval_count = 0, L_of_eval = 0;
     // Vecchia-Laplace state (gpv_plan_vl_begin): data z, prior mean, two latent-mean buffers (current / next), flags + max
     DevBuf<double> d_vl_z, d_vl_pm, d_vl_y[2], d_vl_out;
     DevBuf<double> d_vl_y0;                          // the start value, kept so that a restart needs no upload
@@ -1094,6 +1105,7 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
     hipStreamCaptureStatus cap0 = hipStreamCaptureStatusNone;
     if (hipStreamIsCapturing(st, &cap0) != hipSuccess) { (void)hipGetLastError(); cap0 = hipStreamCaptureStatusNone; }
     if (pl->last_stream && pl->last_stream != st && cap0 == hipStreamCaptureStatusNone) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    pl->L_of_eval = 0;                                            // (nuggets and, with GPV_WANT_U, d_L are about to change)
     if (flags & GPV_WANT_U) GPV_BUF(pl->d_L, ensure((size_t)(pl->rows > 0 ? pl->rows : 1) * pl->P));
     int rc = cs.cov != COV_DENSE ? eval_nuggets(pl, nuggets, n_nuggets, flags, st) : GPV_OK;
     SetArgs a;
@@ -1106,6 +1118,9 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
     if ((flags & kPostFlags) && (rc = posterior_pass_enqueue(pl, flags, a.sums_copy, st)) != GPV_OK) return rc;
     pl->evaluated = true;
     pl->have_U = (flags & GPV_WANT_U) != 0;
+    ++pl->eval_count;
+    // (a dense covariance matrix carries no nugget: U_NZentries_mat, src/U_NZentries.cpp:144)
+    if (pl->have_U && cs.cov != COV_DENSE) pl->L_of_eval = pl->eval_count;
     pl->last_stream = st;
     return GPV_OK;
 }
@@ -1664,6 +1679,7 @@ static int build_posterior_impl(gpv_plan *pl, const int *revNN, const int *revCo
     GPV_BUF(pl->d_mu, ensure((size_t)n));
     GPV_BUF(pl->d_post_part, ensure(2048));                            // launch_sum_pair: 2 x 1024
     if (!pl->post_fused) GPV_BUF(pl->d_L, ensure((size_t)n * pl->P));  // (fused: only when the caller wants U)
+    pl->L_of_eval = 0;                                                 // (evaluations from here on may leave d_L alone: fused)
     pl->have_post = true;
     return GPV_OK;
 }
@@ -1797,6 +1813,7 @@ static int vl_step_enqueue(gpv_plan *pl, const char *covType, const double *covp
     const double *y = pl->d_vl_y[pl->vl_cur];
     double *ynew = pl->d_vl_y[pl->vl_cur ^ 1];
     GPV_HIP(hipMemsetAsync(pl->d_vl_flags, 0, sizeof(int), st));
+    pl->L_of_eval = 0;                              // the pseudo-nuggets overwrite the nuggets d_L was computed with
     // pseudo-data and pseudo-nuggets of this step (:93-109) straight into the plan's data / nugget arrays
     double *data_int = pl->dim <= 3 ? pl->d_locs : pl->d_z;
     const int dstr = pl->dim <= 3 ? 4 : 1, doff = pl->dim <= 3 ? 3 : 0;
@@ -2066,6 +2083,113 @@ int gpv_plan_loglik_fisher(gpv_plan *pl, const char *covType, const double *covp
         }
     }
     return GPV_OK;
+}
+
+// ---- the whitening operator of the plan's latest evaluation applied to a block of columns (gpv_whiten.hip) -----------------
+int gpv_whiten_max_cols(void) { return kWhitenMaxCols; }
+
+// gpv_whiten.hip is part of this link (see GPV_WHITEN_LINKAGE in gpv_whiten.h)
+static bool whiten_linked()
+{
+    return &launch_whiten != nullptr && &launch_whiten_gram != nullptr && &launch_whiten_pack != nullptr &&
+           &launch_whiten_unpack != nullptr && &whiten_grid != nullptr && &whiten_gram_grid != nullptr;
+}
+
+// the two passes on what is resident: d_wh_B -> d_wh_E, partials, totals
+static hipError_t whiten_enqueue(gpv_plan *pl, int cp, hipStream_t st)
+{
+    WhitenArgs a;
+    a.L = pl->d_L; a.nn = pl->d_nn; a.rowid = pl->d_rowid;
+    a.nuggets = pl->nug_is_scalar ? nullptr : pl->d_nuggets.get();
+    a.nug_scalar = pl->nug_scalar;
+    a.B = pl->d_wh_B; a.E = pl->d_wh_E; a.part = pl->d_wh_wpart;
+    a.rows = pl->rows; a.P = pl->P;
+    const hipError_t e = launch_whiten(a, cp, pl->wh_wgrid, st);
+    if (e != hipSuccess) return e;
+    return launch_whiten_gram(pl->d_wh_E, pl->rows, cp, pl->wh_ggrid, pl->d_wh_gpart, pl->d_wh_wpart, pl->wh_wgrid, pl->d_wh_tot, st);
+}
+
+// Reads d_L, the index arrays and the nuggets of the plan's latest evaluation and writes buffers of its own, so the sums, the U
+// entries, the posterior state and the factor stamp stay what they were.
+int gpv_plan_whiten(gpv_plan *pl, const double *B_ord, int64_t ldb, int ncols, double *E_ord, int64_t lde, double *gram,
+                    double *logdet, int64_t *n_failed)
+{
+    if (!pl || !B_ord || !gram || !logdet || !n_failed) return GPV_ERR_BAD_ARG;
+    if (ncols < 1 || ncols > kWhitenMaxCols) return GPV_ERR_BAD_ARG;
+    const int64_t n = pl->Nlocs;
+    if (ldb < n || (E_ord && lde < n)) return GPV_ERR_BAD_ARG;
+    if (!whiten_linked()) return GPV_ERR_STATE;
+    if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L) return GPV_ERR_STATE;
+    if (pl->comm || pl->rows != n || n < 1 || pl->d_obs || pl->latent_nb) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));   // the evaluation's stream
+    const int cp = whiten_cp(ncols);
+    if (cp > pl->wh_cp_cap) {
+        pl->wh_cp_cap = 0;
+        GPV_BUF(pl->d_wh_in, resize((size_t)n * cp));
+        GPV_BUF(pl->d_wh_B, resize((size_t)n * cp));
+        GPV_BUF(pl->d_wh_E, resize((size_t)n * cp));
+        pl->wh_cp_cap = cp;
+    }
+    if (!pl->d_wh_tot) {
+        pl->wh_wgrid = whiten_grid(pl->rows, pl->cus);
+        pl->wh_ggrid = whiten_gram_grid(pl->rows, pl->cus);
+        GPV_BUF(pl->d_wh_wpart, resize((size_t)pl->wh_wgrid * kWhitenNV));
+        GPV_BUF(pl->d_wh_gpart, resize((size_t)pl->wh_ggrid * kGramTile));
+        GPV_BUF(pl->d_wh_tot, resize(kWhitenTotals));
+    }
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    for (int j = 0; j < ncols; ++j)
+        if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_wh_in + (size_t)j * n, B_ord + (int64_t)j * ldb, sizeof(double) * (size_t)n,
+                                          hipMemcpyHostToDevice, st)))
+            return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_whiten_pack(pl->d_wh_in, pl->d_newpos, n, ncols, cp, pl->d_wh_B, st))) return fail(GPV_ERR_HIP);
+    pl->wh_cp_last = cp;
+    if (GPV_HIP_FAILED(whiten_enqueue(pl, cp, st))) return fail(GPV_ERR_HIP);
+    double tot[kWhitenTotals];
+    if (GPV_HIP_FAILED(hipMemcpyAsync(tot, pl->d_wh_tot, sizeof(tot), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+    if (E_ord) {
+        if (GPV_HIP_FAILED(launch_whiten_unpack(pl->d_wh_E, n, ncols, cp, pl->d_wh_in, st))) return fail(GPV_ERR_HIP);
+        for (int j = 0; j < ncols; ++j)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(E_ord + (int64_t)j * lde, pl->d_wh_in + (size_t)j * n, sizeof(double) * (size_t)n,
+                                              hipMemcpyDeviceToHost, st)))
+                return fail(GPV_ERR_HIP);
+    }
+    GPV_HIP(hipStreamSynchronize(st));
+    const bool bad = tot[kGramTile + 1] > 0.0;
+    *n_failed = (int64_t)tot[kGramTile + 1];
+    *logdet = bad ? NAN : tot[kGramTile];
+    for (int i = 0; i < ncols; ++i)
+        for (int j = 0; j < ncols; ++j) gram[i * ncols + j] = bad ? NAN : tot[i * kWhitenMaxCols + j];
+    return GPV_OK;
+}
+
+// developer aid (tools/whiten_timing.py; not part of the public header): device time of `reps` runs of the two passes (whitening,
+// Gram with its sum) over the columns the latest gpv_plan_whiten left on the device, by a pair of events around them alone: no
+// copies, no packing
+extern "C" int gpv_plan_debug_whiten_ms(gpv_plan *pl, int reps, double *ms)
+{
+    if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
+    if (!whiten_linked()) return GPV_ERR_STATE;
+    if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || pl->wh_cp_last == 0 || !pl->d_wh_tot) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    Event a, b;
+    GPV_HIP(hipEventCreate(a.put()));
+    GPV_HIP(hipEventCreate(b.put()));
+    int rc = GPV_OK;
+    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
+        float t = 0.f;
+        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(whiten_enqueue(pl, pl->wh_cp_last, st)) ||
+            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
+            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
+            rc = GPV_ERR_HIP;
+        ms[r] = (double)t;
+    }
+    (void)hipStreamSynchronize(st);
+    return rc;
 }
 
 // LincombArgs::lrec from the plan's structure as it lives on the device (built on the first gpv_plan_lincomb after a

@@ -147,10 +147,35 @@ def _fisher_scoring(fn, x0, reltol, maxit, max_step=1.0, max_halvings=10):
         x, f, g, info = xn, fn_, gn, infon
 
 
+def profile_negloglik_grad(lg, data, X, va, covmodel="matern", smoothness=None):
+    """Negative profile log-likelihood of the GLS trend and its gradient in the log-parameters lg (variance, range[, further
+    covparms], nugget; for 'matern' the smoothness is the fixed `smoothness`).  The value and beta_hat(theta) come from
+    vecchia_profile_likelihood; the gradient is vecchia_likelihood_grad on the residual data - X beta_hat(theta): at beta_hat
+    the derivative of the likelihood in beta vanishes, so the partial gradient in theta IS the gradient of the profile (the
+    envelope theorem).  Returns (value, gradient, profile dict)."""
+    th = np.exp(np.asarray(lg, dtype=np.float64))
+    matern = covmodel == "matern"
+    cp = np.concatenate([th[:2], [float(smoothness)], th[2:-1]]) if matern else th[:-1]
+    prof = A.vecchia_profile_likelihood(data, X, va, cp, th[-1], covmodel=covmodel)
+    if not np.isfinite(prof["loglik"]):
+        return _BIG, np.zeros_like(th), prof
+    _, g = A.vecchia_likelihood_grad(data - X @ prof["beta_hat"], va, cp, th[-1], covmodel=covmodel)
+    g = np.delete(g, 2) if matern else g
+    return -prof["loglik"], -g * th, prof
+
+
 def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini=None, output_level=1,
                      reltol=np.sqrt(np.finfo(float).eps), seed=0, maxit=300, smoothness=None, method="Nelder-Mead",
-                     **specify_args):
-    """smoothness: a value fixes the Matern smoothness and takes it out of the search (theta_ini then holds variance, range,
+                     trend="ols", **specify_args):
+    """trend: "ols" (the reference, R/vecchia_wrappers.R:32-51: coefficients by ordinary least squares once, the covariance
+    fitted to their residuals) or "gls": generalised least squares with the coefficients profiled out of the likelihood
+    (vecchia_profile_likelihood: beta_hat(theta) under the Vecchia precision at every step), for X given or the constant
+    column; needs cond_yz='z'.  Nelder-Mead then minimises the negative profile likelihood; "L-BFGS-B" and "fisher" take value and
+    beta_hat(theta) from the profile call and gradient / information from vecchia_likelihood_grad / _fisher on the residual
+    data - X beta_hat(theta) (the envelope theorem; the expected information is block diagonal between beta and theta, so
+    theta_se keeps its meaning).  With "gls" the result also holds beta_cov and beta_se, beta_hat is the GLS value at theta_hat
+    and z is the GLS residual.
+    smoothness: a value fixes the Matern smoothness and takes it out of the search (theta_ini then holds variance, range,
     nugget).  method: "Nelder-Mead" (the reference's search) or "L-BFGS-B", which minimises over the log-parameters with the
     analytic gradient of the GPU (vecchia_likelihood_grad; d/d log theta = theta d/d theta) and needs cond_yz='z' and, for
     'matern', smoothness in {0.5, 1.5, 2.5}; or "fisher", Fisher scoring over the log-parameters on the expected information of
@@ -162,6 +187,16 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     fix_nu = smoothness is not None
     if fix_nu and covmodel != "matern":
         raise ValueError("smoothness applies to covmodel='matern' only")
+    if trend not in ("ols", "gls"):
+        raise ValueError(f"trend='{trend}' not defined")
+    gls = trend == "gls"
+    if gls:
+        if specify_args.get("cond_yz") != "z":
+            raise ValueError("trend='gls' needs cond_yz='z' (the likelihood whose whitening operator the GPU applies)")
+        if not isinstance(covmodel, str):
+            raise ValueError("trend='gls' needs a named covariance family")
+        if X is None:
+            raise ValueError("trend='gls' needs a trend: X, or the constant column of X='missing'")
     if method in ("L-BFGS-B", "fisher"):
         if specify_args.get("cond_yz") != "z":
             raise ValueError(f"method='{method}' needs cond_yz='z' (the likelihood whose gradient the GPU returns)")
@@ -174,16 +209,18 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     if isinstance(X, str) and X == "missing":                        # :32-37 constant trend
         beta_hat = np.array([data.mean()])
         z = data - beta_hat[0]
-        trend = "constant"
+        trend_kind = "constant"
+        Xg = np.ones((data.shape[0], 1)) if gls else None
     elif X is None:                                                  # :39-44 no trend
         beta_hat = np.array([])
         z = data
-        trend = "none"
+        trend_kind = "none"
     else:                                                            # :46-51 user-specified trend
         X = np.asarray(X, dtype=np.float64)
         beta_hat = np.linalg.solve(X.T @ X, X.T @ data)
         z = data - X @ beta_hat
-        trend = "userspecified"
+        trend_kind = "userspecified"
+        Xg = X if X.ndim == 2 else X[:, None]
     va = A.vecchia_specify(locs, m, **specify_args)                  # :55
     if covmodel == "matern" and (theta_ini is None or np.any(np.isnan(theta_ini))):   # :59-67
         var_res = np.var(z, ddof=1)
@@ -233,6 +270,33 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         infos[lg.tobytes()] = info
         return ll, g * th, info * np.outer(th, th)
 
+    if gls:                                                          # the same three objectives on the profile likelihood
+        def negloglik(lg):                                           # noqa: F811
+            if covmodel == "matern" and not fix_nu and np.exp(lg[2]) > 10:
+                raise RuntimeError("The default optimization routine to find parameters did not converge. "
+                                   "Try writing your own optimization.")
+            evals[0] += 1
+            cp, nug = full(np.exp(lg))
+            return -A.vecchia_profile_likelihood(data, Xg, va, cp, nug, covmodel=covmodel)["loglik"]
+
+        def negloglik_grad(lg):                                      # noqa: F811
+            evals[0] += 1
+            f, g, _ = profile_negloglik_grad(lg, data, Xg, va, covmodel, smoothness)
+            return f, g
+
+        def loglik_fisher(lg):                                       # noqa: F811
+            evals[0] += 1
+            th = np.exp(lg)
+            cp, nug = full(th)
+            prof = A.vecchia_profile_likelihood(data, Xg, va, cp, nug, covmodel=covmodel)
+            if not np.isfinite(prof["loglik"]):
+                return -np.inf, np.zeros_like(th), np.eye(len(th))
+            _, g, info = A.vecchia_likelihood_fisher(data - Xg @ prof["beta_hat"], va, cp, nug, covmodel=covmodel)
+            if covmodel == "matern":
+                g, info = np.delete(g, 2), np.delete(np.delete(info, 2, axis=0), 2, axis=1)
+            infos[lg.tobytes()] = info
+            return prof["loglik"], g * th, info * np.outer(th, th)
+
     parscale = np.ones(n_par)                                        # :83-85 (entries with theta.ini == 1 stay 1; the
     non1 = theta_ini != 1                                            #  reference's rep(1, length(n.par)) leaves them NA)
     parscale[non1] = np.log(theta_ini[non1])
@@ -252,16 +316,24 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         x, fun = xbest, fbest
     res = _Res()
     theta_hat = np.exp(res.x * parscale)
+    if gls:                                                          # the GLS coefficients and residual at the estimate
+        cp_hat, nug_hat = full(theta_hat)
+        prof = A.vecchia_profile_likelihood(data, Xg, va, cp_hat, nug_hat, covmodel=covmodel)
+        beta_hat = prof["beta_hat"]
+        z = data - Xg @ beta_hat
     if output_level > 0:                                             # :98-101
         print("estimated trend coefficients:\n", beta_hat)
         print("estimated covariance parameters:\n",
               dict(zip(("variance", "range", "nugget") if fix_nu else ("variance", "range", "smoothness", "nugget"), theta_hat)))
-    out = dict(z=z, beta_hat=beta_hat, theta_hat=theta_hat, trend=trend, locs=locs, covmodel=covmodel,
+    out = dict(z=z, beta_hat=beta_hat, theta_hat=theta_hat, trend=trend_kind, locs=locs, covmodel=covmodel,
                n_evals=evals[0], neg_loglik=float(res.fun), convergence=conv)
     if method == "fisher":
         out["fisher_info"] = infos[np.asarray(xbest).tobytes()]
         out["theta_cov"] = np.linalg.inv(out["fisher_info"])
         out["theta_se"] = np.sqrt(np.diag(out["theta_cov"]))
+    if gls:
+        out["beta_cov"] = prof["beta_cov"]
+        out["beta_se"] = np.sqrt(np.diag(prof["beta_cov"]))
     return out
 
 

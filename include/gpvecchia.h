@@ -309,6 +309,34 @@ int gpv_plan_loglik_fisher(gpv_plan *plan, const char *covType, const double *co
                            double *loglik, double *grad /* ncovparms + 1 */, double *fisher /* (ncovparms + 1)^2, row-major */,
                            int64_t *n_failed, double *row_terms /* NULL, or Nlocs x (ncovparms + 2 + T), row-major */);
 
+/* The Vecchia whitening operator of the plan's latest evaluation applied to a block of columns, and their Gram matrix: the
+ * primitive behind a generalised-least-squares trend (profile likelihood) and behind the likelihood of replicated data, which
+ * share one factor.  Everything is in the plan's ORDERED row numbering.  For row k of a cond.yz='z' plan with the stored entries
+ * L_kj of that evaluation (neighbours j in J_k), its own entry d_k (the last one) and its nugget tau_k, a column b whitens to
+ *   e_k(b) = (b_k + (sum_{j in J_k} L_kj b_j) / d_k) / sqrt(tau_k + 1/d_k^2),      logdet = sum_k log(tau_k + 1/d_k^2):
+ * the standardised conditional residual of z_k given its neighbours' z under C + tau I, i.e. the density the sums [2], [3]
+ * describe: sum_k e_k(z)^2 is sums[3] and logdet is sums[2].  Needs an evaluation with GPV_WANT_U: the factor in HBM and the
+ * nuggets of THAT evaluation (a constant or a vector) are read, nothing is factorised again.
+ *   B_ord     ncols columns of length Nlocs, column-major with leading dimension ldb >= Nlocs (as gpv_plan_solve_t takes E)
+ *   E_ord     NULL, or out: the whitened columns, Nlocs x ncols with leading dimension lde >= Nlocs
+ *   gram      out, ncols x ncols row-major: E^T E, exactly symmetric
+ *   logdet    out
+ *   n_failed  out: rows whose block was not positive definite in that evaluation (sums[6]); with n_failed > 0 gram and logdet
+ *             are NaN, and so is every entry of E in such a row
+ * 1 <= ncols <= gpv_whiten_max_cols().  Blocking, on the plan's own stream; buffers are allocated on first use and belong to the
+ * plan.  Bitwise reproducible from call to call.  The plan's last evaluation stays intact: gpv_plan_get_sums,
+ * gpv_plan_get_Lentries, the posterior state and gpv_plan_factor_stamp return what they returned before.
+ * Arguments and state are validated before the device is touched.  GPV_ERR_BAD_ARG: a null plan or pointer (E_ord excepted),
+ * ncols outside [1, 16], ldb < Nlocs, lde < Nlocs with E_ord given; GPV_ERR_STATE: the plan's latest evaluation did not ask for
+ * GPV_WANT_U (or there was none, or something has rewritten its nuggets since: a Vecchia-Laplace step), a communicator
+ * attached, a row shard, unobserved locations (gpv_plan_set_observed), or a plan in which some neighbour is conditioned on as
+ * latent y (cond.yz other than 'z'). */
+int gpv_whiten_max_cols(void);         /* 16 */
+int gpv_plan_whiten(gpv_plan *plan, const double *B_ord, int64_t ldb, int ncols,
+                    double *E_ord /* NULL, or Nlocs x ncols, leading dimension lde */, int64_t lde,
+                    double *gram /* ncols x ncols row-major, exactly symmetric */,
+                    double *logdet, int64_t *n_failed);
+
 /* Vecchia-Laplace Newton-Raphson with the state on the device: calculate_posterior_VL of R/vecchia_laplace_NR.R:31-155
  * for fully observed data.  model: position in the reference's family list (:32): 0 gaussian, 1 logistic, 2 poisson,
  * 3 gamma, 4 beta, 5 gamma_alt.  likparms = {alpha, sigma} (:33), for beta {alpha, sigma, beta}.
