@@ -42,6 +42,7 @@ EXPORTS = [
     "gpv_plan_lincomb", "gpv_lincomb_batch", "gpv_plan_factor_stamp", "gpv_plan_solve_t",
     "gpv_draws_normals_host", "gpv_plan_draws_normals", "gpv_plan_draws_summary",
     "gpv_plan_loglik_grad", "gpv_plan_loglik_fisher",
+    "gpv_plan_loglik_grad_nu", "gpv_plan_loglik_fisher_nu", "gpv_matern_derivs_host",
     "gpv_whiten_max_cols", "gpv_plan_whiten",
 ]
 
@@ -115,6 +116,9 @@ def lib():
     L.gpv_plan_factor_stamp.argtypes = [vp, C.POINTER(C.c_int64)]
     L.gpv_plan_loglik_grad.argtypes = [vp, C.c_char_p, dp, C.c_int, C.c_double, dp, dp, C.POINTER(C.c_int64), dp]
     L.gpv_plan_loglik_fisher.argtypes = [vp, C.c_char_p, dp, C.c_int, C.c_double, dp, dp, dp, C.POINTER(C.c_int64), dp]
+    L.gpv_plan_loglik_grad_nu.argtypes = L.gpv_plan_loglik_grad.argtypes
+    L.gpv_plan_loglik_fisher_nu.argtypes = L.gpv_plan_loglik_fisher.argtypes
+    L.gpv_matern_derivs_host.argtypes = [C.c_double, C.c_double, dp, i64, dp]
     L.gpv_whiten_max_cols.restype = C.c_int
     L.gpv_whiten_max_cols.argtypes = []
     L.gpv_plan_whiten.argtypes = [vp, dp, i64, C.c_int, dp, i64, dp, dp, C.POINTER(C.c_int64)]

@@ -183,37 +183,43 @@ class Plan:
         L.check(L.lib().gpv_plan_factor_stamp(self._h, C.byref(st)), "gpv_plan_factor_stamp")
         return int(st.value)
 
-    def loglik_grad(self, covmodel, covparms, nugget, row_terms=False):
+    def loglik_grad(self, covmodel, covparms, nugget, row_terms=False, smoothness_grad=False):
         """Value and analytic gradient of the cond.yz='z' log-likelihood of the plan's data (gpv_plan_loglik_grad): returns
         (loglik, grad, n_failed) and, with row_terms, a fourth array (Nlocs, len(covparms) + 2) of {l_k, its derivatives} per
         ordered row.  grad = d/d covparms, then d/d nugget; the smoothness entry of 'matern' is NaN (not differentiated).
+        smoothness_grad=True (gpv_plan_loglik_grad_nu) accepts 'matern' at any smoothness and differentiates it wherever the
+        covariance is differentiable in it, i.e. everywhere but at exactly 0.5, 1.5 and 2.5, where the entry stays NaN.
         The plan's last evaluation (sums, Lentries, factor stamp) is left as it was."""
         cp = np.ascontiguousarray(covparms, dtype=np.float64)
         ll, nf = C.c_double(0.0), C.c_int64(0)
         grad = np.zeros(cp.size + 1)
         rt = np.zeros((self.Nlocs, cp.size + 2)) if row_terms else None
-        st = L.lib().gpv_plan_loglik_grad(self._h, covmodel.encode() if isinstance(covmodel, str) else bytes(covmodel),
-                                          L.dptr(cp), int(cp.size), float(nugget), C.byref(ll), L.dptr(grad), C.byref(nf),
-                                          L.dptr(rt) if row_terms else None)
-        L.check(st, "gpv_plan_loglik_grad")
+        name = "gpv_plan_loglik_grad_nu" if smoothness_grad else "gpv_plan_loglik_grad"
+        st = getattr(L.lib(), name)(self._h, covmodel.encode() if isinstance(covmodel, str) else bytes(covmodel),
+                                    L.dptr(cp), int(cp.size), float(nugget), C.byref(ll), L.dptr(grad), C.byref(nf),
+                                    L.dptr(rt) if row_terms else None)
+        L.check(st, name)
         out = (float(ll.value), grad, int(nf.value))
         return out + (rt,) if row_terms else out
 
-    def loglik_fisher(self, covmodel, covparms, nugget, row_terms=False):
+    def loglik_fisher(self, covmodel, covparms, nugget, row_terms=False, smoothness_grad=False):
         """Value, analytic gradient and expected Fisher information of the cond.yz='z' log-likelihood of the plan's data
         (gpv_plan_loglik_fisher): returns (loglik, grad, info, n_failed) and, with row_terms, a fifth array
         (Nlocs, len(covparms) + 2 + T), T = (len(covparms) + 1)(len(covparms) + 2) / 2, of {l_k, its derivatives, the upper triangle
         of the row's information, row-major} per ordered row.  info is (len(covparms) + 1) square, symmetric, in the parameter
-        order of grad; for 'matern' the entries that involve the smoothness are NaN.  The plan's last evaluation is left as it was."""
+        order of grad; for 'matern' the entries that involve the smoothness are NaN, unless smoothness_grad=True
+        (gpv_plan_loglik_fisher_nu) and the smoothness is none of 0.5, 1.5, 2.5: then the information is the full matrix.
+        The plan's last evaluation is left as it was."""
         cp = np.ascontiguousarray(covparms, dtype=np.float64)
         ll, nf = C.c_double(0.0), C.c_int64(0)
         npar = cp.size + 1
         grad, info = np.zeros(npar), np.zeros((npar, npar))
         rt = np.zeros((self.Nlocs, npar + 1 + npar * (npar + 1) // 2)) if row_terms else None
-        st = L.lib().gpv_plan_loglik_fisher(self._h, covmodel.encode() if isinstance(covmodel, str) else bytes(covmodel),
-                                            L.dptr(cp), int(cp.size), float(nugget), C.byref(ll), L.dptr(grad), L.dptr(info),
-                                            C.byref(nf), L.dptr(rt) if row_terms else None)
-        L.check(st, "gpv_plan_loglik_fisher")
+        name = "gpv_plan_loglik_fisher_nu" if smoothness_grad else "gpv_plan_loglik_fisher"
+        st = getattr(L.lib(), name)(self._h, covmodel.encode() if isinstance(covmodel, str) else bytes(covmodel),
+                                    L.dptr(cp), int(cp.size), float(nugget), C.byref(ll), L.dptr(grad), L.dptr(info),
+                                    C.byref(nf), L.dptr(rt) if row_terms else None)
+        L.check(st, name)
         out = (float(ll.value), grad, info, int(nf.value))
         return out + (rt,) if row_terms else out
 
@@ -1094,22 +1100,24 @@ def _grad_plan(name, z, va, nuggets, covmodel, device):
     return plan, float(nug[0])
 
 
-def vecchia_likelihood_grad(z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+def vecchia_likelihood_grad(z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0, smoothness_grad=False):
     """(loglik, grad) of the cond.yz='z' Vecchia log-likelihood, both on the GPU in one pass over the conditioning sets
     (Plan.loglik_grad): grad = d loglik / d covparms, then d / d nugget; for 'matern' the smoothness (0.5, 1.5 or 2.5) is not
     differentiated and its entry is NaN.  Only what has an exact, cheap gradient is accepted: cond.yz = 'z' (or m = 0), one
-    constant nugget > 0, complete data, no prediction locations, a named covariance family."""
+    constant nugget > 0, complete data, no prediction locations, a named covariance family.  smoothness_grad=True: any Matern
+    smoothness is accepted and its derivative returned (NaN only at exactly 0.5, 1.5, 2.5: Plan.loglik_grad)."""
     plan, nug = _grad_plan("vecchia_likelihood_grad", z, vecchia_approx, nuggets, covmodel, device)
-    ll, grad, _ = plan.loglik_grad(covmodel, covparms, nug)
+    ll, grad, _ = plan.loglik_grad(covmodel, covparms, nug, smoothness_grad=smoothness_grad)
     return ll, grad
 
 
-def vecchia_likelihood_fisher(z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+def vecchia_likelihood_fisher(z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0, smoothness_grad=False):
     """(loglik, grad, info): vecchia_likelihood_grad together with the expected Fisher information of the same likelihood
     (Plan.loglik_fisher), a symmetric matrix over {covparms, nugget} whose inverse at the estimate approximates the covariance of
-    the estimator.  For 'matern' the row and column of the smoothness are NaN.  Accepts what vecchia_likelihood_grad accepts."""
+    the estimator.  For 'matern' the row and column of the smoothness are NaN, unless smoothness_grad=True and the smoothness is
+    none of 0.5, 1.5, 2.5.  Accepts what vecchia_likelihood_grad accepts."""
     plan, nug = _grad_plan("vecchia_likelihood_fisher", z, vecchia_approx, nuggets, covmodel, device)
-    ll, grad, info, _ = plan.loglik_fisher(covmodel, covparms, nug)
+    ll, grad, info, _ = plan.loglik_fisher(covmodel, covparms, nug, smoothness_grad=smoothness_grad)
     return ll, grad, info
 
 

@@ -388,6 +388,8 @@ struct gpv_plan {
     // the same for gpv_plan_loglik_fisher (gpv_fisher_kernel.hpp)
     DevBuf<double> d_fi_part, d_fi_tot, d_fi_rows;
     int fi_grid = 0;
+    // gpv_plan_loglik_grad_nu / _fisher_nu at a general smoothness: the call's tables (gpv_bessel.hpp, MaternDTab)
+    DevBuf<double> d_gmt;
     // gpv_plan_whiten (gpv_whiten.hip), allocated on first use and grown with the padded column count: the caller's columns as
     // they arrive / E on its way back [cp][Nlocs], the columns by internal position [Nlocs][cp], E [Nlocs][cp], the partials of
     // both passes and the totals
@@ -1945,10 +1947,55 @@ int gpv_plan_factor_stamp(gpv_plan *pl, int64_t *stamp)
     return GPV_OK;
 }
 
-// Argument and state checks shared by gpv_plan_loglik_grad and gpv_plan_loglik_fisher, before the device is touched; on GPV_OK
-// `a` holds everything but the output buffers.
-static int grad_args_checked(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool &matern,
-                             GradArgs &a)
+// psi(x) = d ln Gamma(x) / dx for x > 0 (the C++ library has none): the recurrence psi(x) = psi(x + 1) - 1/x up to x >= 10, then
+// seven terms (k = 1..7) of the asymptotic series ln x - 1/(2x) - sum_k B_2k / (2k x^2k).  The truncation error is below the
+// first omitted term, |B_16| / 16 / x^16 = 0.4433 / x^16: at most 4.5e-17 for x >= 10 (at x = 6 it would be 1.6e-13, hence 10).
+static double gpv_digamma(double x)
+{
+    double acc = 0.0;
+    while (x < 10.0) {
+        acc -= 1.0 / x;
+        x += 1.0;
+    }
+    const double r = 1.0 / x, r2 = r * r;
+    // B_2k / 2k: 1/12, -1/120, 1/252, -1/240, 1/132, -691/32760, 1/12
+    const double ser = r2 * (1.0 / 12.0 - r2 * (1.0 / 120.0 - r2 * (1.0 / 252.0 - r2 * (1.0 / 240.0 - r2 * (1.0 / 132.0
+                       - r2 * (691.0 / 32760.0 - r2 * (1.0 / 12.0)))))));
+    return acc + std::log(x) - 0.5 * r - ser;
+}
+
+static MaternDerivConst matern_deriv_const(double nu)
+{
+    MaternDerivConst k;
+    k.nu = nu;
+    k.lnc = (1.0 - nu) * 0.69314718055994530942 - std::lgamma(nu);
+    k.lpsi = 0.69314718055994530942 + gpv_digamma(nu);
+    return k;
+}
+
+// {C / sigma^2, dC/drho / sigma^2, dC/dnu / sigma^2} of the general-nu Matern at s[i] = distance / range, on the host: the
+// functions the _nu entries tabulate and fall back to (gpv_bessel.hpp, matern_general_derivs)
+int gpv_matern_derivs_host(double nu, double range, const double *s, int64_t n, double *out)
+{
+    if (n < 0 || (n > 0 && (!s || !out))) return GPV_ERR_BAD_ARG;
+    if (!(range > 0.0) || !std::isfinite(range)) return GPV_ERR_BAD_ARG;
+    if (!(nu > 0.0 && nu <= 60.0)) return GPV_ERR_UNSUPPORTED_NU;
+    const MaternDerivConst k = matern_deriv_const(nu);
+    for (int64_t i = 0; i < n; ++i) {
+        double f[3];
+        matern_general_derivs(s[i], k, 0, f);
+        out[3 * i] = f[0];
+        out[3 * i + 1] = f[1] / range;
+        out[3 * i + 2] = f[2];
+    }
+    return GPV_OK;
+}
+
+// Argument and state checks shared by gpv_plan_loglik_grad and gpv_plan_loglik_fisher (and their _nu forms, with_nu: a general
+// smoothness is accepted and differentiated), before the device is touched; on GPV_OK `a` holds everything but the output
+// buffers and the tables of a general smoothness.
+static int grad_args_checked(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
+                             bool &matern, GradArgs &a)
 {
     matern = std::strcmp(covType, "matern") == 0;
     if (!matern && std::strcmp(covType, "esqe") != 0) return GPV_ERR_COVTYPE;
@@ -1957,7 +2004,8 @@ static int grad_args_checked(gpv_plan *pl, const char *covType, const double *co
     CovSetup cs;
     const int rc = cov_setup(covType, covparms, ncovparms, cs);
     if (rc != GPV_OK) return rc;
-    if (cs.cov == COV_MATERN_GEN) return GPV_ERR_UNSUPPORTED_NU;    // the reference's Matern is discontinuous in nu at the closed forms
+    // (the reference's Matern is discontinuous in nu at the closed forms, and analytic in it everywhere else)
+    if (cs.cov == COV_MATERN_GEN && !with_nu) return GPV_ERR_UNSUPPORTED_NU;
     if (pl->p > kGradMaxP) return GPV_ERR_UNSUPPORTED_M;
     if (!pl->has_z || pl->comm || pl->rows != pl->Nlocs || pl->d_obs || pl->latent_nb) return GPV_ERR_STATE;
     a.rec = pl->d_locs; a.locs = pl->d_locs; a.z = pl->d_z;
@@ -1967,18 +2015,39 @@ static int grad_args_checked(gpv_plan *pl, const char *covType, const double *co
     a.sA = cs.sA; a.cA = cs.cA; a.irA = 1.0 / covparms[1];
     a.sB = cs.sB; a.cB = cs.cB; a.irB = matern ? 0.0 : 1.0 / covparms[3];
     a.nug = nugget;
+    a.gen = MaternDerivConst{0.0, 0.0, 0.0};
+    a.gmt = nullptr; a.gmt_base = 0; a.gmt_nseg = 0;
+    if (cs.cov == COV_MATERN_GEN) {
+        a.sA = covparms[0];                                          // (cov_setup's is the normalised constant of the value path)
+        a.gen = matern_deriv_const(covparms[2]);
+    }
+    return GPV_OK;
+}
+
+// general smoothness: fit the call's tables over the plan's range of pair distances on `st`, in front of the pair passes (the
+// range of matern_table_prepare).  GPV_NO_MATERN_TABLE set, or a plan without distances: no table, every pair takes the
+// quadrature.  The calls are blocking, so one buffer serves.
+static int grad_gen_table(gpv_plan *pl, GradArgs &a, hipStream_t st)
+{
+    if (a.cov != COV_MATERN_GEN) return GPV_OK;
+    if (getenv("GPV_NO_MATERN_TABLE") != nullptr || !(pl->dist_min > 0.0) || !(pl->dist_max >= pl->dist_min)) return GPV_OK;
+    int e_lo = 0, base = 0, nseg = 0;
+    if (!matern_dtab_range(0.5 * pl->dist_min * a.cA, 4.0 * pl->dist_max * a.cA, &e_lo, &base, &nseg)) return GPV_OK;
+    GPV_BUF(pl->d_gmt, ensure((size_t)MaternDTab::MAX_SEG * MaternDTab::ROW));
+    GPV_HIP(launch_matern_dtab(a.gen, e_lo, nseg, pl->d_gmt, st));
+    a.gmt = pl->d_gmt; a.gmt_base = base; a.gmt_nseg = nseg;
     return GPV_OK;
 }
 
 // Value and gradient of the cond.yz='z' log-likelihood (gpv_grad.hip).  Reads the plan's records and index arrays only and
 // writes buffers of its own, so the sums, the U entries and the factor of the plan's last evaluation stay what they were.
-int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
-                         double *grad, int64_t *n_failed, double *row_terms)
+static int loglik_grad_impl(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
+                            double *loglik, double *grad, int64_t *n_failed, double *row_terms)
 {
     if (!pl || !covType || !covparms || !loglik || !grad || !n_failed) return GPV_ERR_BAD_ARG;
     bool matern;
     GradArgs a;
-    const int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, matern, a);
+    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a);
     if (rc != GPV_OK) return rc;
     GPV_HIP(hipSetDevice(pl->device));
     const int grid = grad_grid(pl->rows, pl->cus);
@@ -1991,14 +2060,17 @@ int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covpar
     a.row_terms = row_terms ? pl->d_gr_rows : nullptr;
     a.block_part = pl->d_gr_part; a.totals = pl->d_gr_tot;
     hipStream_t st = pl->stream;
+    if ((rc = grad_gen_table(pl, a, st)) != GPV_OK) return rc;
     double tot[kGradNV];
     GPV_HIP(launch_grad(pl->p, a, grid, st));
     GPV_HIP(hipMemcpyAsync(tot, pl->d_gr_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     GPV_HIP(hipStreamSynchronize(st));
-    // kernel parameters -> covparms: matern {variance, range, -, nugget}, esqe {variance 1, range 1, variance 2, range 2, nugget}
-    const int nk = matern ? 3 : 5;                                   // derivatives the kernel produced
+    // kernel parameters -> covparms: matern {variance, range, -, nugget}, esqe {variance 1, range 1, variance 2, range 2, nugget},
+    // matern at a general smoothness {variance, range, smoothness, nugget}
+    const bool gen = a.cov == COV_MATERN_GEN;
+    const int nk = gen ? 4 : (matern ? 3 : 5);                       // derivatives the kernel produced
     auto spread = [&](const double *src, double *dst) {              // src: {derivatives}, dst: ncovparms + 1
-        if (matern) { dst[0] = src[0]; dst[1] = src[1]; dst[2] = NAN; dst[3] = src[2]; }
+        if (matern && !gen) { dst[0] = src[0]; dst[1] = src[1]; dst[2] = NAN; dst[3] = src[2]; }
         else for (int t = 0; t < nk; ++t) dst[t] = src[t];
     };
     *n_failed = (int64_t)tot[6];
@@ -2021,15 +2093,28 @@ int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covpar
     return GPV_OK;
 }
 
+int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                         double *grad, int64_t *n_failed, double *row_terms)
+{
+    return loglik_grad_impl(pl, covType, covparms, ncovparms, nugget, false, loglik, grad, n_failed, row_terms);
+}
+
+// the same, with the smoothness of "matern" differentiated wherever the function is differentiable in it
+int gpv_plan_loglik_grad_nu(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                            double *grad, int64_t *n_failed, double *row_terms)
+{
+    return loglik_grad_impl(pl, covType, covparms, ncovparms, nugget, true, loglik, grad, n_failed, row_terms);
+}
+
 // Value, gradient and expected Fisher information of the same likelihood (gpv_fisher_kernel.hpp).  Like gpv_plan_loglik_grad it
 // writes buffers of its own only.
-int gpv_plan_loglik_fisher(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
-                           double *grad, double *fisher, int64_t *n_failed, double *row_terms)
+static int loglik_fisher_impl(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
+                              double *loglik, double *grad, double *fisher, int64_t *n_failed, double *row_terms)
 {
     if (!pl || !covType || !covparms || !loglik || !grad || !fisher || !n_failed) return GPV_ERR_BAD_ARG;
     bool matern;
     GradArgs a;
-    const int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, matern, a);
+    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a);
     if (rc != GPV_OK) return rc;
     GPV_HIP(hipSetDevice(pl->device));
     const int grid = grad_grid(pl->rows, pl->cus);
@@ -2042,13 +2127,15 @@ int gpv_plan_loglik_fisher(gpv_plan *pl, const char *covType, const double *covp
     a.row_terms = row_terms ? pl->d_fi_rows : nullptr;
     a.block_part = pl->d_fi_part; a.totals = pl->d_fi_tot;
     hipStream_t st = pl->stream;
+    if ((rc = grad_gen_table(pl, a, st)) != GPV_OK) return rc;
     double tot[kFisherNV];
     GPV_HIP(launch_fisher(pl->p, a, grid, st));
     GPV_HIP(hipMemcpyAsync(tot, pl->d_fi_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     GPV_HIP(hipStreamSynchronize(st));
     // kernel parameters -> covparms as above; the triangle of the nk kernel parameters -> that of the np = ncovparms + 1 outputs
-    const int nk = matern ? 3 : 5, np = ncovparms + 1;
-    const int at[5] = {0, 1, matern ? 3 : 2, 3, 4};                  // output position of kernel parameter t
+    const bool gen = a.cov == COV_MATERN_GEN;
+    const int nk = gen ? 4 : (matern ? 3 : 5), np = ncovparms + 1;
+    const int at[5] = {0, 1, (matern && !gen) ? 3 : 2, 3, 4};        // output position of kernel parameter t
     auto spread = [&](const double *src, double *dst) {
         for (int t = 0; t < np; ++t) dst[t] = NAN;
         for (int t = 0; t < nk; ++t) dst[at[t]] = src[t];
@@ -2083,6 +2170,18 @@ int gpv_plan_loglik_fisher(gpv_plan *pl, const char *covType, const double *covp
         }
     }
     return GPV_OK;
+}
+
+int gpv_plan_loglik_fisher(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                           double *grad, double *fisher, int64_t *n_failed, double *row_terms)
+{
+    return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, false, loglik, grad, fisher, n_failed, row_terms);
+}
+
+int gpv_plan_loglik_fisher_nu(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                              double *grad, double *fisher, int64_t *n_failed, double *row_terms)
+{
+    return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, true, loglik, grad, fisher, n_failed, row_terms);
 }
 
 // ---- the whitening operator of the plan's latest evaluation applied to a block of columns (gpv_whiten.hip) -----------------

@@ -186,6 +186,89 @@ hipError_t launch_matern_tab(double nu, int e_lo, int nseg, double scale, double
     return hipGetLastError();
 }
 
+// ---- general-nu Matern, gradient and information: the per-launch tables of the value, the range derivative and the smoothness
+// derivative (gpv_bessel.hpp, MaternDTab), all three e^s-scaled and free of sigma^2 and rho.  The geometry of the fit above: one
+// workgroup per segment, one wavefront per Chebyshev node, whose lanes share the five trapezoidal sums of
+// bessel_k_triple_scaled (same step, same nodes); then 33 threads turn the 3 x 11 node values into monomial coefficients.
+constexpr int kDTabN = MaternDTab::N;
+__global__ void __launch_bounds__(kDTabN * 64) gpv_matern_dtab_kernel(MaternDerivConst kc, int e_lo, double *rows)
+{
+    __shared__ double f[MaternDTab::NF][kDTabN], ch[MaternDTab::NF][kDTabN], tk[kDTabN][kDTabN];
+    const int seg = blockIdx.x, lane = threadIdx.x & 63, j = threadIdx.x >> 6;
+    constexpr int SPO = MaternDTab::SPO;
+    const int e = e_lo + seg / SPO, m = seg % SPO;
+    const double c = ldexp(1.0 + ((double)m + 0.5) / SPO, e), hw = ldexp(1.0, e - 1 - MaternDTab::LSPO);
+    const double x = c + hw * cospi(((double)j + 0.5) / kDTabN);
+    const int n_up = (int)(kc.nu + 0.5);
+    const double mu = kc.nu - (double)n_up;
+    const double h1 = 9.8696044010893586188 / (x + 44.0), h2 = 0.66 / sqrt(x);
+    const double h = h1 < h2 ? h1 : h2;
+    const double t_end = 2.0 * asinh(sqrt(372.5 / x));              // beyond it x (cosh t - 1) > 745: the weight is 0 in FP64
+    const int npts = (int)(t_end / h) + 1;
+    double s0 = 0.0, s1 = 0.0, sm = 0.0, sd0 = 0.0, sd1 = 0.0;
+    for (int q = lane + 1; q <= npts; q += 64) {
+        const double t = (double)q * h;
+        const double sh = sinh(0.5 * t);
+        const double w = exp(-2.0 * x * sh * sh);
+        const double et = exp(t), gm = exp(mu * t), g1 = gm * et, g2 = et / gm;
+        s0 = __builtin_fma(w, 0.5 * (gm + 1.0 / gm), s0);
+        s1 = __builtin_fma(w, 0.5 * (g1 + 1.0 / g1), s1);
+        sm = __builtin_fma(w, 0.5 * (g2 + 1.0 / g2), sm);
+        const double wt = w * t;
+        sd0 = __builtin_fma(wt, 0.5 * (gm - 1.0 / gm), sd0);
+        sd1 = __builtin_fma(wt, 0.5 * (g1 - 1.0 / g1), sd1);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        s0 += __shfl_xor(s0, o);
+        s1 += __shfl_xor(s1, o);
+        sm += __shfl_xor(sm, o);
+        sd0 += __shfl_xor(sd0, o);
+        sd1 += __shfl_xor(sd1, o);
+    }
+    double small_dnu = 0.0;                                          // small arguments: the smoothness derivative free of cancellation
+    if (x < kDnuSmallS) {                                            // (uniform in the wavefront)
+        small_dnu = matern_dnu_small_part(x, kc, lane, 64);
+        for (int o = 32; o > 0; o >>= 1) small_dnu += __shfl_xor(small_dnu, o);
+    }
+    if (threadIdx.x == 0) {                                          // T_k(u) = sum_i tk[k][i] u^i (integers up to 2^9: exact)
+        for (int k = 0; k < kDTabN; ++k)
+            for (int i = 0; i < kDTabN; ++i) tk[k][i] = 0.0;
+        tk[0][0] = 1.0;
+        tk[1][1] = 1.0;
+        for (int k = 2; k < kDTabN; ++k)
+            for (int i = 0; i < kDTabN; ++i) tk[k][i] = (i > 0 ? 2.0 * tk[k - 1][i - 1] : 0.0) - tk[k - 2][i];
+    }
+    if (lane == 0) {
+        // the t = 0 point carries half weight (and nothing for the t sinh sums)
+        const BesselTriple b = bessel_k_triple_climb(n_up, mu, x, h * (s0 + 0.5), h * (s1 + 0.5), h * (sm + 0.5), h * sd0, h * sd1);
+        double o3[3];
+        matern_derivs_from_triple(x, kc, 1, b, small_dnu, o3);
+        f[0][j] = o3[0];
+        f[1][j] = o3[1];
+        f[2][j] = o3[2];
+    }
+    __syncthreads();
+    const int fn = threadIdx.x / kDTabN, k = threadIdx.x % kDTabN;   // threads 0 .. 32: (function, coefficient)
+    if (threadIdx.x < MaternDTab::ROW) {
+        double a = 0.0;
+        for (int i = 0; i < kDTabN; ++i) a = __builtin_fma(f[fn][i], cospi((double)k * ((double)i + 0.5) / kDTabN), a);
+        ch[fn][k] = a * (k == 0 ? 1.0 : 2.0) / kDTabN;
+    }
+    __syncthreads();
+    if (threadIdx.x < MaternDTab::ROW) {
+        double a = 0.0;
+        for (int q = kDTabN - 1; q >= k; --q) a = __builtin_fma(ch[fn][q], tk[q][k], a);          // smallest terms first
+        rows[(size_t)seg * MaternDTab::ROW + threadIdx.x] = a;
+    }
+}
+hipError_t launch_matern_dtab(const MaternDerivConst &kc, int e_lo, int nseg, double *rows, hipStream_t s)
+{
+    if (nseg <= 0) return hipSuccess;
+    if (nseg > MaternDTab::MAX_SEG) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(gpv_matern_dtab_kernel, dim3(nseg), dim3(kDTabN * 64), 0, s, kc, e_lo, rows);
+    return hipGetLastError();
+}
+
 __global__ void gpv_fill_kernel(double *dst, double value, int64_t n)
 {
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)

@@ -310,4 +310,208 @@ inline void matern_tab_build(double nu, double smin, double smax, double scale, 
     }
 }
 
+// ---- derivatives of the general-nu Matern in range and in nu (gpv_plan_loglik_grad_nu / _fisher_nu) ---------------------
+// C(r) / sigma^2 = c_nu s^nu K_nu(s), s = r / rho, c_nu = 2^{1-nu} / Gamma(nu).  With d/ds [s^nu K_nu] = -s^nu K_{nu-1}:
+//     dC/drho = sigma^2 c_nu s^{nu+1} K_{nu-1}(s) / rho,
+//     dC/dnu  = C (ln s - ln 2 - psi(nu)) + sigma^2 c_nu s^nu dK_nu(s)/dnu,
+//     dK_nu(x)/dnu = int_0^inf exp(-x cosh t) t sinh(nu t) dt        (the representation above, differentiated under the integral):
+// the integrand is entire, decays doubly exponentially and every term of its trapezoidal sum has the sign of nu, so the nodes,
+// the step and the weights exp(-x (cosh t - 1)) of bessel_k_scaled serve it as they are.
+// Orders above 1/2 climb from mu, mu + 1 (nu = n + mu, |mu| <= 1/2) by the recurrence and its derivative in the order,
+//     K_{v+1} = K_{v-1} + (2v/x) K_v,        K'_{v+1} = K'_{v-1} + (2/x) K_v + (2v/x) K'_v,
+// carried in the scaled quantities A_i = (x/2)^i K_{mu+i}, B_i = (x/2)^i K'_{mu+i}:
+//     A_{i+1} = (x/2)^2 A_{i-1} + (mu+i) A_i,     B_{i+1} = (x/2)^2 B_{i-1} + A_i + (mu+i) B_i,
+// which hold no division by x: A_n stays near Gamma(nu) / 2 (2/x)^mu as x -> 0, where K_nu itself overflows for large nu.
+// Then s^nu K_nu = 2^n s^mu A_n and s^{nu+1} K_{nu-1} = 2^{n-1} s^{mu+2} A_{n-1}.
+// K_{nu-1} for nu < 1/2 (n = 0) is K_{1-mu}: it has its own weight cosh((1 - mu) t) in the shared sum, because the downward
+// recurrence K_{mu+1} - (2 mu / x) K_mu cancels catastrophically at small x.
+struct BesselTriple {
+    double a_n;      // e^x (x/2)^n K_nu(x)
+    double a_m;      // n >= 1: e^x (x/2)^{n-1} K_{nu-1}(x);  n = 0: e^x K_{1-nu}(x)
+    double b_n;      // e^x (x/2)^n dK_nu(x)/dnu
+    int n_up;
+    double mu;
+};
+
+// from e^x {K_mu, K_{mu+1}, K_{1-mu}, K'_mu, K'_{mu+1}}(x) to the triple: the climb
+__host__ __device__ inline BesselTriple bessel_k_triple_climb(const int n_up, const double mu, const double x, const double k0,
+                                                              const double k1, const double km, const double d0, const double d1)
+{
+    BesselTriple o;
+    o.n_up = n_up;
+    o.mu = mu;
+    if (n_up == 0) {
+        o.a_n = k0; o.a_m = km; o.b_n = d0;
+        return o;
+    }
+    // A_0 = K_mu, A_1 = (x/2) K_{mu+1}; the same for B
+    const double hx = 0.5 * x, hx2 = hx * hx;
+    double a0 = k0, a1 = hx * k1, b0 = d0, b1 = hx * d1;
+    for (int i = 1; i < n_up; ++i) {
+        const double v = mu + (double)i;
+        const double an = __builtin_fma(v, a1, hx2 * a0);
+        const double bn = __builtin_fma(v, b1, __builtin_fma(hx2, b0, a1));
+        a0 = a1; a1 = an;
+        b0 = b1; b1 = bn;
+    }
+    o.a_n = a1; o.a_m = a0; o.b_n = b1;
+    return o;
+}
+
+// one pass over the quadrature nodes, 0 < x; beyond x = 746 (the callers' e^-x is 0 there) Hankel's expansion, three terms
+__host__ __device__ inline BesselTriple bessel_k_triple_scaled(const double nu, const double x)
+{
+    const int n_up = (int)(nu + 0.5);
+    const double mu = nu - (double)n_up;
+    double k0, k1, d0, d1, km;
+    if (x > 746.0) {
+        const double r8 = 0.125 / x, pre = sqrt(1.57079632679489661923 / x);
+        const double m1 = mu + 1.0, m2 = 1.0 - mu;
+        const double a0 = 4.0 * mu * mu, a1 = 4.0 * m1 * m1, a2 = 4.0 * m2 * m2;
+        k0 = pre * (1.0 + (a0 - 1.0) * r8 * (1.0 + (a0 - 9.0) * 0.5 * r8));
+        k1 = pre * (1.0 + (a1 - 1.0) * r8 * (1.0 + (a1 - 9.0) * 0.5 * r8));
+        km = pre * (1.0 + (a2 - 1.0) * r8 * (1.0 + (a2 - 9.0) * 0.5 * r8));
+        d0 = pre * 8.0 * mu * r8 * (1.0 + (a0 - 5.0) * r8);          // d/d mu of the same three terms
+        d1 = pre * 8.0 * m1 * r8 * (1.0 + (a1 - 5.0) * r8);
+    } else {
+        const double h1 = 9.8696044010893586188 / (x + 44.0), h2 = 0.66 / sqrt(x);
+        const double h = h1 < h2 ? h1 : h2;
+        double sum0 = 0.5, sum1 = 0.5, summ = 0.5, sd0 = 0.0, sd1 = 0.0;   // t sinh(.) vanishes at the t = 0 node
+        for (int j = 1; j < 6000; ++j) {
+            const double t = (double)j * h;
+            const double sh = sinh(0.5 * t);
+            const double arg = 2.0 * x * sh * sh;                   // x (cosh t - 1)
+            if (arg > 745.0) break;
+            const double w = exp(-arg);
+            const double et = exp(t), gm = exp(mu * t), g1 = gm * et, g2 = et / gm;
+            const double c1 = 0.5 * (g1 + 1.0 / g1);                // cosh((mu + 1) t): the largest of the five factors / t
+            sum0 = __builtin_fma(w, 0.5 * (gm + 1.0 / gm), sum0);
+            sum1 = __builtin_fma(w, c1, sum1);
+            summ = __builtin_fma(w, 0.5 * (g2 + 1.0 / g2), summ);   // cosh((1 - mu) t)
+            const double wt = w * t;
+            sd0 = __builtin_fma(wt, 0.5 * (gm - 1.0 / gm), sd0);    // t sinh(mu t)
+            sd1 = __builtin_fma(wt, 0.5 * (g1 - 1.0 / g1), sd1);    // t sinh((mu + 1) t)
+            if (w * c1 < 1e-19 * sum1 && wt * c1 < 1e-19 * sd1) break;
+        }
+        k0 = h * sum0; k1 = h * sum1; km = h * summ; d0 = h * sd0; d1 = h * sd1;
+    }
+    return bessel_k_triple_climb(n_up, mu, x, k0, k1, km, d0, d1);
+}
+
+// Constants of one smoothness, prepared on the host (the C++ library has no digamma: gpv_digamma, gpv_api.hip)
+struct MaternDerivConst {
+    double nu;
+    double lnc;      // ln c_nu = (1 - nu) ln 2 - lgamma(nu)
+    double lpsi;     // ln 2 + psi(nu)
+};
+
+// The smoothness derivative at SMALL s.  There C (ln s - ln 2 - psi) and c_nu s^nu dK/dnu are two terms of size ln(1/s) whose sum
+// is O(s^min(2 nu, 2) ln s): formed from the triple it keeps an ABSOLUTE error of a few 1e-15, which the bilinear forms u'Du of a
+// plan whose range is far above its distances multiply by |u|_1^2 ~ 1e4 (measured: the smoothness column of the totals missed the
+// 1e-8 bar at range 50).  Below s = kDnuSmallS it is therefore taken from the mixture representation
+//     C / sigma^2 = E[exp(-s^2 / (4 T))],  T ~ Gamma(nu)            (K_nu(s) = 1/2 (s/2)^-nu int_0^inf e^{-t - s^2/(4t)} t^{nu-1} dt)
+//     d/dnu       = -1 / Gamma(nu) int_0^inf e^-t t^{nu-1} (ln t - psi(nu)) (1 - exp(-s^2 / (4t))) dt       (E[ln T] = psi(nu)),
+// whose integrand holds the small factor 1 - exp(-s^2 / 4t) explicitly (expm1): no cancellation beyond the O(1) one between
+// t < e^psi and t > e^psi, RELATIVE error ~1e-15.  With t = e^x the integrand is entire in x and bounded in |Im x| < pi/2 by
+// exp(nu (1 - cos y)) times its size on the axis: the trapezoidal rule with h = min(0.28, sqrt(0.57 / nu)) errs by < 1e-15
+// (exp(-pi^2 / h), and exp(-2 pi^2 / (h^2 nu)) at the optimal shift for large nu).  It runs from where e^{nu x} has fallen to
+// e^-36 below min(ln(s^2/4), -4) up to t = 2 nu + 50; a few hundred nodes of two exponentials and one expm1, for the table fit
+// and for pairs outside the tables only.  (Below nu ~ 0.01 the node count is capped and the left tail is cut short.)
+// Returns the partial sum over the nodes j_lo + lane, j_lo + lane + nlanes, ...: the table fit shares it among 64 lanes.
+constexpr double kDnuSmallS = 0.25;
+__host__ __device__ inline double matern_dnu_small_part(const double s, const MaternDerivConst &k, const int lane, const int nlanes)
+{
+    const double ln2 = 0.69314718055994530942;
+    const double a = 0.25 * s * s, nu = k.nu, psi = k.lpsi - ln2, lg = (1.0 - nu) * ln2 - k.lnc;   // lg = lgamma(nu)
+    const double h0 = sqrt(0.57 / nu), h = h0 < 0.28 ? h0 : 0.28;
+    const double la = log(a), x_lo = (la < -4.0 ? la : -4.0) - 36.0 / nu, x_hi = log(2.0 * nu + 50.0);
+    const int j_hi = (int)ceil(x_hi / h);
+    const double jl = floor(x_lo / h);
+    const int j_lo = (jl < (double)(j_hi - 20000)) ? j_hi - 20000 : (int)jl;
+    double acc = 0.0;
+    for (int j = j_lo + lane; j <= j_hi; j += nlanes) {
+        const double x = (double)j * h, ex = exp(x);
+        acc = __builtin_fma(exp(nu * x - ex - lg) * (x - psi), expm1(-a / ex), acc);
+    }
+    return h * acc;
+}
+
+// the three functions from the triple (0 < s); small_dnu: the smoothness derivative by matern_dnu_small_part, summed over its lanes
+// (taken for s < kDnuSmallS)
+__host__ __device__ inline void matern_derivs_from_triple(const double s, const MaternDerivConst &k, const int scaled,
+                                                          const BesselTriple &b, const double small_dnu, double (&out)[3])
+{
+    const double ls = log(s);
+    // E = c_nu 2^n s^mu [e^-s]
+    const double E = exp(k.lnc + (double)b.n_up * 0.69314718055994530942 + b.mu * ls - (scaled ? 0.0 : s));
+    out[0] = E * b.a_n;
+    out[1] = (b.n_up == 0) ? E * s * b.a_m : E * (0.5 * s * s) * b.a_m;
+    out[2] = (s < kDnuSmallS) ? (scaled ? small_dnu * exp(s) : small_dnu) : __builtin_fma(out[0], ls - k.lpsi, E * b.b_n);
+}
+
+// out = {C / sigma^2, (rho / sigma^2) dC/drho = c_nu s^{nu+1} K_{nu-1}(s), (1 / sigma^2) dC/dnu} at s = r / rho >= 0.
+// scaled != 0: all three times e^s (what the per-launch tables hold).  s = 0: exactly {1, 0, 0}.  Where e^{-s} underflows all
+// three are exact zeros (never 0 * Inf).
+__host__ __device__ inline void matern_general_derivs(const double s, const MaternDerivConst &k, const int scaled, double (&out)[3])
+{
+    if (!(s > 0.0)) {
+        out[0] = (s == 0.0) ? 1.0 : s;                              // (a NaN distance stays NaN)
+        out[1] = (s == 0.0) ? 0.0 : s;
+        out[2] = (s == 0.0) ? 0.0 : s;
+        return;
+    }
+    if (!scaled && s > 745.0) {
+        out[0] = out[1] = out[2] = 0.0;
+        return;
+    }
+    const double small_dnu = (s < kDnuSmallS) ? matern_dnu_small_part(s, k, 0, 1) : 0.0;
+    matern_derivs_from_triple(s, k, scaled, bessel_k_triple_scaled(k.nu, s), small_dnu, out);
+}
+
+// ---- per-launch tables of the three functions above, e^s-scaled, for the pair passes of the gradient and Fisher kernels ----
+// Segments as MaternTab's mixed rows (eight per octave, degree 10, monomial basis in u), but ALL coefficients doubles and three
+// functions per segment: a row is {a_0..a_10 of e^s f_0, of e^s f_1, of e^s f_2}, 33 doubles.  The rows are read from global
+// memory, not gathered from LDS, so the 72-byte budget behind the FP32 tail of the value row does not apply, and its premise (a_0
+// dominates the row to 2^-24 of the FP64 part) would have to be established for f_1 and f_2, which fall like s^min(2 nu, 2) ln s
+// towards s = 0, before it could be used: all-double rows need no such argument.
+// The device multiplies by exp(-s) (one exp per pair, what the closed forms pay); arguments outside the table take
+// matern_general_derivs.  Fitted by gpv_matern_dtab_kernel (gpv_aux_kernels.hip).
+struct MaternDTab {
+    static constexpr int DEG = 10, N = DEG + 1, NF = 3, ROW = NF * N, LSPO = 3, SPO = 1 << LSPO;
+    static constexpr int MAX_SEG = 80 * SPO;                                // 80 octaves
+};
+inline bool matern_dtab_range(double smin, double smax, int *e_lo_out, int *base_idx, int *nseg)
+{
+    constexpr int SPO = MaternDTab::SPO;
+    *nseg = 0; *base_idx = 0; *e_lo_out = 0;
+    if (!(smin > 0.0) || !(smax >= smin) || !std::isfinite(smax)) return false;
+    int e_lo = (int)std::floor(std::log2(smin)), e_hi = (int)std::floor(std::log2(smax));
+    if (e_lo < -200) e_lo = -200;
+    if (e_hi > 8) e_hi = 8;                                                  // s < 512, as the value table
+    if (e_hi < e_lo) return false;
+    if ((e_hi - e_lo + 1) * SPO > MaternDTab::MAX_SEG) e_lo = e_hi + 1 - MaternDTab::MAX_SEG / SPO;
+    *e_lo_out = e_lo;
+    *base_idx = (e_lo + 1023) << MaternDTab::LSPO;
+    *nseg = (e_hi - e_lo + 1) * SPO;
+    return true;
+}
+__device__ __forceinline__ int matern_dtab_segment(const double s, const int base)
+{
+    return (int)(__double_as_longlong(s) >> (52 - MaternDTab::LSPO)) - base;
+}
+// u = 2 g - 3 with g the mantissa of s shifted left by LSPO bits under the exponent of 1.0 (matern_tab_poly)
+__device__ __forceinline__ double matern_dtab_u(const double s)
+{
+    const unsigned lo = (unsigned)__double2loint(s), hi = (unsigned)__double2hiint(s);
+    const unsigned ghi = (__builtin_amdgcn_alignbit(hi, lo, 32 - MaternDTab::LSPO) & 0x000FFFFFu) | 0x3FF00000u;
+    return __builtin_fma(__hiloint2double((int)ghi, (int)(lo << MaternDTab::LSPO)), 2.0, -3.0);
+}
+__device__ __forceinline__ double matern_dtab_poly(const double *a, const double u)
+{
+    double p = a[MaternDTab::DEG];
+#pragma unroll
+    for (int k = MaternDTab::DEG - 1; k >= 0; --k) p = __builtin_fma(p, u, a[k]);
+    return p;
+}
+
 }  // namespace gpv

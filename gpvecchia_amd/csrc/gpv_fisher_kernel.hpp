@@ -61,7 +61,7 @@ __global__ void __launch_bounds__(64 * kGradWavesPerBlock, (PB == 16 ? 3 : (PB =
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             const double vj = __hiloint2double(__builtin_amdgcn_readlane(vhi, j), 0);
-            a[j] = grad_cov<COV>(a[j], A) * (valid ? vj : 0.0);
+            a[j] = grad_cov<COV>(gen_r2<COV>(a[j], valid && vj != 0.0), A) * (valid ? vj : 0.0);
             __builtin_amdgcn_sched_barrier(0);
         }
         // ---- Gauss-Jordan with the right-hand sides e_last and z_J; a[j] <- the multiplier of step j
@@ -107,7 +107,7 @@ __global__ void __launch_bounds__(64 * kGradWavesPerBlock, (PB == 16 ? 3 : (PB =
                 }
             }
             double d[NPAR];
-            grad_dcov<COV>(q2, A, d);
+            grad_dcov<COV>(gen_r2<COV>(q2, valid), A, d);                 // (the columns from j0 on are valid)
             const double uj = readlane_d(u, j);
 #pragma unroll
             for (int p = 0; p < NPAR; ++p) tt[p] = __builtin_fma(d[p], uj, tt[p]);

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gpv_bessel.hpp"
 
 namespace gpv {
 
@@ -10,6 +11,7 @@ constexpr int kGradNV = 8;             // values per row / partial: {l, d/d(kern
 constexpr int kGradRowLd = 6;          // doubles per row of GradArgs::row_terms: {l_k, its derivatives}
 // kernel parameters, in this order (the smoothness of "matern" is not one of them):
 //   matern: variance, range, nugget                      esqe: variance 1, range 1, variance 2, range 2, nugget
+//   matern at a general smoothness (COV_MATERN_GEN, the _nu entries): variance, range, smoothness, nugget
 constexpr int kGradWavesPerBlock = 4;
 // Grid cap: 4 workgroups of 4 wavefronts per CU, 4096 wavefronts on the 256 CUs of an MI355X.  At n = 40 000 every wavefront
 // then takes 9 or 10 conditioning sets; the per-workgroup partials (kGradNV doubles each) stay a few KB.
@@ -27,15 +29,20 @@ struct GradArgs {
     int64_t rows;
     int P;                   // row stride of nn (the plan's compiled row length; may be shorter than the bucket)
     int dim, locs_ld;
-    int cov;                 // CovKind: COV_MATERN05 / 15 / 25 / COV_ESQE
+    int cov;                 // CovKind: COV_MATERN05 / 15 / 25 / COV_ESQE / COV_MATERN_GEN
     double sA, cA, irA;      // matern: sigma^2, sqrt(2 nu)/range, 1/range        esqe: s1, 1/r1, 1/r1
     double sB, cB, irB;      // esqe: s2, 1/r2^2, 1/r2
     double nug;
+    // COV_MATERN_GEN only (sA = sigma^2, cA = irA = 1/range): the smoothness and its constants, and the launch's tables of the
+    // e^s-scaled value, range derivative and smoothness derivative (gpv_bessel.hpp, MaternDTab), or gmt_nseg = 0: no table
+    MaternDerivConst gen;
+    const double *gmt;       // [gmt_nseg][MaternDTab::ROW]
+    int gmt_base, gmt_nseg;  // segment of s = (bits(s) >> 49) - gmt_base
 };
 
 // gpv_fisher_kernel (gpv_fisher_kernel.hpp) takes the same GradArgs with longer rows and partials: after {l_k, derivatives} comes
-// the upper triangle (row-major, i <= j) of the row's expected information over the kernel parameters, 6 entries for matern and
-// 15 for esqe, zeros behind them
+// the upper triangle (row-major, i <= j) of the row's expected information over the kernel parameters, 6 entries for matern, 10
+// for matern at a general smoothness and 15 for esqe, zeros behind them
 constexpr int kFisherTri = 15;
 constexpr int kFisherRowLd = kGradRowLd + kFisherTri;    // doubles per row of row_terms
 constexpr int kFisherNV = kGradNV + kFisherTri;          // values per partial: the kGradNV of the gradient, then the triangle

@@ -47,8 +47,49 @@ __device__ __forceinline__ double wave_sum(double v)
 
 template <int COV>
 struct CovTraits {
-    static constexpr int NPAR = (COV == COV_ESQE) ? 4 : 2;              // covariance parameters differentiated
+    static constexpr int NPAR = (COV == COV_ESQE) ? 4 : (COV == COV_MATERN_GEN ? 3 : 2);   // covariance parameters differentiated
 };
+
+// ---- general smoothness (COV_MATERN_GEN): variance, range AND smoothness are differentiated ---------------------------------
+// The three functions of a pair, free of sigma^2 and rho (gpv_bessel.hpp: C / sigma^2, c_nu s^{nu+1} K_{nu-1}, d(C / sigma^2)/dnu),
+// come from the launch's tables, read from global memory (a few KB for the few octaves a plan's distances span: cache resident),
+// times one exp(-s); a pair outside the tables takes the quadrature in ONE out-of-line copy (rare, divergent, large).  s = 0
+// (coincident points, and the pairs of padded entries, which gen_r2 sends there) is {1, 0, 0} without either.
+struct Gen3 { double f[3]; };
+static __device__ __attribute__((noinline)) Gen3 gen_direct(const double s, const MaternDerivConst kc)
+{
+    Gen3 o;
+    matern_general_derivs(s, kc, 0, o.f);
+    return o;
+}
+template <int NF>
+__device__ __forceinline__ void gen_eval(const double r2, const GradArgs &A, double (&f)[NF])
+{
+    const double s = sqrt(r2) * A.cA;
+    const int seg = matern_dtab_segment(s, A.gmt_base);
+    if ((unsigned)seg < (unsigned)A.gmt_nseg) {
+        const double *row = A.gmt + (size_t)seg * MaternDTab::ROW;
+        const double u = matern_dtab_u(s), e = exp(-s);
+#pragma unroll
+        for (int q = 0; q < NF; ++q) f[q] = e * matern_dtab_poly(row + q * MaternDTab::N, u);
+    } else if (s == 0.0) {
+        f[0] = 1.0;
+#pragma unroll
+        for (int q = 1; q < NF; ++q) f[q] = 0.0;
+    } else {
+        const Gen3 o = gen_direct(s, A.gen);
+#pragma unroll
+        for (int q = 0; q < NF; ++q) f[q] = o.f[q];
+    }
+}
+// the squared distance a pair is evaluated at: a pair with a padded entry contributes nothing whatever its value, and at 0 it
+// costs nothing (the other families pay one exp for it)
+template <int COV>
+__device__ __forceinline__ double gen_r2(const double r2, const bool live)
+{
+    if constexpr (COV == COV_MATERN_GEN) return live ? r2 : 0.0;
+    else return r2;
+}
 
 // covariance of a pair from its squared distance: the formulas of cov_from_r2 (gpv_sets_kernel.hpp); r2 == 0 gives the
 // variance exactly (t = 0, exp(0) = 1)
@@ -64,6 +105,10 @@ __device__ __forceinline__ double grad_cov(double r2, const GradArgs &A)
     } else if constexpr (COV == COV_MATERN25) {
         const double t = r * A.cA;
         return A.sA * exp(-t) * __builtin_fma(t, __builtin_fma(t, 1.0 / 3.0, 1.0), 1.0);
+    } else if constexpr (COV == COV_MATERN_GEN) {
+        double f[1];
+        gen_eval<1>(r2, A, f);
+        return A.sA * f[0];
     } else {
         return __builtin_fma(A.sA, exp(-(r * A.cA)), A.sB * exp(-(r2 * A.cB)));
     }
@@ -86,6 +131,12 @@ __device__ __forceinline__ void grad_dcov(double r2, const GradArgs &A, double (
         const double t = r * A.cA, e = exp(-t), t3 = t * t * (1.0 / 3.0);
         d[0] = e * __builtin_fma(t, __builtin_fma(t, 1.0 / 3.0, 1.0), 1.0);
         d[1] = A.sA * e * t3 * (1.0 + t) * A.irA;                      // sigma^2 e^{-cr} (c^2 r^2 / 3)(1 + cr) / rho
+    } else if constexpr (COV == COV_MATERN_GEN) {
+        double f[3];
+        gen_eval<3>(r2, A, f);
+        d[0] = f[0];
+        d[1] = A.sA * A.irA * f[1];                                    // sigma^2 c_nu s^{nu+1} K_{nu-1}(s) / rho
+        d[2] = A.sA * f[2];
     } else {
         const double t = r * A.cA, e1 = exp(-t), s = r2 * A.cB, e2 = exp(-s);
         d[0] = e1;
@@ -137,7 +188,7 @@ __global__ void __launch_bounds__(64 * kGradWavesPerBlock, (PB == 16 ? 3 : (PB =
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             const double vj = __hiloint2double(__builtin_amdgcn_readlane(vhi, j), 0);
-            a[j] = grad_cov<COV>(a[j], A) * (valid ? vj : 0.0);
+            a[j] = grad_cov<COV>(gen_r2<COV>(a[j], valid && vj != 0.0), A) * (valid ? vj : 0.0);
             __builtin_amdgcn_sched_barrier(0);                        // one exp at a time: PB interleaved ones spill
         }
         // ---- Gauss-Jordan with the right-hand sides e_last and z_J
@@ -168,7 +219,7 @@ __global__ void __launch_bounds__(64 * kGradWavesPerBlock, (PB == 16 ? 3 : (PB =
 #pragma unroll
         for (int j = 0; j < PB; ++j) {
             double d[NPAR];
-            grad_dcov<COV>(a[j], A, d);
+            grad_dcov<COV>(gen_r2<COV>(a[j], valid && ((vmask >> j) & 1ull)), A, d);
             const double uj = readlane_d(u, j);
 #pragma unroll
             for (int p = 0; p < NPAR; ++p) tp[p] = __builtin_fma(d[p], uj, tp[p]);
@@ -229,6 +280,7 @@ hipError_t GPV_GRAD_NAME(GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t s
         case COV_MATERN15: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_MATERN15>), g, b, 0, stream, a); break;
         case COV_MATERN25: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_MATERN25>), g, b, 0, stream, a); break;
         case COV_ESQE: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_ESQE>), g, b, 0, stream, a); break;
+        case COV_MATERN_GEN: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_MATERN_GEN>), g, b, 0, stream, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -245,6 +297,7 @@ hipError_t GPV_FISHER_NAME(GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t
         case COV_MATERN15: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN15>), g, b, 0, stream, a); break;
         case COV_MATERN25: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN25>), g, b, 0, stream, a); break;
         case COV_ESQE: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_ESQE>), g, b, 0, stream, a); break;
+        case COV_MATERN_GEN: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN_GEN>), g, b, 0, stream, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -99,6 +99,8 @@ hipError_t launch_publish_sums(const double *sums, double *host_sums, unsigned l
 
 // general nu: fit the nseg rows of the Matern table whose first segment has binary exponent e_lo (gpv_bessel.hpp) on the device
 hipError_t launch_matern_tab(double nu, int e_lo, int nseg, double scale, double *rows, hipStream_t s);
+// general nu, gradient and information: fit the nseg <= MaternDTab::MAX_SEG rows of the three-function table (MaternDTab)
+hipError_t launch_matern_dtab(const MaternDerivConst &kc, int e_lo, int nseg, double *rows, hipStream_t s);
 
 // small helper kernels (gpv_aux_kernels.hip)
 hipError_t launch_fill(double *dst, double value, int64_t n, hipStream_t s);

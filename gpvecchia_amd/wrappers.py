@@ -147,6 +147,14 @@ def _fisher_scoring(fn, x0, reltol, maxit, max_step=1.0, max_halvings=10):
         x, f, g, info = xn, fn_, gn, infon
 
 
+def _nu_slot_checked(g_nu, ll, nu):
+    """A free smoothness whose derivative is NaN although the likelihood is finite: the trial point sits exactly on a closed form."""
+    if np.isfinite(ll) and np.isnan(g_nu):
+        raise ValueError(f"the Matern covariance is not differentiable in the smoothness at exactly {float(nu)!r} (the closed "
+                         "forms 0.5, 1.5, 2.5 scale the distance differently): choose a different starting value for the "
+                         "smoothness in theta_ini, e.g. one a little off that value")
+
+
 def profile_negloglik_grad(lg, data, X, va, covmodel="matern", smoothness=None):
     """Negative profile log-likelihood of the GLS trend and its gradient in the log-parameters lg (variance, range[, further
     covparms], nugget; for 'matern' the smoothness is the fixed `smoothness`).  The value and beta_hat(theta) come from
@@ -166,7 +174,7 @@ def profile_negloglik_grad(lg, data, X, va, covmodel="matern", smoothness=None):
 
 def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini=None, output_level=1,
                      reltol=np.sqrt(np.finfo(float).eps), seed=0, maxit=300, smoothness=None, method="Nelder-Mead",
-                     trend="ols", **specify_args):
+                     trend="ols", smoothness_grad=False, **specify_args):
     """trend: "ols" (the reference, R/vecchia_wrappers.R:32-51: coefficients by ordinary least squares once, the covariance
     fitted to their residuals) or "gls": generalised least squares with the coefficients profiled out of the likelihood
     (vecchia_profile_likelihood: beta_hat(theta) under the Vecchia precision at every step), for X given or the constant
@@ -181,7 +189,12 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     'matern', smoothness in {0.5, 1.5, 2.5}; or "fisher", Fisher scoring over the log-parameters on the expected information of
     the GPU (vecchia_likelihood_fisher, _fisher_scoring), with the preconditions of "L-BFGS-B".  n_evals counts likelihood (or
     value + gradient [+ information]) evaluations.  For "fisher" the result also holds fisher_info (the information over the
-    searched parameters at theta_hat), theta_cov (its inverse) and theta_se (the square roots of that one's diagonal)."""
+    searched parameters at theta_hat), theta_cov (its inverse) and theta_se (the square roots of that one's diagonal).
+    smoothness_grad=True (covmodel='matern'): "L-BFGS-B" and "fisher" differentiate the smoothness as well
+    (vecchia_likelihood_grad / _fisher with smoothness_grad=True), so they take a free smoothness -- four searched log-parameters,
+    for L-BFGS-B inside box bounds that keep the smoothness in (0.01, 10], the reference's guard (:72-74) as a bound; Fisher
+    scoring keeps the same interval by rejecting (and halving) a trial step that leaves it, and returns a 4 x 4 fisher_info and four theta_se, the smoothness's among them -- or any fixed one.  The covariance is
+    not differentiable in the smoothness at exactly 0.5, 1.5 and 2.5: a trial point there raises ValueError.  Not with trend="gls"."""
     if method not in ("Nelder-Mead", "L-BFGS-B", "fisher"):
         raise ValueError(f"method='{method}' not defined")
     fix_nu = smoothness is not None
@@ -190,6 +203,10 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     if trend not in ("ols", "gls"):
         raise ValueError(f"trend='{trend}' not defined")
     gls = trend == "gls"
+    if smoothness_grad and gls:
+        raise ValueError("smoothness_grad=True is not available with trend='gls'")
+    if smoothness_grad and covmodel != "matern":
+        raise ValueError("smoothness_grad applies to covmodel='matern' only")
     if gls:
         if specify_args.get("cond_yz") != "z":
             raise ValueError("trend='gls' needs cond_yz='z' (the likelihood whose whitening operator the GPU applies)")
@@ -202,7 +219,7 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
             raise ValueError(f"method='{method}' needs cond_yz='z' (the likelihood whose gradient the GPU returns)")
         if not isinstance(covmodel, str):
             raise ValueError(f"method='{method}' needs a named covariance family")
-        if covmodel == "matern" and (not fix_nu or float(smoothness) not in (0.5, 1.5, 2.5)):
+        if covmodel == "matern" and not smoothness_grad and (not fix_nu or float(smoothness) not in (0.5, 1.5, 2.5)):
             raise ValueError(f"method='{method}' with covmodel='matern' needs smoothness in {{0.5, 1.5, 2.5}}")
     data = np.asarray(data, dtype=np.float64)
     locs = np.asarray(locs, dtype=np.float64)
@@ -238,6 +255,7 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         return cp, th[-1]
     n_par = len(theta_ini)
     evals = [0]
+    nu_kw = dict(smoothness_grad=True) if smoothness_grad else {}    # (the default call is the call it always was)
 
     def negloglik(lg):                                               # :72-78
         if covmodel == "matern" and not fix_nu and np.exp(lg[2]) > 10:
@@ -252,8 +270,11 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         evals[0] += 1
         th = np.exp(lg)
         cp, nug = full(th)
-        ll, g = A.vecchia_likelihood_grad(z, va, cp, nug, covmodel=covmodel)
-        g = np.delete(g, 2) if covmodel == "matern" else g           # the smoothness is fixed
+        ll, g = A.vecchia_likelihood_grad(z, va, cp, nug, covmodel=covmodel, **nu_kw)
+        if covmodel == "matern" and fix_nu:
+            g = np.delete(g, 2)
+        elif covmodel == "matern":
+            _nu_slot_checked(g[2], ll, cp[2])
         if not np.isfinite(ll):
             return _BIG, np.zeros_like(lg)
         return -ll, -g * th
@@ -264,9 +285,13 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         evals[0] += 1
         th = np.exp(lg)
         cp, nug = full(th)
-        ll, g, info = A.vecchia_likelihood_fisher(z, va, cp, nug, covmodel=covmodel)
-        if covmodel == "matern":                                     # the smoothness is fixed
+        if covmodel == "matern" and not fix_nu and not 0.01 < cp[2] <= 10.0:   # the reference's guard (:72-74) and L-BFGS-B's
+            return -np.inf, np.zeros_like(th), np.eye(len(th))                 #  box: a trial step the halving loop rejects
+        ll, g, info = A.vecchia_likelihood_fisher(z, va, cp, nug, covmodel=covmodel, **nu_kw)
+        if covmodel == "matern" and fix_nu:
             g, info = np.delete(g, 2), np.delete(np.delete(info, 2, axis=0), 2, axis=1)
+        elif covmodel == "matern":
+            _nu_slot_checked(g[2], ll, cp[2])
         infos[lg.tobytes()] = info
         return ll, g * th, info * np.outer(th, th)
 
@@ -303,7 +328,11 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     x0 = np.log(theta_ini) / parscale                                # optim works on par / parscale
     if method == "L-BFGS-B":
         from scipy.optimize import minimize
-        r = minimize(negloglik_grad, np.log(theta_ini), jac=True, method="L-BFGS-B",
+        bounds = None
+        if covmodel == "matern" and not fix_nu:                      # the reference's guard (:72-74: smoothness > 10 is an error)
+            bounds = [(None, None)] * n_par
+            bounds[2] = (np.log(0.01), np.log(10.0))
+        r = minimize(negloglik_grad, np.log(theta_ini), jac=True, method="L-BFGS-B", bounds=bounds,
                      options=dict(maxiter=maxit, ftol=1e-3 * reltol, gtol=1e-5))   # (relative decrease per iteration; gradient in log-parameters)
         xbest, fbest, conv, parscale = r.x, float(r.fun), (0 if r.success else 1), np.ones(n_par)
     elif method == "fisher":

@@ -309,6 +309,33 @@ int gpv_plan_loglik_fisher(gpv_plan *plan, const char *covType, const double *co
                            double *loglik, double *grad /* ncovparms + 1 */, double *fisher /* (ncovparms + 1)^2, row-major */,
                            int64_t *n_failed, double *row_terms /* NULL, or Nlocs x (ncovparms + 2 + T), row-major */);
 
+/* gpv_plan_loglik_grad and gpv_plan_loglik_fisher with the smoothness of "matern" differentiated as well: the capability behind
+ * gradient-based estimation and standard errors of the model whose smoothness is searched.  Same arguments, same layouts of grad,
+ * fisher and row_terms, same state checks, failure semantics and guarantees (blocking, bitwise reproducible, the plan's last
+ * evaluation stays intact, arguments validated before the device is touched).
+ * For "matern" at any accepted smoothness (finite, > 0, <= 60) other than 0.5, 1.5 and 2.5 the covariance is the general branch
+ *   C(r) = sigma^2 c_nu s^nu K_nu(s),  s = r / range,  c_nu = 2^{1-nu} / Gamma(nu)           (no sqrt(2 nu) scaling)
+ * which is analytic in nu: all four entries of grad and the full 4 x 4 information are finite,
+ *   dC/dsigma^2 = C / sigma^2,   dC/drange = sigma^2 c_nu s^{nu+1} K_{nu-1}(s) / range,
+ *   dC/dnu = C (ln s - ln 2 - psi(nu)) + sigma^2 c_nu s^nu dK_nu(s)/dnu,   dK_nu(x)/dnu = int_0^inf e^{-x cosh t} t sinh(nu t) dt.
+ * At exactly 0.5, 1.5 and 2.5 the reference's covariance switches to closed forms with another scaling of the distance, so it is
+ * not differentiable in nu there: the entries return exactly what gpv_plan_loglik_grad / _fisher return, NaN in the smoothness
+ * slot included; likewise for "esqe".  GPV_ERR_UNSUPPORTED_NU is left for a smoothness that no entry accepts.
+ * The environment variable GPV_NO_MATERN_TABLE (any value, read at every call) makes the pair passes evaluate the quadrature
+ * per pair instead of reading the call's tables: the cross-check of the tables, many times slower. */
+int gpv_plan_loglik_grad_nu(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
+                            double *loglik, double *grad /* ncovparms + 1 */, int64_t *n_failed,
+                            double *row_terms /* NULL, or Nlocs x (ncovparms + 2), row-major */);
+int gpv_plan_loglik_fisher_nu(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
+                              double *loglik, double *grad /* ncovparms + 1 */, double *fisher /* (ncovparms + 1)^2, row-major */,
+                              int64_t *n_failed, double *row_terms /* NULL, or Nlocs x (ncovparms + 2 + T), row-major */);
+/* The pair functions of the general branch on the host (no device needed), for n arguments s[i] = distance / range >= 0 and
+ * sigma^2 = 1: out[3 i] = C, out[3 i + 1] = dC/drange, out[3 i + 2] = dC/dnu.  s = 0 gives exactly {1, 0, 0}; where e^{-s}
+ * underflows all three are 0.  Any smoothness in (0, 60] is evaluated by the general formula, the three closed-form values
+ * included (there it is NOT the covariance the library evaluates).  GPV_ERR_BAD_ARG: a null pointer with n > 0, n < 0, range not
+ * finite or <= 0; GPV_ERR_UNSUPPORTED_NU. */
+int gpv_matern_derivs_host(double nu, double range, const double *s, int64_t n, double *out /* 3 n */);
+
 /* The Vecchia whitening operator of the plan's latest evaluation applied to a block of columns, and their Gram matrix: the
  * primitive behind a generalised-least-squares trend (profile likelihood) and behind the likelihood of replicated data, which
  * share one factor.  Everything is in the plan's ORDERED row numbering.  For row k of a cond.yz='z' plan with the stored entries

@@ -81,6 +81,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_loglik_grad.log; then
     echo "== $tag: loglik_grad_driver FAILED (rc $rc)"; return 1
   fi
+  # ... and under the driver of the entries that differentiate the smoothness (tests/sanitize/loglik_grad_nu_driver.cpp)
+  mkdir -p $B/loglik_grad_nu
+  $HIPCC $CF -c $ROOT/tests/sanitize/loglik_grad_nu_driver.cpp -o $B/loglik_grad_nu/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/loglik_grad_nu/driver.o -o $B/loglik_grad_nu_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./loglik_grad_nu_driver ) 2>&1 | tee $B/run_loglik_grad_nu.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_loglik_grad_nu.log; then
+    echo "== $tag: loglik_grad_nu_driver FAILED (rc $rc)"; return 1
+  fi
   # ... and under the driver of the whitening entry (tests/sanitize/whiten_driver.cpp)
   mkdir -p $B/whiten
   $HIPCC $CF -c $ROOT/tests/sanitize/whiten_driver.cpp -o $B/whiten/driver.o
