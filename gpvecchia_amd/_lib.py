@@ -44,6 +44,7 @@ EXPORTS = [
     "gpv_plan_loglik_grad", "gpv_plan_loglik_fisher",
     "gpv_plan_loglik_grad_nu", "gpv_plan_loglik_fisher_nu", "gpv_matern_derivs_host",
     "gpv_whiten_max_cols", "gpv_plan_whiten",
+    "gpv_plan_set_replicates", "gpv_plan_replicates", "gpv_plan_loglik_rep", "gpv_plan_loglik_rep_nu",
 ]
 
 
@@ -122,6 +123,10 @@ def lib():
     L.gpv_whiten_max_cols.restype = C.c_int
     L.gpv_whiten_max_cols.argtypes = []
     L.gpv_plan_whiten.argtypes = [vp, dp, i64, C.c_int, dp, i64, dp, dp, C.POINTER(C.c_int64)]
+    L.gpv_plan_set_replicates.argtypes = [vp, dp, i64, C.c_int]
+    L.gpv_plan_replicates.argtypes = [vp, ip]
+    L.gpv_plan_loglik_rep.argtypes = L.gpv_plan_loglik_fisher.argtypes
+    L.gpv_plan_loglik_rep_nu.argtypes = L.gpv_plan_loglik_fisher.argtypes
     L.gpv_loglik_from_sums.argtypes = [dp, i64, dp]
     L.gpv_mplan_create.argtypes = [C.POINTER(vp), ip, C.c_int, i64, C.c_int, C.c_int, dp, ip, ip]
     L.gpv_mplan_destroy.argtypes = [vp]

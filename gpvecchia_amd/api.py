@@ -223,6 +223,58 @@ class Plan:
         out = (float(ll.value), grad, info, int(nf.value))
         return out + (rt,) if row_terms else out
 
+    def set_replicates(self, Z_ord):
+        """Uploads R replicates of the data, the columns of Z_ord (Nlocs, R) in the plan's ORDERED row numbering, and keeps
+        them on the device for loglik_replicates (gpv_plan_set_replicates).  None, or an array without columns, releases them.
+        The column of set_data is a separate thing and stays what it was."""
+        self._user_Z = None                              # whatever set_user_replicates remembered is no longer on the device
+        if Z_ord is None or np.asarray(Z_ord).size == 0:
+            L.check(L.lib().gpv_plan_set_replicates(self._h, None, 0, 0), "gpv_plan_set_replicates")
+            return
+        Z = np.asarray(Z_ord, dtype=np.float64)
+        if Z.ndim == 1:
+            Z = Z[:, None]
+        if Z.ndim != 2 or Z.shape[0] != self.Nlocs:
+            raise ValueError("Z_ord must have one row per ordered location of the plan")
+        Z = np.asfortranarray(Z)
+        L.check(L.lib().gpv_plan_set_replicates(self._h, L.dptr(Z), self.Nlocs, int(Z.shape[1])), "gpv_plan_set_replicates")
+
+    def set_user_replicates(self, Z, ord_z):
+        """set_replicates(Z[ord_z - 1]) unless exactly this Z is what the device holds already (compared by content against a
+        private copy, like set_user_data): an optimiser evaluates one set of replicates many times."""
+        prev = getattr(self, "_user_Z", None)
+        if prev is not None and prev.shape == Z.shape and np.array_equal(prev, Z):
+            return False
+        self.set_replicates(Z[ord_z - 1])
+        self._user_Z = np.array(Z, dtype=np.float64, copy=True)
+        return True
+
+    def replicates(self):
+        """The number of replicates on the device (0: none)."""
+        R = C.c_int(0)
+        L.check(L.lib().gpv_plan_replicates(self._h, C.byref(R)), "gpv_plan_replicates")
+        return int(R.value)
+
+    def loglik_replicates(self, covmodel, covparms, nugget, fisher=True, row_terms=False, smoothness_grad=False):
+        """Value, gradient and expected information of the cond.yz='z' log-likelihood SUMMED over the replicates of
+        set_replicates, from one pass over the conditioning sets (gpv_plan_loglik_rep): returns (loglik, grad, info, n_failed)
+        -- info None with fisher=False -- and, with row_terms, a fifth array in the layout of loglik_fisher's whose row k holds
+        the sums over the replicates of row k's terms.  info is R times the information of one column.  smoothness_grad as
+        for loglik_fisher.  The plan's last evaluation and its data column are left as they were."""
+        cp = np.ascontiguousarray(covparms, dtype=np.float64)
+        ll, nf = C.c_double(0.0), C.c_int64(0)
+        npar = cp.size + 1
+        grad = np.zeros(npar)
+        info = np.zeros((npar, npar)) if fisher else None
+        rt = np.zeros((self.Nlocs, npar + 1 + npar * (npar + 1) // 2)) if row_terms else None
+        name = "gpv_plan_loglik_rep_nu" if smoothness_grad else "gpv_plan_loglik_rep"
+        st = getattr(L.lib(), name)(self._h, covmodel.encode() if isinstance(covmodel, str) else bytes(covmodel),
+                                    L.dptr(cp), int(cp.size), float(nugget), C.byref(ll), L.dptr(grad),
+                                    L.dptr(info) if fisher else None, C.byref(nf), L.dptr(rt) if row_terms else None)
+        L.check(st, name)
+        out = (float(ll.value), grad, info, int(nf.value))
+        return out + (rt,) if row_terms else out
+
     def whiten(self, B_ord, want_E=False):
         """The whitening operator of the plan's latest evaluation (which must have asked for GPV_WANT_U) applied to the columns
         of B_ord, (Nlocs, ncols) or (Nlocs,) in the plan's ORDERED row numbering, ncols <= 16 (gpv_plan_whiten): returns
@@ -1118,6 +1170,45 @@ def vecchia_likelihood_fisher(z, vecchia_approx, covparms, nuggets, covmodel="ma
     none of 0.5, 1.5, 2.5.  Accepts what vecchia_likelihood_grad accepts."""
     plan, nug = _grad_plan("vecchia_likelihood_fisher", z, vecchia_approx, nuggets, covmodel, device)
     ll, grad, info, _ = plan.loglik_fisher(covmodel, covparms, nug, smoothness_grad=smoothness_grad)
+    return ll, grad, info
+
+
+def _rep_plan(name, Z, va, nuggets, covmodel, device):
+    """The plan and the nugget of vecchia_likelihood_grad_replicates / _fisher_replicates, after the refusals of _grad_plan and
+    _user_columns; Z (n x R, the caller's order) is uploaded only when it is not what the plan holds already."""
+    if va["cond_yz"] not in ("z", "false"):
+        raise ValueError(f"{name} needs cond_yz='z' (the gradient of the other modes goes through the "
+                         "posterior factor)")
+    if not isinstance(covmodel, str):
+        raise ValueError(f"{name} needs a named covariance family ('matern' or 'esqe'), not a function or matrix")
+    nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
+    if nug.size != 1:
+        raise ValueError(f"{name} takes one constant nugget")
+    if int(np.sum(va["obs"])) != va["locsord"].shape[0]:
+        raise ValueError(f"{name} does not take plans with prediction locations")
+    Z = _user_columns(name, Z, va)
+    plan = _plan_for(va, device)
+    plan.set_user_replicates(Z, va["ord_z"])
+    return plan, float(nug[0])
+
+
+def vecchia_likelihood_grad_replicates(Z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0,
+                                       smoothness_grad=False):
+    """(loglik_sum, grad) of R realisations over the same locations, the columns of Z (n x R, in the CALLER's order): the sum
+    over the columns of vecchia_likelihood_grad, from ONE pass over the conditioning sets (Plan.loglik_replicates) -- the
+    factorisation of a block does not depend on the data.  Accepts what vecchia_likelihood_grad accepts, with complete, finite
+    columns."""
+    plan, nug = _rep_plan("vecchia_likelihood_grad_replicates", Z, vecchia_approx, nuggets, covmodel, device)
+    ll, grad, _, _ = plan.loglik_replicates(covmodel, covparms, nug, fisher=False, smoothness_grad=smoothness_grad)
+    return ll, grad
+
+
+def vecchia_likelihood_fisher_replicates(Z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0,
+                                         smoothness_grad=False):
+    """(loglik_sum, grad, info): vecchia_likelihood_grad_replicates together with the expected Fisher information of the R
+    realisations, R times that of one column (vecchia_likelihood_fisher)."""
+    plan, nug = _rep_plan("vecchia_likelihood_fisher_replicates", Z, vecchia_approx, nuggets, covmodel, device)
+    ll, grad, info, _ = plan.loglik_replicates(covmodel, covparms, nug, smoothness_grad=smoothness_grad)
     return ll, grad, info
 
 

@@ -390,6 +390,11 @@ struct gpv_plan {
     int fi_grid = 0;
     // gpv_plan_loglik_grad_nu / _fisher_nu at a general smoothness: the call's tables (gpv_bessel.hpp, MaternDTab)
     DevBuf<double> d_gmt;
+    // gpv_plan_set_replicates / gpv_plan_loglik_rep (gpv_rep_kernel.hpp): the replicates by internal position [Nlocs][rep_RP],
+    // zeros behind column rep_R; rep_R = 0: none set.  The calls are blocking and their partials, totals and rows have the
+    // layout of gpv_plan_loglik_fisher's, so they use d_fi_part / d_fi_tot / d_fi_rows.
+    DevBuf<double> d_rep_Z;
+    int rep_R = 0, rep_RP = 0;
     // gpv_plan_whiten (gpv_whiten.hip), allocated on first use and grown with the padded column count: the caller's columns as
     // they arrive / E on its way back [cp][Nlocs], the columns by internal position [Nlocs][cp], E [Nlocs][cp], the partials of
     // both passes and the totals
@@ -1993,9 +1998,9 @@ int gpv_matern_derivs_host(double nu, double range, const double *s, int64_t n, 
 
 // Argument and state checks shared by gpv_plan_loglik_grad and gpv_plan_loglik_fisher (and their _nu forms, with_nu: a general
 // smoothness is accepted and differentiated), before the device is touched; on GPV_OK `a` holds everything but the output
-// buffers and the tables of a general smoothness.
+// buffers and the tables of a general smoothness.  rep: the data are the plan's replicates (gpv_plan_set_replicates), not its column.
 static int grad_args_checked(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
-                             bool &matern, GradArgs &a)
+                             bool &matern, GradArgs &a, bool rep = false)
 {
     matern = std::strcmp(covType, "matern") == 0;
     if (!matern && std::strcmp(covType, "esqe") != 0) return GPV_ERR_COVTYPE;
@@ -2007,7 +2012,8 @@ static int grad_args_checked(gpv_plan *pl, const char *covType, const double *co
     // (the reference's Matern is discontinuous in nu at the closed forms, and analytic in it everywhere else)
     if (cs.cov == COV_MATERN_GEN && !with_nu) return GPV_ERR_UNSUPPORTED_NU;
     if (pl->p > kGradMaxP) return GPV_ERR_UNSUPPORTED_M;
-    if (!pl->has_z || pl->comm || pl->rows != pl->Nlocs || pl->d_obs || pl->latent_nb) return GPV_ERR_STATE;
+    if (!(rep ? pl->rep_R > 0 && pl->d_rep_Z : pl->has_z) || pl->comm || pl->rows != pl->Nlocs || pl->d_obs || pl->latent_nb)
+        return GPV_ERR_STATE;
     a.rec = pl->d_locs; a.locs = pl->d_locs; a.z = pl->d_z;
     a.nn = pl->d_nn; a.rowid = pl->d_rowid;
     a.row_terms = nullptr; a.block_part = nullptr; a.totals = nullptr;
@@ -2107,14 +2113,14 @@ int gpv_plan_loglik_grad_nu(gpv_plan *pl, const char *covType, const double *cov
 }
 
 // Value, gradient and expected Fisher information of the same likelihood (gpv_fisher_kernel.hpp).  Like gpv_plan_loglik_grad it
-// writes buffers of its own only.
+// writes buffers of its own only.  rep: the same sums over the plan's replicates (gpv_rep_kernel.hpp; fisher may be NULL).
 static int loglik_fisher_impl(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
-                              double *loglik, double *grad, double *fisher, int64_t *n_failed, double *row_terms)
+                              double *loglik, double *grad, double *fisher, int64_t *n_failed, double *row_terms, bool rep = false)
 {
-    if (!pl || !covType || !covparms || !loglik || !grad || !fisher || !n_failed) return GPV_ERR_BAD_ARG;
+    if (!pl || !covType || !covparms || !loglik || !grad || !(fisher || rep) || !n_failed) return GPV_ERR_BAD_ARG;
     bool matern;
     GradArgs a;
-    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a);
+    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a, rep);
     if (rc != GPV_OK) return rc;
     GPV_HIP(hipSetDevice(pl->device));
     const int grid = grad_grid(pl->rows, pl->cus);
@@ -2129,7 +2135,13 @@ static int loglik_fisher_impl(gpv_plan *pl, const char *covType, const double *c
     hipStream_t st = pl->stream;
     if ((rc = grad_gen_table(pl, a, st)) != GPV_OK) return rc;
     double tot[kFisherNV];
-    GPV_HIP(launch_fisher(pl->p, a, grid, st));
+    if (rep) {
+        RepArgs ra;
+        ra.g = a; ra.Z = pl->d_rep_Z; ra.R = pl->rep_R; ra.RP = pl->rep_RP;
+        GPV_HIP(launch_rep(pl->p, ra, grid, st));
+    } else {
+        GPV_HIP(launch_fisher(pl->p, a, grid, st));
+    }
     GPV_HIP(hipMemcpyAsync(tot, pl->d_fi_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
     GPV_HIP(hipStreamSynchronize(st));
     // kernel parameters -> covparms as above; the triangle of the nk kernel parameters -> that of the np = ncovparms + 1 outputs
@@ -2149,13 +2161,13 @@ static int loglik_fisher_impl(gpv_plan *pl, const char *covType, const double *c
     if (tot[6] > 0.0) {
         *loglik = -INFINITY;
         for (int t = 0; t < np; ++t) grad[t] = NAN;
-        for (int t = 0; t < np * np; ++t) fisher[t] = NAN;
+        for (int t = 0; fisher && t < np * np; ++t) fisher[t] = NAN;
     } else {
         *loglik = tot[0];
         spread(tot + 1, grad);
         double tri[kFisherTri];
         spread_tri(tot + kGradNV, tri);
-        for (int i = 0, s = 0; i < np; ++i)                          // mirrored here: exactly symmetric
+        for (int i = 0, s = 0; fisher && i < np; ++i)                // mirrored here: exactly symmetric
             for (int j = i; j < np; ++j, ++s) fisher[i * np + j] = fisher[j * np + i] = tri[s];
     }
     if (row_terms) {
@@ -2182,6 +2194,55 @@ int gpv_plan_loglik_fisher_nu(gpv_plan *pl, const char *covType, const double *c
                               double *grad, double *fisher, int64_t *n_failed, double *row_terms)
 {
     return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, true, loglik, grad, fisher, n_failed, row_terms);
+}
+
+// ---- replicated data: R realisations over the plan's locations, one pass for their summed value, gradient and information ---
+// Uploads the columns (the staging buffer lives for the call only) and packs them by internal position.  Touches nothing of the
+// plan but d_rep_Z: the data column, the last evaluation and the factor stamp stay what they were.
+int gpv_plan_set_replicates(gpv_plan *pl, const double *Z_ord, int64_t ldz, int R)
+{
+    if (!pl || R < 0 || (R > 0 && (!Z_ord || ldz < pl->Nlocs))) return GPV_ERR_BAD_ARG;
+    const int64_t n = pl->Nlocs;
+    if (R > 0 && (n < 1 || !pl->d_newpos)) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    pl->rep_R = pl->rep_RP = 0;
+    if (R == 0) {
+        GPV_BUF(pl->d_rep_Z, reset());
+        return GPV_OK;
+    }
+    const int rp = rep_rp(R);
+    DevBuf<double> d_in;
+    GPV_BUF(d_in, resize((size_t)n * R));
+    GPV_BUF(pl->d_rep_Z, resize((size_t)n * rp));
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    for (int j = 0; j < R; ++j)
+        if (GPV_HIP_FAILED(hipMemcpyAsync(d_in + (size_t)j * n, Z_ord + (int64_t)j * ldz, sizeof(double) * (size_t)n,
+                                          hipMemcpyHostToDevice, st)))
+            return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_rep_pack(d_in, pl->d_newpos, n, R, rp, pl->d_rep_Z, st))) return fail(GPV_ERR_HIP);
+    GPV_HIP(hipStreamSynchronize(st));
+    pl->rep_R = R; pl->rep_RP = rp;
+    return GPV_OK;
+}
+
+int gpv_plan_replicates(gpv_plan *pl, int *R)
+{
+    if (!pl || !R) return GPV_ERR_BAD_ARG;
+    *R = pl->rep_R;
+    return GPV_OK;
+}
+
+int gpv_plan_loglik_rep(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                        double *grad, double *fisher, int64_t *n_failed, double *row_terms)
+{
+    return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, false, loglik, grad, fisher, n_failed, row_terms, true);
+}
+
+int gpv_plan_loglik_rep_nu(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                           double *grad, double *fisher, int64_t *n_failed, double *row_terms)
+{
+    return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, true, loglik, grad, fisher, n_failed, row_terms, true);
 }
 
 // ---- the whitening operator of the plan's latest evaluation applied to a block of columns (gpv_whiten.hip) -----------------

@@ -47,6 +47,17 @@ constexpr int kFisherTri = 15;
 constexpr int kFisherRowLd = kGradRowLd + kFisherTri;    // doubles per row of row_terms
 constexpr int kFisherNV = kGradNV + kFisherTri;          // values per partial: the kGradNV of the gradient, then the triangle
 
+// gpv_rep_kernel (gpv_rep_kernel.hpp): the same rows, partials and totals as gpv_fisher_kernel, summed over R replicates of the
+// data.  The kernel reads no datum of GradArgs (rec's fourth slot, z) but the replicates below.
+constexpr int kRepChunk = 8;           // replicates a lane reads and reduces together; RP is a multiple of it
+struct RepArgs {
+    GradArgs g;
+    const double *Z;         // [Nlocs][RP] the replicates by internal position, zeros in the columns R .. RP - 1; 16-byte aligned
+    int R, RP;
+};
+// padded replicate count
+inline int rep_rp(int R) { return (R + kRepChunk - 1) / kRepChunk * kRepChunk; }
+
 // row-length bucket of a row of p entries (16, 32 or 64), 0: too long
 inline int grad_bucket(int p) { return p <= 16 ? 16 : (p <= 32 ? 32 : (p <= kGradMaxP ? 64 : 0)); }
 // workgroups of the launch for `rows` sets on a device of `cus` compute units
@@ -55,5 +66,9 @@ int grad_grid(int64_t rows, int cus);
 hipError_t launch_grad(int p, const GradArgs &a, int grid, hipStream_t stream);
 // the same for value, gradient and information: row_terms [rows][kFisherRowLd], block_part [grid][kFisherNV], totals [kFisherNV]
 hipError_t launch_fisher(int p, const GradArgs &a, int grid, hipStream_t stream);
+// the same for R replicates: buffers of a.g as for launch_fisher
+hipError_t launch_rep(int p, const RepArgs &a, int grid, hipStream_t stream);
+// in: R columns of length n, n apart (ORDERED layout) -> Z[newpos[i]][rp], zeros in the columns R .. rp - 1
+hipError_t launch_rep_pack(const double *in, const int32_t *newpos, int64_t n, int R, int rp, double *Z, hipStream_t stream);
 
 }  // namespace gpv

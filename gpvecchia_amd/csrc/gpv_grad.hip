@@ -266,6 +266,7 @@ __global__ void __launch_bounds__(64 * kGradWavesPerBlock, (PB == 16 ? 3 : (PB =
 }
 
 #include "gpv_fisher_kernel.hpp"
+#include "gpv_rep_kernel.hpp"
 
 }  // namespace
 
@@ -298,6 +299,23 @@ hipError_t GPV_FISHER_NAME(GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t
         case COV_MATERN25: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN25>), g, b, 0, stream, a); break;
         case COV_ESQE: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_ESQE>), g, b, 0, stream, a); break;
         case COV_MATERN_GEN: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN_GEN>), g, b, 0, stream, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
+#define GPV_REP_NAME2(pb) launch_rep_pb##pb
+#define GPV_REP_NAME(pb) GPV_REP_NAME2(pb)
+hipError_t GPV_REP_NAME(GPV_GRAD_PB)(const RepArgs &a, int grid, hipStream_t stream)
+{
+    constexpr int PB = GPV_GRAD_PB;
+    const dim3 g((unsigned)grid), b(64 * kGradWavesPerBlock);
+    switch (a.g.cov) {
+        case COV_MATERN05: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_MATERN05>), g, b, 0, stream, a); break;
+        case COV_MATERN15: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_MATERN15>), g, b, 0, stream, a); break;
+        case COV_MATERN25: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_MATERN25>), g, b, 0, stream, a); break;
+        case COV_ESQE: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_ESQE>), g, b, 0, stream, a); break;
+        case COV_MATERN_GEN: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_MATERN_GEN>), g, b, 0, stream, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -336,6 +354,23 @@ __global__ void __launch_bounds__(64) gpv_fisher_total_kernel(const double *part
 }
 }  // namespace
 
+hipError_t launch_rep_pb16(const RepArgs &a, int grid, hipStream_t stream);
+hipError_t launch_rep_pb32(const RepArgs &a, int grid, hipStream_t stream);
+hipError_t launch_rep_pb64(const RepArgs &a, int grid, hipStream_t stream);
+
+namespace {
+// the replicates as they arrive (columns of the ORDERED rows) -> rows by internal position, any padded count rp
+__global__ void __launch_bounds__(256) gpv_rep_pack_kernel(const double *__restrict__ in, const int32_t *__restrict__ newpos,
+                                                           int64_t n, int R, int rp, double *__restrict__ Z)
+{
+    const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n * rp) return;
+    const int64_t i = t / rp;
+    const int c = (int)(t - i * rp);
+    Z[(int64_t)newpos[i] * rp + c] = c < R ? in[(int64_t)c * n + i] : 0.0;
+}
+}  // namespace
+
 int grad_grid(int64_t rows, int cus)
 {
     int64_t grid = (rows + kGradWavesPerBlock - 1) / kGradWavesPerBlock;
@@ -371,6 +406,29 @@ hipError_t launch_fisher(int p, const GradArgs &a, int grid, hipStream_t stream)
     }
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(gpv_fisher_total_kernel, dim3(1), dim3(64), 0, stream, a.block_part, grid, a.totals);
+    return hipGetLastError();
+}
+
+hipError_t launch_rep(int p, const RepArgs &a, int grid, hipStream_t stream)
+{
+    if (grid < 1 || a.g.rows < 0 || a.Z == nullptr || a.R < 1 || a.RP < a.R || a.RP % kRepChunk != 0) return hipErrorInvalidValue;
+    hipError_t e;
+    switch (grad_bucket(p)) {
+        case 16: e = launch_rep_pb16(a, grid, stream); break;
+        case 32: e = launch_rep_pb32(a, grid, stream); break;
+        case 64: e = launch_rep_pb64(a, grid, stream); break;
+        default: return hipErrorInvalidValue;
+    }
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gpv_fisher_total_kernel, dim3(1), dim3(64), 0, stream, a.g.block_part, grid, a.g.totals);
+    return hipGetLastError();
+}
+
+hipError_t launch_rep_pack(const double *in, const int32_t *newpos, int64_t n, int R, int rp, double *Z, hipStream_t stream)
+{
+    if (n < 1 || R < 1 || rp < R) return hipErrorInvalidValue;
+    const int64_t blocks = (n * rp + 255) / 256;
+    hipLaunchKernelGGL(gpv_rep_pack_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, in, newpos, n, R, rp, Z);
     return hipGetLastError();
 }
 

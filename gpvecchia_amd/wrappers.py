@@ -194,7 +194,13 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     (vecchia_likelihood_grad / _fisher with smoothness_grad=True), so they take a free smoothness -- four searched log-parameters,
     for L-BFGS-B inside box bounds that keep the smoothness in (0.01, 10], the reference's guard (:72-74) as a bound; Fisher
     scoring keeps the same interval by rejecting (and halving) a trial step that leaves it, and returns a 4 x 4 fisher_info and four theta_se, the smoothness's among them -- or any fixed one.  The covariance is
-    not differentiable in the smoothness at exactly 0.5, 1.5 and 2.5: a trial point there raises ValueError.  Not with trend="gls"."""
+    not differentiable in the smoothness at exactly 0.5, 1.5 and 2.5: a trial point there raises ValueError.  Not with trend="gls".
+    Replicated data: `data` as n x R with R > 1 holds R realisations over the same locations (an ensemble, repeated time slices);
+    needs cond_yz='z', complete columns and trend="ols".  X="missing" subtracts the grand mean, X=None nothing, a given X one
+    common beta_hat by OLS on the replicate mean.  "Nelder-Mead" minimises the negative sum of vecchia_likelihood_replicates;
+    "L-BFGS-B" and "fisher" take value, gradient and information of the sum from ONE pass per step
+    (vecchia_likelihood_grad_replicates / _fisher_replicates); fisher_info is the R-fold information, so theta_se shrinks with
+    sqrt(R).  z is then the n x R residual and the result holds n_replicates.  A 1-D `data` takes the path it always took."""
     if method not in ("Nelder-Mead", "L-BFGS-B", "fisher"):
         raise ValueError(f"method='{method}' not defined")
     fix_nu = smoothness is not None
@@ -223,7 +229,37 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
             raise ValueError(f"method='{method}' with covmodel='matern' needs smoothness in {{0.5, 1.5, 2.5}}")
     data = np.asarray(data, dtype=np.float64)
     locs = np.asarray(locs, dtype=np.float64)
-    if isinstance(X, str) and X == "missing":                        # :32-37 constant trend
+    replicated = data.ndim == 2 and data.shape[1] > 1                # R > 1 realisations over the same locations
+    if replicated:
+        if gls:
+            raise ValueError("trend='gls' is not available with replicated data (data n x R)")
+        if specify_args.get("cond_yz") != "z":
+            raise ValueError("replicated data (data n x R) needs cond_yz='z' (the likelihood whose factor the replicates share)")
+        if not isinstance(covmodel, str):
+            raise ValueError("replicated data (data n x R) needs a named covariance family")
+        if not np.all(np.isfinite(data)):
+            raise ValueError("replicated data (data n x R) must be complete and finite (no NaN)")
+        if data.shape[0] != locs.shape[0]:
+            raise ValueError("replicated data (data n x R) must have one row per location")
+    # the three likelihood calls of the objectives below: of the one data vector, or summed over the replicates (one pass)
+    if replicated:
+        lik = lambda z, *a, **kw: float(np.sum(A.vecchia_likelihood_replicates(z, *a, **kw)))    # noqa: E731
+        lik_grad = lambda *a, **kw: A.vecchia_likelihood_grad_replicates(*a, **kw)               # noqa: E731
+        lik_fisher = lambda *a, **kw: A.vecchia_likelihood_fisher_replicates(*a, **kw)           # noqa: E731
+    else:
+        lik = lambda *a, **kw: A.vecchia_likelihood(*a, **kw)                                     # noqa: E731
+        lik_grad = lambda *a, **kw: A.vecchia_likelihood_grad(*a, **kw)                           # noqa: E731
+        lik_fisher = lambda *a, **kw: A.vecchia_likelihood_fisher(*a, **kw)                       # noqa: E731
+    if replicated and isinstance(X, str) and X == "missing":         # the grand mean
+        beta_hat = np.array([data.mean()])
+        z = data - beta_hat[0]
+        trend_kind = "constant"
+    elif replicated and X is not None:                               # one common beta_hat: OLS on the replicate mean
+        X = np.asarray(X, dtype=np.float64)
+        beta_hat = np.linalg.solve(X.T @ X, X.T @ data.mean(axis=1))
+        z = data - (X @ beta_hat)[:, None]
+        trend_kind = "userspecified"
+    elif isinstance(X, str) and X == "missing":                      # :32-37 constant trend
         beta_hat = np.array([data.mean()])
         z = data - beta_hat[0]
         trend_kind = "constant"
@@ -240,7 +276,7 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         Xg = X if X.ndim == 2 else X[:, None]
     va = A.vecchia_specify(locs, m, **specify_args)                  # :55
     if covmodel == "matern" and (theta_ini is None or np.any(np.isnan(theta_ini))):   # :59-67
-        var_res = np.var(z, ddof=1)
+        var_res = np.var(z, ddof=1)                                  # (replicates: over all entries)
         n = len(z)
         idx = np.random.default_rng(seed).permutation(n)[: min(n, 300)]   # R: sample(1:n, min(n,300)) with R's RNG
         sub = locs[idx]
@@ -264,13 +300,13 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         evals[0] += 1
         th = np.exp(lg)
         cp, nug = full(th)
-        return -A.vecchia_likelihood(z, va, cp, nug, covmodel=covmodel)
+        return -lik(z, va, cp, nug, covmodel=covmodel)
 
     def negloglik_grad(lg):                                          # value and gradient in the log-parameters
         evals[0] += 1
         th = np.exp(lg)
         cp, nug = full(th)
-        ll, g = A.vecchia_likelihood_grad(z, va, cp, nug, covmodel=covmodel, **nu_kw)
+        ll, g = lik_grad(z, va, cp, nug, covmodel=covmodel, **nu_kw)
         if covmodel == "matern" and fix_nu:
             g = np.delete(g, 2)
         elif covmodel == "matern":
@@ -287,7 +323,7 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         cp, nug = full(th)
         if covmodel == "matern" and not fix_nu and not 0.01 < cp[2] <= 10.0:   # the reference's guard (:72-74) and L-BFGS-B's
             return -np.inf, np.zeros_like(th), np.eye(len(th))                 #  box: a trial step the halving loop rejects
-        ll, g, info = A.vecchia_likelihood_fisher(z, va, cp, nug, covmodel=covmodel, **nu_kw)
+        ll, g, info = lik_fisher(z, va, cp, nug, covmodel=covmodel, **nu_kw)
         if covmodel == "matern" and fix_nu:
             g, info = np.delete(g, 2), np.delete(np.delete(info, 2, axis=0), 2, axis=1)
         elif covmodel == "matern":
@@ -356,6 +392,8 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
               dict(zip(("variance", "range", "nugget") if fix_nu else ("variance", "range", "smoothness", "nugget"), theta_hat)))
     out = dict(z=z, beta_hat=beta_hat, theta_hat=theta_hat, trend=trend_kind, locs=locs, covmodel=covmodel,
                n_evals=evals[0], neg_loglik=float(res.fun), convergence=conv)
+    if replicated:
+        out["n_replicates"] = int(data.shape[1])
     if method == "fisher":
         out["fisher_info"] = infos[np.asarray(xbest).tobytes()]
         out["theta_cov"] = np.linalg.inv(out["fisher_info"])

@@ -336,6 +336,45 @@ int gpv_plan_loglik_fisher_nu(gpv_plan *plan, const char *covType, const double 
  * finite or <= 0; GPV_ERR_UNSUPPORTED_NU. */
 int gpv_matern_derivs_host(double nu, double range, const double *s, int64_t n, double *out /* 3 n */);
 
+/* Replicated data: R realisations z_1 .. z_R over the plan's locations (an ensemble, repeated time slices, computer-model runs
+ * over one design) under one parameter value.  Value, gradient and expected information of sum_r loglik(z_r) come out of ONE pass
+ * over the conditioning sets: the factorisation of a block does not depend on the data, and with u, t_p, a_p, y_p = S'^-1 t_p as
+ * above a replicate enters only through q_r = u'z_r and b_{p,r} = z_r'y_p (S' is symmetric, so w_r't_p = z_r'y_p):
+ *   sum_r l_{k,r}           = R (1/2 log u_last - 1/2 log 2 pi) - 1/2 Q2 / u_last,                      Q2   = sum_r q_r^2
+ *   sum_r dl_{k,r}/dtheta_p = -1/2 R a_p / u_last + QB_p / u_last - 1/2 Q2 a_p / u_last^2,             QB_p = sum_r q_r b_{p,r}
+ *   information             = R sum_k F_k          (the expected information does not depend on the data)
+ * i.e. one gpv_plan_loglik_fisher pass plus ncovparms + 2 dot products per replicate and set.
+ *
+ * gpv_plan_set_replicates uploads the columns once and keeps them on the device, packed by internal position:
+ *   Z_ord   R columns of length Nlocs in the plan's ORDERED row numbering, column-major with leading dimension ldz >= Nlocs
+ *           (rows Nlocs .. ldz - 1 of a column are not read)
+ *   R       > 0; R = 0 releases the buffer (Z_ord is then not read) and leaves the plan without replicates
+ * A second call replaces the first upload.  The column of gpv_plan_set_data is a separate thing: neither call touches the
+ * other's data, and gpv_plan_loglik_rep needs no gpv_plan_set_data.  GPV_ERR_BAD_ARG (before the device is touched): a null
+ * plan, R < 0, with R > 0 a null Z_ord or ldz < Nlocs.  gpv_plan_replicates returns the R in effect (0: none).
+ *
+ * gpv_plan_loglik_rep: arguments, layouts of grad, fisher and row_terms, and statuses of gpv_plan_loglik_fisher, with every
+ * quantity summed over the replicates (row_terms: row k = {sum_r l_{k,r}, its derivatives, the triangle of R F_k}); fisher may
+ * be NULL (value and gradient only).  Values must be finite: a NaN in Z_ord gives NaN sums, not a failed row.  n_failed, -Inf and
+ * NaN as for gpv_plan_loglik_fisher; NaN in the smoothness slots of "matern" exactly where the one-column entries put it.
+ * gpv_plan_loglik_rep_nu differentiates the smoothness as gpv_plan_loglik_fisher_nu does.  At R = 1 the result agrees with
+ * gpv_plan_loglik_fisher on the same column to rounding, not bitwise (b takes another route).
+ * Blocking, on the plan's own stream; two ordinary launches; bitwise reproducible from call to call.  Arguments and state are
+ * validated before the device is touched.  The plan's last evaluation, its data column and its factor stamp stay intact:
+ * gpv_plan_get_sums, gpv_plan_get_Lentries, gpv_plan_factor_stamp and a following gpv_plan_loglik_grad return what they returned
+ * before.  GPV_ERR_STATE: no replicates set, a communicator attached, a row shard, unobserved locations, latent conditioning;
+ * GPV_ERR_UNSUPPORTED_M: m + 1 > 64; the other statuses as for gpv_plan_loglik_grad. */
+int gpv_plan_set_replicates(gpv_plan *plan, const double *Z_ord, int64_t ldz, int R);
+int gpv_plan_replicates(gpv_plan *plan, int *R);
+int gpv_plan_loglik_rep(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
+                        double *loglik, double *grad /* ncovparms + 1 */,
+                        double *fisher /* NULL, or (ncovparms + 1)^2, row-major */, int64_t *n_failed,
+                        double *row_terms /* NULL, or Nlocs x (ncovparms + 2 + T), row-major */);
+int gpv_plan_loglik_rep_nu(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
+                           double *loglik, double *grad /* ncovparms + 1 */,
+                           double *fisher /* NULL, or (ncovparms + 1)^2, row-major */, int64_t *n_failed,
+                           double *row_terms /* NULL, or Nlocs x (ncovparms + 2 + T), row-major */);
+
 /* The Vecchia whitening operator of the plan's latest evaluation applied to a block of columns, and their Gram matrix: the
  * primitive behind a generalised-least-squares trend (profile likelihood) and behind the likelihood of replicated data, which
  * share one factor.  Everything is in the plan's ORDERED row numbering.  For row k of a cond.yz='z' plan with the stored entries

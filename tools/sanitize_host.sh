@@ -35,6 +35,9 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
     if [ $P -gt 16 ] && [ $P -lt 32 ]; then      # likelihood-only kernels: a unit of their own (gpvecchia_amd/build.py lik_p)
       $HIPCC $CF "-DGPV_P_LIST(X)=$plx" -DGPV_INST_P=$P -DGPV_INST_LIK -c $CSRC/gpv_sets_inst.hip -o $B/sets_p${P}_lik.o & pids+=($!)
     fi
+    if [ $P -eq 21 ] || [ $P -eq 26 ] || [ $P -eq 31 ]; then   # lean likelihood-only kernels (gpvecchia_amd/build.py lean_p)
+      $HIPCC $CF "-DGPV_P_LIST(X)=$plx" -DGPV_INST_P=$P -DGPV_INST_LEAN -c $CSRC/gpv_sets_inst.hip -o $B/sets_p${P}_lean.o & pids+=($!)
+    fi
   done
   $HIPCC $CF -x c++ -c $CSRC/gpv_order.cpp -o $B/order.o & pids+=($!)
   $HIPCC $CF -c $ROOT/tests/sanitize/mock_hip_runtime.cpp -o $B/mock.o & pids+=($!)
@@ -100,6 +103,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   rc=${PIPESTATUS[0]}
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_whiten.log; then
     echo "== $tag: whiten_driver FAILED (rc $rc)"; return 1
+  fi
+  # ... and under the driver of the replicate entries (tests/sanitize/loglik_rep_driver.cpp)
+  mkdir -p $B/loglik_rep
+  $HIPCC $CF -c $ROOT/tests/sanitize/loglik_rep_driver.cpp -o $B/loglik_rep/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/loglik_rep/driver.o -o $B/loglik_rep_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./loglik_rep_driver ) 2>&1 | tee $B/run_loglik_rep.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_loglik_rep.log; then
+    echo "== $tag: loglik_rep_driver FAILED (rc $rc)"; return 1
   fi
   echo "== $tag: clean"
 }
