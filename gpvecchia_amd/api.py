@@ -783,7 +783,7 @@ def vecchia_specify(locs, m=-1, ordering=None, cond_yz=None, locs_pred=None, ord
         # both searches implement the same exact definition and return identical arrays (tests); "gpu" is the
         # library's brute-force kernel, "host" the cKDTree search
         use_gpu = (nn_backend == "gpu" or (nn_backend == "auto" and L.device_count() > 0 and nall >= 2000)) and \
-            spatial_dim <= 8 and m <= 255                                    # limits of the brute-force kernel
+            spatial_dim <= 8 and m <= L.lib().gpv_nn_max_m()                 # limits of gpv_find_ordered_nn (LDS of one CU)
         NNarray = S.find_ordered_nn_gpu(locsord, m) if use_gpu else S.find_ordered_nn(locsord, m)
     NNarray = np.asarray(NNarray).astype(np.int32)
     if have_pred and pred_cond == "independent":                             # :168-178

@@ -21,6 +21,17 @@
 
 namespace gpv {
 
+// Every lane keeps its best-(m+1) list in dynamic LDS: a distance and an index per entry, 64 lanes per workgroup.  One
+// workgroup cannot have more than the LDS of one compute unit, which bounds m: 768 (m+1) <= 160 KB  =>  m <= 212.  The
+// library's longest row (gpv_max_p() = 192, m = 191) asks for 144 KB.  The launches beyond 64 KB (m >= 85) go without
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize): measured on gfx950, the runtime serves them as they are
+// (tests/test_gpu_nn_search.py runs m = 85, 127, 191 and 212 through both kernels and would report a refused launch).
+constexpr size_t kNnLdsPerCU = 160 * 1024;
+constexpr size_t nn_smem_bytes(int p) { return (sizeof(double) + sizeof(int32_t)) * (size_t)p * 64; }
+constexpr int kNnMaxM = (int)(kNnLdsPerCU / nn_smem_bytes(1)) - 1;
+static_assert(nn_smem_bytes(kNnMaxM + 1) <= kNnLdsPerCU && nn_smem_bytes(kNnMaxM + 2) > kNnLdsPerCU, "kNnMaxM");
+static_assert(kNnMaxM + 1 >= 192, "the search must serve every row length the library takes (kGenericMaxP)");
+
 template <int D>
 __global__ void __launch_bounds__(64) gpv_nn_kernel(const double *__restrict__ locs, int64_t n, int dim, int m,
                                                     int64_t row_begin, int64_t row_end, int32_t *__restrict__ out)
@@ -204,10 +215,20 @@ __global__ void __launch_bounds__(64) gpv_nn_grid_kernel(const double *__restric
 
 using namespace gpv;
 
+extern "C" int gpv_nn_max_m(void) { return kNnMaxM; }
+
+// Statuses: GPV_ERR_BAD_ARG for a NULL pointer, n <= 0 or n >= 2^31, dim outside 1..8, m outside 0..gpv_nn_max_m() (the list
+// of a lane must fit the LDS of one compute unit) or rows outside 0 <= row_begin <= row_end <= n -- all of it before the device
+// is touched, NNarray unwritten; GPV_ERR_NO_DEVICE; GPV_ERR_HIP for a failing runtime call (NNarray unwritten as well: it is
+// filled after the last of them).  An empty shard is GPV_OK and writes nothing.  Rows outside the shard are never written.
+// Non-finite coordinates: the grid is not used, and a candidate at a NaN or infinite distance never enters a list.  So the
+// row of a point with a NaN or infinite coordinate is all 0 (itself included: Inf - Inf is NaN), the row of a finite point
+// lists its finite predecessors only, 0-padded if they are fewer than m + 1, and a row with m + 1 finite predecessors or
+// more is the row of the definition (where such distances sort last).
 extern "C" int gpv_find_ordered_nn(int device, const double *locs, int64_t n, int dim, int m, int64_t row_begin,
                                    int64_t row_end, int *NNarray)
 {
-    if (!locs || !NNarray || n <= 0 || dim < 1 || dim > kMaxDimGeneric || m < 0 || m > 255) return GPV_ERR_BAD_ARG;
+    if (!locs || !NNarray || n <= 0 || dim < 1 || dim > kMaxDimGeneric || m < 0 || m > kNnMaxM) return GPV_ERR_BAD_ARG;
     if (row_begin < 0 || row_end > n || row_begin > row_end || n >= ((int64_t)1 << 31)) return GPV_ERR_BAD_ARG;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0 || device < 0 || device >= ndev) return GPV_ERR_NO_DEVICE;
@@ -227,7 +248,7 @@ extern "C" int gpv_find_ordered_nn(int device, const double *locs, int64_t n, in
         return GPV_ERR_HIP;
     }
     std::vector<int32_t> res((size_t)rows * p);
-    const size_t smem = (sizeof(double) + sizeof(int32_t)) * (size_t)p * 64;
+    const size_t smem = nn_smem_bytes(p);
     if (hipMemcpy(d_locs, lr.data(), sizeof(double) * lr.size(), hipMemcpyHostToDevice) != hipSuccess) rc = GPV_ERR_HIP;
     // rows from kGridFrom on: through the grid (one to three dimensions); the rows below, and everything else: brute force
     static const bool brute_only = getenv("GPV_NN_BRUTE") != nullptr;

@@ -555,7 +555,15 @@ int gpv_ic0(int64_t N, const int *ptrs, const int *inds, double *vals, int64_t *
 /* Exact ordered nearest neighbours on the GPU (brute force, bit-exact): the definition of R/NN_kdtree.R:73-83
  * (what GpGp::find_ordered_nn computes at R/vecchia_specify.R:159, without its random jitter).  locs: n x dim
  * column-major in the ORDERED layout; NNarray: n x (m+1) column-major, 1-based, 0 = NA; only rows
- * [row_begin, row_end) are written (a row shard of a multi-GPU plan). */
+ * [row_begin, row_end) are written (a row shard of a multi-GPU plan); an empty shard writes nothing and is GPV_OK.
+ * Limits: 1 <= dim <= 8, 0 <= m <= gpv_nn_max_m() (every lane keeps its m+1 best in the LDS of one compute unit; the limit
+ * covers every row length the library takes, m + 1 <= gpv_max_p()), 0 < n < 2^31, 0 <= row_begin <= row_end <= n.
+ * Statuses: GPV_ERR_BAD_ARG for a NULL pointer or anything outside these limits, checked before the device is touched;
+ * GPV_ERR_NO_DEVICE; GPV_ERR_HIP for a failing runtime call.  NNarray is written only by a call that returns GPV_OK.
+ * Non-finite coordinates: a candidate at a NaN or infinite distance never enters a list.  The row of a point with such a
+ * coordinate is all 0, the row of a finite point lists its finite predecessors only (0-padded if fewer than m + 1); rows
+ * with at least m + 1 finite predecessors are those of the definition. */
+int gpv_nn_max_m(void);                /* 212 */
 int gpv_find_ordered_nn(int device, const double *locs, int64_t n, int dim, int m, int64_t row_begin, int64_t row_end,
                         int *NNarray);
 

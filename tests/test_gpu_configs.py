@@ -437,17 +437,10 @@ def test_full_size_maxmin_mode_L_n1e6_m30():
 # ordered nearest neighbours through the grid (round 4, csrc/gpv_nn.hip): bit-exact with the definition
 # ----------------------------------------------------------------------------------------------------------------
 def _nn_definition_rows(locs, m, rows):
-    """The definition, row by row in NumPy: sqrt of the left-to-right sum of squared differences, ties -> lower index."""
-    out = np.zeros((len(rows), m + 1), dtype=np.int32)
-    for t, k in enumerate(rows):
-        ssq = np.zeros(k + 1)
-        for c in range(locs.shape[1]):
-            df = locs[k, c] - locs[: k + 1, c]
-            ssq = ssq + df * df
-        d = np.sqrt(ssq)
-        o = np.lexsort((np.arange(k + 1), d))[: min(m + 1, k + 1)]
-        out[t, : len(o)] = o + 1
-    return out
+    """The definition, row by row in NumPy: sqrt of the left-to-right sum of squared differences, ties -> lower index
+    (tests/_nn_truth.py states it once for every test of the search)."""
+    import _nn_truth
+    return _nn_truth.nn_rows(locs, m, rows)
 
 
 @pytest.mark.parametrize("case", ["uniform2d", "uniform3d", "line1d", "lattice_ties", "duplicates", "clustered", "flat_dimension",
