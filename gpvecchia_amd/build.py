@@ -113,8 +113,8 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
     grad = os.path.join(CSRC, "gpv_grad.hip")                # value + gradient (+ information) kernels: one object per row-length bucket
     for pb in (64, 32, 16):
         work.append((grad, os.path.join(BUILD, f"grad_pb{pb}.o"), [f"-DGPV_GRAD_PB={pb}"] + extra_flags,
-                     internal + H("gpv_grad.h", "gpv_fisher_kernel.hpp", "gpv_rep_kernel.hpp"), force))
-    work.append((grad, os.path.join(BUILD, "grad.o"), list(extra_flags), internal + H("gpv_grad.h", "gpv_fisher_kernel.hpp", "gpv_rep_kernel.hpp"), force))
+                     internal + H("gpv_grad.h", "gpv_grad_set_pass.inc", "gpv_rep_kernel.hpp"), force))
+    work.append((grad, os.path.join(BUILD, "grad.o"), list(extra_flags), internal + H("gpv_grad.h", "gpv_grad_set_pass.inc", "gpv_rep_kernel.hpp"), force))
     work.append((os.path.join(CSRC, "gpv_whiten.hip"), os.path.join(BUILD, "whiten.o"), list(extra_flags), H("gpv_whiten.h"), force))
     work.append((os.path.join(CSRC, "gpv_order.cpp"), os.path.join(BUILD, "order.o"), ["-x", "c++"], [pub], force))
     work.append((os.path.join(CSRC, "gpv_nn.hip"), os.path.join(BUILD, "nn.o"), ["-ffp-contract=off"], internal + [pub], force))

@@ -385,7 +385,7 @@ struct gpv_plan {
     // gpv_plan_loglik_grad (gpv_grad.hip), allocated on first use: per-workgroup partials, their totals, per-row terms
     DevBuf<double> d_gr_part, d_gr_tot, d_gr_rows;
     int gr_grid = 0;
-    // the same for gpv_plan_loglik_fisher (gpv_fisher_kernel.hpp)
+    // the same for gpv_plan_loglik_fisher (the kSetsFisher mode of gpv_grad.hip)
     DevBuf<double> d_fi_part, d_fi_tot, d_fi_rows;
     int fi_grid = 0;
     // gpv_plan_loglik_grad_nu / _fisher_nu at a general smoothness: the call's tables (gpv_bessel.hpp, MaternDTab)
@@ -2045,115 +2045,56 @@ static int grad_gen_table(gpv_plan *pl, GradArgs &a, hipStream_t st)
     return GPV_OK;
 }
 
-// Value and gradient of the cond.yz='z' log-likelihood (gpv_grad.hip).  Reads the plan's records and index arrays only and
-// writes buffers of its own, so the sums, the U entries and the factor of the plan's last evaluation stay what they were.
-static int loglik_grad_impl(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
-                            double *loglik, double *grad, int64_t *n_failed, double *row_terms)
+// Value and gradient of the cond.yz='z' log-likelihood (gpv_grad.hip), with the expected Fisher information of the same
+// likelihood (GK_FISHER, the kSetsFisher mode) or the same sums over the plan's replicates (GK_REP, gpv_rep_kernel.hpp; fisher
+// may be NULL): the one implementation behind the six entries.  Reads the plan's records and index arrays only and writes
+// buffers of its own, so the sums, the U entries and the factor of the plan's last evaluation stay what they were.
+enum GradKind { GK_GRAD, GK_FISHER, GK_REP };
+static int loglik_family_impl(gpv_plan *pl, GradKind kind, const char *covType, const double *covparms, int ncovparms, double nugget,
+                              bool with_nu, double *loglik, double *grad, double *fisher, int64_t *n_failed, double *row_terms)
 {
-    if (!pl || !covType || !covparms || !loglik || !grad || !n_failed) return GPV_ERR_BAD_ARG;
+    if (!pl || !covType || !covparms || !loglik || !grad || (kind == GK_FISHER && !fisher) || !n_failed) return GPV_ERR_BAD_ARG;
     bool matern;
-    GradArgs a;
-    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a);
+    RepArgs ra;
+    GradArgs &a = ra.g;
+    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a, kind == GK_REP);
     if (rc != GPV_OK) return rc;
     GPV_HIP(hipSetDevice(pl->device));
+    // partials, totals and rows: the gradient's, or the wider ones the information and the replicates share
+    const bool info = kind != GK_GRAD;
+    const int nv = info ? kFisherNV : kGradNV, ld = info ? kFisherRowLd : kGradRowLd;
+    DevBuf<double> &d_part = info ? pl->d_fi_part : pl->d_gr_part, &d_tot = info ? pl->d_fi_tot : pl->d_gr_tot,
+                   &d_rows = info ? pl->d_fi_rows : pl->d_gr_rows;
+    int &part_grid = info ? pl->fi_grid : pl->gr_grid;
     const int grid = grad_grid(pl->rows, pl->cus);
-    if (!pl->d_gr_part || pl->gr_grid < grid) {
-        GPV_BUF(pl->d_gr_part, resize(kGradNV * (size_t)grid));
-        pl->gr_grid = grid;
+    if (!d_part || part_grid < grid) {
+        GPV_BUF(d_part, resize(nv * (size_t)grid));
+        part_grid = grid;
     }
-    GPV_BUF(pl->d_gr_tot, ensure(kGradNV));
-    if (row_terms) GPV_BUF(pl->d_gr_rows, ensure(kGradRowLd * (size_t)pl->rows));
-    a.row_terms = row_terms ? pl->d_gr_rows : nullptr;
-    a.block_part = pl->d_gr_part; a.totals = pl->d_gr_tot;
+    GPV_BUF(d_tot, ensure(nv));
+    if (row_terms) GPV_BUF(d_rows, ensure(ld * (size_t)pl->rows));
+    a.row_terms = row_terms ? d_rows.get() : nullptr;
+    a.block_part = d_part; a.totals = d_tot;
     hipStream_t st = pl->stream;
     if ((rc = grad_gen_table(pl, a, st)) != GPV_OK) return rc;
-    double tot[kGradNV];
-    GPV_HIP(launch_grad(pl->p, a, grid, st));
-    GPV_HIP(hipMemcpyAsync(tot, pl->d_gr_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
+    ra.Z = pl->d_rep_Z; ra.R = pl->rep_R; ra.RP = pl->rep_RP;
+    double tot[kFisherNV];
+    GPV_HIP(kind == GK_GRAD ? launch_grad(pl->p, a, grid, st)
+                            : (kind == GK_FISHER ? launch_fisher(pl->p, a, grid, st) : launch_rep(pl->p, ra, grid, st)));
+    GPV_HIP(hipMemcpyAsync(tot, d_tot, sizeof(double) * nv, hipMemcpyDeviceToHost, st));
     GPV_HIP(hipStreamSynchronize(st));
     // kernel parameters -> covparms: matern {variance, range, -, nugget}, esqe {variance 1, range 1, variance 2, range 2, nugget},
-    // matern at a general smoothness {variance, range, smoothness, nugget}
+    // matern at a general smoothness {variance, range, smoothness, nugget}; the triangle of the nk kernel parameters -> that of
+    // the np = ncovparms + 1 outputs
     const bool gen = a.cov == COV_MATERN_GEN;
-    const int nk = gen ? 4 : (matern ? 3 : 5);                       // derivatives the kernel produced
-    auto spread = [&](const double *src, double *dst) {              // src: {derivatives}, dst: ncovparms + 1
-        if (matern && !gen) { dst[0] = src[0]; dst[1] = src[1]; dst[2] = NAN; dst[3] = src[2]; }
-        else for (int t = 0; t < nk; ++t) dst[t] = src[t];
-    };
-    *n_failed = (int64_t)tot[6];
-    if (tot[6] > 0.0) {
-        *loglik = -INFINITY;
-        for (int t = 0; t <= ncovparms; ++t) grad[t] = NAN;
-    } else {
-        *loglik = tot[0];
-        spread(tot + 1, grad);
-    }
-    if (row_terms) {
-        std::vector<double> h((size_t)pl->rows * kGradRowLd);
-        GPV_HIP(hipMemcpy(h.data(), pl->d_gr_rows, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-        const int ld = ncovparms + 2;
-        for (int64_t k = 0; k < pl->rows; ++k) {
-            row_terms[k * ld] = h[(size_t)k * kGradRowLd];
-            spread(&h[(size_t)k * kGradRowLd + 1], row_terms + k * ld + 1);
-        }
-    }
-    return GPV_OK;
-}
-
-int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
-                         double *grad, int64_t *n_failed, double *row_terms)
-{
-    return loglik_grad_impl(pl, covType, covparms, ncovparms, nugget, false, loglik, grad, n_failed, row_terms);
-}
-
-// the same, with the smoothness of "matern" differentiated wherever the function is differentiable in it
-int gpv_plan_loglik_grad_nu(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
-                            double *grad, int64_t *n_failed, double *row_terms)
-{
-    return loglik_grad_impl(pl, covType, covparms, ncovparms, nugget, true, loglik, grad, n_failed, row_terms);
-}
-
-// Value, gradient and expected Fisher information of the same likelihood (gpv_fisher_kernel.hpp).  Like gpv_plan_loglik_grad it
-// writes buffers of its own only.  rep: the same sums over the plan's replicates (gpv_rep_kernel.hpp; fisher may be NULL).
-static int loglik_fisher_impl(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
-                              double *loglik, double *grad, double *fisher, int64_t *n_failed, double *row_terms, bool rep = false)
-{
-    if (!pl || !covType || !covparms || !loglik || !grad || !(fisher || rep) || !n_failed) return GPV_ERR_BAD_ARG;
-    bool matern;
-    GradArgs a;
-    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a, rep);
-    if (rc != GPV_OK) return rc;
-    GPV_HIP(hipSetDevice(pl->device));
-    const int grid = grad_grid(pl->rows, pl->cus);
-    if (!pl->d_fi_part || pl->fi_grid < grid) {
-        GPV_BUF(pl->d_fi_part, resize(kFisherNV * (size_t)grid));
-        pl->fi_grid = grid;
-    }
-    GPV_BUF(pl->d_fi_tot, ensure(kFisherNV));
-    if (row_terms) GPV_BUF(pl->d_fi_rows, ensure(kFisherRowLd * (size_t)pl->rows));
-    a.row_terms = row_terms ? pl->d_fi_rows : nullptr;
-    a.block_part = pl->d_fi_part; a.totals = pl->d_fi_tot;
-    hipStream_t st = pl->stream;
-    if ((rc = grad_gen_table(pl, a, st)) != GPV_OK) return rc;
-    double tot[kFisherNV];
-    if (rep) {
-        RepArgs ra;
-        ra.g = a; ra.Z = pl->d_rep_Z; ra.R = pl->rep_R; ra.RP = pl->rep_RP;
-        GPV_HIP(launch_rep(pl->p, ra, grid, st));
-    } else {
-        GPV_HIP(launch_fisher(pl->p, a, grid, st));
-    }
-    GPV_HIP(hipMemcpyAsync(tot, pl->d_fi_tot, sizeof(tot), hipMemcpyDeviceToHost, st));
-    GPV_HIP(hipStreamSynchronize(st));
-    // kernel parameters -> covparms as above; the triangle of the nk kernel parameters -> that of the np = ncovparms + 1 outputs
-    const bool gen = a.cov == COV_MATERN_GEN;
-    const int nk = gen ? 4 : (matern ? 3 : 5), np = ncovparms + 1;
+    const int nk = gen ? 4 : (matern ? 3 : 5), np = ncovparms + 1, ntri = np * (np + 1) / 2;
     const int at[5] = {0, 1, (matern && !gen) ? 3 : 2, 3, 4};        // output position of kernel parameter t
-    auto spread = [&](const double *src, double *dst) {
+    auto spread = [&](const double *src, double *dst) {              // src: {derivatives}, dst: np
         for (int t = 0; t < np; ++t) dst[t] = NAN;
         for (int t = 0; t < nk; ++t) dst[at[t]] = src[t];
     };
-    auto spread_tri = [&](const double *src, double *dst) {          // dst: np (np + 1) / 2, row-major with i <= j
-        for (int t = 0; t < np * (np + 1) / 2; ++t) dst[t] = NAN;
+    auto spread_tri = [&](const double *src, double *dst) {          // dst: ntri, row-major with i <= j
+        for (int t = 0; t < ntri; ++t) dst[t] = NAN;
         for (int i = 0, s = 0; i < nk; ++i)
             for (int j = i; j < nk; ++j, ++s) dst[at[i] * np - at[i] * (at[i] - 1) / 2 + (at[j] - at[i])] = src[s];
     };
@@ -2165,35 +2106,50 @@ static int loglik_fisher_impl(gpv_plan *pl, const char *covType, const double *c
     } else {
         *loglik = tot[0];
         spread(tot + 1, grad);
-        double tri[kFisherTri];
-        spread_tri(tot + kGradNV, tri);
-        for (int i = 0, s = 0; fisher && i < np; ++i)                // mirrored here: exactly symmetric
-            for (int j = i; j < np; ++j, ++s) fisher[i * np + j] = fisher[j * np + i] = tri[s];
+        if (fisher) {
+            double tri[kFisherTri];
+            spread_tri(tot + kGradNV, tri);
+            for (int i = 0, s = 0; i < np; ++i)                      // mirrored here: exactly symmetric
+                for (int j = i; j < np; ++j, ++s) fisher[i * np + j] = fisher[j * np + i] = tri[s];
+        }
     }
     if (row_terms) {
-        std::vector<double> h((size_t)pl->rows * kFisherRowLd);
-        GPV_HIP(hipMemcpy(h.data(), pl->d_fi_rows, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
-        const int64_t ld = np + 1 + np * (np + 1) / 2;
+        std::vector<double> h((size_t)pl->rows * ld);
+        GPV_HIP(hipMemcpy(h.data(), d_rows, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        const int64_t out_ld = np + 1 + (info ? ntri : 0);
         for (int64_t k = 0; k < pl->rows; ++k) {
-            const double *src = &h[(size_t)k * kFisherRowLd];
-            row_terms[k * ld] = src[0];
-            spread(src + 1, row_terms + k * ld + 1);
-            spread_tri(src + kGradRowLd, row_terms + k * ld + 1 + np);
+            const double *src = &h[(size_t)k * ld];
+            row_terms[k * out_ld] = src[0];
+            spread(src + 1, row_terms + k * out_ld + 1);
+            if (info) spread_tri(src + kGradRowLd, row_terms + k * out_ld + 1 + np);
         }
     }
     return GPV_OK;
 }
 
+int gpv_plan_loglik_grad(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                         double *grad, int64_t *n_failed, double *row_terms)
+{
+    return loglik_family_impl(pl, GK_GRAD, covType, covparms, ncovparms, nugget, false, loglik, grad, nullptr, n_failed, row_terms);
+}
+
+// the same, with the smoothness of "matern" differentiated wherever the function is differentiable in it
+int gpv_plan_loglik_grad_nu(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                            double *grad, int64_t *n_failed, double *row_terms)
+{
+    return loglik_family_impl(pl, GK_GRAD, covType, covparms, ncovparms, nugget, true, loglik, grad, nullptr, n_failed, row_terms);
+}
+
 int gpv_plan_loglik_fisher(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
                            double *grad, double *fisher, int64_t *n_failed, double *row_terms)
 {
-    return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, false, loglik, grad, fisher, n_failed, row_terms);
+    return loglik_family_impl(pl, GK_FISHER, covType, covparms, ncovparms, nugget, false, loglik, grad, fisher, n_failed, row_terms);
 }
 
 int gpv_plan_loglik_fisher_nu(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
                               double *grad, double *fisher, int64_t *n_failed, double *row_terms)
 {
-    return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, true, loglik, grad, fisher, n_failed, row_terms);
+    return loglik_family_impl(pl, GK_FISHER, covType, covparms, ncovparms, nugget, true, loglik, grad, fisher, n_failed, row_terms);
 }
 
 // ---- replicated data: R realisations over the plan's locations, one pass for their summed value, gradient and information ---
@@ -2236,13 +2192,13 @@ int gpv_plan_replicates(gpv_plan *pl, int *R)
 int gpv_plan_loglik_rep(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
                         double *grad, double *fisher, int64_t *n_failed, double *row_terms)
 {
-    return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, false, loglik, grad, fisher, n_failed, row_terms, true);
+    return loglik_family_impl(pl, GK_REP, covType, covparms, ncovparms, nugget, false, loglik, grad, fisher, n_failed, row_terms);
 }
 
 int gpv_plan_loglik_rep_nu(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
                            double *grad, double *fisher, int64_t *n_failed, double *row_terms)
 {
-    return loglik_fisher_impl(pl, covType, covparms, ncovparms, nugget, true, loglik, grad, fisher, n_failed, row_terms, true);
+    return loglik_family_impl(pl, GK_REP, covType, covparms, ncovparms, nugget, true, loglik, grad, fisher, n_failed, row_terms);
 }
 
 // ---- the whitening operator of the plan's latest evaluation applied to a block of columns (gpv_whiten.hip) -----------------

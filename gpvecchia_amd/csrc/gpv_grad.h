@@ -40,15 +40,15 @@ struct GradArgs {
     int gmt_base, gmt_nseg;  // segment of s = (bits(s) >> 49) - gmt_base
 };
 
-// gpv_fisher_kernel (gpv_fisher_kernel.hpp) takes the same GradArgs with longer rows and partials: after {l_k, derivatives} comes
+// the Fisher mode of the kernel (kSetsFisher) takes the same GradArgs with longer rows and partials: after {l_k, derivatives} comes
 // the upper triangle (row-major, i <= j) of the row's expected information over the kernel parameters, 6 entries for matern, 10
 // for matern at a general smoothness and 15 for esqe, zeros behind them
 constexpr int kFisherTri = 15;
 constexpr int kFisherRowLd = kGradRowLd + kFisherTri;    // doubles per row of row_terms
 constexpr int kFisherNV = kGradNV + kFisherTri;          // values per partial: the kGradNV of the gradient, then the triangle
 
-// gpv_rep_kernel (gpv_rep_kernel.hpp): the same rows, partials and totals as gpv_fisher_kernel, summed over R replicates of the
-// data.  The kernel reads no datum of GradArgs (rec's fourth slot, z) but the replicates below.
+// the replicate mode (kSetsRep, gpv_rep_kernel.hpp): the same rows, partials and totals as the Fisher mode, summed over R
+// replicates of the data.  The kernel reads no datum of GradArgs (rec's fourth slot, z) but the replicates below.
 constexpr int kRepChunk = 8;           // replicates a lane reads and reduces together; RP is a multiple of it
 struct RepArgs {
     GradArgs g;

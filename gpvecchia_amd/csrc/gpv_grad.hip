@@ -1,4 +1,7 @@
-// gpv_grad.hip — value and analytic gradient of the cond.yz='z' Vecchia log-likelihood (gpv_plan_loglik_grad), gfx950, FP64.
+// gpv_grad.hip — value and analytic gradient of the cond.yz='z' Vecchia log-likelihood (gpv_plan_loglik_grad), gfx950, FP64, and
+// the set pass its two siblings share with it: with the expected information (gpv_plan_loglik_fisher) and summed over replicates
+// (gpv_rep_kernel.hpp).  Every phase of a conditioning set is written once, in gpv_grad_set_pass.inc, the body of all three
+// kernels.
 //
 // The likelihood is a sum of independent conditional densities, one per conditioning set.  With S' = C(J, J) + tau I over the
 // valid entries J of a row (the set's own point last), u = S'^-1 e_last, w = S'^-1 z_J, q = u'z_J:
@@ -22,6 +25,7 @@
 // them costs 2 PB more live doubles per lane through the elimination (256 VGPRs at PB = 64).
 //
 // Builtins only, no inline assembly: the compiler owns every read-lane wait state.
+#include <type_traits>
 #include "gpv_grad.h"
 #include "gpv_internal.h"
 
@@ -146,217 +150,141 @@ __device__ __forceinline__ void grad_dcov(double r2, const GradArgs &A, double (
     }
 }
 
-template <int PB, int COV>
-__global__ void __launch_bounds__(64 * kGradWavesPerBlock, (PB == 16 ? 3 : (PB == 32 ? 2 : 1)))
-    gpv_grad_kernel(const GradArgs A)
-{
-    constexpr int NPAR = CovTraits<COV>::NPAR;
-    __shared__ double s_part[kGradWavesPerBlock][kGradNV];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const bool packed = A.dim <= 3;
-    const int64_t nwaves = (int64_t)gridDim.x * kGradWavesPerBlock;
-    double acc[kGradNV];
-#pragma unroll
-    for (int t = 0; t < kGradNV; ++t) acc[t] = 0.0;
+#include "gpv_rep_kernel.hpp"      // rep_reduce_scatter, and what the replicate mode computes
 
-    for (int64_t k = (int64_t)blockIdx.x * kGradWavesPerBlock + wave; k < A.rows; k += nwaves) {
-        // ---- gather: lane i of the bucket takes entry P - PB + i of the stored row (the valid entries are its LAST n0)
-        const int e = A.P - PB + lane;
-        const int v = (lane < PB && e >= 0) ? A.nn[k * A.P + e] : -1;
-        const bool valid = v >= 0;
-        const unsigned long long vmask = __ballot(valid);
-        const bool own_ok = (vmask >> (PB - 1)) & 1ull;
-        const double zi = valid ? (packed ? A.rec[(int64_t)v * 4 + 3] : (A.z ? A.z[v] : 0.0)) : 0.0;
-        double a[PB];
-        auto distances = [&]() {                                      // a[j] <- squared distance of (lane, j), src/dist.cpp:12-14
-#pragma unroll
-            for (int j = 0; j < PB; ++j) a[j] = 0.0;
-            for (int t = 0; t < A.dim; ++t) {
-                const double x = valid ? (packed ? A.rec[(int64_t)v * 4 + t] : A.locs[(int64_t)v * A.locs_ld + t]) : 0.0;
-#pragma unroll
-                for (int j = 0; j < PB; ++j) {
-                    const double df = x - readlane_d(x, j);
-                    a[j] = __builtin_fma(df, df, a[j]);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        };
-        distances();
-        // ---- C on the valid rows and columns, zero elsewhere (a product with the 0 / 1 flags of both entries: no per-column
-        // lane masks to keep); tau joins the diagonal where the pivot is read, so a padded row is tau times an identity row
-        const int vhi = __double2hiint(valid ? 1.0 : 0.0);
-#pragma unroll
-        for (int j = 0; j < PB; ++j) {
-            const double vj = __hiloint2double(__builtin_amdgcn_readlane(vhi, j), 0);
-            a[j] = grad_cov<COV>(gen_r2<COV>(a[j], valid && vj != 0.0), A) * (valid ? vj : 0.0);
-            __builtin_amdgcn_sched_barrier(0);                        // one exp at a time: PB interleaved ones spill
-        }
-        // ---- Gauss-Jordan with the right-hand sides e_last and z_J
-        double r1 = (lane == PB - 1) ? 1.0 : 0.0, r2 = zi, dg = 1.0;   // dg: 1 / pivot of the lane's own row
-        bool fail = !own_ok;
-#pragma unroll
-        for (int j = 0; j < PB; ++j) {
-            const double d = readlane_d(a[j], j) + A.nug;
-            fail |= !(d > 0.0);                                      // (uniform: every lane holds the same pivot)
-            const bool pivot = lane == j;
-            const double inv = 1.0 / d;                               // (needed on both sides of the select: stays branch-free)
-            const double f = pivot ? 0.0 : a[j] * inv;
-            dg = pivot ? inv : dg;
-#pragma unroll
-            for (int c = j + 1; c < PB; ++c) {
-                a[c] = __builtin_fma(-f, readlane_d(a[c], j), a[c]);
-            }
-            r1 = __builtin_fma(-f, readlane_d(r1, j), r1);
-            r2 = __builtin_fma(-f, readlane_d(r2, j), r2);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        const double u = r1 * dg, w = r2 * dg;                        // exact zeros on the padded rows
-        // ---- second pair pass: t_p = sum_j D_p(lane, j) u_j
-        distances();
-        double tp[NPAR];
-#pragma unroll
-        for (int p = 0; p < NPAR; ++p) tp[p] = 0.0;
-#pragma unroll
-        for (int j = 0; j < PB; ++j) {
-            double d[NPAR];
-            grad_dcov<COV>(gen_r2<COV>(a[j], valid && ((vmask >> j) & 1ull)), A, d);
-            const double uj = readlane_d(u, j);
-#pragma unroll
-            for (int p = 0; p < NPAR; ++p) tp[p] = __builtin_fma(d[p], uj, tp[p]);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        // ---- row terms (every lane ends with the same values)
-        const double ul = readlane_d(u, PB - 1);
-        const double q = wave_sum(u * zi);
-        double val[kGradRowLd];
-        val[0] = 0.5 * log(ul) - 0.5 * q * q / ul - 0.91893853320467274178;   // 1/2 log 2 pi
-#pragma unroll
-        for (int p = 0; p <= NPAR; ++p) {
-            const double ai = wave_sum(p < NPAR ? u * tp[p] : u * u);          // the nugget's block is the identity
-            const double bi = wave_sum(p < NPAR ? w * tp[p] : w * u);
-            val[1 + p] = -0.5 * ai / ul + q * bi / ul - 0.5 * q * q * ai / (ul * ul);
-        }
-#pragma unroll
-        for (int p = NPAR + 2; p < kGradRowLd; ++p) val[p] = 0.0;
-        acc[7] += 1.0;
-        if (fail) {
-            acc[6] += 1.0;
-        } else {
-#pragma unroll
-            for (int p = 0; p < kGradRowLd; ++p) acc[p] += val[p];
-        }
-        if (A.row_terms != nullptr && lane < kGradRowLd) {
-            double mine = 0.0;
-#pragma unroll
-            for (int p = 0; p < kGradRowLd; ++p) mine = (lane == p) ? val[p] : mine;
-            A.row_terms[(int64_t)A.rowid[k] * kGradRowLd + lane] = fail ? __builtin_nan("") : mine;
-        }
+// a[j] <- squared distance of (lane, j), src/dist.cpp:12-14.  Text and no function, like every phase: see the kernel below
+#define GPV_FILL_DISTANCES                                                                                              \
+    _Pragma("unroll") for (int j = 0; j < PB; ++j) a[j] = 0.0;                                                          \
+    for (int t = 0; t < A.dim; ++t) {                                                                                   \
+        const double x = valid ? (packed ? A.rec[(int64_t)v * 4 + t] : A.locs[(int64_t)v * A.locs_ld + t]) : 0.0;       \
+        _Pragma("unroll") for (int j = 0; j < PB; ++j) {                                                                \
+            const double df = x - readlane_d(x, j);                                                                     \
+            a[j] = __builtin_fma(df, df, a[j]);                                                                         \
+        }                                                                                                               \
+        __builtin_amdgcn_sched_barrier(0);                                                                              \
     }
-    // ---- per-workgroup partials, waves added in wave order
-    if (lane == 0) {
-#pragma unroll
-        for (int t = 0; t < kGradNV; ++t) s_part[wave][t] = acc[t];
-    }
-    __syncthreads();
-    if (threadIdx.x < kGradNV) {
-        double s = 0.0;
-        for (int wv = 0; wv < kGradWavesPerBlock; ++wv) s += s_part[wv][threadIdx.x];
-        A.block_part[(int64_t)blockIdx.x * kGradNV + threadIdx.x] = s;
-    }
+
+// ---- the three kernels: the sets of one wavefront, grid-stride ------------------------------------------------------------------
+// Every phase of a conditioning set is written once, in the one body gpv_grad_set_pass.inc that each kernel includes; KIND
+// selects what a kernel does with it:
+//   kSetsGrad    value and gradient: its own pair pass, unrolled, with a[] as scratch for the distances (faster)
+//   kSetsFisher  with the expected information: the sweep keeps its multipliers, pair pass tt[], replay y[], triangle (below)
+//   kSetsRep     the same summed over the R replicates of Z (gpv_rep_kernel.hpp) instead of the plan's column: the sweep carries
+//                no data right-hand side and the row terms are sums over the replicates; nothing else differs from kSetsFisher
+// The phases are NOT functions of their own, and the body is text inside each __global__ function.  Behind a function boundary
+// (forced inline or not, a lambda, a member function that returns a flag, a device function around the whole body) the compiler
+// sees the same arithmetic but schedules and allocates it differently: the sweep gains a third more wait states, and the
+// general-nu kernels at PB = 16, which sit at their register cap, spill more and run up to 10 % slower.  Included
+// as text, under the kernels' old names, the three code objects are what three separate bodies gave, instruction for instruction
+// and at the same offsets (one kernel template with KIND as a parameter gives the same instructions 0x300 bytes further on, and
+// two legs at m = 60 then measure 0.4 - 0.9 % slower).  kSetsGrad fills the distances through a lambda, twice, as gpv_grad_kernel
+// always did; the other two expand the same text in place.
+//
+// The information, per set, with t_i = D_i u (t = u for the nugget), a_i = u't_i and y_j = S'^-1 t_j:
+//     F_k[i, j] = t_i'y_j / u_last - 1/2 a_i a_j / u_last^2
+// which is 1/2 tr(S'^-1 D_i S'^-1 D_j) of the block minus the same trace of its leading block without the set's own point: with
+// L L' = S' only the last row of L^-1 D_i L^-T differs between the two, and that row is (L^-1 D_i v)' with v = u / sqrt(u_last).
+// It is the expectation of -d2 l_k / dtheta_i dtheta_j under the exact process.  The solves y_j REPLAY the elimination instead of
+// repeating it: after step j of the sweep column j of the block is dead, so the step's multiplier is kept there (and 1 / pivot in
+// dg); a further right-hand side then costs PB fused multiply-adds and read-lanes.  The pair pass that forms t_i therefore may
+// not use a[] as scratch: it recomputes each pair's squared distance inside its loop over the columns, from coordinates held in
+// registers (dimension <= 3) or loaded per (column, coordinate), summing over the coordinates in the order of the first pass, so
+// the distances are the same bits.  That loop indexes no register array and is not unrolled over the whole row.
+enum { kSetsGrad, kSetsFisher, kSetsRep };
+#define GPV_GRAD_BOUNDS __launch_bounds__(64 * kGradWavesPerBlock, (PB == 16 ? 3 : (PB == 32 ? 2 : 1)))
+template <int PB, int COV>
+__global__ void GPV_GRAD_BOUNDS gpv_grad_kernel(const GradArgs A)
+{
+    constexpr int KIND = kSetsGrad;
+    const double *const repZ = nullptr;
+    constexpr int repR = 0, repRP = 0;
+#include "gpv_grad_set_pass.inc"
 }
 
-#include "gpv_fisher_kernel.hpp"
-#include "gpv_rep_kernel.hpp"
+template <int PB, int COV>
+__global__ void GPV_GRAD_BOUNDS gpv_fisher_kernel(const GradArgs A)
+{
+    constexpr int KIND = kSetsFisher;
+    const double *const repZ = nullptr;
+    constexpr int repR = 0, repRP = 0;
+#include "gpv_grad_set_pass.inc"
+}
+
+template <int PB, int COV>
+__global__ void GPV_GRAD_BOUNDS gpv_rep_kernel(const RepArgs B)
+{
+    constexpr int KIND = kSetsRep;
+    const GradArgs &A = B.g;
+    const double *const repZ = B.Z;
+    const int repR = B.R, repRP = B.RP;
+#include "gpv_grad_set_pass.inc"
+}
+
+#undef GPV_FILL_DISTANCES
+
+template <int KIND, int COV, class ARGS>
+void launch_one(dim3 g, dim3 b, hipStream_t stream, const ARGS &a)
+{
+    constexpr int PB = GPV_GRAD_PB;
+    if constexpr (KIND == kSetsGrad) hipLaunchKernelGGL((gpv_grad_kernel<PB, COV>), g, b, 0, stream, a);
+    else if constexpr (KIND == kSetsFisher) hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV>), g, b, 0, stream, a);
+    else hipLaunchKernelGGL((gpv_rep_kernel<PB, COV>), g, b, 0, stream, a);
+}
+
+template <int KIND, class ARGS>
+hipError_t launch_cov(const int cov, const ARGS &a, const int grid, hipStream_t stream)
+{
+    const dim3 g((unsigned)grid), b(64 * kGradWavesPerBlock);
+    switch (cov) {
+        case COV_MATERN05: launch_one<KIND, COV_MATERN05>(g, b, stream, a); break;
+        case COV_MATERN15: launch_one<KIND, COV_MATERN15>(g, b, stream, a); break;
+        case COV_MATERN25: launch_one<KIND, COV_MATERN25>(g, b, stream, a); break;
+        case COV_ESQE: launch_one<KIND, COV_ESQE>(g, b, stream, a); break;
+        case COV_MATERN_GEN: launch_one<KIND, COV_MATERN_GEN>(g, b, stream, a); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
 
 }  // namespace
 
-#define GPV_GRAD_NAME2(pb) launch_grad_pb##pb
-#define GPV_GRAD_NAME(pb) GPV_GRAD_NAME2(pb)
-hipError_t GPV_GRAD_NAME(GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t stream)
+#define GPV_GRAD_NAME2(kind, pb) launch_##kind##_pb##pb
+#define GPV_GRAD_NAME(kind, pb) GPV_GRAD_NAME2(kind, pb)
+hipError_t GPV_GRAD_NAME(grad, GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t stream)
 {
-    constexpr int PB = GPV_GRAD_PB;
-    const dim3 g((unsigned)grid), b(64 * kGradWavesPerBlock);
-    switch (a.cov) {
-        case COV_MATERN05: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_MATERN05>), g, b, 0, stream, a); break;
-        case COV_MATERN15: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_MATERN15>), g, b, 0, stream, a); break;
-        case COV_MATERN25: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_MATERN25>), g, b, 0, stream, a); break;
-        case COV_ESQE: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_ESQE>), g, b, 0, stream, a); break;
-        case COV_MATERN_GEN: hipLaunchKernelGGL((gpv_grad_kernel<PB, COV_MATERN_GEN>), g, b, 0, stream, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_cov<kSetsGrad>(a.cov, a, grid, stream);
 }
-
-#define GPV_FISHER_NAME2(pb) launch_fisher_pb##pb
-#define GPV_FISHER_NAME(pb) GPV_FISHER_NAME2(pb)
-hipError_t GPV_FISHER_NAME(GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t stream)
+hipError_t GPV_GRAD_NAME(fisher, GPV_GRAD_PB)(const GradArgs &a, int grid, hipStream_t stream)
 {
-    constexpr int PB = GPV_GRAD_PB;
-    const dim3 g((unsigned)grid), b(64 * kGradWavesPerBlock);
-    switch (a.cov) {
-        case COV_MATERN05: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN05>), g, b, 0, stream, a); break;
-        case COV_MATERN15: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN15>), g, b, 0, stream, a); break;
-        case COV_MATERN25: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN25>), g, b, 0, stream, a); break;
-        case COV_ESQE: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_ESQE>), g, b, 0, stream, a); break;
-        case COV_MATERN_GEN: hipLaunchKernelGGL((gpv_fisher_kernel<PB, COV_MATERN_GEN>), g, b, 0, stream, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_cov<kSetsFisher>(a.cov, a, grid, stream);
 }
-
-#define GPV_REP_NAME2(pb) launch_rep_pb##pb
-#define GPV_REP_NAME(pb) GPV_REP_NAME2(pb)
-hipError_t GPV_REP_NAME(GPV_GRAD_PB)(const RepArgs &a, int grid, hipStream_t stream)
+hipError_t GPV_GRAD_NAME(rep, GPV_GRAD_PB)(const RepArgs &a, int grid, hipStream_t stream)
 {
-    constexpr int PB = GPV_GRAD_PB;
-    const dim3 g((unsigned)grid), b(64 * kGradWavesPerBlock);
-    switch (a.g.cov) {
-        case COV_MATERN05: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_MATERN05>), g, b, 0, stream, a); break;
-        case COV_MATERN15: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_MATERN15>), g, b, 0, stream, a); break;
-        case COV_MATERN25: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_MATERN25>), g, b, 0, stream, a); break;
-        case COV_ESQE: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_ESQE>), g, b, 0, stream, a); break;
-        case COV_MATERN_GEN: hipLaunchKernelGGL((gpv_rep_kernel<PB, COV_MATERN_GEN>), g, b, 0, stream, a); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_cov<kSetsRep>(a.g.cov, a, grid, stream);
 }
 
 #else  // the launcher that picks the bucket, and the second launch
 
-hipError_t launch_grad_pb16(const GradArgs &a, int grid, hipStream_t stream);
-hipError_t launch_grad_pb32(const GradArgs &a, int grid, hipStream_t stream);
-hipError_t launch_grad_pb64(const GradArgs &a, int grid, hipStream_t stream);
+#define GPV_GRAD_BUCKETS(kind, ARGS)                                                 \
+    hipError_t launch_##kind##_pb16(const ARGS &a, int grid, hipStream_t stream); \
+    hipError_t launch_##kind##_pb32(const ARGS &a, int grid, hipStream_t stream); \
+    hipError_t launch_##kind##_pb64(const ARGS &a, int grid, hipStream_t stream);
+GPV_GRAD_BUCKETS(grad, GradArgs)
+GPV_GRAD_BUCKETS(fisher, GradArgs)
+GPV_GRAD_BUCKETS(rep, RepArgs)
 
 namespace {
 // totals[t] = sum over the workgroups, in workgroup order: the same bits for the same launch geometry
+template <int NV>
 __global__ void __launch_bounds__(64) gpv_grad_total_kernel(const double *part, int grid, double *totals)
 {
-    if (threadIdx.x < kGradNV) {
+    if (threadIdx.x < NV) {
         double s = 0.0;
-        for (int b = 0; b < grid; ++b) s += part[(int64_t)b * kGradNV + threadIdx.x];
+        for (int b = 0; b < grid; ++b) s += part[(int64_t)b * NV + threadIdx.x];
         totals[threadIdx.x] = s;
     }
 }
 }  // namespace
-
-hipError_t launch_fisher_pb16(const GradArgs &a, int grid, hipStream_t stream);
-hipError_t launch_fisher_pb32(const GradArgs &a, int grid, hipStream_t stream);
-hipError_t launch_fisher_pb64(const GradArgs &a, int grid, hipStream_t stream);
-
-namespace {
-__global__ void __launch_bounds__(64) gpv_fisher_total_kernel(const double *part, int grid, double *totals)
-{
-    if (threadIdx.x < kFisherNV) {
-        double s = 0.0;
-        for (int b = 0; b < grid; ++b) s += part[(int64_t)b * kFisherNV + threadIdx.x];
-        totals[threadIdx.x] = s;
-    }
-}
-}  // namespace
-
-hipError_t launch_rep_pb16(const RepArgs &a, int grid, hipStream_t stream);
-hipError_t launch_rep_pb32(const RepArgs &a, int grid, hipStream_t stream);
-hipError_t launch_rep_pb64(const RepArgs &a, int grid, hipStream_t stream);
 
 namespace {
 // the replicates as they arrive (columns of the ORDERED rows) -> rows by internal position, any padded count rp
@@ -379,49 +307,35 @@ int grad_grid(int64_t rows, int cus)
     return (int)(grid < 1 ? 1 : grid);
 }
 
+namespace {
+// both launches of a call: the set pass of the row's bucket (pb[] = its launchers for 16, 32, 64), then the sum of its partials
+template <int NV, class ARGS>
+hipError_t launch_sets(int p, const ARGS &a, const GradArgs &g, int grid, hipStream_t stream,
+                       hipError_t (*const (&pb)[3])(const ARGS &, int, hipStream_t))
+{
+    const int bucket = grad_bucket(p);
+    if (grid < 1 || g.rows < 0 || bucket == 0) return hipErrorInvalidValue;
+    const hipError_t e = pb[bucket == 16 ? 0 : (bucket == 32 ? 1 : 2)](a, grid, stream);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gpv_grad_total_kernel<NV>, dim3(1), dim3(64), 0, stream, g.block_part, grid, g.totals);
+    return hipGetLastError();
+}
+}  // namespace
+
 hipError_t launch_grad(int p, const GradArgs &a, int grid, hipStream_t stream)
 {
-    if (grid < 1 || a.rows < 0) return hipErrorInvalidValue;
-    hipError_t e;
-    switch (grad_bucket(p)) {
-        case 16: e = launch_grad_pb16(a, grid, stream); break;
-        case 32: e = launch_grad_pb32(a, grid, stream); break;
-        case 64: e = launch_grad_pb64(a, grid, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gpv_grad_total_kernel, dim3(1), dim3(64), 0, stream, a.block_part, grid, a.totals);
-    return hipGetLastError();
+    return launch_sets<kGradNV>(p, a, a, grid, stream, {launch_grad_pb16, launch_grad_pb32, launch_grad_pb64});
 }
 
 hipError_t launch_fisher(int p, const GradArgs &a, int grid, hipStream_t stream)
 {
-    if (grid < 1 || a.rows < 0) return hipErrorInvalidValue;
-    hipError_t e;
-    switch (grad_bucket(p)) {
-        case 16: e = launch_fisher_pb16(a, grid, stream); break;
-        case 32: e = launch_fisher_pb32(a, grid, stream); break;
-        case 64: e = launch_fisher_pb64(a, grid, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gpv_fisher_total_kernel, dim3(1), dim3(64), 0, stream, a.block_part, grid, a.totals);
-    return hipGetLastError();
+    return launch_sets<kFisherNV>(p, a, a, grid, stream, {launch_fisher_pb16, launch_fisher_pb32, launch_fisher_pb64});
 }
 
 hipError_t launch_rep(int p, const RepArgs &a, int grid, hipStream_t stream)
 {
-    if (grid < 1 || a.g.rows < 0 || a.Z == nullptr || a.R < 1 || a.RP < a.R || a.RP % kRepChunk != 0) return hipErrorInvalidValue;
-    hipError_t e;
-    switch (grad_bucket(p)) {
-        case 16: e = launch_rep_pb16(a, grid, stream); break;
-        case 32: e = launch_rep_pb32(a, grid, stream); break;
-        case 64: e = launch_rep_pb64(a, grid, stream); break;
-        default: return hipErrorInvalidValue;
-    }
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(gpv_fisher_total_kernel, dim3(1), dim3(64), 0, stream, a.g.block_part, grid, a.g.totals);
-    return hipGetLastError();
+    if (a.Z == nullptr || a.R < 1 || a.RP < a.R || a.RP % kRepChunk != 0) return hipErrorInvalidValue;
+    return launch_sets<kFisherNV>(p, a, a.g, grid, stream, {launch_rep_pb16, launch_rep_pb32, launch_rep_pb64});
 }
 
 hipError_t launch_rep_pack(const double *in, const int32_t *newpos, int64_t n, int R, int rp, double *Z, hipStream_t stream)

@@ -6,7 +6,7 @@ One process, one plan (d = 2, cond.yz = 'z', maxmin ordering).  After a clock wa
 does) the two legs run in alternating rounds -- `reps` gradient calls, `reps` plan.eval(GPV_WANT_LOGLIK_Z) + sums() -- and each
 is reported as the median over the rounds of the round's median, wall clock around the blocking calls.  The second leg is the
 code the benchmark measures and is the yardstick; central differences over the 3 parameters would cost 2 * 3 + 1 = 7 of them.
---fisher adds a third leg to every round, `reps` calls of gpv_plan_loglik_fisher (gpv_fisher_kernel.hpp), and
+--fisher adds a third leg to every round, `reps` calls of gpv_plan_loglik_fisher (gpv_grad.hip), and
 reports it beside the gradient call of the same build, which is its yardstick (loglik_fisher_ms, fisher_over_grad).
 --nu-leg NU (a general smoothness, e.g. 0.8) adds the legs of DESIGN.md §4j to every round, on the same plan: `reps` calls of
 gpv_plan_loglik_grad_nu and of gpv_plan_loglik_fisher_nu at that smoothness, and `reps` general-nu likelihood-only evaluations,
