@@ -23,7 +23,7 @@ gpv_plan <- function(vecchia.approx, device = 0L) {
 
 # same arguments and value as vecchia_likelihood() (R/vecchia_likelihood.R:14-27), plus the plan
 vecchia_likelihood_hip <- function(z, vecchia.approx, covparms, nuggets, covmodel = "matern", plan = gpv_plan(vecchia.approx)) {
-  if (!is.character(covmodel)) stop("vecchia_likelihood_hip: covmodel must be 'matern' or 'esqe'")
+  if (!is.character(covmodel)) stop("vecchia_likelihood_hip: covmodel must be 'matern', 'matern_scaledim' or 'esqe'")
   removeNAs()                                                              # R/vecchia_likelihood.R:20 (edits z, nuggets in place)
   n <- length(z)
   if (length(nuggets) > 1L) nuggets <- nuggets[vecchia.approx$ord]         # nuggets.all.ord, R/createU.R:74-77

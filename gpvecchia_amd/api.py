@@ -699,16 +699,35 @@ def EsqeFun(distmat, covparms):
 # vecchia_specify — R/vecchia_specify.R:29-240
 # ---------------------------------------------------------------------------
 def vecchia_specify(locs, m=-1, ordering=None, cond_yz=None, locs_pred=None, ordering_pred=None, pred_cond=None,
-                    conditioning=None, mra_options=None, ic0=False, verbose=False, NNarray=None, nn_backend="auto"):
+                    conditioning=None, mra_options=None, ic0=False, verbose=False, NNarray=None, nn_backend="auto", scale=None):
     """Parameter-independent specification of the Vecchia approximation, conditioning='NN':
     ordering in {'coord','maxmin','outsidein','none'}; cond.yz in {'SGV','SGVT','y','z','zy','RVP','LK'}; prediction
     locations with ordering.pred in {'obspred','general'} and pred.cond in {'general','independent'}; the m = 0
     independent case.  MRA / 'firstm' conditioning goes through ic0 in the reference, never through U_NZentries
-    (R/createU.R:89): not built (NotImplementedError)."""
+    (R/createU.R:89): not built (NotImplementedError).
+    scale: None, or one positive number per coordinate (for covmodel='matern_scaledim': the ranges).  Ordering and neighbour
+    search then run on locs / scale (and locs_pred / scale) -- neighbours chosen in unscaled space are poor under strong
+    anisotropy -- while locsord keeps the true coordinates.  scale=None is the specification it always was."""
     locs = np.asarray(locs, dtype=np.float64)
     if locs.ndim != 2:
         warnings.warn("Locations must be in matrix form")                    # :32-35
         return None
+    if scale is not None:
+        sc = np.asarray(scale, dtype=np.float64).reshape(-1)
+        if sc.size != locs.shape[1] or not np.all(np.isfinite(sc)) or not np.all(sc > 0):
+            raise ValueError("scale must hold one positive finite number per coordinate")
+        lp = None if locs_pred is None else np.asarray(locs_pred, dtype=np.float64).reshape(-1, locs.shape[1])
+        va = vecchia_specify(locs / sc, m, ordering=ordering, cond_yz=cond_yz, locs_pred=None if lp is None else lp / sc,
+                             ordering_pred=ordering_pred, pred_cond=pred_cond, conditioning=conditioning,
+                             mra_options=mra_options, ic0=ic0, verbose=verbose, NNarray=NNarray, nn_backend=nn_backend)
+        # the true coordinates in the rows of the scaled specification's locsord: the ordering of (locs, locs_pred), and for the
+        # response-latent layouts ('zy') the observed block once more in front (R/vecchia_specify.R:196)
+        true = (locs if lp is None else np.vstack([locs, lp]))[va["ord"] - 1]
+        if va["locsord"].shape[0] != true.shape[0]:
+            true = np.vstack([true[:locs.shape[0]], true])
+        assert true.shape == va["locsord"].shape
+        va["locsord"] = true
+        return va
     if m is None or m == -1:
         raise ValueError("neither m nor r defined!")                        # :36-40
     if conditioning not in (None, "NN"):
@@ -1132,13 +1151,31 @@ def vecchia_likelihood(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
     return vecchia_likelihood_U(z, U_obj)
 
 
+def _scaledim_checked(name, va, covparms, covmodel):
+    """covmodel='matern_scaledim' in the gradient-type functions: what the library refuses (gpv_plan_loglik_grad), said here
+    before a plan is built: one range per coordinate, at most three coordinates, a closed-form smoothness."""
+    if not (isinstance(covmodel, str) and covmodel == "matern_scaledim"):
+        return
+    dim = va["locsord"].shape[1]
+    cp = np.atleast_1d(np.asarray(covparms, dtype=np.float64))
+    if cp.size != dim + 2:
+        raise ValueError(f"{name}: covmodel='matern_scaledim' takes variance, {dim} ranges and the smoothness, got {cp.size} covparms")
+    if np.any(cp[1:1 + dim] <= 0) or np.any(np.isinf(cp[1:1 + dim])):
+        raise ValueError(f"{name}: the ranges of covmodel='matern_scaledim' must be positive and finite")
+    if dim > 3:
+        raise ValueError(f"{name}: covmodel='matern_scaledim' has a gradient for at most three coordinates (the kernels carry "
+                         "five parameter slots: variance, three ranges, nugget)")
+    if float(cp[-1]) not in (0.5, 1.5, 2.5):
+        raise ValueError(f"{name}: covmodel='matern_scaledim' needs smoothness in {{0.5, 1.5, 2.5}} (it is not differentiated)")
+
+
 def _grad_plan(name, z, va, nuggets, covmodel, device):
     """The plan and the nugget of vecchia_likelihood_grad / vecchia_likelihood_fisher, after their common refusals."""
     if va["cond_yz"] not in ("z", "false"):
         raise ValueError(f"{name} needs cond_yz='z' (the gradient of the other modes goes through the "
                          "posterior factor)")
     if not isinstance(covmodel, str):
-        raise ValueError(f"{name} needs a named covariance family ('matern' or 'esqe'), not a function or matrix")
+        raise ValueError(f"{name} needs a named covariance family ('matern', 'matern_scaledim' or 'esqe'), not a function or matrix")
     nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
     if nug.size != 1:
         raise ValueError(f"{name} takes one constant nugget")
@@ -1157,7 +1194,10 @@ def vecchia_likelihood_grad(z, vecchia_approx, covparms, nuggets, covmodel="mate
     (Plan.loglik_grad): grad = d loglik / d covparms, then d / d nugget; for 'matern' the smoothness (0.5, 1.5 or 2.5) is not
     differentiated and its entry is NaN.  Only what has an exact, cheap gradient is accepted: cond.yz = 'z' (or m = 0), one
     constant nugget > 0, complete data, no prediction locations, a named covariance family.  smoothness_grad=True: any Matern
-    smoothness is accepted and its derivative returned (NaN only at exactly 0.5, 1.5, 2.5: Plan.loglik_grad)."""
+    smoothness is accepted and its derivative returned (NaN only at exactly 0.5, 1.5, 2.5: Plan.loglik_grad).
+    covmodel='matern_scaledim' (covparms = variance, one range per coordinate, smoothness in {0.5, 1.5, 2.5}; at most three
+    coordinates): grad = d / d variance, d / d range_1 .. range_dim, NaN, d / d nugget."""
+    _scaledim_checked("vecchia_likelihood_grad", vecchia_approx, covparms, covmodel)
     plan, nug = _grad_plan("vecchia_likelihood_grad", z, vecchia_approx, nuggets, covmodel, device)
     ll, grad, _ = plan.loglik_grad(covmodel, covparms, nug, smoothness_grad=smoothness_grad)
     return ll, grad
@@ -1168,6 +1208,7 @@ def vecchia_likelihood_fisher(z, vecchia_approx, covparms, nuggets, covmodel="ma
     (Plan.loglik_fisher), a symmetric matrix over {covparms, nugget} whose inverse at the estimate approximates the covariance of
     the estimator.  For 'matern' the row and column of the smoothness are NaN, unless smoothness_grad=True and the smoothness is
     none of 0.5, 1.5, 2.5.  Accepts what vecchia_likelihood_grad accepts."""
+    _scaledim_checked("vecchia_likelihood_fisher", vecchia_approx, covparms, covmodel)
     plan, nug = _grad_plan("vecchia_likelihood_fisher", z, vecchia_approx, nuggets, covmodel, device)
     ll, grad, info, _ = plan.loglik_fisher(covmodel, covparms, nug, smoothness_grad=smoothness_grad)
     return ll, grad, info
@@ -1180,7 +1221,7 @@ def _rep_plan(name, Z, va, nuggets, covmodel, device):
         raise ValueError(f"{name} needs cond_yz='z' (the gradient of the other modes goes through the "
                          "posterior factor)")
     if not isinstance(covmodel, str):
-        raise ValueError(f"{name} needs a named covariance family ('matern' or 'esqe'), not a function or matrix")
+        raise ValueError(f"{name} needs a named covariance family ('matern', 'matern_scaledim' or 'esqe'), not a function or matrix")
     nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
     if nug.size != 1:
         raise ValueError(f"{name} takes one constant nugget")
@@ -1198,6 +1239,7 @@ def vecchia_likelihood_grad_replicates(Z, vecchia_approx, covparms, nuggets, cov
     over the columns of vecchia_likelihood_grad, from ONE pass over the conditioning sets (Plan.loglik_replicates) -- the
     factorisation of a block does not depend on the data.  Accepts what vecchia_likelihood_grad accepts, with complete, finite
     columns."""
+    _scaledim_checked("vecchia_likelihood_grad_replicates", vecchia_approx, covparms, covmodel)
     plan, nug = _rep_plan("vecchia_likelihood_grad_replicates", Z, vecchia_approx, nuggets, covmodel, device)
     ll, grad, _, _ = plan.loglik_replicates(covmodel, covparms, nug, fisher=False, smoothness_grad=smoothness_grad)
     return ll, grad
@@ -1207,6 +1249,7 @@ def vecchia_likelihood_fisher_replicates(Z, vecchia_approx, covparms, nuggets, c
                                          smoothness_grad=False):
     """(loglik_sum, grad, info): vecchia_likelihood_grad_replicates together with the expected Fisher information of the R
     realisations, R times that of one column (vecchia_likelihood_fisher)."""
+    _scaledim_checked("vecchia_likelihood_fisher_replicates", vecchia_approx, covparms, covmodel)
     plan, nug = _rep_plan("vecchia_likelihood_fisher_replicates", Z, vecchia_approx, nuggets, covmodel, device)
     ll, grad, info, _ = plan.loglik_replicates(covmodel, covparms, nug, smoothness_grad=smoothness_grad)
     return ll, grad, info
@@ -1221,7 +1264,7 @@ def _whiten_plan(name, va, covparms, nuggets, covmodel, device):
     if va["cond_yz"] not in ("z", "false"):
         raise ValueError(f"{name} needs cond_yz='z' (the whitening of the other modes goes through the posterior factor)")
     if not isinstance(covmodel, str):
-        raise ValueError(f"{name} needs a named covariance family ('matern' or 'esqe'), not a function or matrix")
+        raise ValueError(f"{name} needs a named covariance family ('matern', 'matern_scaledim' or 'esqe'), not a function or matrix")
     n = va["locsord"].shape[0]
     if int(np.sum(va["obs"])) != n:
         raise ValueError(f"{name} does not take plans with prediction locations")

@@ -91,41 +91,78 @@ namespace {
 struct CovSetup {
     int cov;
     double sig0, sA, cA, sB, cB;
+    // "matern_scaledim": the kernels run the isotropic family at range 1 on a copy of the coordinates multiplied by inv[t] =
+    // 1 / range_t (launch_scale_locs); nscale = the dimension, 0 for every other family.  inv_min / inv_max: the smallest and
+    // largest of them (1 and 1 otherwise), by which the plan's distance bounds are stretched
+    int nscale = 0;
+    double inv[kMaxDimGeneric] = {0, 0, 0, 0, 0, 0, 0, 0};
+    double inv_min = 1.0, inv_max = 1.0;
 };
 
+// the constants of the Matern branches at (sigma^2, range, nu): src/Matern.cpp:24
+static int matern_setup(double sigma2, double range, double nu, CovSetup &c)
+{
+    c.sig0 = sigma2;
+    c.sA = sigma2;
+    if (nu == 0.5) {                   // branch chosen by exact == like the reference
+        c.cov = COV_MATERN05;
+        c.cA = 1.0 / range;
+    } else if (nu == 1.5) {
+        c.cov = COV_MATERN15;
+        c.cA = std::sqrt(3.0) / range;
+    } else if (nu == 2.5) {
+        c.cov = COV_MATERN25;
+        c.cA = std::sqrt(5.0) / range;
+    } else if (nu > 0.0 && nu <= 60.0 && std::isfinite(nu)) {
+        // general smoothness: Bessel branch, src/Matern.cpp:72-84.  NOTE the reference applies no sqrt(2 nu)
+        // scaling there, so the covariance is discontinuous in nu at 0.5, 1.5, 2.5 (reproduced, not fixed).
+        c.cov = COV_MATERN_GEN;
+        c.sA = sigma2 / (std::pow(2.0, nu - 1.0) * std::tgamma(nu));   // normcon, :73
+        c.cA = 1.0 / range;
+        c.sB = nu;
+    } else {
+        return GPV_ERR_UNSUPPORTED_NU;
+    }
+    return GPV_OK;
+}
+
 // covType / covparms -> kernel constants.  matern: covparms = (sigma^2, range, nu)
-// (src/Matern.cpp:24), esqe: (sigma1^2, r1, sigma2^2, r2) (src/Esqe.cpp:17).
-int cov_setup(const char *covType, const double *cp, int ncov, CovSetup &c)
+// (src/Matern.cpp:24), esqe: (sigma1^2, r1, sigma2^2, r2) (src/Esqe.cpp:17), matern_scaledim: (sigma^2, range_1 .. range_dim,
+// nu), which needs the dimension of the locations (`dim`; the other two ignore it).  No device is touched.
+int cov_setup(const char *covType, const double *cp, int ncov, int dim, CovSetup &c)
 {
     if (covType == nullptr || cp == nullptr) return GPV_ERR_BAD_ARG;
-    c = CovSetup{0, 0, 0, 0, 0, 0};
+    c = CovSetup{};                                                   // (zeros; nscale = 0, inv_min = inv_max = 1)
     if (std::strcmp(covType, "matern") == 0) {
         if (ncov < 3) return GPV_ERR_BAD_ARG;
-        c.sig0 = cp[0];
-        c.sA = cp[0];
-        if (cp[2] == 0.5) {            // branch chosen by exact == like the reference
-            c.cov = COV_MATERN05;
-            c.cA = 1.0 / cp[1];
-        } else if (cp[2] == 1.5) {
-            c.cov = COV_MATERN15;
-            c.cA = std::sqrt(3.0) / cp[1];
-        } else if (cp[2] == 2.5) {
-            c.cov = COV_MATERN25;
-            c.cA = std::sqrt(5.0) / cp[1];
-        } else if (cp[2] > 0.0 && cp[2] <= 60.0 && std::isfinite(cp[2])) {
-            // general smoothness: Bessel branch, src/Matern.cpp:72-84.  NOTE the reference applies no sqrt(2 nu)
-            // scaling there, so the covariance is discontinuous in nu at 0.5, 1.5, 2.5 (reproduced, not fixed).
-            c.cov = COV_MATERN_GEN;
-            c.sA = cp[0] / (std::pow(2.0, cp[2] - 1.0) * std::tgamma(cp[2]));   // normcon, :73
-            c.cA = 1.0 / cp[1];
-            c.sB = cp[2];
-        } else {
-            return GPV_ERR_UNSUPPORTED_NU;
-        }
+        const int rc = matern_setup(cp[0], cp[1], cp[2], c);
+        if (rc != GPV_OK) return rc;
         // a NaN variance or range makes every covariance NaN in the reference, every block fails and the rows stay zero
         // (src/U_NZentries.cpp:64-66).  The kernels clamp the exponent's argument with v_min_f64, which drops a NaN, so the
         // NaN is planted where nothing can drop it: on the diagonal of every block.
         if (!(cp[0] == cp[0]) || !(cp[1] == cp[1])) c.sig0 = NAN;
+        return GPV_OK;
+    }
+    if (std::strcmp(covType, "matern_scaledim") == 0) {
+        // the Matern above at range 1 and distance sqrt(sum_t ((x_t - x'_t) / range_t)^2); the inverse ranges are parameters of
+        // the kernel that writes the scaled copy, hence at most kMaxDimGeneric of them
+        if (dim < 1 || dim > kMaxDimGeneric || ncov != dim + 2) return GPV_ERR_BAD_ARG;
+        bool nan = !(cp[0] == cp[0]);
+        for (int t = 0; t < dim; ++t) {
+            const double r = cp[1 + t];
+            if (r == r && (!(r > 0.0) || std::isinf(r))) return GPV_ERR_BAD_ARG;
+            nan = nan || !(r == r);
+        }
+        const int rc = matern_setup(cp[0], 1.0, cp[dim + 1], c);
+        if (rc != GPV_OK) return rc;
+        c.nscale = dim;
+        c.inv_min = INFINITY; c.inv_max = 0.0;
+        for (int t = 0; t < dim; ++t) {
+            c.inv[t] = 1.0 / cp[1 + t];
+            if (c.inv[t] < c.inv_min) c.inv_min = c.inv[t];
+            if (c.inv[t] > c.inv_max) c.inv_max = c.inv[t];
+        }
+        if (nan) { c.sig0 = NAN; c.inv_min = c.inv_max = 1.0; }           // as for matern: the diagonal of every block
         return GPV_OK;
     }
     if (std::strcmp(covType, "esqe") == 0) {
@@ -300,6 +337,9 @@ struct gpv_plan {
     // d_locs: dim <= 3: packed records [Nlocs][4] = {c0,c1,c2,data} in the plan's INTERNAL (Morton) order;
     //         dim  > 3: coordinates [Nlocs][dim] in internal order, data in d_z
     // d_nuggets: internal order (gathered by the kernel); d_nug_user: caller's ordered layout (Zentries)
+    // d_locs_sc: matern_scaledim's copy of d_locs with the coordinates divided by the ranges, rewritten by every evaluation of
+    //         that family (eval_scaled_locs) and by its gradient-type calls; allocated on first use
+    DevBuf<double> d_locs_sc;
     DevBuf<double> d_locs, d_nuggets, d_nug_user, d_z, d_L, d_block, d_sums, d_Z, d_tmp, d_covvals, d_stage;
     DevBuf<int32_t> d_nn, d_newpos, d_rowid;
     DevBuf<unsigned> d_ticket;                       // arrival counter of the set kernel's workgroups (gpv_reduce_tail.hpp)
@@ -440,7 +480,7 @@ const char *gpv_status_string(int status)
         case GPV_OK: return "ok";
         case GPV_ERR_NO_DEVICE: return "no usable HIP device (libgpvecchia_hip has no CPU fallback)";
         case GPV_ERR_BAD_ARG: return "bad argument";
-        case GPV_ERR_COVTYPE: return "covariance is not implemented (covType must be \"matern\" or \"esqe\")";
+        case GPV_ERR_COVTYPE: return "covariance is not implemented (covType must be \"matern\", \"matern_scaledim\" or \"esqe\")";
         case GPV_ERR_UNSUPPORTED_NU: return "Matern smoothness must be finite, > 0 and <= 60";
         case GPV_ERR_UNSUPPORTED_M: return "m+1 exceeds 192 (or 64 for the device posterior pass)";
         case GPV_ERR_HIP: return "HIP runtime error";
@@ -911,8 +951,23 @@ static int eval_set_args(gpv_plan *pl, const CovSetup &cs, int flags, hipStream_
     // pair.  Where c * |x| would overflow (range below 1e-300 of the coordinates' magnitude) the reference's own dist/range
     // is Inf for every pair of distinct points and its covariance NaN (Inf * 0, src/Matern.cpp:52,68,80): all blocks fail.
     // Same outcome here, through the diagonal.  (nu = 0.5 gives exact zeros there instead, an independent model: not mirrored.)
-    if (cs.cov != COV_DENSE && cs.cov != COV_ESQE && !(std::fabs(cs.cA) * pl->coord_maxabs < 1e300)) a.sig0 = NAN;
+    // (matern_scaledim: the same of the scaled copy, whose coordinates are at most inv_max times the plan's)
+    if (cs.cov != COV_DENSE && cs.cov != COV_ESQE && !(std::fabs(cs.cA) * cs.inv_max * pl->coord_maxabs < 1e300)) a.sig0 = NAN;
     a.mt = nullptr; a.mt_base = 0; a.mt_nseg = 0; a.mt_full = 0; a.mt_win = 0;
+    return GPV_OK;
+}
+
+// matern_scaledim: the set kernel reads a copy of the records (dim <= 3; the coordinate array otherwise) whose coordinates are
+// multiplied by 1 / range_t and whose datum slot is the plan's, written on the evaluation's stream in front of the kernel at
+// EVERY evaluation: gpv_plan_set_data and the Vecchia-Laplace steps rewrite the datum slot of d_locs between evaluations.  The
+// inverse ranges are arguments of that launch, which is no part of a captured graph (the posterior pass reads no coordinate).
+static int eval_scaled_locs(gpv_plan *pl, const CovSetup &cs, hipStream_t st, const double *&rec, const double *&locs)
+{
+    const size_t cnt = (size_t)pl->Nlocs * (size_t)pl->locs_ld;
+    GPV_BUF(pl->d_locs_sc, ensure(cnt));
+    GPV_HIP(launch_scale_locs(pl->d_locs, pl->d_locs_sc, pl->Nlocs, pl->locs_ld, pl->dim, cs.inv, st));
+    rec = pl->d_locs_sc;
+    locs = pl->d_locs_sc;
     return GPV_OK;
 }
 
@@ -924,12 +979,14 @@ static int eval_set_args(gpv_plan *pl, const CovSetup &cs, int flags, hipStream_
 //     1000 (500 leaves the rounding of this product and of the kernel's own sum of squares a wide margin);
 //   idx32; flags exactly GPV_WANT_LOGLIK_Z.
 // GPV_NO_LEAN=1: always the general likelihood-only kernel (tests and A/B runs).
-static void lean_facts(const gpv_plan *pl, SetArgs &a)
+static void lean_facts(const gpv_plan *pl, const CovSetup &cs, SetArgs &a)
 {
     static const bool no_lean = getenv("GPV_NO_LEAN") != nullptr;
     const bool nug_ok = pl->nug_is_scalar ? (std::isfinite(pl->nug_scalar) && pl->nug_scalar <= 0x1p990) : pl->nug_vec_ok;
     const bool parms_ok = std::isfinite(a.sig0) && std::fabs(a.sig0) <= 0x1p930 && std::isfinite(a.sA) && std::isfinite(a.cA);
-    const bool t_bounded = parms_ok && std::fabs(a.cA) * pl->bbox_diam <= 500.0;
+    // (matern_scaledim: no pair of the scaled copy is farther apart than inv_max times the bounding box's diagonal, and the
+    // copy is finite where the coordinates are, by the test of eval_set_args; inv_max is 1 for the other families)
+    const bool t_bounded = parms_ok && std::fabs(a.cA) * cs.inv_max * pl->bbox_diam <= 500.0;
     const bool only_z = a.flags == GPV_WANT_LOGLIK_Z;
     a.task_pad = pl->d_task_pad;
     a.lean_ok = (!no_lean && pl->d_task_pad && pl->coords_finite && nug_ok && pl->idx32 && t_bounded && only_z) ? 1 : 0;
@@ -976,14 +1033,16 @@ static int matern_table_prepare(gpv_plan *pl, const CovSetup &cs, hipStream_t st
     else GPV_HIP(hipEventSynchronize(pl->mt_ev[sl]));             // two evaluations ago: long done in steady state
     int full = 0, e_lo = 0;
     static const bool host_fit = getenv("GPV_MATERN_TABLE_HOST") != nullptr;    // cross-check of the device fit
-    const double s_lo = 0.5 * pl->dist_min * cs.cA, s_hi = 4.0 * pl->dist_max * cs.cA;
+    // (matern_scaledim: a pair at distance d has the scaled distance between inv_min d and inv_max d; both are 1 otherwise)
+    const double s_lo = 0.5 * pl->dist_min * cs.cA * cs.inv_min, s_hi = 4.0 * pl->dist_max * cs.cA * cs.inv_max;
     if (host_fit) matern_tab_build(cs.sB, s_lo, s_hi, cs.sA, pl->h_mt2[sl], &a.mt_base, &a.mt_nseg, kMaxSeg, &full);
     else (void)matern_tab_range(s_lo, s_hi, kMaxSeg, &e_lo, &a.mt_base, &a.mt_nseg, &full);
     a.mt_full = (a.mt_nseg > 0 && full) ? 1 : 0;
     const int win_oct = sets_mt_window_rows(pl->P, pl->dim) / MaternTab::SPO;   // as many octaves as the instantiation has room for
     if (a.mt_nseg > 0 && win_oct > 0 && !pl->dist_hist.empty())
         a.mt_win = MaternTab::SPO * matern_window_octave(pl->dist_hist, (a.mt_base >> MaternTab::LSPO) - 1023,
-                                                         a.mt_nseg / MaternTab::SPO, win_oct, std::log2(std::fabs(cs.cA)));
+                                                         a.mt_nseg / MaternTab::SPO, win_oct,
+                                                         std::log2(std::fabs(cs.cA) * std::sqrt(cs.inv_min * cs.inv_max)));
     if (a.mt_nseg > 0) {
         // the fit runs on the evaluation's stream in front of the set kernel (~10 us; on the host it was 0.3 ms in
         // series with every optimiser step); the stream orders it behind the previous evaluation's reads
@@ -1118,7 +1177,8 @@ static int plan_eval_impl(gpv_plan *pl, const CovSetup &cs, const double *nugget
     SetArgs a;
     if (rc == GPV_OK) rc = eval_set_args(pl, cs, flags, st, d_sums_out, a);
     if (rc != GPV_OK) return rc;
-    lean_facts(pl, a);
+    lean_facts(pl, cs, a);
+    if (cs.nscale > 0 && (rc = eval_scaled_locs(pl, cs, st, a.rec, a.locs)) != GPV_OK) return rc;
     if (cs.cov == COV_MATERN_GEN && (rc = matern_table_prepare(pl, cs, st, a)) != GPV_OK) return rc;
     if ((rc = eval_launch_sets(pl, a, st)) != GPV_OK) return rc;
     if (pl->comm && (rc = eval_allreduce(pl, st, d_sums_out)) != GPV_OK) return rc;
@@ -1147,7 +1207,7 @@ int gpv_plan_eval(gpv_plan *pl, const char *covType, const double *covparms, int
 {
     if (!pl) return GPV_ERR_BAD_ARG;
     CovSetup cs;
-    const int st = cov_setup(covType, covparms, ncovparms, cs);
+    const int st = cov_setup(covType, covparms, ncovparms, pl->dim, cs);
     if (st != GPV_OK) return st;
     return plan_eval_checked(pl, cs, nuggets, n_nuggets, flags, stream, d_sums_out);
 }
@@ -1813,7 +1873,7 @@ static int vl_step_enqueue(gpv_plan *pl, const char *covType, const double *covp
     if (!pl) return GPV_ERR_BAD_ARG;
     if (pl->vl_model < 0) return GPV_ERR_STATE;
     CovSetup cs;
-    const int st0 = cov_setup(covType, covparms, ncovparms, cs);
+    const int st0 = cov_setup(covType, covparms, ncovparms, pl->dim, cs);
     if (st0 != GPV_OK) return st0;
     GPV_HIP(hipSetDevice(pl->device));
     hipStream_t st = pl->stream;
@@ -1915,7 +1975,7 @@ int gpv_plan_vl_loglik(gpv_plan *pl, const char *covType, const double *covparms
     if (!pl || !terms) return GPV_ERR_BAD_ARG;
     if (pl->vl_model < 0 || !pl->have_mean) return GPV_ERR_STATE;
     CovSetup cs;
-    const int st0 = cov_setup(covType, covparms, ncovparms, cs);
+    const int st0 = cov_setup(covType, covparms, ncovparms, pl->dim, cs);
     if (st0 != GPV_OK) return st0;
     GPV_HIP(hipSetDevice(pl->device));
     hipStream_t st = pl->stream;
@@ -1998,19 +2058,23 @@ int gpv_matern_derivs_host(double nu, double range, const double *s, int64_t n, 
 
 // Argument and state checks shared by gpv_plan_loglik_grad and gpv_plan_loglik_fisher (and their _nu forms, with_nu: a general
 // smoothness is accepted and differentiated), before the device is touched; on GPV_OK `a` holds everything but the output
-// buffers and the tables of a general smoothness.  rep: the data are the plan's replicates (gpv_plan_set_replicates), not its column.
+// buffers and the tables of a general smoothness, and `cs` the parsed family (matern_scaledim: its inverse ranges, for the scaled
+// copy).  rep: the data are the plan's replicates (gpv_plan_set_replicates), not its column.
 static int grad_args_checked(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
-                             bool &matern, GradArgs &a, bool rep = false)
+                             bool &matern, GradArgs &a, CovSetup &cs, bool rep = false)
 {
     matern = std::strcmp(covType, "matern") == 0;
-    if (!matern && std::strcmp(covType, "esqe") != 0) return GPV_ERR_COVTYPE;
-    if (ncovparms != (matern ? 3 : 4)) return GPV_ERR_BAD_ARG;
+    const bool scaled = std::strcmp(covType, "matern_scaledim") == 0;
+    if (!matern && !scaled && std::strcmp(covType, "esqe") != 0) return GPV_ERR_COVTYPE;
+    // matern_scaledim: variance, up to three ranges and the nugget fill the five parameter slots of the kernels
+    if (scaled && pl->dim > 3) return GPV_ERR_STATE;
+    if (ncovparms != (matern ? 3 : (scaled ? pl->dim + 2 : 4))) return GPV_ERR_BAD_ARG;
     if (!(nugget > 0.0) || !std::isfinite(nugget)) return GPV_ERR_BAD_ARG;
-    CovSetup cs;
-    const int rc = cov_setup(covType, covparms, ncovparms, cs);
+    const int rc = cov_setup(covType, covparms, ncovparms, pl->dim, cs);
     if (rc != GPV_OK) return rc;
-    // (the reference's Matern is discontinuous in nu at the closed forms, and analytic in it everywhere else)
-    if (cs.cov == COV_MATERN_GEN && !with_nu) return GPV_ERR_UNSUPPORTED_NU;
+    // (the reference's Matern is discontinuous in nu at the closed forms, and analytic in it everywhere else; the smoothness of
+    // matern_scaledim is not differentiated, with_nu or not)
+    if (cs.cov == COV_MATERN_GEN && (!with_nu || scaled)) return GPV_ERR_UNSUPPORTED_NU;
     if (pl->p > kGradMaxP) return GPV_ERR_UNSUPPORTED_M;
     if (!(rep ? pl->rep_R > 0 && pl->d_rep_Z : pl->has_z) || pl->comm || pl->rows != pl->Nlocs || pl->d_obs || pl->latent_nb)
         return GPV_ERR_STATE;
@@ -2018,8 +2082,9 @@ static int grad_args_checked(gpv_plan *pl, const char *covType, const double *co
     a.nn = pl->d_nn; a.rowid = pl->d_rowid;
     a.row_terms = nullptr; a.block_part = nullptr; a.totals = nullptr;
     a.rows = pl->rows; a.P = pl->P; a.dim = pl->dim; a.locs_ld = pl->locs_ld; a.cov = cs.cov;
-    a.sA = cs.sA; a.cA = cs.cA; a.irA = 1.0 / covparms[1];
-    a.sB = cs.sB; a.cB = cs.cB; a.irB = matern ? 0.0 : 1.0 / covparms[3];
+    // irA, irB per family: covparms holds ncovparms entries, 3 for matern_scaledim in one dimension (no covparms[3] there)
+    a.sA = cs.sA; a.cA = cs.cA; a.irA = scaled ? cs.inv[0] : 1.0 / covparms[1];
+    a.sB = cs.sB; a.cB = cs.cB; a.irB = (matern || scaled) ? 0.0 : 1.0 / covparms[3];
     a.nug = nugget;
     a.gen = MaternDerivConst{0.0, 0.0, 0.0};
     a.gmt = nullptr; a.gmt_base = 0; a.gmt_nseg = 0;
@@ -2027,7 +2092,24 @@ static int grad_args_checked(gpv_plan *pl, const char *covType, const double *co
         a.sA = covparms[0];                                          // (cov_setup's is the normalised constant of the value path)
         a.gen = matern_deriv_const(covparms[2]);
     }
+    if (scaled) {
+        // the kernels read the scaled copy, which the entry writes itself (grad_scaled_copy): they pass through no evaluation
+        a.cov = cs.cov + kCovScaled05;                               // COV_MATERN05 / 15 / 25 are 0, 1, 2
+        a.irB = pl->dim > 1 ? cs.inv[1] : 0.0;                       // irA, irB, sB: 1 / range_1, _2, _3 (0: no such coordinate)
+        a.sB = pl->dim > 2 ? cs.inv[2] : 0.0;
+        a.cB = 0.0;
+    }
     return GPV_OK;
+}
+
+// matern_scaledim: the copy of the records with the coordinates divided by the ranges, on `st` in front of the pair passes.  It
+// shares d_locs_sc with the evaluations, which rewrite the copy in front of their own kernel; `st` is the plan's stream, so an
+// evaluation enqueued earlier on a caller's stream is waited for first.
+static int grad_scaled_copy(gpv_plan *pl, const CovSetup &cs, GradArgs &a, hipStream_t st)
+{
+    if (cs.nscale == 0) return GPV_OK;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    return eval_scaled_locs(pl, cs, st, a.rec, a.locs);
 }
 
 // general smoothness: fit the call's tables over the plan's range of pair distances on `st`, in front of the pair passes (the
@@ -2057,7 +2139,8 @@ static int loglik_family_impl(gpv_plan *pl, GradKind kind, const char *covType, 
     bool matern;
     RepArgs ra;
     GradArgs &a = ra.g;
-    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a, kind == GK_REP);
+    CovSetup cs;
+    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, with_nu, matern, a, cs, kind == GK_REP);
     if (rc != GPV_OK) return rc;
     GPV_HIP(hipSetDevice(pl->device));
     // partials, totals and rows: the gradient's, or the wider ones the information and the replicates share
@@ -2077,6 +2160,7 @@ static int loglik_family_impl(gpv_plan *pl, GradKind kind, const char *covType, 
     a.block_part = d_part; a.totals = d_tot;
     hipStream_t st = pl->stream;
     if ((rc = grad_gen_table(pl, a, st)) != GPV_OK) return rc;
+    if ((rc = grad_scaled_copy(pl, cs, a, st)) != GPV_OK) return rc;
     ra.Z = pl->d_rep_Z; ra.R = pl->rep_R; ra.RP = pl->rep_RP;
     double tot[kFisherNV];
     GPV_HIP(kind == GK_GRAD ? launch_grad(pl->p, a, grid, st)
@@ -2086,17 +2170,25 @@ static int loglik_family_impl(gpv_plan *pl, GradKind kind, const char *covType, 
     // kernel parameters -> covparms: matern {variance, range, -, nugget}, esqe {variance 1, range 1, variance 2, range 2, nugget},
     // matern at a general smoothness {variance, range, smoothness, nugget}; the triangle of the nk kernel parameters -> that of
     // the np = ncovparms + 1 outputs
-    const bool gen = a.cov == COV_MATERN_GEN;
-    const int nk = gen ? 4 : (matern ? 3 : 5), np = ncovparms + 1, ntri = np * (np + 1) / 2;
-    const int at[5] = {0, 1, (matern && !gen) ? 3 : 2, 3, 4};        // output position of kernel parameter t
+    // matern_scaledim {variance, range_1 .. range_dim, -, nugget} from the kernels' {variance, three ranges, nugget}: the slots of
+    // the coordinates the plan does not have (exact zeros) are dropped (at = -1)
+    const bool gen = a.cov == COV_MATERN_GEN, scaled = a.cov >= kCovScaled05;
+    const int nk = scaled ? 5 : (gen ? 4 : (matern ? 3 : 5)), np = ncovparms + 1, ntri = np * (np + 1) / 2;
+    int at[5] = {0, 1, (matern && !gen) ? 3 : 2, 3, 4};              // output position of kernel parameter t
+    if (scaled) {
+        for (int t = 0; t < 3; ++t) at[1 + t] = t < pl->dim ? 1 + t : -1;
+        at[4] = pl->dim + 2;
+    }
     auto spread = [&](const double *src, double *dst) {              // src: {derivatives}, dst: np
         for (int t = 0; t < np; ++t) dst[t] = NAN;
-        for (int t = 0; t < nk; ++t) dst[at[t]] = src[t];
+        for (int t = 0; t < nk; ++t)
+            if (at[t] >= 0) dst[at[t]] = src[t];
     };
     auto spread_tri = [&](const double *src, double *dst) {          // dst: ntri, row-major with i <= j
         for (int t = 0; t < ntri; ++t) dst[t] = NAN;
         for (int i = 0, s = 0; i < nk; ++i)
-            for (int j = i; j < nk; ++j, ++s) dst[at[i] * np - at[i] * (at[i] - 1) / 2 + (at[j] - at[i])] = src[s];
+            for (int j = i; j < nk; ++j, ++s)
+                if (at[i] >= 0 && at[j] >= 0) dst[at[i] * np - at[i] * (at[i] - 1) / 2 + (at[j] - at[i])] = src[s];
     };
     *n_failed = (int64_t)tot[6];
     if (tot[6] > 0.0) {
@@ -2107,7 +2199,7 @@ static int loglik_family_impl(gpv_plan *pl, GradKind kind, const char *covType, 
         *loglik = tot[0];
         spread(tot + 1, grad);
         if (fisher) {
-            double tri[kFisherTri];
+            double tri[kFisherTri + 6];                              // (np <= 6: matern_scaledim in three dimensions, NaN smoothness row)
             spread_tri(tot + kGradNV, tri);
             for (int i = 0, s = 0; i < np; ++i)                      // mirrored here: exactly symmetric
                 for (int j = i; j < np; ++j, ++s) fisher[i * np + j] = fisher[j * np + i] = tri[s];
@@ -2968,7 +3060,7 @@ void gpv_U_NZentries(const int *Ncores, const int *n, const int *Nlocs, const in
         return;
     }
     CovSetup cs;
-    int rc = cov_setup(*covType, covparms, *ncovparms, cs);   // checked first: src/U_NZentries.cpp:27-29
+    int rc = cov_setup(*covType, covparms, *ncovparms, *dim, cs);   // checked first: src/U_NZentries.cpp:27-29
     if (rc != GPV_OK) { *status = rc; return; }
     gpv_plan *pl = nullptr;
     PhaseTimer tm;
@@ -3080,7 +3172,8 @@ void gpv_U_NZentries_mat(const int *Ncores, const int *n, const int *Nlocs, cons
         *status = GPV_ERR_HIP;
         return;
     }
-    CovSetup cs{COV_DENSE, 0, 0, 0, 0, 0};
+    CovSetup cs{};
+    cs.cov = COV_DENSE;
     rc = plan_eval_impl(pl, cs, nullptr, 0, GPV_WANT_U, nullptr, nullptr);
     if (rc == GPV_OK) rc = gpv_plan_get_Lentries(pl, Lentries);
     double sums[GPV_NSUMS];
@@ -3112,7 +3205,7 @@ void gpv_MaternFun(const double *distmat, const int *nelem, const double *covpar
     if (!status) status = &dummy;
     if (!distmat || !nelem || !covparms || !covmat) { *status = GPV_ERR_BAD_ARG; return; }
     CovSetup cs;
-    const int rc = cov_setup("matern", covparms, 3, cs);
+    const int rc = cov_setup("matern", covparms, 3, 0, cs);
     if (rc != GPV_OK) { *status = rc; return; }
     covfun_host(distmat, nelem, cs, covmat, status);
 }
@@ -3123,7 +3216,7 @@ void gpv_EsqeFun(const double *distmat, const int *nelem, const double *covparms
     if (!status) status = &dummy;
     if (!distmat || !nelem || !covparms || !covmat) { *status = GPV_ERR_BAD_ARG; return; }
     CovSetup cs;
-    const int rc = cov_setup("esqe", covparms, 4, cs);
+    const int rc = cov_setup("esqe", covparms, 4, 0, cs);
     if (rc != GPV_OK) { *status = rc; return; }
     covfun_host(distmat, nelem, cs, covmat, status);
 }

@@ -309,6 +309,50 @@ hipError_t launch_scatter(const double *src, const int32_t *pos, int64_t n, doub
     return hipGetLastError();
 }
 
+// ---- matern_scaledim: the copy of the location records the set kernel reads, coordinates times 1 / range_t --------------------
+// One streaming pass, 32 bytes in and out per location for dim <= 3 (one thread per record, two 16-byte accesses each way); for
+// dim > 3 one thread per coordinate.  The inverse ranges are launch arguments; they are selected by compares, not by an index
+// into the argument block, so they stay in SGPRs.
+struct ScaleInv { double v[kMaxDimGeneric]; };
+__global__ void __launch_bounds__(256) gpv_scale_rec_kernel(const double2 *__restrict__ src, double2 *__restrict__ dst, int64_t n,
+                                                            int dim, ScaleInv inv)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        double2 lo = src[2 * i], hi = src[2 * i + 1];            // {c0, c1}, {c2, datum}
+        lo.x *= inv.v[0];
+        if (dim > 1) lo.y *= inv.v[1];
+        if (dim > 2) hi.x *= inv.v[2];
+        dst[2 * i] = lo;
+        dst[2 * i + 1] = hi;
+    }
+}
+__global__ void __launch_bounds__(256) gpv_scale_locs_kernel(const double *__restrict__ src, double *__restrict__ dst, int64_t cnt,
+                                                             int dim, ScaleInv inv)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt; i += (int64_t)gridDim.x * blockDim.x) {
+        const int t = (int)(i % dim);
+        double f = inv.v[0];
+#pragma unroll
+        for (int q = 1; q < kMaxDimGeneric; ++q) f = (t == q) ? inv.v[q] : f;
+        dst[i] = src[i] * f;
+    }
+}
+hipError_t launch_scale_locs(const double *src, double *dst, int64_t n, int ld, int dim, const double *inv, hipStream_t s)
+{
+    if (n <= 0) return hipSuccess;
+    if (dim < 1 || dim > kMaxDimGeneric || !(dim <= 3 ? ld == 4 : ld == dim)) return hipErrorInvalidValue;
+    ScaleInv iv;
+    for (int t = 0; t < kMaxDimGeneric; ++t) iv.v[t] = t < dim ? inv[t] : 1.0;
+    const int64_t cnt = dim <= 3 ? n : n * dim;
+    const int grid = (int)((cnt + 255) / 256 < 4096 ? (cnt + 255) / 256 : 4096);
+    if (dim <= 3)
+        hipLaunchKernelGGL(gpv_scale_rec_kernel, dim3(grid), dim3(256), 0, s, reinterpret_cast<const double2 *>(src),
+                           reinterpret_cast<double2 *>(dst), n, dim, iv);
+    else
+        hipLaunchKernelGGL(gpv_scale_locs_kernel, dim3(grid), dim3(256), 0, s, src, dst, cnt, dim, iv);
+    return hipGetLastError();
+}
+
 // src/U_NZentries.cpp:111-115: Z[2i] = -1/sqrt(tau_i), Z[2i+1] = +1/sqrt(tau_i)
 __global__ void gpv_zentries_kernel(const double *nug, int64_t n, double *Z)
 {

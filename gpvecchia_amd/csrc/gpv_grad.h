@@ -12,6 +12,10 @@ constexpr int kGradRowLd = 6;          // doubles per row of GradArgs::row_terms
 // kernel parameters, in this order (the smoothness of "matern" is not one of them):
 //   matern: variance, range, nugget                      esqe: variance 1, range 1, variance 2, range 2, nugget
 //   matern at a general smoothness (COV_MATERN_GEN, the _nu entries): variance, range, smoothness, nugget
+//   matern_scaledim (kCovScaled05 / 15 / 25, dimension <= 3): variance, range_1, range_2, range_3, nugget; the kernels always
+//   carry three ranges, a coordinate the plan does not have differs by exactly 0 in every pair, its slot sums exact zeros and
+//   the host drops it.  Five slots are what kGradNV and kFisherTri hold, hence the limit of three dimensions.
+constexpr int kCovScaled05 = 6, kCovScaled15 = 7, kCovScaled25 = 8;   // GradArgs::cov beyond CovKind: COV_MATERN05 / 15 / 25 + 6
 constexpr int kGradWavesPerBlock = 4;
 // Grid cap: 4 workgroups of 4 wavefronts per CU, 4096 wavefronts on the 256 CUs of an MI355X.  At n = 40 000 every wavefront
 // then takes 9 or 10 conditioning sets; the per-workgroup partials (kGradNV doubles each) stay a few KB.
@@ -29,20 +33,24 @@ struct GradArgs {
     int64_t rows;
     int P;                   // row stride of nn (the plan's compiled row length; may be shorter than the bucket)
     int dim, locs_ld;
-    int cov;                 // CovKind: COV_MATERN05 / 15 / 25 / COV_ESQE / COV_MATERN_GEN
-    double sA, cA, irA;      // matern: sigma^2, sqrt(2 nu)/range, 1/range        esqe: s1, 1/r1, 1/r1
-    double sB, cB, irB;      // esqe: s2, 1/r2^2, 1/r2
+    int cov;                 // CovKind: COV_MATERN05 / 15 / 25 / COV_ESQE / COV_MATERN_GEN, or kCovScaled05 / 15 / 25
+    double sA, cA, irA;      // matern: sigma^2, sqrt(2 nu)/range, 1/range        esqe: s1, 1/r1, 1/r1     scaled: sigma^2, sqrt(2 nu), 1/range_1
+    double sB, cB, irB;      // esqe: s2, 1/r2^2, 1/r2                                                  scaled: 1/range_3, -, 1/range_2
     double nug;
     // COV_MATERN_GEN only (sA = sigma^2, cA = irA = 1/range): the smoothness and its constants, and the launch's tables of the
     // e^s-scaled value, range derivative and smoothness derivative (gpv_bessel.hpp, MaternDTab), or gmt_nseg = 0: no table
     MaternDerivConst gen;
     const double *gmt;       // [gmt_nseg][MaternDTab::ROW]
     int gmt_base, gmt_nseg;  // segment of s = (bits(s) >> 49) - gmt_base
+    // kCovScaled*: rec is the copy with the coordinates divided by their ranges (launch_scale_locs), sA = sigma^2, cA = 1, sqrt(3),
+    // sqrt(5) (range 1), and the three inverse ranges 1 / range_t (0 for an absent coordinate) stand in irA, irB, sB, which
+    // these kinds do not use otherwise.  No member of their own: the argument block keeps the layout every other kernel was
+    // compiled against (the general-nu replicate kernels reload arguments inside their loops and change with it).
 };
 
 // the Fisher mode of the kernel (kSetsFisher) takes the same GradArgs with longer rows and partials: after {l_k, derivatives} comes
 // the upper triangle (row-major, i <= j) of the row's expected information over the kernel parameters, 6 entries for matern, 10
-// for matern at a general smoothness and 15 for esqe, zeros behind them
+// for matern at a general smoothness and 15 for esqe and matern_scaledim, zeros behind them
 constexpr int kFisherTri = 15;
 constexpr int kFisherRowLd = kGradRowLd + kFisherTri;    // doubles per row of row_terms
 constexpr int kFisherNV = kGradNV + kFisherTri;          // values per partial: the kGradNV of the gradient, then the triangle

@@ -51,7 +51,9 @@ __device__ __forceinline__ double wave_sum(double v)
 
 template <int COV>
 struct CovTraits {
-    static constexpr int NPAR = (COV == COV_ESQE) ? 4 : (COV == COV_MATERN_GEN ? 3 : 2);   // covariance parameters differentiated
+    static constexpr bool SCALED = COV >= kCovScaled05;                // matern_scaledim: one range per coordinate
+    static constexpr int BASE = SCALED ? COV - kCovScaled05 : COV;      // the isotropic family its value is (at range 1)
+    static constexpr int NPAR = (COV == COV_ESQE || SCALED) ? 4 : (COV == COV_MATERN_GEN ? 3 : 2);   // covariance parameters differentiated
 };
 
 // ---- general smoothness (COV_MATERN_GEN): variance, range AND smoothness are differentiated ---------------------------------
@@ -97,9 +99,10 @@ __device__ __forceinline__ double gen_r2(const double r2, const bool live)
 
 // covariance of a pair from its squared distance: the formulas of cov_from_r2 (gpv_sets_kernel.hpp); r2 == 0 gives the
 // variance exactly (t = 0, exp(0) = 1)
-template <int COV>
+template <int COVK>
 __device__ __forceinline__ double grad_cov(double r2, const GradArgs &A)
 {
+    constexpr int COV = CovTraits<COVK>::BASE;                          // (matern_scaledim: on the scaled coordinates, cA = sqrt(2 nu))
     const double r = sqrt(r2);
     if constexpr (COV == COV_MATERN05) {
         return A.sA * exp(-(r * A.cA));
@@ -148,6 +151,31 @@ __device__ __forceinline__ void grad_dcov(double r2, const GradArgs &A, double (
         d[2] = e2;
         d[3] = A.sB * e2 * (2.0 * s) * A.irB;                          // s2 e^{-(r/r2)^2} 2 r^2 / r2^3
     }
+}
+
+// matern_scaledim: variance and the three ranges.  r2 = h^2 is the squared distance of the scaled coordinates, dq[t] the squared
+// difference of scaled coordinate t, c = A.cA = sqrt(2 nu) (1 at nu = 0.5):
+//     dC/drange_t = g(h) dq[t] / range_t,   g = sigma^2 e^{-h} / h,  sigma^2 c^2 e^{-ch},  sigma^2 e^{-ch} (c^2 / 3)(1 + ch)
+// At h = 0 every dq[t] is 0; nu = 0.5 would form 0 / 0 there and takes g = 0 instead (the derivative of e^{-h} along a range at a
+// coincident pair is 0: h does not move).  An absent coordinate has dq[t] = 0 and an inverse range of 0: exact zeros.
+template <int COV>
+__device__ __forceinline__ void grad_dcov_scaled(double r2, const double (&dq)[3], const GradArgs &A, double (&d)[4])
+{
+    const double r = sqrt(r2), t = r * A.cA, e = exp(-t);
+    double g;
+    if constexpr (COV == kCovScaled05) {
+        d[0] = e;
+        g = r2 > 0.0 ? A.sA * e / r : 0.0;
+    } else if constexpr (COV == kCovScaled15) {
+        d[0] = __builtin_fma(t, e, e);
+        g = A.sA * (A.cA * A.cA) * e;
+    } else {
+        d[0] = e * __builtin_fma(t, __builtin_fma(t, 1.0 / 3.0, 1.0), 1.0);
+        g = A.sA * e * (A.cA * A.cA * (1.0 / 3.0)) * (1.0 + t);
+    }
+    d[1] = g * dq[0] * A.irA;                                          // (the inverse ranges: GradArgs)
+    d[2] = g * dq[1] * A.irB;
+    d[3] = g * dq[2] * A.sB;
 }
 
 #include "gpv_rep_kernel.hpp"      // rep_reduce_scatter, and what the replicate mode computes
@@ -241,6 +269,9 @@ hipError_t launch_cov(const int cov, const ARGS &a, const int grid, hipStream_t 
         case COV_MATERN25: launch_one<KIND, COV_MATERN25>(g, b, stream, a); break;
         case COV_ESQE: launch_one<KIND, COV_ESQE>(g, b, stream, a); break;
         case COV_MATERN_GEN: launch_one<KIND, COV_MATERN_GEN>(g, b, stream, a); break;
+        case kCovScaled05: launch_one<KIND, kCovScaled05>(g, b, stream, a); break;
+        case kCovScaled15: launch_one<KIND, kCovScaled15>(g, b, stream, a); break;
+        case kCovScaled25: launch_one<KIND, kCovScaled25>(g, b, stream, a); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

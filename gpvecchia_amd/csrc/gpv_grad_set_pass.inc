@@ -4,6 +4,7 @@
 // template that the kernels call, and not one kernel template either: see the comment above the kernels.
     constexpr bool INFO = KIND != kSetsGrad, REP = KIND == kSetsRep;
     constexpr int NPAR = CovTraits<COV>::NPAR, NP1 = NPAR + 1;
+    constexpr bool SCALED = CovTraits<COV>::SCALED;                   // matern_scaledim: the pair passes need the differences per coordinate
     constexpr int NROW = INFO ? kFisherRowLd : kGradRowLd, NV = INFO ? kFisherNV : kGradNV;
     __shared__ double s_part[kGradWavesPerBlock][NV];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -24,8 +25,8 @@
         const bool own_ok = (vmask >> (PB - 1)) & 1ull;
         double zi = 0.0;                                              // the datum (the replicates are read in their own loop)
         if constexpr (!REP) zi = valid ? (packed ? A.rec[(int64_t)v * 4 + 3] : (A.z ? A.z[v] : 0.0)) : 0.0;
-        double xc[3];                                                 // INFO: the coordinates its pair pass keeps (dimension <= 3)
-        if constexpr (INFO) {
+        double xc[3];                                                 // INFO, SCALED: the coordinates the pair pass keeps (dimension <= 3)
+        if constexpr (INFO || SCALED) {
 #pragma unroll
             for (int t = 0; t < 3; ++t) xc[t] = (packed && valid && t < A.dim) ? A.rec[(int64_t)v * 4 + t] : 0.0;
         }
@@ -78,7 +79,17 @@
 #pragma unroll
             for (int j = 0; j < PB; ++j) {
                 double d[NPAR];
-                grad_dcov<COV>(gen_r2<COV>(a[j], valid && ((vmask >> j) & 1ull)), A, d);
+                if constexpr (SCALED) {                               // a[] holds the distances: the differences again, by read-lanes
+                    double dq[3];
+#pragma unroll
+                    for (int t = 0; t < 3; ++t) {
+                        const double df = xc[t] - readlane_d(xc[t], j);
+                        dq[t] = df * df;
+                    }
+                    grad_dcov_scaled<COV>(a[j], dq, A, d);
+                } else {
+                    grad_dcov<COV>(gen_r2<COV>(a[j], valid && ((vmask >> j) & 1ull)), A, d);
+                }
                 const double uj = readlane_d(u, j);
 #pragma unroll
                 for (int p = 0; p < NPAR; ++p) tp[p] = __builtin_fma(d[p], uj, tp[p]);
@@ -103,11 +114,12 @@
             const int j0 = vmask ? __ffsll((long long)vmask) - 1 : 0;    // the columns in front of the first valid one hold u_j = 0
 #pragma unroll 1
             for (int j = j0; j < PB; ++j) {
-                double q2 = 0.0;
+                double q2 = 0.0, dq[3] = {0.0, 0.0, 0.0};                // dq: SCALED only
                 if (packed) {
 #pragma unroll
                     for (int t = 0; t < 3; ++t) {
                         const double df = xc[t] - readlane_d(xc[t], j);
+                        if constexpr (SCALED) dq[t] = df * df;
                         q2 = __builtin_fma(df, df, q2);
                     }
                 } else {
@@ -118,7 +130,8 @@
                     }
                 }
                 double d[NPAR];
-                grad_dcov<COV>(gen_r2<COV>(q2, valid), A, d);             // (the columns from j0 on are valid)
+                if constexpr (SCALED) grad_dcov_scaled<COV>(q2, dq, A, d);
+                else grad_dcov<COV>(gen_r2<COV>(q2, valid), A, d);        // (the columns from j0 on are valid)
                 const double uj = readlane_d(u, j);
 #pragma unroll
                 for (int p = 0; p < NPAR; ++p) tt[p] = __builtin_fma(d[p], uj, tt[p]);

@@ -106,6 +106,9 @@ hipError_t launch_matern_dtab(const MaternDerivConst &kc, int e_lo, int nseg, do
 hipError_t launch_fill(double *dst, double value, int64_t n, hipStream_t s);
 // dst[pos[i] * stride + offset] = src[i]
 hipError_t launch_scatter(const double *src, const int32_t *pos, int64_t n, double *dst, int stride, int offset, hipStream_t s);
+// matern_scaledim: dst <- src ([n][ld]) with coordinate t of every location multiplied by inv[t], t < dim <= kMaxDimGeneric.
+// ld == 4 (dim <= 3): the packed records, whose slots dim .. 3 (zeros and the datum) are copied; otherwise ld == dim
+hipError_t launch_scale_locs(const double *src, double *dst, int64_t n, int ld, int dim, const double *inv, hipStream_t s);
 // x[i] = +Inf where keep[i] == 0 (per-location nuggets as the posterior pass reads them: no observation at a prediction location)
 hipError_t launch_mask_unobserved(const double *src, double *dst, const uint8_t *keep, int64_t n, hipStream_t s);
 hipError_t launch_zentries(const double *nuggets_obsord, int64_t n, double *Z, hipStream_t s);

@@ -162,19 +162,20 @@ def profile_negloglik_grad(lg, data, X, va, covmodel="matern", smoothness=None):
     the derivative of the likelihood in beta vanishes, so the partial gradient in theta IS the gradient of the profile (the
     envelope theorem).  Returns (value, gradient, profile dict)."""
     th = np.exp(np.asarray(lg, dtype=np.float64))
-    matern = covmodel == "matern"
-    cp = np.concatenate([th[:2], [float(smoothness)], th[2:-1]]) if matern else th[:-1]
+    matern = covmodel in ("matern", "matern_scaledim")
+    nu_at = len(th) - 1 if covmodel == "matern_scaledim" else 2      # ('matern_scaledim': variance, the ranges, smoothness)
+    cp = np.concatenate([th[:nu_at], [float(smoothness)], th[nu_at:-1]]) if matern else th[:-1]
     prof = A.vecchia_profile_likelihood(data, X, va, cp, th[-1], covmodel=covmodel)
     if not np.isfinite(prof["loglik"]):
         return _BIG, np.zeros_like(th), prof
     _, g = A.vecchia_likelihood_grad(data - X @ prof["beta_hat"], va, cp, th[-1], covmodel=covmodel)
-    g = np.delete(g, 2) if matern else g
+    g = np.delete(g, nu_at) if matern else g
     return -prof["loglik"], -g * th, prof
 
 
 def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini=None, output_level=1,
                      reltol=np.sqrt(np.finfo(float).eps), seed=0, maxit=300, smoothness=None, method="Nelder-Mead",
-                     trend="ols", smoothness_grad=False, **specify_args):
+                     trend="ols", smoothness_grad=False, reneighbor=False, **specify_args):
     """trend: "ols" (the reference, R/vecchia_wrappers.R:32-51: coefficients by ordinary least squares once, the covariance
     fitted to their residuals) or "gls": generalised least squares with the coefficients profiled out of the likelihood
     (vecchia_profile_likelihood: beta_hat(theta) under the Vecchia precision at every step), for X given or the constant
@@ -200,12 +201,23 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     common beta_hat by OLS on the replicate mean.  "Nelder-Mead" minimises the negative sum of vecchia_likelihood_replicates;
     "L-BFGS-B" and "fisher" take value, gradient and information of the sum from ONE pass per step
     (vecchia_likelihood_grad_replicates / _fisher_replicates); fisher_info is the R-fold information, so theta_se shrinks with
-    sqrt(R).  z is then the n x R residual and the result holds n_replicates.  A 1-D `data` takes the path it always took."""
+    sqrt(R).  z is then the n x R residual and the result holds n_replicates.  A 1-D `data` takes the path it always took.
+    covmodel='matern_scaledim': the Matern with one range per coordinate; theta_ini, theta_hat and theta_se are in the order
+    variance, range_1 .. range_dim, smoothness, nugget (without the smoothness when it is fixed).  Nelder-Mead handles any
+    smoothness; "L-BFGS-B" and "fisher" need a fixed smoothness in {0.5, 1.5, 2.5} and at most three coordinates.  The default
+    start gives every coordinate the isotropic start's rule on its own extent (a quarter of the mean absolute difference of that
+    coordinate over the sampled pairs).  trend="gls" and n x R data work as for 'matern'.  reneighbor=True: after the search the
+    approximation is specified once more with scale = the fitted ranges (vecchia_specify) and the search continues from the
+    estimate; the default leaves every call as it was."""
     if method not in ("Nelder-Mead", "L-BFGS-B", "fisher"):
         raise ValueError(f"method='{method}' not defined")
     fix_nu = smoothness is not None
-    if fix_nu and covmodel != "matern":
-        raise ValueError("smoothness applies to covmodel='matern' only")
+    scaledim = isinstance(covmodel, str) and covmodel == "matern_scaledim"
+    mfam = scaledim or (isinstance(covmodel, str) and covmodel == "matern")   # the families with a smoothness among the covparms
+    if fix_nu and not mfam:
+        raise ValueError("smoothness applies to covmodel='matern' and 'matern_scaledim' only")
+    if reneighbor and not scaledim:
+        raise ValueError("reneighbor applies to covmodel='matern_scaledim' only")
     if trend not in ("ols", "gls"):
         raise ValueError(f"trend='{trend}' not defined")
     gls = trend == "gls"
@@ -227,8 +239,15 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
             raise ValueError(f"method='{method}' needs a named covariance family")
         if covmodel == "matern" and not smoothness_grad and (not fix_nu or float(smoothness) not in (0.5, 1.5, 2.5)):
             raise ValueError(f"method='{method}' with covmodel='matern' needs smoothness in {{0.5, 1.5, 2.5}}")
+        if scaledim and (not fix_nu or float(smoothness) not in (0.5, 1.5, 2.5)):
+            raise ValueError(f"method='{method}' with covmodel='matern_scaledim' needs smoothness in {{0.5, 1.5, 2.5}}")
     data = np.asarray(data, dtype=np.float64)
     locs = np.asarray(locs, dtype=np.float64)
+    if scaledim and locs.ndim != 2:
+        raise ValueError("covmodel='matern_scaledim' needs locs as an n x dim matrix")
+    if scaledim and method in ("L-BFGS-B", "fisher") and locs.shape[1] > 3:
+        raise ValueError(f"method='{method}' with covmodel='matern_scaledim' needs at most three coordinates")
+    nu_at = locs.shape[1] + 1 if scaledim else 2                     # where the smoothness stands among the covparms
     replicated = data.ndim == 2 and data.shape[1] > 1                # R > 1 realisations over the same locations
     if replicated:
         if gls:
@@ -284,17 +303,26 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         theta_ini = np.array([.9 * var_res, dm.mean() / 4, .8, .1 * var_res])        # var, range, smooth, nugget
         if fix_nu:
             theta_ini = np.delete(theta_ini, 2)
+    if scaledim and (theta_ini is None or np.any(np.isnan(theta_ini))):
+        var_res = np.var(z, ddof=1)
+        n = len(z)
+        idx = np.random.default_rng(seed).permutation(n)[: min(n, 300)]
+        sub = locs[idx]
+        ranges = np.abs(sub[:, None, :] - sub[None, :, :]).mean(axis=(0, 1)) / 4   # the rule above, per coordinate
+        theta_ini = np.concatenate([[.9 * var_res], ranges, [.8, .1 * var_res]])
+        if fix_nu:
+            theta_ini = np.delete(theta_ini, nu_at)
     theta_ini = np.asarray(theta_ini, dtype=np.float64)
 
     def full(th):                                                    # searched parameters -> (covparms, nugget)
-        cp = np.concatenate([th[:2], [float(smoothness)], th[2:-1]]) if fix_nu else th[:-1]
+        cp = np.concatenate([th[:nu_at], [float(smoothness)], th[nu_at:-1]]) if fix_nu else th[:-1]
         return cp, th[-1]
     n_par = len(theta_ini)
     evals = [0]
     nu_kw = dict(smoothness_grad=True) if smoothness_grad else {}    # (the default call is the call it always was)
 
     def negloglik(lg):                                               # :72-78
-        if covmodel == "matern" and not fix_nu and np.exp(lg[2]) > 10:
+        if mfam and not fix_nu and np.exp(lg[nu_at]) > 10:
             raise RuntimeError("The default optimization routine to find parameters did not converge. "
                                "Try writing your own optimization.")
         evals[0] += 1
@@ -307,8 +335,8 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         th = np.exp(lg)
         cp, nug = full(th)
         ll, g = lik_grad(z, va, cp, nug, covmodel=covmodel, **nu_kw)
-        if covmodel == "matern" and fix_nu:
-            g = np.delete(g, 2)
+        if mfam and fix_nu:
+            g = np.delete(g, nu_at)
         elif covmodel == "matern":
             _nu_slot_checked(g[2], ll, cp[2])
         if not np.isfinite(ll):
@@ -324,8 +352,8 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         if covmodel == "matern" and not fix_nu and not 0.01 < cp[2] <= 10.0:   # the reference's guard (:72-74) and L-BFGS-B's
             return -np.inf, np.zeros_like(th), np.eye(len(th))                 #  box: a trial step the halving loop rejects
         ll, g, info = lik_fisher(z, va, cp, nug, covmodel=covmodel, **nu_kw)
-        if covmodel == "matern" and fix_nu:
-            g, info = np.delete(g, 2), np.delete(np.delete(info, 2, axis=0), 2, axis=1)
+        if mfam and fix_nu:
+            g, info = np.delete(g, nu_at), np.delete(np.delete(info, nu_at, axis=0), nu_at, axis=1)
         elif covmodel == "matern":
             _nu_slot_checked(g[2], ll, cp[2])
         infos[lg.tobytes()] = info
@@ -333,7 +361,7 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
 
     if gls:                                                          # the same three objectives on the profile likelihood
         def negloglik(lg):                                           # noqa: F811
-            if covmodel == "matern" and not fix_nu and np.exp(lg[2]) > 10:
+            if mfam and not fix_nu and np.exp(lg[nu_at]) > 10:
                 raise RuntimeError("The default optimization routine to find parameters did not converge. "
                                    "Try writing your own optimization.")
             evals[0] += 1
@@ -353,29 +381,38 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
             if not np.isfinite(prof["loglik"]):
                 return -np.inf, np.zeros_like(th), np.eye(len(th))
             _, g, info = A.vecchia_likelihood_fisher(data - Xg @ prof["beta_hat"], va, cp, nug, covmodel=covmodel)
-            if covmodel == "matern":
-                g, info = np.delete(g, 2), np.delete(np.delete(info, 2, axis=0), 2, axis=1)
+            if mfam:
+                g, info = np.delete(g, nu_at), np.delete(np.delete(info, nu_at, axis=0), nu_at, axis=1)
             infos[lg.tobytes()] = info
             return prof["loglik"], g * th, info * np.outer(th, th)
 
-    parscale = np.ones(n_par)                                        # :83-85 (entries with theta.ini == 1 stay 1; the
-    non1 = theta_ini != 1                                            #  reference's rep(1, length(n.par)) leaves them NA)
-    parscale[non1] = np.log(theta_ini[non1])
-    x0 = np.log(theta_ini) / parscale                                # optim works on par / parscale
-    if method == "L-BFGS-B":
-        from scipy.optimize import minimize
-        bounds = None
-        if covmodel == "matern" and not fix_nu:                      # the reference's guard (:72-74: smoothness > 10 is an error)
-            bounds = [(None, None)] * n_par
-            bounds[2] = (np.log(0.01), np.log(10.0))
-        r = minimize(negloglik_grad, np.log(theta_ini), jac=True, method="L-BFGS-B", bounds=bounds,
-                     options=dict(maxiter=maxit, ftol=1e-3 * reltol, gtol=1e-5))   # (relative decrease per iteration; gradient in log-parameters)
-        xbest, fbest, conv, parscale = r.x, float(r.fun), (0 if r.success else 1), np.ones(n_par)
-    elif method == "fisher":
-        xbest, ll_best, _, _, _, conv = _fisher_scoring(loglik_fisher, np.log(theta_ini), reltol=reltol, maxit=maxit)
-        fbest, parscale = -ll_best, np.ones(n_par)
-    else:
+    def search(theta_ini):                                           # -> (xbest, fbest, conv, parscale)
+        parscale = np.ones(n_par)                                        # :83-85 (entries with theta.ini == 1 stay 1; the
+        non1 = theta_ini != 1                                            #  reference's rep(1, length(n.par)) leaves them NA)
+        parscale[non1] = np.log(theta_ini[non1])
+        x0 = np.log(theta_ini) / parscale                                # optim works on par / parscale
+        if method == "L-BFGS-B":
+            from scipy.optimize import minimize
+            bounds = None
+            if covmodel == "matern" and not fix_nu:                      # the reference's guard (:72-74: smoothness > 10 is an error)
+                bounds = [(None, None)] * n_par
+                bounds[2] = (np.log(0.01), np.log(10.0))
+            r = minimize(negloglik_grad, np.log(theta_ini), jac=True, method="L-BFGS-B", bounds=bounds,
+                         options=dict(maxiter=maxit, ftol=1e-3 * reltol, gtol=1e-5))   # (relative decrease per iteration; gradient in log-parameters)
+            return r.x, float(r.fun), (0 if r.success else 1), np.ones(n_par)
+        if method == "fisher":
+            xbest, ll_best, _, _, _, conv = _fisher_scoring(loglik_fisher, np.log(theta_ini), reltol=reltol, maxit=maxit)
+            return xbest, -ll_best, conv, np.ones(n_par)
         xbest, fbest, _, conv = _nelder_mead_nash(lambda x: negloglik(x * parscale), x0, reltol=reltol, maxit=maxit)   # :87-93
+        return xbest, fbest, conv, parscale
+
+    xbest, fbest, conv, parscale = search(theta_ini)
+    if reneighbor:
+        # neighbours chosen in unscaled space are poor under strong anisotropy: once more on locs / fitted ranges, from the estimate
+        th = np.exp(xbest * parscale)
+        va = A.vecchia_specify(locs, m, **dict(specify_args, scale=th[1:1 + locs.shape[1]]))
+        infos.clear()
+        xbest, fbest, conv, parscale = search(th)
 
     class _Res:
         x, fun = xbest, fbest
@@ -386,10 +423,12 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         prof = A.vecchia_profile_likelihood(data, Xg, va, cp_hat, nug_hat, covmodel=covmodel)
         beta_hat = prof["beta_hat"]
         z = data - Xg @ beta_hat
+    rnames = tuple(f"range_{t + 1}" for t in range(locs.shape[1])) if scaledim else ("range",)
+    par_names = ("variance",) + rnames + (() if fix_nu else ("smoothness",)) + ("nugget",)
     if output_level > 0:                                             # :98-101
         print("estimated trend coefficients:\n", beta_hat)
         print("estimated covariance parameters:\n",
-              dict(zip(("variance", "range", "nugget") if fix_nu else ("variance", "range", "smoothness", "nugget"), theta_hat)))
+              dict(zip(par_names, theta_hat)))
     out = dict(z=z, beta_hat=beta_hat, theta_hat=theta_hat, trend=trend_kind, locs=locs, covmodel=covmodel,
                n_evals=evals[0], neg_loglik=float(res.fun), convergence=conv)
     if replicated:

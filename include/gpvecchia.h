@@ -34,7 +34,7 @@ enum {
     GPV_OK = 0,
     GPV_ERR_NO_DEVICE = 1,      /* no HIP device / HIP runtime error at init        */
     GPV_ERR_BAD_ARG = 2,        /* null pointer, negative size, bad shard range      */
-    GPV_ERR_COVTYPE = 3,        /* covType not "matern"/"esqe" (src/U_NZentries.cpp:27-29) */
+    GPV_ERR_COVTYPE = 3,        /* covType not "matern"/"matern_scaledim"/"esqe" (src/U_NZentries.cpp:27-29) */
     GPV_ERR_UNSUPPORTED_NU = 4, /* Matern smoothness not in (0, 60] or not finite                */
     GPV_ERR_UNSUPPORTED_M = 5,  /* m+1 > 192 (m+1 <= 64: unrolled register kernels; up to 192 and any dimension: a slow
                                    workgroup-per-set kernel); m+1 > 64 for gpv_plan_build_posterior and for
@@ -108,8 +108,17 @@ int gpv_max_p(void);                   /* widest supported row length m+1 (192) 
  *   revNNarray      Nlocs x ncolNN int, 1-based, 0 or NA_INTEGER = missing
  *   revCondOnLatent Nlocs x ncolNN int (R logical: 1 TRUE latent, 0 FALSE observed, NA_INTEGER ignored)
  *   nuggets         Nlocs double (R/createU.R:77), nuggets_obsord n double (R/createU.R:78)
- *   covType         pointer to a C string, "matern" or "esqe"
- *   covparms        ncovparms doubles (3 for matern, 4 for esqe)
+ *   covType         pointer to a C string, "matern", "matern_scaledim" or "esqe"
+ *   covparms        ncovparms doubles (3 for matern, 4 for esqe, dim + 2 for matern_scaledim)
+ *                   "matern_scaledim": the Matern with one range per coordinate, covparms = (variance, range_1 .. range_dim,
+ *                   smoothness).  With h = sqrt(sum_t ((x_t - x'_t) / range_t)^2), summed in coordinate order, it is "matern"
+ *                   at distance h and range 1 (the closed forms at smoothness 0.5, 1.5, 2.5, the general branch otherwise;
+ *                   h == 0 gives the variance exactly).  Every entry that takes a covType and evaluates accepts it
+ *                   (this one, gpv_plan_eval, gpv_mplan_eval*, the Vecchia-Laplace steps), for dim <= 8: each evaluation
+ *                   first writes a plan-owned copy of the locations with the coordinates multiplied by 1 / range_t, on its
+ *                   own stream, and the set kernel of "matern" runs on that copy.  Checked before the device is touched:
+ *                   ncovparms != dim + 2, dim > 8, a range <= 0 or infinite are GPV_ERR_BAD_ARG; a NaN range or variance
+ *                   fails every block, like "matern".
  *   Lentries        out, Nlocs x ncolNN double, rows left-aligned and zero padded
  *   Zentries        out, 2n double  (src/U_NZentries.cpp:111-115)
  *   n_failed        out, rows left all-zero because the block was not PD
@@ -285,7 +294,12 @@ int gpv_plan_factor_stamp(gpv_plan *plan, int64_t *stamp);
  * Arguments are validated before the device is touched.  GPV_ERR_BAD_ARG: a null plan or pointer, ncovparms not 3 / 4, nugget
  * not finite or <= 0; GPV_ERR_COVTYPE; GPV_ERR_UNSUPPORTED_NU: a smoothness other than 0.5, 1.5, 2.5; GPV_ERR_UNSUPPORTED_M:
  * m + 1 > 64; GPV_ERR_STATE: no data set, a communicator attached, a row shard, unobserved locations (gpv_plan_set_observed), or
- * a plan in which some neighbour is conditioned on as latent y (cond.yz other than 'z'). */
+ * a plan in which some neighbour is conditioned on as latent y (cond.yz other than 'z').
+ * covType "matern_scaledim" (ncovparms = dim + 2) is accepted by this entry, gpv_plan_loglik_fisher and gpv_plan_loglik_rep for
+ * dim <= 3 and a smoothness in {0.5, 1.5, 2.5}: grad, fisher and row_terms are in the order variance, range_1 .. range_dim,
+ * smoothness (NaN, not differentiated), nugget.  dim > 3 is GPV_ERR_STATE: the kernels carry five parameter slots, which the
+ * variance, three ranges and the nugget fill.  Another smoothness is GPV_ERR_UNSUPPORTED_NU, from the _nu entries as well, which
+ * return for this family what the plain entries return.  The entry writes the plan's scaled copy of the locations itself. */
 int gpv_plan_loglik_grad(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
                          double *loglik, double *grad /* ncovparms + 1 */, int64_t *n_failed,
                          double *row_terms /* NULL, or Nlocs x (ncovparms + 2), row-major */);

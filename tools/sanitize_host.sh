@@ -114,6 +114,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_loglik_rep.log; then
     echo "== $tag: loglik_rep_driver FAILED (rc $rc)"; return 1
   fi
+  # ... and under the driver of the family with one range per coordinate (tests/sanitize/scaledim_driver.cpp)
+  mkdir -p $B/scaledim
+  $HIPCC $CF -c $ROOT/tests/sanitize/scaledim_driver.cpp -o $B/scaledim/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/scaledim/driver.o -o $B/scaledim_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./scaledim_driver ) 2>&1 | tee $B/run_scaledim.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_scaledim.log; then
+    echo "== $tag: scaledim_driver FAILED (rc $rc)"; return 1
+  fi
   # ... and under the driver of the ordered nearest-neighbour search (tests/sanitize/nn_driver.cpp)
   mkdir -p $B/nn
   $HIPCC $CF -c $ROOT/tests/sanitize/nn_driver.cpp -o $B/nn/driver.o
