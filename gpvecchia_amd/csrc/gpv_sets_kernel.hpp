@@ -924,6 +924,19 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
     }
     int prow = 0, pcb = 0;
     unsigned ppad = 1;                                       // lean: the next task's byte of task_pad (wave-uniform)
+    // lean: where a lane's entries of nn / cond lie inside a task's SPW * P entries, as byte offsets (a slot that owns no row
+    // reads entry 0 of the task), opaque like ctab below: the task part of the address is wave-uniform and stays on the SALU
+    unsigned ic_nn[RPL], ic_cd[RPL];
+    if constexpr (LEAN) {
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = i_const + q * LPS;
+            ic_cd[q] = (lane_on && r < P) ? (unsigned)(sub * P + r) : 0u;
+            ic_nn[q] = ic_cd[q] * 4u;
+            asm volatile("" : "+v"(ic_cd[q]));
+            asm volatile("" : "+v"(ic_nn[q]));
+        }
+    }
     auto load_ic = [&](const int64_t t) __attribute__((always_inline)) {
         // lean: rows * P < 2^31 (and a task index past the wavefront's last one stays far below 2^31 / SPW): 32-bit products
         using idx_t = std::conditional_t<LEAN, int, int64_t>;
@@ -936,6 +949,41 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
             const int tu = tu0 < (int)task_hi ? tu0 : 0;
             const uint32_t w = ((k_cu32 *)kargs_now()->task_pad)[tu >> 2];
             ppad = (w >> ((tu & 3) * 8)) & 0xffu;
+            // A task of this wavefront with all its sets inside `rows` (wave-uniform): SGPR base + the lane's constant offset, and
+            // no selects -- a slot without a row keeps what entry 0 holds, which only the padded gather reads (it masks there)
+            // Past the wavefront's last task (the request made during its last task) there is nothing to fetch: the general
+            // loads below would read entry 0 and, joined with the straight loads, are waited for on the spot -- a trip to memory
+            // in every wavefront's last task, which a launch of 12 tasks per wavefront (n = 1e5) feels
+            if (tu0 >= (int)task_hi) {
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    pidx[q] = -1;
+                    pcnd[q] = 1;
+                }
+                return;
+            }
+            if (tu0 * SPW + SPW <= (int)A.rows) {
+                typedef __attribute__((address_space(1))) const char gl_cc;
+                typedef __attribute__((address_space(1))) const int32_t gl_ci32s;
+                typedef __attribute__((address_space(1))) const uint8_t gl_cu8s;
+#if GPV_OPT_KARGS
+                gl_cc *const nb = (gl_cc *)kargs_now()->nn + (int64_t)(tu0 * (SPW * P)) * 4;
+                gl_cc *const cb = (gl_cc *)kargs_now()->cond + (int64_t)(tu0 * (SPW * P));
+#else
+                gl_cc *const nb = (gl_cc *)A.nn + (int64_t)(tu0 * (SPW * P)) * 4;
+                gl_cc *const cb = (gl_cc *)A.cond + (int64_t)(tu0 * (SPW * P));
+#endif
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    // (opaque again here, in place: else their 64-bit extensions are hoisted, twice the registers and a 64-bit add
+                    // per load instead of the SGPR-base form)
+                    asm volatile("" : "+v"(ic_nn[q]));
+                    asm volatile("" : "+v"(ic_cd[q]));
+                    pidx[q] = *(gl_ci32s *)(nb + ic_nn[q]);
+                    pcnd[q] = *(gl_cu8s *)(cb + ic_cd[q]);
+                }
+                return;
+            }
         }
 #if GPV_OPT_KARGS
         KSetArgs *const Kg = kargs_now();
@@ -1017,6 +1065,25 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
 #pragma unroll
         for (int q = 0; q < RPL; ++q) {                      // no branches: a missing neighbour reads record 0 and is masked
             const int at = pidx[q] >= 0 ? pidx[q] : 0;
+            if constexpr (LEAN && D <= 2) {
+                // Only the doubles the kernel reads.  A 16-byte load whose first half nothing reads leaves hipcc two dead
+                // registers with a load in flight: it hands them out as temporaries of the sweep and waits for the load to land
+                // first (s_waitcnt vmcnt right behind the request: the gather's trip to memory, exposed in every task).
+#if GPV_OPT_KARGS
+                gl_cd *const rd = (gl_cd *)recp + (int64_t)at * 4;
+#else
+                const double *const rd = reinterpret_cast<const double *>(recp) + (int64_t)at * 4;
+#endif
+                if constexpr (D == 2) {
+                    const auto ra = recp[(int64_t)at * 2];
+                    pr0[q].x = ra.x; pr0[q].y = ra.y;
+                } else {
+                    pr0[q].x = rd[0];
+                }
+                pr1[q].y = rd[3];
+                pnug[q] = (nugp != nullptr) ? nugp[at] : nugs;
+                continue;
+            }
             const auto ra = recp[(int64_t)at * 2], rb = recp[(int64_t)at * 2 + 1];
             pr0[q].x = ra.x; pr0[q].y = ra.y;
             pr1[q].x = rb.x; pr1[q].y = rb.y;
@@ -1047,6 +1114,46 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
             }
         }
     }
+    // Lean: the other LDS addresses of a task that depend on the lane's row and constants only, once per wavefront and
+    // opaque like ctab.  A slot that owns no row gets the address of a dump cell where the straight (unpadded) task path
+    // stores without a lane mask: the two spare cells behind the row slots of the set's data-row staging, which nothing reads.
+    // Only where a set has at most two such slots (P = 31: row 31): eleven lanes of a set (P = 21) storing to one address are
+    // an eleven-way bank conflict per store, which cost the short launches of m = 20 more than the masks had (kernel +3.4 %
+    // at n = 1e5, measured); there, and for three coordinates in their coordinate-major layout, which do not fit the two
+    // cells, a negative address marks such a slot and the store keeps one compare.
+    //   st_xy / st_xyx  staged coordinates of the slot's row and their copy behind row P - 1 (rows below P / 2)
+    //   st_xo           the row whose coordinates the slot's rounds use: its own, or row 0 (the shadow rows of the rounds)
+    //   st_dg / st_z    the row's diagonal cell of the triangle and its cell of the data row; row P - 1 has no cell of the
+    //                   data row (it is the point itself): that cell is cleared here, once, and every task leaves it at 0
+    //   st_row          what the slot reads as its matrix row: its row of the triangle, the data row, or zeros
+    constexpr bool DUMP = LEAN && G::SLOTS - P <= 2, XYDUMP = DUMP && D <= 2;
+    unsigned st_xy[RPL], st_xyx[RPL], st_xo[RPL], st_dg[RPL], st_z[RPL], st_row[RPL];
+    if constexpr (LEAN) {
+        static_assert(COLS >= G::SLOTS + 2 && ZROW && Lds::XYEXT, "lean: two dump cells behind the row slots, a data row, extended coordinate rows");
+        const unsigned xy0 = lds_addr(&L.xy[sub][0]), tr0 = lds_addr(&L.tri[sub][0]);
+        const unsigned zr0 = lds_addr(&L.col[Lds::NCOL - 1][sub][0]);
+        const unsigned dump = zr0 + 8u * G::SLOTS;                   // 16 bytes, 16-byte aligned
+        if (lane < SPW) L.col[Lds::NCOL - 1][lane][P - 1] = 0.0;
+#pragma unroll
+        for (int q = 0; q < RPL; ++q) {
+            const int r = i_const + q * LPS;
+            const bool own = lane_on && r < P;
+            const unsigned rc = own ? (unsigned)r : 0u;
+            const unsigned nowhere = XYDUMP ? dump : 0x80000000u;
+            st_xo[q] = xy0 + rc * (Lds::XS_ROW * 8);
+            st_xy[q] = own ? st_xo[q] : nowhere;
+            st_xyx[q] = (lane_on && r < P / 2) ? st_xo[q] + P * Lds::XS_ROW * 8 : nowhere;
+            st_dg[q] = own ? tr0 + (__umul24(rc, rc + 1) * 4 + rc * 8) : (DUMP ? dump : 0x80000000u);
+            st_z[q] = (own && r != P - 1) ? zr0 + rc * 8 : (DUMP ? dump : 0x80000000u);
+            st_row[q] = own ? tr0 + __umul24(rc, rc + 1) * 4 : ((lane_on && r == P) ? zr0 : lds_addr(&L.zero[0]));
+            asm volatile("" : "+v"(st_xo[q]));
+            asm volatile("" : "+v"(st_xy[q]));
+            asm volatile("" : "+v"(st_xyx[q]));
+            asm volatile("" : "+v"(st_dg[q]));
+            asm volatile("" : "+v"(st_z[q]));
+            asm volatile("" : "+v"(st_row[q]));
+        }
+    }
     int task_layer = 0;
     for (int64_t task = task_lo + vfirst, task_next; task < task_hi; task = task_next) {
         task_next = task + step_from(task_layer);
@@ -1055,6 +1162,8 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
         const bool set_on = lane_on && (LEAN ? ((int)task * SPW + sub < (int)A.rows) : (k < A.rows));
         // re-materialise the lane's row index per task: otherwise hipcc hoists all P (row == j) lane masks
         // out of the task loop (2P SGPRs -> SGPR spills through v_writelane/v_readlane inside the sweep)
+        // (lean: the copy stays -- without it the masks of the PADDED rounds are hoisted and spilled, 90 v_readlane / v_writelane;
+        // the unpadded task path takes the lane's addresses from the wavefront's tables instead and hardly reads it)
         int i = i_const;
         asm volatile("" : "+v"(i));
         const int row_out = prow;                             // this task's output row / block offset (the loads below replace them)
@@ -1067,12 +1176,53 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
         double xi[RPL][(D == 0) ? 1 : D];
         double nugraw[RPL], zi[RPL];
         unsigned long long vmask[RPL];
+        // lean, a task the plan knows to be unpadded (wave-uniform): every set is on and every row slot below P holds a
+        // neighbour, so the prefetched records go straight to their use and to the staging addresses of the wavefront
+        bool straight = false;
+        if constexpr (LEAN) {
+            straight = pad_now == 0u;
+            if (straight) {
+#pragma unroll
+                for (int q = 0; q < RPL; ++q) {
+                    row[q] = i + q * LPS;
+                    wslot[q] = row[q];
+                    idx[q] = pidx[q];
+                    cndraw[q] = pcnd[q];
+                    valid[q] = true;
+                    poison[q] = false;
+                    xi[q][0] = pr0[q].x;
+                    if constexpr (D >= 2) xi[q][1] = pr0[q].y;
+                    if constexpr (D >= 3) xi[q][2] = pr1[q].x;
+                    zi[q] = pr1[q].y;
+                    nugraw[q] = pnug[q];
+                    if constexpr (PRESCALE) {
+#pragma unroll
+                        for (int t = 0; t < D; ++t) xi[q][t] *= cA;
+                    }
+                    if (XYDUMP || (q + 1) * LPS <= P || (int)st_xy[q] >= 0) {
+                        lds_wdouble *const p = lds_wptr(st_xy[q]);
+#pragma unroll
+                        for (int t = 0; t < D; ++t) p[t * Lds::XS_DIM] = xi[q][t];
+                    }
+                    if (q * LPS < P / 2) {
+                        if (XYDUMP || (int)st_xyx[q] >= 0) {
+                            lds_wdouble *const p = lds_wptr(st_xyx[q]);
+#pragma unroll
+                            for (int t = 0; t < D; ++t) p[t * Lds::XS_DIM] = xi[q][t];
+                        }
+                    }
+                    vmask[q] = 0ull;
+                }
+            }
+        }
+        if (!straight) {
 #pragma unroll
         for (int q = 0; q < RPL; ++q) {
             row[q] = i + q * LPS;
             wslot[q] = lane_on ? row[q] : COLS - 1;          // idle lanes write to the dump slot: no branches in the sweep
-            idx[q] = pidx[q];
-            cndraw[q] = pcnd[q];
+            // (lean: a slot without a row may hold entry 0 of its task: load_ic)
+            idx[q] = (LEAN && !(lane_on && row[q] < P)) ? -1 : pidx[q];
+            cndraw[q] = (LEAN && !(lane_on && row[q] < P)) ? 1 : pcnd[q];
             valid[q] = idx[q] >= 0;
             poison[q] = false;                                // non-finite coordinate => NaN block => "Cholesky failed"
             nugraw[q] = 0.0;
@@ -1131,6 +1281,7 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
                 }
             }
             if (COV == COV_DENSE && lane_on && row[q] < P) L.ix[sub][row[q]] = idx[q];
+        }
         }
         // wave-uniform: does any set of this task have padding (missing neighbours / rows beyond the data)?
         int nvalid = 0;
@@ -1238,9 +1389,15 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
                 const bool own = lane_on && row[q] < P;
                 rq[q] = own ? row[q] : 0;                               // shadows row 0 of the set
 #pragma unroll
-                for (int t = 0; t < D; ++t) xq[q][t] = own ? xi[q][t] : L.xyat(sub, 0, t);
+                for (int t = 0; t < D; ++t) {
+                    // (lean: a slot whose rows all lie below P keeps its registers; the last one reads back what its row, or the
+                    // row it shadows, staged: the same bits without a select)
+                    if constexpr (LEAN) xq[q][t] = ((q + 1) * LPS <= P) ? xi[q][t] : lds_ptr(st_xo[q])[t * Lds::XS_DIM];
+                    else xq[q][t] = own ? xi[q][t] : L.xyat(sub, 0, t);
+                }
                 vq[q] = own ? valid[q] : (bool)((vmask[0] >> (sub * LPS)) & 1ull);
-                xoA[q] = xy0 + __umul24(rq[q], Lds::XS_ROW * 8);
+                if constexpr (LEAN) xoA[q] = st_xo[q];
+                else xoA[q] = xy0 + __umul24(rq[q], Lds::XS_ROW * 8);
                 xoB[q] = xoA[q] - P * Lds::XS_ROW * 8;                  // (used by the lanes with row + s >= P only)
                 rq8[q] = rq[q] * 8;
                 // slot of the pair (r, r+s), minus 8 s: r+s < P: tri + 8 (rt + r (s+1) + s(s+1)/2 - s), kept incrementally;
@@ -1392,6 +1549,16 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
         double a[RPL][P];
 #pragma unroll
         for (int q = 0; q < RPL; ++q) {
+            if constexpr (LEAN) {
+                if (straight) {                               // the same values; slots without a cell: the dump cell, or masked
+                    // (a slot whose rows all lie below P - 1 has both cells in every lane)
+                    if (DUMP || (q + 1) * LPS <= P - 1 || (int)st_dg[q] >= 0)
+                        *lds_wptr(st_dg[q]) = sig0 + nugraw[q] * (1.0 - (double)(cndraw[q] & 1));
+                    if (DUMP || (q + 1) * LPS <= P - 1 || (int)st_z[q] >= 0)
+                        *lds_wptr(st_z[q]) = ((cndraw[q] & 1) == 0) ? zi[q] : 0.0;
+                    continue;
+                }
+            }
             double diag;
             if constexpr (COV == COV_DENSE) diag = valid[q] ? A.covvals[(int64_t)idx[q] * A.nlocs + idx[q]] : 1.0;
             else diag = valid[q] ? (sig0 + nugraw[q] * (1.0 - (double)(cndraw[q] & 1))) : 1.0;   // src/U_NZentries.cpp:47,52
@@ -1413,6 +1580,14 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
         for (int q = 0; q < RPL; ++q) {
             // (r,c) lives at r(r+1)/2 + c for c <= r and at c(c+1)/2 + r above the diagonal: one select per column;
             // slot P reads the staged data row, slots beyond read zeros
+            if constexpr (LEAN) {                                 // the same cells from the wavefront's row address
+                lds_cdouble *const rowL = lds_ptr(st_row[q]);
+                static_for<0, P>([&](auto cc) __attribute__((always_inline)) {
+                    constexpr int c = decltype(cc)::value;
+                    if (c <= lik_maxcol<P>(q)) a[q][c] = rowL[c];
+                });
+                continue;
+            }
             const int r = row[q];
             const int rc = r < P ? r : 0;
             const double *extra = (ZROW && r == P) ? &L.col[Lds::NCOL - 1][sub][0] : &L.zero[0];
@@ -1456,7 +1631,7 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
         // which fails vlast > 0.  An integer OR instead of v_min_f64: hipcc puts a canonicalising v_max_f64 in front of every
         // minimum whose operand crosses a basic block (45 instructions for the 30 pivots).  One v_or_b32 per pivot, as inline
         // asm: from a plain `|=` hipcc keeps all 30 reciprocals alive to the end of the sweep and ORs both of their halves there.
-        int psign = 0;
+        int psign = 0, phold = 0;
         if constexpr (LIK) {
             // Lower-triangle LDL^T sweep (dpotf2's outer-product form) over pivots 0..P-2.  Row r keeps its cells c <= r; pivot j
             // takes the multiplier nw = -a_rj / p_j from its own register and updates a_rc += nw a_cj for j < c <= r, where a_cj is
@@ -1475,8 +1650,12 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
                 if constexpr (qj + 2 < RPL) d2 = a[qj + 2][j];
                 const double pj = dpp_row_bcast<j % 16>(a[qj][j], d1, d2);   // pivot = Schur complement d_j^2
                 const double rinv = rcp_pivot_bounded(pj);
-                if constexpr (LEAN) asm("v_or_b32 %0, %0, %1" : "+v"(psign) : "v"(__double2hiint(rinv)));
-                else pivot_lane_keep<j % 16>(prinv[qj], rinv);
+                if constexpr (LEAN) {
+                    // two pivots per instruction: an even pivot's high word waits for the next one (the last pivot alone if odd)
+                    if constexpr ((j & 1) == 0 && j + 1 < P - 1) phold = __double2hiint(rinv);
+                    else if constexpr ((j & 1) == 1) asm("v_or3_b32 %0, %0, %1, %2" : "+v"(psign) : "v"(phold), "v"(__double2hiint(rinv)));
+                    else asm("v_or_b32 %0, %0, %1" : "+v"(psign) : "v"(__double2hiint(rinv)));
+                } else pivot_lane_keep<j % 16>(prinv[qj], rinv);
                 double nw[RPL];
 #pragma unroll
                 for (int q = qj; q < RPL; ++q) nw[q] = a[q][j] * -rinv;   // (slot qj after its last column: dead, removed)
@@ -1689,7 +1868,9 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
             const bool okp = LEAN ? (psign >= 0 && vlast > 0.0) : ((row[q] == P - 1) ? (vlast > 0.0) : (prinv[q] > 0.0));
             bad = bad | (lane_on && row[q] < P && !okp);
         }
-        const bool fail = (__ballot(bad) & setmask) != 0ull;
+        // (lean: the verdict is uniform over the set's lanes as it stands -- broadcast pivots, broadcast vlast -- and every
+        // set has rows: no ballot)
+        const bool fail = LEAN ? !(psign >= 0 && vlast > 0.0) : ((__ballot(bad) & setmask) != 0ull);
         // (lean, flags == GPV_WANT_LOGLIK_Z: neither is read)
         const double rs = LEAN ? 0.0 : rsqrt_pos(vlast);   // M[n0-1] = d_k = 1/R[n0-1][n0-1]
         const double dlast = vlast * rs;               // R[n0-1][n0-1] = sqrt(v)
