@@ -44,6 +44,7 @@ EXPORTS = [
     "gpv_plan_loglik_grad", "gpv_plan_loglik_fisher",
     "gpv_plan_loglik_grad_nu", "gpv_plan_loglik_fisher_nu", "gpv_matern_derivs_host",
     "gpv_whiten_max_cols", "gpv_plan_whiten",
+    "gpv_unwhiten_narrow", "gpv_plan_unwhiten_levels", "gpv_plan_unwhiten", "gpv_plan_simulate",
     "gpv_plan_set_replicates", "gpv_plan_replicates", "gpv_plan_loglik_rep", "gpv_plan_loglik_rep_nu",
 ]
 
@@ -123,6 +124,11 @@ def lib():
     L.gpv_whiten_max_cols.restype = C.c_int
     L.gpv_whiten_max_cols.argtypes = []
     L.gpv_plan_whiten.argtypes = [vp, dp, i64, C.c_int, dp, i64, dp, dp, C.POINTER(C.c_int64)]
+    L.gpv_unwhiten_narrow.restype = C.c_int
+    L.gpv_unwhiten_narrow.argtypes = []
+    L.gpv_plan_unwhiten_levels.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gpv_plan_unwhiten.argtypes = [vp, dp, i64, C.c_int, dp, i64, C.POINTER(C.c_int64)]
+    L.gpv_plan_simulate.argtypes = [vp, C.c_uint64, i64, i64, dp, i64, C.POINTER(C.c_int64)]
     L.gpv_plan_set_replicates.argtypes = [vp, dp, i64, C.c_int]
     L.gpv_plan_replicates.argtypes = [vp, ip]
     L.gpv_plan_loglik_rep.argtypes = L.gpv_plan_loglik_fisher.argtypes

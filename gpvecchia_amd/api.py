@@ -300,6 +300,49 @@ class Plan:
         out = (G, float(ld.value), int(nf.value))
         return out + (E,) if want_E else out
 
+    def unwhiten(self, E_ord):
+        """The inverse of whiten: the colouring operator of the plan's latest evaluation (GPV_WANT_U) applied to the columns of
+        E_ord, (Nlocs, ncols) or (Nlocs,) in the plan's ORDERED row numbering, ncols <= 16 (gpv_plan_unwhiten).  Returns
+        (B_ord, n_failed), B_ord (Nlocs, ncols): whiten(B_ord) gives E_ord back, and standard normal columns become draws from
+        the Vecchia approximation of N(0, C + tau I).  With n_failed > 0 (blocks that were not positive definite) B_ord is all
+        NaN.  The plan's last evaluation (sums, Lentries, factor stamp) is left as it was."""
+        E = np.asarray(E_ord, dtype=np.float64)
+        if E.ndim == 1:
+            E = E[:, None]
+        if E.ndim != 2 or E.shape[0] != self.Nlocs:
+            raise ValueError("E_ord must have one row per ordered location of the plan")
+        ncols = int(E.shape[1])
+        if ncols < 1 or ncols > WHITEN_MAX_COLS:
+            raise ValueError(f"unwhiten takes 1 to {WHITEN_MAX_COLS} columns per call")
+        E = np.asfortranarray(E)
+        B = np.zeros((self.Nlocs, ncols), order="F")
+        nf = C.c_int64(0)
+        L.check(L.lib().gpv_plan_unwhiten(self._h, L.dptr(E), self.Nlocs, ncols, L.dptr(B), self.Nlocs, C.byref(nf)),
+                "gpv_plan_unwhiten")
+        return B, int(nf.value)
+
+    def unwhiten_levels(self):
+        """(n_levels, n_launches) of the level schedule unwhiten and simulate sweep through, built at first use
+        (gpv_plan_unwhiten_levels): the rows of a level depend on earlier levels only; a launch is one level wider than
+        gpv_unwhiten_narrow() rows or one maximal run of consecutive narrower ones."""
+        nl, nk = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().gpv_plan_unwhiten_levels(self._h, C.byref(nl), C.byref(nk)), "gpv_plan_unwhiten_levels")
+        return int(nl.value), int(nk.value)
+
+    def simulate(self, seed, ncols, col0=0):
+        """Draws col0 .. col0 + ncols - 1 from the Vecchia approximation of N(0, C + tau I) of the plan's latest evaluation
+        (GPV_WANT_U), in the ORDERED row numbering (gpv_plan_simulate): the colouring of the library's own normals, the
+        function of (seed, ordered location, draw) that draws_normals_host returns, made on the device.  Returns
+        (Z_ord (Nlocs, ncols), n_failed).  A draw's bits do not depend on col0, ncols or the other draws of the call."""
+        ncols, col0 = int(ncols), int(col0)
+        if ncols < 1 or col0 < 0:
+            raise ValueError("simulate needs ncols >= 1 and col0 >= 0")
+        Z = np.zeros((self.Nlocs, ncols), order="F")
+        nf = C.c_int64(0)
+        L.check(L.lib().gpv_plan_simulate(self._h, int(seed) & 0xFFFFFFFFFFFFFFFF, col0, ncols, L.dptr(Z), self.Nlocs, C.byref(nf)),
+                "gpv_plan_simulate")
+        return Z, int(nf.value)
+
     def lincomb(self, H_ord, cov_mat=False):
         """Var(H y | z) (or, with cov_mat, Cov) for the rows of H_ord, a scipy.sparse or dense matrix with Nlocs columns in
         the plan's ORDERED latent index, from the factor of the latest evaluation with GPV_WANT_DENOM / GPV_WANT_MEAN /
@@ -1302,6 +1345,47 @@ def vecchia_whiten(B, vecchia_approx, covparms, nuggets, covmodel="matern", devi
         _, logdet, _, Ec = plan.whiten(Bord[:, c0:c0 + WHITEN_MAX_COLS], want_E=True)
         E[:, c0:c0 + WHITEN_MAX_COLS] = Ec
     return E, logdet
+
+
+def vecchia_unwhiten(E, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+    """The mirror of vecchia_whiten: colours the columns of E (n x c, or a vector), given in the ORDERED row numbering of the
+    approximation (as vecchia_whiten returns them), with the Vecchia factor at these parameters: one evaluation (GPV_WANT_U),
+    then ceil(c / 16) Plan.unwhiten calls.  Returns B (n x c) in the CALLER's order of the locations, so that
+    vecchia_whiten(B, ...)[0] is E; standard normal columns become draws from the approximation of N(0, C + tau I).  All NaN
+    when some block was not positive definite at these parameters."""
+    va = vecchia_approx
+    E = _user_columns("vecchia_unwhiten", E, va)
+    plan = _whiten_plan("vecchia_unwhiten", va, covparms, nuggets, covmodel, device)
+    Bord = np.empty(E.shape)
+    for c0 in range(0, E.shape[1], WHITEN_MAX_COLS):
+        Bord[:, c0:c0 + WHITEN_MAX_COLS], _ = plan.unwhiten(E[:, c0:c0 + WHITEN_MAX_COLS])
+    B = np.empty(E.shape)
+    B[va["ord_z"] - 1] = Bord
+    return B
+
+
+def vecchia_simulate(vecchia_approx, covparms, nuggets, covmodel="matern", nsim=1, seed=0, mean=None, device=0):
+    """nsim draws from the Vecchia approximation of N(mean, C + tau I) at these parameters, an (n, nsim) array in the CALLER's
+    order of the locations: one evaluation (GPV_WANT_U), then Plan.simulate, which colours normals made on the device (draw j is
+    the colouring of draws_normals_host(seed, 0, n, j, 1), reproducible per seed and independent of nsim).  nuggets: one value
+    or one per location (caller's order); mean: None, a scalar or one value per location (caller's order), added on the host.
+    All NaN when some block was not positive definite at these parameters."""
+    va = vecchia_approx
+    n = va["locsord"].shape[0]
+    if int(nsim) != nsim or int(nsim) < 1:
+        raise ValueError("vecchia_simulate: nsim must be an integer >= 1")
+    mu = None
+    if mean is not None:
+        mu = np.asarray(mean, dtype=np.float64)
+        if mu.ndim > 1 or (mu.ndim == 1 and mu.size != n):
+            raise ValueError("vecchia_simulate: mean must be a scalar or one value per location")
+    plan = _whiten_plan("vecchia_simulate", va, covparms, nuggets, covmodel, device)
+    Zord, _ = plan.simulate(seed, int(nsim))
+    Z = np.empty(Zord.shape)
+    Z[va["ord_z"] - 1] = Zord
+    if mu is not None:
+        Z += mu if mu.ndim == 0 else mu[:, None]
+    return Z
 
 
 def profile_from_gram(G, logdet, n):

@@ -11,6 +11,8 @@
 #include "gpv_grad.h"
 #define GPV_WHITEN_LINKAGE __attribute__((weak))
 #include "gpv_whiten.h"
+#define GPV_UNWHITEN_LINKAGE __attribute__((weak))
+#include "gpv_unwhiten.h"
 #include "gpv_hip_raii.hpp"
 
 #include <dlfcn.h>
@@ -440,6 +442,20 @@ struct gpv_plan {
     // both passes and the totals
     DevBuf<double> d_wh_in, d_wh_B, d_wh_E, d_wh_wpart, d_wh_gpart, d_wh_tot;
     int wh_cp_cap = 0, wh_cp_last = 0, wh_wgrid = 0, wh_ggrid = 0;
+    // gpv_plan_unwhiten / gpv_plan_simulate (gpv_unwhiten.hip).  The level schedule is built from d_nn / d_rowid at first use
+    // (unwhiten_schedule) and never changes: the stored sets level by level (d_uw_order), where the levels start in that list
+    // (uw_levptr, d_uw_levptr) and the launches of one sweep.  The column buffers are allocated on first use and grown with the
+    // padded column count: the caller's columns as they arrive / B on its way back [cp][Nlocs], E by ordered row [Nlocs][cp],
+    // B by internal position [Nlocs][cp]; d_uw_nfail: the sweep's counter of failed rows.
+    struct UwLaunch { int lev0, lev1; bool narrow; };    // levels lev0 .. lev1 - 1: one run of narrow levels, or one wide level
+    bool uw_sched = false, uw_holes = false;
+    std::vector<int32_t> uw_levptr;
+    std::vector<UwLaunch> uw_launches;
+    DevBuf<int32_t> d_uw_order, d_uw_levptr;
+    DevBuf<double> d_uw_in, d_uw_E, d_uw_B;
+    DevBuf<unsigned> d_uw_nfail;
+    int uw_cp_cap = 0, uw_cp_last = 0;
+    int64_t uw_graph_eval[5] = {0, 0, 0, 0, 0};      // the evaluation whose addresses and nugget uw_graph[log2 cp] holds
     // d_L and the nuggets on the device (d_nuggets / nug_scalar) belong to evaluation L_of_eval of the plan (evaluations are
     // counted from 1; 0: to none).  Set at the end of an evaluation that materialised U, cleared before anything of the two is
     // rewritten: an evaluation that starts, a Vecchia-Laplace step that writes its pseudo-nuggets, a rebuilt posterior structure.
@@ -464,11 +480,13 @@ struct gpv_plan {
     PostGraph pgraph[8];                             // index = want_mean + 2 * (nuggets are a vector) + 4 * (mean from B: 'zy')
     GraphExec lc_graph;                              // gpv_plan_lincomb's sweep (levels, top block, column sums)
     GraphExec st_graph;                              // the transposed sweep (top block, levels)
+    GraphExec uw_graph[5];                           // the colouring sweep at cp = 1, 2, 4, 8, 16 (see uw_graph_eval)
     void drop_graphs()                               // they hold addresses and a schedule that are about to change
     {
         for (auto &g : pgraph) g.exec.reset();
         lc_graph.reset();
         st_graph.reset();
+        for (auto &g : uw_graph) g.reset();
     }
 };
 
@@ -2391,6 +2409,254 @@ extern "C" int gpv_plan_debug_whiten_ms(gpv_plan *pl, int reps, double *ms)
     for (int r = 0; r < reps && rc == GPV_OK; ++r) {
         float t = 0.f;
         if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(whiten_enqueue(pl, pl->wh_cp_last, st)) ||
+            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
+            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
+            rc = GPV_ERR_HIP;
+        ms[r] = (double)t;
+    }
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// ---- the colouring operator, the inverse of the whitening operator: simulation from the Vecchia model (gpv_unwhiten.hip) ----
+int gpv_unwhiten_narrow(void) { return kUnwhitenNarrow; }
+
+// gpv_unwhiten.hip is part of this link (see GPV_UNWHITEN_LINKAGE in gpv_unwhiten.h)
+static bool unwhiten_linked()
+{
+    return &launch_unwhiten_pack != nullptr && &launch_unwhiten_unpack != nullptr && &launch_unwhiten_normals != nullptr &&
+           &launch_unwhiten_wide != nullptr && &launch_unwhiten_narrow != nullptr;
+}
+
+// what the plan's structure must be for the schedule to mean anything / what gpv_plan_whiten asks of the latest evaluation
+static int unwhiten_structure(const gpv_plan *pl)
+{
+    if (!unwhiten_linked()) return GPV_ERR_STATE;
+    if (pl->rows != pl->Nlocs || pl->Nlocs < 1 || pl->latent_nb || !pl->d_nn || !pl->d_rowid) return GPV_ERR_STATE;
+    return GPV_OK;
+}
+static int unwhiten_state(const gpv_plan *pl)
+{
+    if (const int rc = unwhiten_structure(pl)) return rc;
+    if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L) return GPV_ERR_STATE;
+    if (pl->comm || pl->d_obs) return GPV_ERR_STATE;
+    return GPV_OK;
+}
+
+// The level schedule from the plan's own index arrays, read back once: level(k) = 0 for a row without neighbours, else
+// 1 + max_j level(j), taken in the ordered row sequence (every neighbour precedes its row); the stored sets sorted by level,
+// ascending (the plan's Morton order) inside a level; maximal runs of consecutive narrow levels become one launch each.
+static int unwhiten_schedule(gpv_plan *pl)
+{
+    if (pl->uw_sched) return GPV_OK;
+    const int64_t rows = pl->rows, n = pl->Nlocs;
+    const int P = pl->P;
+    std::vector<int32_t> nn((size_t)rows * P), rowid((size_t)rows);
+    GPV_HIP(hipMemcpy(nn.data(), pl->d_nn, nn.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(rowid.data(), pl->d_rowid, rowid.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    // lev_pos: level of the row that wrote a position last (-1: none yet); touch: highest level of a row that has read or
+    // written it.  In a plan whose rows end in distinct points that their neighbours' rows precede, touch of a row's own point
+    // is still -1 when the row comes, and the level is the definition's.  Rows that share their last entry (the ordered
+    // nearest-neighbour search can name a coincident earlier point as a row's last entry) are kept in the ordered row
+    // sequence: such a row goes to a later level than every row that has read or written the point before it.
+    std::vector<int32_t> set_of_row((size_t)rows, -1), lev_pos((size_t)n, -1), touch((size_t)n, -1), lev_set((size_t)rows, 0);
+    for (int64_t s = 0; s < rows; ++s) {
+        if (rowid[(size_t)s] < 0 || rowid[(size_t)s] >= rows) return GPV_ERR_STATE;
+        set_of_row[(size_t)rowid[(size_t)s]] = (int32_t)s;
+    }
+    int32_t top = 0;
+    for (int64_t k = 0; k < rows; ++k) {
+        const int32_t s = set_of_row[(size_t)k];
+        if (s < 0) return GPV_ERR_STATE;
+        const int32_t *nr = &nn[(size_t)s * P];
+        const int32_t own = nr[P - 1];
+        if (own >= n) return GPV_ERR_STATE;
+        int32_t lv = own >= 0 ? touch[(size_t)own] + 1 : 0;
+        for (int q = 0; q < P - 1; ++q) {
+            if (nr[q] < 0) continue;
+            if (nr[q] >= n) return GPV_ERR_STATE;
+            const int32_t l = lev_pos[(size_t)nr[q]] + 1;          // (a position no earlier row owns counts as level -1)
+            lv = l > lv ? l : lv;
+        }
+        for (int q = 0; q < P - 1; ++q)
+            if (nr[q] >= 0 && touch[(size_t)nr[q]] < lv) touch[(size_t)nr[q]] = lv;
+        lev_set[(size_t)s] = lv;
+        if (own >= 0) lev_pos[(size_t)own] = touch[(size_t)own] = lv;
+        top = lv > top ? lv : top;
+    }
+    pl->uw_holes = false;                                          // positions that no row owns: kept at zero (unwhiten_sweep)
+    for (int64_t i = 0; i < n; ++i) pl->uw_holes = pl->uw_holes || lev_pos[(size_t)i] < 0;
+    const int nlev = top + 1;
+    std::vector<int32_t> levptr((size_t)nlev + 1, 0), order((size_t)rows);
+    for (int64_t s = 0; s < rows; ++s) levptr[(size_t)lev_set[(size_t)s] + 1]++;
+    for (int l = 0; l < nlev; ++l) levptr[(size_t)l + 1] += levptr[(size_t)l];
+    {
+        std::vector<int32_t> fill(levptr.begin(), levptr.end() - 1);
+        for (int64_t s = 0; s < rows; ++s) order[(size_t)fill[(size_t)lev_set[(size_t)s]]++] = (int32_t)s;
+    }
+    std::vector<gpv_plan::UwLaunch> launches;
+    for (int l = 0; l < nlev; ++l) {
+        const bool narrow = levptr[(size_t)l + 1] - levptr[(size_t)l] <= kUnwhitenNarrow;
+        if (narrow && !launches.empty() && launches.back().narrow) launches.back().lev1 = l + 1;
+        else launches.push_back(gpv_plan::UwLaunch{l, l + 1, narrow});
+    }
+    GPV_BUF(pl->d_uw_order, upload(order.data(), order.size()));
+    GPV_BUF(pl->d_uw_levptr, upload(levptr.data(), levptr.size()));
+    GPV_BUF(pl->d_uw_nfail, resize(2));
+    pl->uw_levptr.swap(levptr);
+    pl->uw_launches.swap(launches);
+    pl->uw_sched = true;
+    return GPV_OK;
+}
+
+int gpv_plan_unwhiten_levels(gpv_plan *pl, int64_t *n_levels, int64_t *n_launches)
+{
+    if (!pl || !n_levels || !n_launches) return GPV_ERR_BAD_ARG;
+    if (const int rc = unwhiten_structure(pl)) return rc;
+    GPV_HIP(hipSetDevice(pl->device));
+    if (const int rc = unwhiten_schedule(pl)) return rc;
+    *n_levels = (int64_t)pl->uw_levptr.size() - 1;
+    *n_launches = (int64_t)pl->uw_launches.size();
+    return GPV_OK;
+}
+
+// the sweep on what is resident: d_uw_E -> d_uw_B, level by level
+static hipError_t unwhiten_enqueue(gpv_plan *pl, int cp, hipStream_t st)
+{
+    UnwhitenArgs a;
+    a.L = pl->d_L; a.nn = pl->d_nn; a.rowid = pl->d_rowid;
+    a.nuggets = pl->nug_is_scalar ? nullptr : pl->d_nuggets.get();
+    a.nug_scalar = pl->nug_scalar;
+    a.E = pl->d_uw_E; a.B = pl->d_uw_B; a.order = pl->d_uw_order; a.levptr = pl->d_uw_levptr; a.nfail = pl->d_uw_nfail;
+    a.P = pl->P;
+    for (const gpv_plan::UwLaunch &u : pl->uw_launches) {
+        const hipError_t e = u.narrow ? launch_unwhiten_narrow(a, cp, u.lev0, u.lev1, st)
+                                      : launch_unwhiten_wide(a, cp, pl->uw_levptr[(size_t)u.lev0], pl->uw_levptr[(size_t)u.lev1], st);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
+// the counter cleared, then the sweep: replayed from one captured linear graph per padded column count, captured again when
+// another evaluation has left its factor (the launches carry d_L, the nuggets' address and the constant nugget by value)
+static hipError_t unwhiten_sweep(gpv_plan *pl, int cp, hipStream_t st)
+{
+    int gi = 0;
+    while ((1 << gi) < cp) ++gi;
+    hipError_t e = hipMemsetAsync(pl->d_uw_nfail, 0, sizeof(unsigned), st);
+    if (e != hipSuccess) return e;
+    if (pl->uw_holes) {                                // some position belongs to no row: what a row reads there is zero, every call
+        e = hipMemsetAsync(pl->d_uw_B, 0, sizeof(double) * (size_t)pl->Nlocs * cp, st);
+        if (e != hipSuccess) return e;
+    }
+    const bool stale = pl->uw_graph_eval[gi] != pl->eval_count;
+    pl->uw_graph_eval[gi] = pl->eval_count;
+    return graph_replay(pl->uw_graph[gi], st, [&] { return unwhiten_enqueue(pl, cp, st); }, stale);
+}
+
+// device, schedule and the column buffers at the padded column count cp
+static int unwhiten_prepare(gpv_plan *pl, int cp)
+{
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream && pl->last_stream != pl->stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));   // the evaluation's stream
+    if (const int rc = unwhiten_schedule(pl)) return rc;
+    if (cp > pl->uw_cp_cap) {
+        const size_t cnt = (size_t)pl->Nlocs * cp;
+        pl->uw_cp_cap = 0;
+        for (auto &g : pl->uw_graph) g.reset();                   // they hold the buffers' addresses
+        GPV_BUF(pl->d_uw_in, resize(cnt));
+        GPV_BUF(pl->d_uw_E, resize(cnt));
+        GPV_BUF(pl->d_uw_B, resize(cnt));
+        pl->uw_cp_cap = cp;
+    }
+    return GPV_OK;
+}
+
+// Reads d_L, the index arrays and the nuggets of the plan's latest evaluation and writes buffers of its own, so the sums, the U
+// entries, the posterior state, the factor stamp and what gpv_plan_whiten left on the device stay what they were.
+int gpv_plan_unwhiten(gpv_plan *pl, const double *E_ord, int64_t lde, int ncols, double *B_ord, int64_t ldb, int64_t *n_failed)
+{
+    if (!pl || !E_ord || !B_ord || !n_failed) return GPV_ERR_BAD_ARG;
+    if (ncols < 1 || ncols > kUnwhitenMaxCols) return GPV_ERR_BAD_ARG;
+    const int64_t n = pl->Nlocs;
+    if (lde < n || ldb < n) return GPV_ERR_BAD_ARG;
+    if (const int rc = unwhiten_state(pl)) return rc;
+    const int cp = whiten_cp(ncols);
+    if (const int rc = unwhiten_prepare(pl, cp)) return rc;
+    hipStream_t st = pl->stream;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    for (int j = 0; j < ncols; ++j)
+        if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_uw_in + (size_t)j * n, E_ord + (int64_t)j * lde, sizeof(double) * (size_t)n,
+                                          hipMemcpyHostToDevice, st)))
+            return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_unwhiten_pack(pl->d_uw_in, n, ncols, cp, pl->d_uw_E, st))) return fail(GPV_ERR_HIP);
+    pl->uw_cp_last = cp;
+    if (GPV_HIP_FAILED(unwhiten_sweep(pl, cp, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_unwhiten_unpack(pl->d_uw_B, pl->d_newpos, n, ncols, cp, pl->d_uw_in, st))) return fail(GPV_ERR_HIP);
+    unsigned nf = 0;
+    if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_uw_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+    for (int j = 0; j < ncols; ++j)                                               // (B_ord may be E_ord: the columns were read before)
+        if (GPV_HIP_FAILED(hipMemcpyAsync(B_ord + (int64_t)j * ldb, pl->d_uw_in + (size_t)j * n, sizeof(double) * (size_t)n,
+                                          hipMemcpyDeviceToHost, st)))
+            return fail(GPV_ERR_HIP);
+    GPV_HIP(hipStreamSynchronize(st));
+    *n_failed = (int64_t)nf;
+    if (nf > 0)                                                                   // the recursion hands a failed row's NaN on: no entry is trusted
+        for (int j = 0; j < ncols; ++j) std::fill_n(B_ord + (int64_t)j * ldb, (size_t)n, (double)NAN);
+    return GPV_OK;
+}
+
+// Draw j is always made in the batch of the 16 draws [16 floor(j / 16), + 16) at the padded column count 16, whatever col0 and
+// ncols are: a column's bits depend on (seed, j) and the evaluation alone.
+int gpv_plan_simulate(gpv_plan *pl, uint64_t seed, int64_t col0, int64_t ncols, double *Z_ord, int64_t ldz, int64_t *n_failed)
+{
+    constexpr int NB = kUnwhitenMaxCols;
+    if (!pl || !Z_ord || !n_failed || col0 < 0 || ncols < 1) return GPV_ERR_BAD_ARG;
+    const int64_t n = pl->Nlocs;
+    if (ldz < n || col0 > INT64_MAX - ncols) return GPV_ERR_BAD_ARG;
+    if (const int rc = unwhiten_state(pl)) return rc;
+    if (const int rc = unwhiten_prepare(pl, NB)) return rc;
+    hipStream_t st = pl->stream;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    const int64_t end = col0 + ncols;
+    unsigned nf = 0;
+    pl->uw_cp_last = NB;
+    for (int64_t b = col0 / NB; b * NB < end; ++b) {
+        const int64_t base = b * NB;
+        if (GPV_HIP_FAILED(launch_unwhiten_normals(pl->d_uw_E, n, seed, base, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(unwhiten_sweep(pl, NB, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_unwhiten_unpack(pl->d_uw_B, pl->d_newpos, n, NB, NB, pl->d_uw_in, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_uw_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+        for (int64_t j = std::max(base, col0); j < std::min(base + NB, end); ++j)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(Z_ord + (j - col0) * ldz, pl->d_uw_in + (size_t)(j - base) * n, sizeof(double) * (size_t)n,
+                                              hipMemcpyDeviceToHost, st)))
+                return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+    }
+    *n_failed = (int64_t)nf;
+    if (nf > 0)
+        for (int64_t j = 0; j < ncols; ++j) std::fill_n(Z_ord + j * ldz, (size_t)n, (double)NAN);
+    return GPV_OK;
+}
+
+// developer aid (tools/unwhiten_timing.py; not part of the public header): device time of `reps` sweeps over the columns the
+// latest gpv_plan_unwhiten / gpv_plan_simulate left on the device, by a pair of events around the sweep alone: no copies, no
+// packing
+extern "C" int gpv_plan_debug_unwhiten_ms(gpv_plan *pl, int reps, double *ms)
+{
+    if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
+    if (const int rc = unwhiten_state(pl)) return rc;
+    if (pl->uw_cp_last == 0 || !pl->uw_sched) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    Event a, b;
+    GPV_HIP(hipEventCreate(a.put()));
+    GPV_HIP(hipEventCreate(b.put()));
+    int rc = GPV_OK;
+    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
+        float t = 0.f;
+        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(unwhiten_sweep(pl, pl->uw_cp_last, st)) ||
             GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
             GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
             rc = GPV_ERR_HIP;

@@ -417,6 +417,36 @@ int gpv_plan_whiten(gpv_plan *plan, const double *B_ord, int64_t ldb, int ncols,
                     double *gram /* ncols x ncols row-major, exactly symmetric */,
                     double *logdet, int64_t *n_failed);
 
+/* The colouring operator of the plan's latest evaluation: the exact inverse of the whitening operator above, and with it
+ * simulation from the Vecchia model.  A column e colours to
+ *   b_k = sqrt(tau_k + 1/d_k^2) e_k - (sum_{j in J_k} L_kj b_j) / d_k,      k = 0, 1, .., Nlocs - 1 in the ORDERED row sequence
+ * (every j in J_k precedes k), so that gpv_plan_whiten of b returns e, and for e ~ N(0, I) the column b is a draw from the
+ * Vecchia approximation of N(0, C + tau I) that the evaluation describes: the density whose log the cond.yz='z' likelihood is.
+ * Reads the factor in HBM (GPV_WANT_U), the index arrays and the nuggets of THAT evaluation (a constant or a vector); nothing is
+ * factorised again, every family an evaluation accepts is covered.  The rows are solved level by level (level(k) = 0 for a row
+ * without neighbours, else 1 + max_j level(j)); the schedule is built from the plan's index arrays at first use.  A level of
+ * more than gpv_unwhiten_narrow() rows is one kernel launch, a maximal run of consecutive narrower levels is one launch of one
+ * workgroup.  Bitwise reproducible from call to call, with or without GPV_NO_GRAPH=1.
+ *   gpv_plan_unwhiten_levels  builds the schedule if it is absent; out: the number of levels and of launches per sweep (the runs
+ *             of narrow levels plus the wide levels).  GPV_ERR_STATE for a row shard or a plan with latent conditioning.
+ *   gpv_plan_unwhiten   E_ord: 1 <= ncols <= gpv_whiten_max_cols() columns of length Nlocs, column-major with leading dimension
+ *             lde >= Nlocs, in the ORDERED row numbering; B_ord (leading dimension ldb >= Nlocs) may be E_ord.  n_failed: rows
+ *             whose block was not positive definite in that evaluation; with n_failed > 0 every entry of B_ord is NaN.
+ *   gpv_plan_simulate   colours the library's own normals: the normal of (ordered location k, draw j) is the function of
+ *             (seed, k, j) of gpv_draws_normals_host, made on the device.  Z_ord: the draws col0 .. col0 + ncols - 1, any
+ *             ncols >= 1, Nlocs x ncols with leading dimension ldz.  Draw j is always computed in the batch of the 16 draws
+ *             [16 floor(j / 16), + 16): a column is bitwise independent of col0, of ncols and of its neighbours in the call.
+ * Blocking, on the plan's own stream; buffers are allocated on first use and belong to the plan.  The plan's last evaluation
+ * and what a following gpv_plan_whiten returns stay as they were (sums, Lentries, posterior state, factor stamp).  Arguments
+ * and state are validated before the device is touched, with the statuses of gpv_plan_whiten: GPV_ERR_BAD_ARG for a null
+ * pointer, a column count out of range or a leading dimension < Nlocs; GPV_ERR_STATE where gpv_plan_whiten returns it. */
+int gpv_unwhiten_narrow(void);         /* 256 */
+int gpv_plan_unwhiten_levels(gpv_plan *plan, int64_t *n_levels, int64_t *n_launches);
+int gpv_plan_unwhiten(gpv_plan *plan, const double *E_ord, int64_t lde, int ncols, double *B_ord, int64_t ldb,
+                      int64_t *n_failed);
+int gpv_plan_simulate(gpv_plan *plan, uint64_t seed, int64_t col0, int64_t ncols, double *Z_ord, int64_t ldz,
+                      int64_t *n_failed);
+
 /* Vecchia-Laplace Newton-Raphson with the state on the device: calculate_posterior_VL of R/vecchia_laplace_NR.R:31-155
  * for fully observed data.  model: position in the reference's family list (:32): 0 gaussian, 1 logistic, 2 poisson,
  * 3 gamma, 4 beta, 5 gamma_alt.  likparms = {alpha, sigma} (:33), for beta {alpha, sigma, beta}.
