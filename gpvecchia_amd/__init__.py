@@ -12,7 +12,7 @@ from .api import (Comm, EsqeFun, MaternFun, MultiPlan, Plan, ReplicaPlans, U2V, 
 from .laplace import (calculate_posterior_VL, vecchia_laplace_likelihood,  # noqa: F401,E402
                       vecchia_laplace_likelihood_from_posterior, vecchia_laplace_prediction, vecchia_prediction)
 
-from .lincomb import draws_normals_host, vecchia_lincomb, vecchia_posterior_sample, vecchia_posterior_summary  # noqa: F401,E402
+from .lincomb import draws_normals_host, vecchia_lincomb, vecchia_posterior_sample, vecchia_posterior_summary, vecchia_selinv  # noqa: F401,E402
 
 from .wrappers import vecchia_estimate, vecchia_pred  # noqa: F401,E402
 

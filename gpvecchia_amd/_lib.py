@@ -39,7 +39,7 @@ EXPORTS = [
     "gpv_mplan_create_replicas", "gpv_mplan_count", "gpv_mplan_set_data_one", "gpv_mplan_build_posterior",
     "gpv_mplan_eval_each", "gpv_mplan_vl_begin_one", "gpv_mplan_vl_step_each", "gpv_mplan_vl_get_one",
     "gpv_plan_set_observed", "gpv_rccl_version", "gpv_comm_unique_id", "gpv_comm_create", "gpv_comm_destroy", "gpv_plan_set_comm",
-    "gpv_plan_lincomb", "gpv_lincomb_batch", "gpv_plan_factor_stamp", "gpv_plan_solve_t",
+    "gpv_plan_lincomb", "gpv_lincomb_batch", "gpv_plan_factor_stamp", "gpv_plan_solve_t", "gpv_plan_selinv",
     "gpv_draws_normals_host", "gpv_plan_draws_normals", "gpv_plan_draws_summary",
     "gpv_plan_loglik_grad", "gpv_plan_loglik_fisher",
     "gpv_plan_loglik_grad_nu", "gpv_plan_loglik_fisher_nu", "gpv_matern_derivs_host",
@@ -113,6 +113,7 @@ def lib():
     L.gpv_draws_normals_host.argtypes = [C.c_uint64, i64, i64, i64, i64, dp, i64]
     L.gpv_plan_draws_normals.argtypes = [vp, C.c_uint64, i64, i64, i64, dp, i64]
     L.gpv_plan_draws_summary.argtypes = [vp, i64, C.c_uint64, i64, dp, C.c_int, C.c_int, dp, C.POINTER(C.c_uint8), dp, dp, dp, dp, dp]
+    L.gpv_plan_selinv.argtypes = [vp, i64, dp, C.POINTER(C.c_int64)]
     L.gpv_lincomb_batch.restype = C.c_int
     L.gpv_lincomb_batch.argtypes = []
     L.gpv_plan_factor_stamp.argtypes = [vp, C.POINTER(C.c_int64)]

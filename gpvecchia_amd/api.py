@@ -364,6 +364,17 @@ class Plan:
         L.check(st, "gpv_plan_lincomb")
         return cov if cov_mat else vars_[:nrows]
 
+    def selinv(self, skip_front=0):
+        """Every posterior variance of the plan in one pass: the diagonal of the selected inverse of the factor lincomb reads
+        (gpv_plan_selinv: the Takahashi recursion on the factor's own pattern, level scheduled, on the device).  Returns
+        (vars_ord (Nlocs,), ordered layout, zeros in the first skip_front rows; n_dropped): n_dropped == 0 means vars_ord is
+        diag(W^-1) exactly, otherwise n_dropped terms lie outside the pattern and the result is the reference's
+        var.exact = FALSE approximation."""
+        out = np.zeros(self.Nlocs)
+        nd = C.c_int64(0)
+        L.check(L.lib().gpv_plan_selinv(self._h, int(skip_front), L.dptr(out), C.byref(nd)), "gpv_plan_selinv")
+        return out, int(nd.value)
+
     def solve_t(self, E_ord):
         """R^T x = e for every row e of E_ord, (ncols, Nlocs) or (Nlocs,) float64 in the plan's ORDERED latent layout, with
         the factor lincomb reads (gpv_plan_solve_t: batched, level scheduled, on the device).  For e ~ N(0, I) the rows of the

@@ -13,6 +13,8 @@
 #include "gpv_whiten.h"
 #define GPV_UNWHITEN_LINKAGE __attribute__((weak))
 #include "gpv_unwhiten.h"
+#define GPV_SELINV_LINKAGE __attribute__((weak))
+#include "gpv_selinv.h"
 #include "gpv_hip_raii.hpp"
 
 #include <dlfcn.h>
@@ -404,6 +406,15 @@ struct gpv_plan {
     bool lc_ready = false;
     DevBuf<double> d_lc_X, d_lc_part, d_lc_vars, d_lc_gpart, d_lc_gram;
     DevBuf<double> d_st_E;                           // gpv_plan_solve_t: one batch of dense columns, [kLincombNB][Nlocs]
+    // gpv_plan_selinv (gpv_selinv.hip), built and allocated on first use after gpv_plan_build_posterior: the column records in
+    // the order of the pass (top block, then the ascending schedule), the pair records by entry of crow, Sigma on the pattern
+    // of C, its diagonal by column and as the caller gets it; the tile of every level's kernel; the dropped terms of the pattern
+    DevBuf<int4> d_sel_rec;
+    DevBuf<int2> d_sel_pair;
+    DevBuf<double> d_sel_S, d_sel_vars, d_sel_out;
+    std::vector<int> sel_lev_tile;
+    int64_t sel_dropped = 0;
+    bool sel_ready = false;
     // gpv_plan_draws_summary: mu, S1, S2, mean, var [Nlocs] each, exceed [8][Nlocs], the accumulation's block partials; counts
     // [8][Nlocs]; mask [Nlocs]; draw_max, draw_mean [ds_draw_cap] each.  Allocated on first use.
     DevBuf<double> d_ds, d_ds_draw;
@@ -480,12 +491,14 @@ struct gpv_plan {
     PostGraph pgraph[8];                             // index = want_mean + 2 * (nuggets are a vector) + 4 * (mean from B: 'zy')
     GraphExec lc_graph;                              // gpv_plan_lincomb's sweep (levels, top block, column sums)
     GraphExec st_graph;                              // the transposed sweep (top block, levels)
+    GraphExec sel_graph;                             // the selected inverse (top block, levels)
     GraphExec uw_graph[5];                           // the colouring sweep at cp = 1, 2, 4, 8, 16 (see uw_graph_eval)
     void drop_graphs()                               // they hold addresses and a schedule that are about to change
     {
         for (auto &g : pgraph) g.exec.reset();
         lc_graph.reset();
         st_graph.reset();
+        sel_graph.reset();
         for (auto &g : uw_graph) g.reset();
     }
 };
@@ -1339,6 +1352,7 @@ static int build_posterior_impl(gpv_plan *pl, const int *revNN, const int *revCo
     pl->have_post = false;
     pl->have_factor = false;
     pl->lc_ready = false;
+    pl->sel_ready = false;
     if (pl->last_stream) { GPV_HIP(hipSetDevice(pl->device)); GPV_HIP(hipStreamSynchronize(pl->last_stream)); }
     pl->drop_graphs();
     if (pl->row_begin != 0 || pl->row_end != pl->Nlocs) return GPV_ERR_BAD_ARG;   // not shardable
@@ -2859,6 +2873,176 @@ extern "C" int gpv_plan_debug_solve_t_ms(gpv_plan *pl, int reps, double *ms)
         float t = 0.f;
         if (GPV_HIP_FAILED(launch_solvet_pack(pl->d_lc_X, pl->d_st_E, pl->Nlocs, pl->Nlocs, kLincombNB, st)) ||
             GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(solvet_sweep(pl, st)) || GPV_HIP_FAILED(hipEventRecord(b, st)) ||
+            GPV_HIP_FAILED(hipStreamSynchronize(st)) || GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
+            rc = GPV_ERR_HIP;
+        ms[r] = (double)t;
+    }
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// ---- the selected inverse of the factor: every posterior variance in one pass (gpv_selinv.hip) -------------------------------
+// gpv_selinv.hip is part of this link (see GPV_SELINV_LINKAGE in gpv_selinv.h)
+static bool selinv_linked()
+{
+    return &selinv_tile != nullptr && &launch_selinv_top != nullptr && &launch_selinv_level != nullptr && &launch_selinv_out != nullptr;
+}
+
+// what gpv_plan_lincomb and gpv_plan_solve_t ask of the plan
+static int selinv_state(const gpv_plan *pl)
+{
+    if (!selinv_linked()) return GPV_ERR_STATE;
+    if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
+    if (pl->post_ld > 64 || !pl->d_meanrec) return GPV_ERR_STATE;
+    return GPV_OK;
+}
+
+// The records of the pass from the plan's structure as it lives on the device (built on the first gpv_plan_selinv after a
+// gpv_plan_build_posterior, like lincomb_prepare): the row lists are rebuilt as build_posterior_impl lays them out, which gives
+// every entry of a column the row-list position of its pair and with it the pair's match records; the terms the pattern
+// drops are counted here, once: they depend on the structure alone.
+static int selinv_prepare(gpv_plan *pl)
+{
+    const int64_t n = pl->Nlocs;
+    const size_t nnz = (size_t)pl->post_nnz, K = (size_t)pl->top_K;
+    if (nnz < (size_t)n || K > (size_t)kSelinvTopMax || K > (size_t)n) return GPV_ERR_STATE;
+    std::vector<int32_t> colptr((size_t)n + 1), crow(nnz), cboff((size_t)n);
+    std::vector<int2> topinfo(K);
+    std::vector<int4> rowrec(nnz), rec((size_t)n);
+    GPV_HIP(hipMemcpy(colptr.data(), pl->d_colptr, colptr.size() * 4, hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(crow.data(), pl->d_crow, nnz * 4, hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(cboff.data(), pl->d_cboff, cboff.size() * 4, hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(rowrec.data(), pl->d_rowrec, nnz * sizeof(int4), hipMemcpyDeviceToHost));
+    if (K > 0) GPV_HIP(hipMemcpy(topinfo.data(), pl->d_topinfo, K * sizeof(int2), hipMemcpyDeviceToHost));
+    if ((size_t)n > K) GPV_HIP(hipMemcpy(rec.data() + K, pl->d_meanrec, ((size_t)n - K) * sizeof(int4), hipMemcpyDeviceToHost));
+    if (colptr[0] != 0 || (size_t)colptr[(size_t)n] != nnz) return GPV_ERR_STATE;
+    int64_t c_entries = 0;
+    for (int64_t c = 0; c < n; ++c) {
+        const int32_t cn = colptr[(size_t)c + 1] - colptr[(size_t)c];
+        if (cn < 1 || cn > 64 || cboff[(size_t)c] < 0 || crow[(size_t)colptr[(size_t)c + 1] - 1] != (int32_t)c) return GPV_ERR_STATE;
+        c_entries = std::max<int64_t>(c_entries, (int64_t)cboff[(size_t)c] + cn + 1);
+    }
+    for (size_t j = 0; j < K; ++j) {                          // the top block: ascending, before the schedule
+        const int32_t k = topinfo[j].x;
+        if (k < 0 || k >= n || (j > 0 && k <= topinfo[j - 1].x)) return GPV_ERR_STATE;
+        rec[j] = make_int4(k, cboff[(size_t)k], colptr[(size_t)k + 1] - colptr[(size_t)k], colptr[(size_t)k]);
+    }
+    for (size_t i = K; i < (size_t)n; ++i) {                  // (the schedule's records name the same columns' own numbers)
+        const int4 r = rec[i];
+        if (r.x < 0 || r.x >= n || r.y != cboff[(size_t)r.x] || r.w != colptr[(size_t)r.x] ||
+            r.z != colptr[(size_t)r.x + 1] - colptr[(size_t)r.x])
+            return GPV_ERR_STATE;
+    }
+    std::vector<int32_t> fill((size_t)n + 1, 0);
+    for (size_t e = 0; e < nnz; ++e) {
+        if (crow[e] < 0 || crow[e] >= n) return GPV_ERR_STATE;
+        fill[(size_t)crow[e] + 1]++;
+    }
+    for (int64_t i = 0; i < n; ++i) fill[(size_t)i + 1] += fill[(size_t)i];
+    std::vector<int2> pair(nnz);
+    int64_t tp_size = 0;
+    for (int64_t c = 0; c < n; ++c) {
+        const int32_t b0 = colptr[(size_t)c], cn = colptr[(size_t)c + 1] - b0;
+        for (int32_t e = 0; e < cn; ++e) {
+            const int32_t i = crow[(size_t)(b0 + e)];
+            const int4 rr = rowrec[(size_t)fill[(size_t)i]++];                       // the pair (row i, column c)
+            if (rr.x != cboff[(size_t)c] || (rr.z & 0xFF) != e || rr.y < 0) return GPV_ERR_STATE;
+            pair[(size_t)(b0 + e)] = make_int2(cboff[(size_t)i], e + 1 < cn ? rr.y : 0);
+            if (e + 1 < cn) tp_size = std::max<int64_t>(tp_size, (int64_t)rr.y + e + 1);
+        }
+    }
+    // the match records: a position must lie inside the column it names (the kernels index Sigma with it); 0xFF = a dropped term
+    std::vector<uint8_t> tp((size_t)tp_size);
+    if (tp_size > 0) GPV_HIP(hipMemcpy(tp.data(), pl->d_tp, (size_t)tp_size, hipMemcpyDeviceToHost));
+    int64_t dropped = 0;
+    for (int64_t c = 0; c < n; ++c) {
+        const int32_t b0 = colptr[(size_t)c], cn = colptr[(size_t)c + 1] - b0;
+        for (int32_t ek = 0; ek + 1 < cn; ++ek) {
+            const int32_t i = crow[(size_t)(b0 + ek)], in = colptr[(size_t)i + 1] - colptr[(size_t)i];
+            const uint8_t *t = tp.data() + pair[(size_t)(b0 + ek)].y;
+            for (int32_t e = 0; e <= ek; ++e) {
+                if (t[e] == 0xFF) ++dropped;
+                else if ((int32_t)t[e] >= in) return GPV_ERR_STATE;
+            }
+            if ((int32_t)t[ek] != in - 1) return GPV_ERR_STATE;                      // (row i of column i: its diagonal, last)
+        }
+    }
+    const size_t nlev = pl->levptr2.size() > 0 ? pl->levptr2.size() - 1 : 0;
+    if (nlev > 0 && (size_t)pl->levptr2[nlev] != (size_t)n - K) return GPV_ERR_STATE;
+    pl->sel_lev_tile.assign(nlev, 16);
+    for (size_t lv = 0; lv < nlev; ++lv) {
+        int mx = 1;
+        for (int32_t i = pl->levptr2[lv]; i < pl->levptr2[lv + 1]; ++i) mx = std::max(mx, rec[K + (size_t)i].z);
+        pl->sel_lev_tile[lv] = selinv_tile(mx);
+    }
+    pl->sel_graph.reset();
+    GPV_BUF(pl->d_sel_rec, upload(rec.data(), rec.size()));
+    GPV_BUF(pl->d_sel_pair, upload(pair.data(), pair.size()));
+    GPV_BUF(pl->d_sel_S, resize((size_t)c_entries));
+    GPV_BUF(pl->d_sel_vars, resize((size_t)n));
+    GPV_BUF(pl->d_sel_out, resize((size_t)n));
+    GPV_HIP(hipMemset(pl->d_sel_S, 0, sizeof(double) * (size_t)c_entries));
+    pl->sel_dropped = dropped;
+    pl->sel_ready = true;
+    return GPV_OK;
+}
+
+// the pass: the dense top block, then the mean sweep's levels in ascending order, one launch each
+static hipError_t selinv_enqueue(gpv_plan *pl, hipStream_t st)
+{
+    SelinvArgs a;
+    a.rec = pl->d_sel_rec; a.pair = pl->d_sel_pair; a.tp = pl->d_tp; a.C = pl->d_C; a.S = pl->d_sel_S; a.vars = pl->d_sel_vars;
+    hipError_t e = launch_selinv_top(a, pl->top_K, pl->d_toprows, st);
+    for (size_t lv = 0; e == hipSuccess && lv < pl->sel_lev_tile.size(); ++lv)
+        e = launch_selinv_level(a, pl->top_K + pl->levptr2[lv], pl->levptr2[lv + 1] - pl->levptr2[lv], pl->sel_lev_tile[lv], st);
+    return e;
+}
+// ... as the plan's captured graph
+static hipError_t selinv_sweep(gpv_plan *pl, hipStream_t st)
+{
+    return graph_replay(pl->sel_graph, st, [&] { return selinv_enqueue(pl, st); });
+}
+
+// Reads C and the structure and writes buffers of its own: the factor, its stamp and every later result of the plan stay what
+// they were.
+int gpv_plan_selinv(gpv_plan *pl, int64_t skip_front, double *vars_ord, int64_t *n_dropped)
+{
+    if (!pl || !vars_ord || !n_dropped) return GPV_ERR_BAD_ARG;
+    if (skip_front < 0 || skip_front >= pl->Nlocs) return GPV_ERR_BAD_ARG;
+    if (const int rc = selinv_state(pl)) return rc;
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (!pl->sel_ready)
+        if (const int rc = selinv_prepare(pl)) return rc;
+    hipStream_t st = pl->stream;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    if (GPV_HIP_FAILED(selinv_sweep(pl, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_selinv_out(pl->d_sel_vars, pl->Nlocs, skip_front, pl->d_sel_out, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(vars_ord, pl->d_sel_out, sizeof(double) * (size_t)pl->Nlocs, hipMemcpyDeviceToHost, st)))
+        return fail(GPV_ERR_HIP);
+    GPV_HIP(hipStreamSynchronize(st));
+    *n_dropped = pl->sel_dropped;
+    pl->last_stream = st;
+    return GPV_OK;
+}
+
+// developer aid (tools/selinv_timing.py; not part of the public header): device time of `reps` passes on the factor the latest
+// gpv_plan_selinv read, by a pair of events around the pass alone: no copies
+extern "C" int gpv_plan_debug_selinv_ms(gpv_plan *pl, int reps, double *ms)
+{
+    if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
+    if (const int rc = selinv_state(pl)) return rc;
+    if (!pl->sel_ready) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    Event a, b;
+    GPV_HIP(hipEventCreate(a.put()));
+    GPV_HIP(hipEventCreate(b.put()));
+    int rc = GPV_OK;
+    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
+        float t = 0.f;
+        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(selinv_sweep(pl, st)) || GPV_HIP_FAILED(hipEventRecord(b, st)) ||
             GPV_HIP_FAILED(hipStreamSynchronize(st)) || GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
             rc = GPV_ERR_HIP;
         ms[r] = (double)t;

@@ -77,12 +77,13 @@ def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
     'meanmat' (also `factor`, the opaque handle vecchia_lincomb takes: on the device routes the plan and a stamp of this
     evaluation, on the host route (U_obj, lu)) or 'all' (both).
 
-    Variances are EXACT for the factor in use: diag(W^-1) through unit-vector rows of vecchia_lincomb (the reference's
-    var.exact = TRUE path, :223-244), zeros for zero-nugget observations (:210-212).  var_exact=None stands for the
-    reference's rule sum(!obs) < 4e4 (:46) and var_exact=False for its SelInv approximation; there is no selected inverse
-    here, so the same exact values are computed either way.  For an exact fill-closed factor (SGV, the obs-pred branch, the
-    filled 'y' structure) that IS the diagonal SelInv returns; for 'zy' and ic0 it differs from the reference's
-    var.exact = FALSE approximation."""
+    var_exact=None (the default) and True: variances EXACT for the factor in use, diag(W^-1) through unit-vector rows of
+    vecchia_lincomb (the reference's var.exact = TRUE path, :223-244), zeros for zero-nugget observations (:210-212): one
+    triangular solve per location.  var_exact=False: on the device routes the reference's SelInv branch (:193-221), ONE pass of
+    the selected inverse of the factor on its own pattern (gpv_plan_selinv); the result then carries `var_dropped`, the number
+    of terms of the recursion that lie outside the pattern and count as zero.  var_dropped == 0 (fully observed SGV / 'z' plans,
+    the filled 'y' structure): the same exact values; var_dropped > 0 (prediction plans whose sets are no cliques, 'zy'): the
+    reference's var.exact = FALSE approximation, and a warning says so.  The host route computes the exact values either way."""
     from . import lincomb as LC
     if return_values not in _RETURN_VALUES:
         raise ValueError(f"return_values must be one of {_RETURN_VALUES}")
@@ -97,7 +98,13 @@ def vecchia_prediction(z, vecchia_approx, covparms, nuggets, covmodel="matern", 
         if want_mat:
             out["factor"] = LC._device_factor(plan, ord_, obs, offset)
         if want_var:
-            var_ord = LC.exact_variances_device(plan, len(ord_), offset)
+            if var_exact is False:
+                var_ord, out["var_dropped"] = LC.selected_variances_device(plan, len(ord_), offset)
+                if out["var_dropped"] > 0:
+                    warnings.warn(f"var_exact=False: {out['var_dropped']} terms of the selected inverse lie outside the factor's "
+                                  "pattern; the variances are the reference's var.exact = FALSE approximation, not diag(W^-1)")
+            else:
+                var_ord = LC.exact_variances_device(plan, len(ord_), offset)
             out["var_obs"], out["var_pred"] = A.split_mean(var_ord, dict(ord=ord_, obs=obs))
         return out
 
@@ -183,7 +190,8 @@ def vecchia_laplace_prediction(vl_posterior, vecchia_approx, covparms, pred_mean
                                return_values="mean", var_exact=None):
     """R/vecchia_laplace_NR.R:523-551: vecchia_prediction with the pseudo-data and pseudo-nuggets of a calculate_posterior_VL
     result, on a vecchia.approx that may carry prediction locations; the latent means and their images under the family's
-    link function.  return_values / var_exact pass through to vecchia_prediction (the default 'mean': means only).  With
+    link function.  return_values / var_exact pass through to vecchia_prediction (the default 'mean': means only; var_exact=False:
+    the variances from one pass of the selected inverse, with `var_dropped` in the result).  With
     'meanvar' / 'all' also the data-scale 5% / 95% quantiles of :541-548; with 'meanmat' / 'all' the `factor` handle, so that
     vecchia_posterior_sample draws the latent field of a Vecchia-Laplace posterior (data_link of a draw: the data scale), and
     vecchia_posterior_summary(preds, nsim, link='exp' | 'logistic') gives Monte-Carlo moments on the data scale for the

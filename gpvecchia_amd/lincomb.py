@@ -100,6 +100,37 @@ def exact_variances_device(plan, nlat, offset=0):
     return out
 
 
+def selected_variances_device(plan, nlat, offset=0):
+    """The variances of the ordered latent variables [offset, offset + nlat) of the plan from ONE pass of the selected inverse
+    (gpv_plan_selinv, R/vecchia_prediction.R:193-221): (vars, n_dropped).  n_dropped == 0: what exact_variances_device
+    returns; otherwise the reference's var.exact = FALSE approximation."""
+    v, dropped = plan.selinv(skip_front=offset)
+    return v[offset:offset + nlat], dropped
+
+
+def vecchia_selinv(preds):
+    """Posterior variances at every observed and prediction location from one pass of the selected inverse of the posterior
+    factor (the SelInv branch of vecchia_var, R/vecchia_prediction.R:193-221).  preds: the result of vecchia_prediction(...,
+    return_values='meanmat' | 'all') on a device route, as for vecchia_lincomb.  Returns dict(var_obs, var_pred, n_dropped),
+    locations in the caller's order.  n_dropped == 0 (fully observed 'SGV' and 'z' plans, the filled 'y' structure): the exact
+    variances; n_dropped > 0: that many terms lie outside the factor's pattern and count as zero, the reference's
+    var.exact = FALSE approximation."""
+    fac = preds.get("factor") if isinstance(preds, dict) else None
+    if fac is None:
+        raise ValueError("vecchia_selinv needs the result of vecchia_prediction(..., return_values='meanmat' or 'all')")
+    if fac["kind"] != "device":
+        raise ValueError("vecchia_selinv: this prediction was made on the host route, which has no selected inverse; "
+                         "its var_obs / var_pred are exact")
+    plan = _check_stamp(fac)
+    nlat, off = int(fac["ord"].size), fac["offset"]
+    if off + nlat != plan.Nlocs:
+        raise ValueError("preds does not match the plan of this prediction")
+    var_ord, dropped = selected_variances_device(plan, nlat, off)
+    from .api import split_mean
+    var_obs, var_pred = split_mean(var_ord, dict(ord=fac["ord"], obs=fac["obs"]))
+    return dict(var_obs=var_obs, var_pred=var_pred, n_dropped=dropped)
+
+
 def exact_variances_host(lu, nlat):
     """diag(W^-1) in ordered layout from the host factor of the reversed matrix."""
     out = np.empty(nlat)

@@ -272,6 +272,20 @@ int gpv_plan_draws_summary(gpv_plan *plan, int64_t ndraws, uint64_t seed, int64_
                            int nthr, const double *thr, const uint8_t *mask, double *mean, double *var, double *exceed,
                            double *draw_max, double *draw_mean);
 int gpv_lincomb_batch(void);   /* right-hand sides per sweep (32) */
+/* The selected inverse of the factor: Sigma = W^-1 on the pattern of R (W = R R^T; for GPV_WANT_MEAN_B, R = B) by the Takahashi
+ * recursion, the SelInv branch of vecchia_var (R/vecchia_prediction.R:193-221), in ONE level-scheduled pass over the structure
+ * and the factor of the latest evaluation (the schedule of gpv_plan_solve_t): vars_ord[k] = Sigma_kk, every posterior variance
+ * of the plan, length Nlocs in the ORDERED latent layout; zeros in the rows k < skip_front (the n dummy rows of cond.yz = 'zy').
+ * With column c of R holding the rows N(c) and itself:
+ *   Sigma_ic = -(1 / R_cc) sum_{k in N(c)} Sigma_ik R_kc  (i in N(c)),   Sigma_cc = 1 / R_cc^2 - (1 / R_cc) sum_k Sigma_ck R_kc.
+ * A term Sigma_ik with i < k both rows of a column c, but i no row of column k, is outside the pattern and counts as 0 (the
+ * zero-fill rule of the factor pass).  *n_dropped: the number of such (i, k, c), a property of the structure alone.  0 (fully
+ * observed SGV plans, 'z' plans, the filled 'y' structure): vars_ord is diag(W^-1) exactly, what unit rows of gpv_plan_lincomb
+ * give.  Otherwise (prediction plans whose sets are no cliques, 'zy') it is the reference's var.exact = FALSE approximation.
+ * The factor is only read: gpv_plan_factor_stamp and every later result of the plan stay what they were.  Blocking.  Results are
+ * bitwise reproducible from call to call.  GPV_ERR_BAD_ARG: a null pointer, skip_front outside [0, Nlocs); GPV_ERR_STATE: as for
+ * gpv_plan_lincomb.  Arguments are validated before the device is touched. */
+int gpv_plan_selinv(gpv_plan *plan, int64_t skip_front, double *vars_ord, int64_t *n_dropped);
 /* stamp: 0 when the plan holds no factor, else a number that changes with every evaluation that writes one (callers that keep
  * a result of gpv_plan_lincomb's inputs around can tell whether the factor is still the one they mean) */
 int gpv_plan_factor_stamp(gpv_plan *plan, int64_t *stamp);
