@@ -46,5 +46,17 @@ vecchia_mean_hip <- function(z, vecchia.approx, covparms, nuggets, covmodel = "m
   mu.ord[order(vecchia.approx$ord)]                                        # R/vecchia_prediction.R:135-136
 }
 
+# value and analytic gradient of vecchia_likelihood() at the default conditioning (cond.yz = 'SGV'; 'z' plans are accepted when
+# built with a posterior structure): list(loglik, grad) with grad = d / d covparms, then d / d nugget (NA for the smoothness of
+# 'matern', which must be 0.5, 1.5 or 2.5).  One constant nugget, complete data.  For optim(method = "L-BFGS-B") over log-parameters.
+vecchia_likelihood_grad_sgv_hip <- function(z, vecchia.approx, covparms, nuggets, covmodel = "matern", plan = gpv_plan(vecchia.approx)) {
+  if (!is.character(covmodel) || !(covmodel %in% c("matern", "esqe"))) stop("vecchia_likelihood_grad_sgv_hip: covmodel must be 'matern' or 'esqe'")
+  if (!(vecchia.approx$cond.yz %in% c("SGV", "SGVT"))) stop("vecchia_likelihood_grad_sgv_hip: cond.yz = 'SGV' plans")
+  if (length(nuggets) != 1L || anyNA(z)) stop("vecchia_likelihood_grad_sgv_hip: one constant nugget and complete data")
+  .Call("gpvR_plan_set_data", PACKAGE = "gpvR_plan", plan$handle, as.double(z[vecchia.approx$ord.z]))
+  g <- .Call("gpvR_plan_loglik_grad_sgv", PACKAGE = "gpvR_plan", plan$handle, covmodel, as.double(covparms), as.double(nuggets))
+  list(loglik = if (attr(g, "n_failed") > 0) -Inf else attr(g, "loglik"), grad = as.vector(g))
+}
+
 print.gpv_plan <- function(x, ...) cat("<gpv_plan: ", x$Nlocs, " locations, m = ", x$p - 1L, ", cond.yz = '", x$cond.yz,
                                        "', ", x$levels, " posterior levels>\n", sep = "")

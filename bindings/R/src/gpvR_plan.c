@@ -182,6 +182,29 @@ SEXP gpvR_plan_Lentries(SEXP xp, SEXP p_r)
     return L;
 }
 
+/* Value and analytic gradient of the log-likelihood of a cond.yz = 'SGV' plan (gpv_plan_loglik_grad_sgv; the plan needs
+ * gpvR_plan_build_posterior).  nugget: one constant.  Returns the gradient, length(covparms) + 1 (d / d covparms, then
+ * d / d nugget; NA for the smoothness of "matern"); attr "loglik" = the value, attr "n_failed" = the rows that failed.  The call
+ * evaluates the plan: afterwards gpvR_plan_posterior_mean returns the mean at these parameters. */
+SEXP gpvR_plan_loglik_grad_sgv(SEXP xp, SEXP covType, SEXP covparms, SEXP nugget)
+{
+    gpv_plan *pl = gpvR_get(xp);
+    if (!Rf_isReal(covparms) || !Rf_isReal(nugget) || XLENGTH(nugget) != 1) Rf_error("covparms must be double, nugget one double");
+    if (TYPEOF(covType) != STRSXP || LENGTH(covType) < 1) Rf_error("covType must be a character string");
+    const int np = LENGTH(covparms);
+    SEXP grad = PROTECT(Rf_allocVector(REALSXP, np + 1));
+    double ll = NA_REAL;
+    int64_t nf = 0;
+    gpvR_fail(gpv_plan_loglik_grad_sgv(pl, CHAR(STRING_ELT(covType, 0)), REAL(covparms), np, REAL(nugget)[0], &ll, REAL(grad), &nf,
+                                       NULL), "gpv_plan_loglik_grad_sgv");
+    for (int t = 0; t <= np; ++t)
+        if (REAL(grad)[t] != REAL(grad)[t]) REAL(grad)[t] = NA_REAL;    /* NaN: not differentiated, or a failed call */
+    Rf_setAttrib(grad, Rf_install("loglik"), Rf_ScalarReal(ll));
+    Rf_setAttrib(grad, Rf_install("n_failed"), Rf_ScalarReal((double)nf));
+    UNPROTECT(1);
+    return grad;
+}
+
 static const R_CallMethodDef gpvR_calls[] = {
     {"gpvR_device_count", (DL_FUNC)&gpvR_device_count, 0},
     {"gpvR_last_error", (DL_FUNC)&gpvR_last_error, 0},
@@ -192,6 +215,7 @@ static const R_CallMethodDef gpvR_calls[] = {
     {"gpvR_plan_eval", (DL_FUNC)&gpvR_plan_eval, 6},
     {"gpvR_plan_posterior_mean", (DL_FUNC)&gpvR_plan_posterior_mean, 2},
     {"gpvR_plan_Lentries", (DL_FUNC)&gpvR_plan_Lentries, 2},
+    {"gpvR_plan_loglik_grad_sgv", (DL_FUNC)&gpvR_plan_loglik_grad_sgv, 4},
     {NULL, NULL, 0}
 };
 

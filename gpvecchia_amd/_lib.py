@@ -41,7 +41,7 @@ EXPORTS = [
     "gpv_plan_set_observed", "gpv_rccl_version", "gpv_comm_unique_id", "gpv_comm_create", "gpv_comm_destroy", "gpv_plan_set_comm",
     "gpv_plan_lincomb", "gpv_lincomb_batch", "gpv_plan_factor_stamp", "gpv_plan_solve_t", "gpv_plan_selinv",
     "gpv_draws_normals_host", "gpv_plan_draws_normals", "gpv_plan_draws_summary",
-    "gpv_plan_loglik_grad", "gpv_plan_loglik_fisher",
+    "gpv_plan_loglik_grad", "gpv_plan_loglik_fisher", "gpv_plan_loglik_grad_sgv",
     "gpv_plan_loglik_grad_nu", "gpv_plan_loglik_fisher_nu", "gpv_matern_derivs_host",
     "gpv_whiten_max_cols", "gpv_plan_whiten",
     "gpv_unwhiten_narrow", "gpv_plan_unwhiten_levels", "gpv_plan_unwhiten", "gpv_plan_simulate",
@@ -120,6 +120,7 @@ def lib():
     L.gpv_plan_loglik_grad.argtypes = [vp, C.c_char_p, dp, C.c_int, C.c_double, dp, dp, C.POINTER(C.c_int64), dp]
     L.gpv_plan_loglik_fisher.argtypes = [vp, C.c_char_p, dp, C.c_int, C.c_double, dp, dp, dp, C.POINTER(C.c_int64), dp]
     L.gpv_plan_loglik_grad_nu.argtypes = L.gpv_plan_loglik_grad.argtypes
+    L.gpv_plan_loglik_grad_sgv.argtypes = L.gpv_plan_loglik_grad.argtypes
     L.gpv_plan_loglik_fisher_nu.argtypes = L.gpv_plan_loglik_fisher.argtypes
     L.gpv_matern_derivs_host.argtypes = [C.c_double, C.c_double, dp, i64, dp]
     L.gpv_whiten_max_cols.restype = C.c_int

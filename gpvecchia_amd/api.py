@@ -202,6 +202,23 @@ class Plan:
         out = (float(ll.value), grad, int(nf.value))
         return out + (rt,) if row_terms else out
 
+    def loglik_grad_sgv(self, covmodel, covparms, nugget, col_terms=False):
+        """Value and analytic gradient of the log-likelihood of a plan with latent conditioning (cond.yz='SGV';
+        gpv_plan_loglik_grad_sgv): returns (loglik, grad, n_failed) and, with col_terms, a fourth array (Nlocs, len(covparms) + 1)
+        whose rows (ordered numbering) sum to grad.  grad = d/d covparms, then d/d nugget; the smoothness entry of 'matern' is NaN.
+        Needs the posterior structure (build_posterior / ensure_posterior).  Unlike loglik_grad this call EVALUATES the plan:
+        afterwards sums(), posterior_mean() and factor_stamp() are those of eval(..., GPV_WANT_MEAN) at these parameters."""
+        cp = np.ascontiguousarray(covparms, dtype=np.float64)
+        ll, nf = C.c_double(0.0), C.c_int64(0)
+        grad = np.zeros(cp.size + 1)
+        ct = np.zeros((self.Nlocs, cp.size + 1)) if col_terms else None
+        st = L.lib().gpv_plan_loglik_grad_sgv(self._h, covmodel.encode() if isinstance(covmodel, str) else bytes(covmodel),
+                                              L.dptr(cp), int(cp.size), float(nugget), C.byref(ll), L.dptr(grad), C.byref(nf),
+                                              L.dptr(ct) if col_terms else None)
+        L.check(st, "gpv_plan_loglik_grad_sgv")
+        out = (float(ll.value), grad, int(nf.value))
+        return out + (ct,) if col_terms else out
+
     def loglik_fisher(self, covmodel, covparms, nugget, row_terms=False, smoothness_grad=False):
         """Value, analytic gradient and expected Fisher information of the cond.yz='z' log-likelihood of the plan's data
         (gpv_plan_loglik_fisher): returns (loglik, grad, info, n_failed) and, with row_terms, a fifth array
@@ -1254,6 +1271,41 @@ def vecchia_likelihood_grad(z, vecchia_approx, covparms, nuggets, covmodel="mate
     _scaledim_checked("vecchia_likelihood_grad", vecchia_approx, covparms, covmodel)
     plan, nug = _grad_plan("vecchia_likelihood_grad", z, vecchia_approx, nuggets, covmodel, device)
     ll, grad, _ = plan.loglik_grad(covmodel, covparms, nug, smoothness_grad=smoothness_grad)
+    return ll, grad
+
+
+def _sgv_grad_checked(name, z, va, nuggets, covmodel):
+    """The refusals of vecchia_likelihood_grad_sgv that need no device; returns (z, nugget)."""
+    if va["cond_yz"] not in ("SGV", "z", "false"):
+        raise ValueError(f"{name} needs cond_yz='SGV' (or 'z'), not {va['cond_yz']!r}")
+    if not isinstance(covmodel, str) or covmodel not in ("matern", "esqe"):
+        raise ValueError(f"{name} needs a named covariance family ('matern' or 'esqe')")
+    nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
+    if nug.size != 1:
+        raise ValueError(f"{name} takes one constant nugget")
+    z = np.asarray(z, dtype=np.float64)
+    if np.isnan(z.sum()):
+        raise ValueError(f"{name} needs complete data (no NaN)")
+    if int(np.sum(va["obs"])) != va["locsord"].shape[0]:
+        raise ValueError(f"{name} does not take plans with prediction locations")
+    return z, float(nug[0])
+
+
+def vecchia_likelihood_grad_sgv(z, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+    """(loglik, grad) of the Vecchia log-likelihood at the default conditioning cond.yz='SGV', on the GPU (Plan.loglik_grad_sgv):
+    one evaluation with the posterior mean, the selected inverse of its factor and one pass over the conditioning sets.
+    grad = d loglik / d covparms, then d / d nugget; for 'matern' the smoothness (0.5, 1.5 or 2.5) is not differentiated and its
+    entry is NaN.  Accepts cond_yz 'SGV' (and 'z' / 'false', where it agrees with vecchia_likelihood_grad), one constant nugget
+    > 0, complete data, no prediction locations, 'matern' or 'esqe'; ValueError otherwise, and when the device posterior
+    structure is refused for the plan (a conditioning set with more than 64 latent entries)."""
+    va = vecchia_approx
+    z, nug = _sgv_grad_checked("vecchia_likelihood_grad_sgv", z, va, nuggets, covmodel)
+    plan = _plan_for(va, device)
+    if not plan.ensure_posterior():
+        raise ValueError("vecchia_likelihood_grad_sgv: the device posterior structure is refused for this plan "
+                         "(a conditioning set has more than 64 latent entries)")
+    plan.set_user_data(z, va["ord_z"])
+    ll, grad, _ = plan.loglik_grad_sgv(covmodel, covparms, nug)
     return ll, grad
 
 

@@ -102,7 +102,7 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
                  kern + H("gpv_plist.h"), force))
     work.append((os.path.join(CSRC, "gpv_api.hip"), os.path.join(BUILD, "api.o"), list(extra_flags),
                  internal + [pub] + H("gpv_laplace.h", "gpv_generic.h", "gpv_posterior_ext.h", "gpv_philox.hpp", "gpv_grad.h",
-                                      "gpv_whiten.h", "gpv_unwhiten.h", "gpv_selinv.h", "gpv_hip_raii.hpp"), force))
+                                      "gpv_whiten.h", "gpv_unwhiten.h", "gpv_selinv.h", "gpv_grad_sgv.h", "gpv_hip_raii.hpp"), force))
     work.append((os.path.join(CSRC, "gpv_posterior.hip"), os.path.join(BUILD, "posterior.o"), list(extra_flags),
                  internal + H("gpv_posterior_ext.h"), force))
     work.append((os.path.join(CSRC, "gpv_lincomb.hip"), os.path.join(BUILD, "lincomb.o"), list(extra_flags),
@@ -115,6 +115,11 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
         work.append((grad, os.path.join(BUILD, f"grad_pb{pb}.o"), [f"-DGPV_GRAD_PB={pb}"] + extra_flags,
                      internal + H("gpv_grad.h", "gpv_grad_set_pass.inc", "gpv_rep_kernel.hpp"), force))
     work.append((grad, os.path.join(BUILD, "grad.o"), list(extra_flags), internal + H("gpv_grad.h", "gpv_grad_set_pass.inc", "gpv_rep_kernel.hpp"), force))
+    sgv = os.path.join(CSRC, "gpv_grad_sgv.hip")             # gradient pass of the SGV likelihood: the same buckets
+    for pb in (64, 32, 16):
+        work.append((sgv, os.path.join(BUILD, f"grad_sgv_pb{pb}.o"), [f"-DGPV_SGV_PB={pb}"] + extra_flags,
+                     internal + H("gpv_grad.h", "gpv_grad_sgv.h"), force))
+    work.append((sgv, os.path.join(BUILD, "grad_sgv.o"), list(extra_flags), internal + H("gpv_grad.h", "gpv_grad_sgv.h"), force))
     work.append((os.path.join(CSRC, "gpv_whiten.hip"), os.path.join(BUILD, "whiten.o"), list(extra_flags), H("gpv_whiten.h"), force))
     work.append((os.path.join(CSRC, "gpv_unwhiten.hip"), os.path.join(BUILD, "unwhiten.o"), list(extra_flags),
                  H("gpv_unwhiten.h", "gpv_philox.hpp"), force))

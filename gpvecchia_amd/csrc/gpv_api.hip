@@ -15,6 +15,8 @@
 #include "gpv_unwhiten.h"
 #define GPV_SELINV_LINKAGE __attribute__((weak))
 #include "gpv_selinv.h"
+#define GPV_GRAD_SGV_LINKAGE __attribute__((weak))
+#include "gpv_grad_sgv.h"
 #include "gpv_hip_raii.hpp"
 
 #include <dlfcn.h>
@@ -415,6 +417,15 @@ struct gpv_plan {
     std::vector<int> sel_lev_tile;
     int64_t sel_dropped = 0;
     bool sel_ready = false;
+    // gpv_plan_loglik_grad_sgv (gpv_grad_sgv.hip), built and allocated on first use after gpv_plan_build_posterior: by stored
+    // set, the position of every entry in the set's posterior column and the column's record (SgvGradArgs::cpos, setrec);
+    // per-workgroup partials, their totals, per-row terms
+    DevBuf<uint8_t> d_sgv_cpos;
+    DevBuf<int4> d_sgv_rec;
+    DevBuf<double> d_sgv_part, d_sgv_tot, d_sgv_rows;
+    int sgv_grid = 0;
+    bool sgv_ready = false;
+    bool post_filled = false;                        // the structure is a filled one (gpv_plan_build_posterior_fill)
     // gpv_plan_draws_summary: mu, S1, S2, mean, var [Nlocs] each, exceed [8][Nlocs], the accumulation's block partials; counts
     // [8][Nlocs]; mask [Nlocs]; draw_max, draw_mean [ds_draw_cap] each.  Allocated on first use.
     DevBuf<double> d_ds, d_ds_draw;
@@ -1353,6 +1364,7 @@ static int build_posterior_impl(gpv_plan *pl, const int *revNN, const int *revCo
     pl->have_factor = false;
     pl->lc_ready = false;
     pl->sel_ready = false;
+    pl->sgv_ready = false;
     if (pl->last_stream) { GPV_HIP(hipSetDevice(pl->device)); GPV_HIP(hipStreamSynchronize(pl->last_stream)); }
     pl->drop_graphs();
     if (pl->row_begin != 0 || pl->row_end != pl->Nlocs) return GPV_ERR_BAD_ARG;   // not shardable
@@ -1779,6 +1791,7 @@ static int build_posterior_impl(gpv_plan *pl, const int *revNN, const int *revCo
     GPV_BUF(pl->d_post_part, ensure(2048));                            // launch_sum_pair: 2 x 1024
     if (!pl->post_fused) GPV_BUF(pl->d_L, ensure((size_t)n * pl->P));  // (fused: only when the caller wants U)
     pl->L_of_eval = 0;                                                 // (evaluations from here on may leave d_L alone: fused)
+    pl->post_filled = with_fill;
     pl->have_post = true;
     return GPV_OK;
 }
@@ -2093,7 +2106,7 @@ int gpv_matern_derivs_host(double nu, double range, const double *s, int64_t n, 
 // buffers and the tables of a general smoothness, and `cs` the parsed family (matern_scaledim: its inverse ranges, for the scaled
 // copy).  rep: the data are the plan's replicates (gpv_plan_set_replicates), not its column.
 static int grad_args_checked(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, bool with_nu,
-                             bool &matern, GradArgs &a, CovSetup &cs, bool rep = false)
+                             bool &matern, GradArgs &a, CovSetup &cs, bool rep = false, bool sgv = false)
 {
     matern = std::strcmp(covType, "matern") == 0;
     const bool scaled = std::strcmp(covType, "matern_scaledim") == 0;
@@ -2108,7 +2121,8 @@ static int grad_args_checked(gpv_plan *pl, const char *covType, const double *co
     // matern_scaledim is not differentiated, with_nu or not)
     if (cs.cov == COV_MATERN_GEN && (!with_nu || scaled)) return GPV_ERR_UNSUPPORTED_NU;
     if (pl->p > kGradMaxP) return GPV_ERR_UNSUPPORTED_M;
-    if (!(rep ? pl->rep_R > 0 && pl->d_rep_Z : pl->has_z) || pl->comm || pl->rows != pl->Nlocs || pl->d_obs || pl->latent_nb)
+    if (!(rep ? pl->rep_R > 0 && pl->d_rep_Z : pl->has_z) || pl->comm || pl->rows != pl->Nlocs || pl->d_obs ||
+        (pl->latent_nb && !sgv))                                     // (sgv: gpv_plan_loglik_grad_sgv, which is for such plans)
         return GPV_ERR_STATE;
     a.rec = pl->d_locs; a.locs = pl->d_locs; a.z = pl->d_z;
     a.nn = pl->d_nn; a.rowid = pl->d_rowid;
@@ -3049,6 +3063,133 @@ extern "C" int gpv_plan_debug_selinv_ms(gpv_plan *pl, int reps, double *ms)
     }
     (void)hipStreamSynchronize(st);
     return rc;
+}
+
+// ---- value and analytic gradient of the cond.yz='SGV' log-likelihood (gpv_grad_sgv.hip) ---------------------------------------
+// gpv_grad_sgv.hip is part of this link (see GPV_GRAD_SGV_LINKAGE in gpv_grad_sgv.h)
+static bool grad_sgv_linked() { return &grad_sgv_grid != nullptr && &launch_grad_sgv != nullptr; }
+
+// The index data of the pass from the plan's arrays as they live on the device (built on the first call after a
+// gpv_plan_build_posterior): for every stored set the record of its posterior column, and for every entry of the set the
+// position of its point among the column's entries.  Every position is found in the column itself and checked against it:
+// the latent entries of a set must be the entries of its column, one each, the set's own point last; the kernel indexes its
+// tile of Sigma and the match records with them.
+static int sgv_prepare(gpv_plan *pl)
+{
+    const int64_t n = pl->Nlocs, rows = pl->rows;
+    const int P = pl->P;
+    const size_t nnz = (size_t)pl->post_nnz;
+    if (rows != n || pl->h_newpos.size() != (size_t)n || nnz < (size_t)n) return GPV_ERR_STATE;
+    std::vector<int32_t> nn((size_t)rows * P), rid((size_t)rows), colptr((size_t)n + 1), crow(nnz), cboff((size_t)n), inv((size_t)n, -1);
+    std::vector<uint8_t> cd((size_t)rows * P);
+    GPV_HIP(hipMemcpy(nn.data(), pl->d_nn, nn.size() * 4, hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(cd.data(), pl->d_cond, cd.size(), hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(rid.data(), pl->d_rowid, rid.size() * 4, hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(colptr.data(), pl->d_colptr, colptr.size() * 4, hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(crow.data(), pl->d_crow, nnz * 4, hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(cboff.data(), pl->d_cboff, cboff.size() * 4, hipMemcpyDeviceToHost));
+    if (colptr[0] != 0 || (size_t)colptr[(size_t)n] != nnz) return GPV_ERR_STATE;
+    for (int64_t i = 0; i < n; ++i) {                         // ordered index of every internal position
+        const int32_t r = pl->h_newpos[(size_t)i];
+        if (r < 0 || r >= n || inv[(size_t)r] != -1) return GPV_ERR_STATE;
+        inv[(size_t)r] = (int32_t)i;
+    }
+    std::vector<uint8_t> cpos((size_t)rows * P, (uint8_t)0xFF);
+    std::vector<int4> rec((size_t)rows);
+    for (int64_t r = 0; r < rows; ++r) {
+        const int32_t k = rid[(size_t)r];
+        if (k < 0 || k >= n) return GPV_ERR_STATE;
+        const int32_t b0 = colptr[(size_t)k], cn = colptr[(size_t)k + 1] - b0;
+        if (cn < 1 || cn > kGradMaxP || b0 < 0 || (size_t)b0 + (size_t)cn > nnz || cboff[(size_t)k] < 0) return GPV_ERR_STATE;
+        const int32_t *col = crow.data() + b0;
+        unsigned long long seen = 0ull;
+        for (int t = 0; t < P; ++t) {
+            const int32_t v = nn[(size_t)r * P + t];
+            if (v < 0 || !(cd[(size_t)r * P + t] & 1u)) continue;
+            if (v >= n) return GPV_ERR_STATE;
+            const int32_t *at = std::lower_bound(col, col + cn, inv[(size_t)v]);
+            if (at == col + cn || *at != inv[(size_t)v]) return GPV_ERR_STATE;      // a latent entry outside the column
+            const int pos = (int)(at - col);
+            const int stored = cd[(size_t)r * P + t] >> 1;                           // (the set kernel's own record, where it has one)
+            if ((seen >> pos) & 1ull || (stored != 0 && stored != pos + 1)) return GPV_ERR_STATE;
+            seen |= 1ull << pos;
+            cpos[(size_t)r * P + t] = (uint8_t)pos;
+        }
+        if (seen != (cn == 64 ? ~0ull : (1ull << cn) - 1ull)) return GPV_ERR_STATE;  // every entry of the column, once
+        if (cpos[(size_t)r * P + P - 1] != (uint8_t)(cn - 1) || col[cn - 1] != k) return GPV_ERR_STATE;   // the own point: last
+        rec[(size_t)r] = make_int4(cboff[(size_t)k], b0, cn, k);
+    }
+    GPV_BUF(pl->d_sgv_cpos, upload(cpos.data(), cpos.size()));
+    GPV_BUF(pl->d_sgv_rec, upload(rec.data(), rec.size()));
+    pl->sgv_ready = true;
+    return GPV_OK;
+}
+
+// Unlike the 'z' entries this one EVALUATES the plan: an evaluation with GPV_WANT_MEAN at these parameters, the selected
+// inverse of its factor, then the per-set pass; the plan's last evaluation afterwards is that evaluation.
+int gpv_plan_loglik_grad_sgv(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, double nugget, double *loglik,
+                             double *grad, int64_t *n_failed, double *col_terms)
+{
+    if (!pl || !covType || !covparms || !loglik || !grad || !n_failed) return GPV_ERR_BAD_ARG;
+    if (std::strcmp(covType, "matern_scaledim") == 0) return GPV_ERR_UNSUPPORTED_NU;
+    bool matern;
+    SgvGradArgs sa;
+    GradArgs &a = sa.g;
+    CovSetup cs;
+    int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, false, matern, a, cs, false, true);
+    if (rc != GPV_OK) return rc;
+    if (!grad_sgv_linked() || !selinv_linked()) return GPV_ERR_STATE;
+    if (!pl->have_post || pl->post_filled || pl->post_ld > 64 || !pl->d_meanrec || pl->row_begin != 0) return GPV_ERR_STATE;
+    // the structure's own facts, established once: the terms its selected inverse drops (none for SGV) and the index data.
+    // They read the plan's arrays and write buffers of their own; a refusal here leaves every result of the plan as it was.
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (!pl->sel_ready && (rc = selinv_prepare(pl)) != GPV_OK) return rc;
+    if (pl->sel_dropped > 0) return GPV_ERR_STATE;
+    if (!pl->sgv_ready && (rc = sgv_prepare(pl)) != GPV_OK) return rc;
+    const int grid = grad_sgv_grid(pl->p, pl->rows, pl->cus);
+    if (!pl->d_sgv_part || pl->sgv_grid < grid) {
+        GPV_BUF(pl->d_sgv_part, resize(kSgvNV * (size_t)grid));
+        pl->sgv_grid = grid;
+    }
+    GPV_BUF(pl->d_sgv_tot, ensure(kSgvNV));
+    if (col_terms) GPV_BUF(pl->d_sgv_rows, ensure(kSgvRowLd * (size_t)pl->rows));
+    // the evaluation, on the plan's stream; its sums, mean, U entries and factor stamp are what the caller finds afterwards
+    if ((rc = plan_eval_checked(pl, cs, &nugget, 1, GPV_WANT_MEAN, nullptr, nullptr)) != GPV_OK) return rc;
+    hipStream_t st = pl->stream;
+    auto fail = [&](int rc2) { (void)hipStreamSynchronize(st); return rc2; };
+    if (GPV_HIP_FAILED(selinv_sweep(pl, st))) return fail(GPV_ERR_HIP);
+    a.row_terms = col_terms ? pl->d_sgv_rows.get() : nullptr;
+    a.block_part = pl->d_sgv_part; a.totals = pl->d_sgv_tot;
+    sa.cpos = pl->d_sgv_cpos; sa.setrec = pl->d_sgv_rec; sa.crow = pl->d_crow;
+    sa.pair = pl->d_sel_pair; sa.tp = pl->d_tp; sa.S = pl->d_sel_S; sa.vars = pl->d_sel_vars; sa.mu = pl->d_u;
+    double tot[kSgvNV];
+    if (GPV_HIP_FAILED(launch_grad_sgv(pl->p, sa, grid, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(tot, pl->d_sgv_tot, sizeof(tot), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+    GPV_HIP(hipStreamSynchronize(st));
+    double sums[kNSums];
+    if ((rc = gpv_plan_get_sums(pl, sums)) != GPV_OK) return rc;
+    // kernel parameters -> covparms: matern {variance, range, - (NaN), nugget}, esqe {variance 1, range 1, variance 2, range 2, nugget}
+    const int nk = matern ? 3 : 5, np = ncovparms + 1;
+    const int at[5] = {0, 1, matern ? 3 : 2, 3, 4};
+    auto spread = [&](const double *src, double *dst) {
+        for (int t = 0; t < np; ++t) dst[t] = NAN;
+        for (int t = 0; t < nk; ++t) dst[at[t]] = src[t];
+    };
+    *n_failed = (int64_t)tot[6];
+    if (tot[6] > 0.0) {
+        *loglik = -INFINITY;
+        for (int t = 0; t < np; ++t) grad[t] = NAN;
+    } else {
+        if ((rc = gpv_loglik_from_sums(sums, pl->Nlocs, loglik)) != GPV_OK) return rc;
+        spread(tot, grad);
+    }
+    if (col_terms) {
+        std::vector<double> h((size_t)pl->rows * kSgvRowLd);
+        GPV_HIP(hipMemcpy(h.data(), pl->d_sgv_rows, sizeof(double) * h.size(), hipMemcpyDeviceToHost));
+        for (int64_t k = 0; k < pl->rows; ++k) spread(&h[(size_t)k * kSgvRowLd], col_terms + k * np);
+    }
+    return GPV_OK;
 }
 
 // ---- Monte-Carlo summaries of posterior draws: normals made on the device, the transposed sweep, fused sums ------------------

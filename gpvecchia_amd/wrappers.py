@@ -187,7 +187,8 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     smoothness: a value fixes the Matern smoothness and takes it out of the search (theta_ini then holds variance, range,
     nugget).  method: "Nelder-Mead" (the reference's search) or "L-BFGS-B", which minimises over the log-parameters with the
     analytic gradient of the GPU (vecchia_likelihood_grad; d/d log theta = theta d/d theta) and needs cond_yz='z' and, for
-    'matern', smoothness in {0.5, 1.5, 2.5}; or "fisher", Fisher scoring over the log-parameters on the expected information of
+    'matern', smoothness in {0.5, 1.5, 2.5} -- or an explicit cond_yz='SGV', the reference's default conditioning, whose gradient
+    is vecchia_likelihood_grad_sgv ('matern' at such a smoothness, or 'esqe'; trend="ols", one data vector); or "fisher", Fisher scoring over the log-parameters on the expected information of
     the GPU (vecchia_likelihood_fisher, _fisher_scoring), with the preconditions of "L-BFGS-B".  n_evals counts likelihood (or
     value + gradient [+ information]) evaluations.  For "fisher" the result also holds fisher_info (the information over the
     searched parameters at theta_hat), theta_cov (its inverse) and theta_se (the square roots of that one's diagonal).
@@ -232,8 +233,14 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
             raise ValueError("trend='gls' needs a named covariance family")
         if X is None:
             raise ValueError("trend='gls' needs a trend: X, or the constant column of X='missing'")
+    # method="L-BFGS-B" with an EXPLICIT cond_yz='SGV': the gradient of the default conditioning (vecchia_likelihood_grad_sgv)
+    sgv_grad = method == "L-BFGS-B" and specify_args.get("cond_yz") == "SGV"
+    if sgv_grad:
+        if smoothness_grad or scaledim or not isinstance(covmodel, str) or covmodel not in ("matern", "esqe"):
+            raise ValueError("method='L-BFGS-B' with cond_yz='SGV' takes covmodel 'matern' (smoothness in {0.5, 1.5, 2.5}, "
+                             "smoothness_grad=False) or 'esqe'")
     if method in ("L-BFGS-B", "fisher"):
-        if specify_args.get("cond_yz") != "z":
+        if specify_args.get("cond_yz") != "z" and not sgv_grad:
             raise ValueError(f"method='{method}' needs cond_yz='z' (the likelihood whose gradient the GPU returns)")
         if not isinstance(covmodel, str):
             raise ValueError(f"method='{method}' needs a named covariance family")
@@ -268,6 +275,8 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     else:
         lik = lambda *a, **kw: A.vecchia_likelihood(*a, **kw)                                     # noqa: E731
         lik_grad = lambda *a, **kw: A.vecchia_likelihood_grad(*a, **kw)                           # noqa: E731
+        if sgv_grad:
+            lik_grad = lambda *a, **kw: A.vecchia_likelihood_grad_sgv(*a, **kw)                   # noqa: E731
         lik_fisher = lambda *a, **kw: A.vecchia_likelihood_fisher(*a, **kw)                       # noqa: E731
     if replicated and isinstance(X, str) and X == "missing":         # the grand mean
         beta_hat = np.array([data.mean()])

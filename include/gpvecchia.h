@@ -318,7 +318,37 @@ int gpv_plan_loglik_grad(gpv_plan *plan, const char *covType, const double *covp
                          double *loglik, double *grad /* ncovparms + 1 */, int64_t *n_failed,
                          double *row_terms /* NULL, or Nlocs x (ncovparms + 2), row-major */);
 
-/* The same value and gradient together with the expected Fisher information of that likelihood, for standard errors and Fisher
+/* Value and analytic gradient of the log-likelihood of a plan whose sets condition on latent y (cond.yz = 'SGV', the default of
+ * vecchia_specify; R/vecchia_likelihood.R:63-99 with the sparse W), for gradient-based estimation at the default conditioning.
+ * Set k with valid entries J (own point l last) and flags c_j (1: conditioned on as latent y, c_l = 1):
+ *   S = C(J, J) + nugget diag(1 - c),  u = S^-1 e_l,  M = u / sqrt(u_l);  a_k = sum_{c_j = 0} M_j z_j;  m_k: the latent part of M;
+ *   W = sum_k m_k m_k' + I / nugget,  z2 = sum_k m_k a_k - z / nugget,  mu~ = W^-1 z2,  Sigma = W^-1  (on the pattern of W only).
+ * With delta_k = a_k - m_k'mu~, v = Sigma_LL m_k over the latent members of the set, f_j = 2 delta_k z_j (c_j = 0),
+ * 2 (v_j - delta_k mu~_j) (c_j = 1) and -2 / M_l more at j = l, w~ = S^-1 f, D = dS/dtheta elementwise (the nugget: diag(1 - c)):
+ *   c_k = -(w~'D u) / sqrt(u_l) + 1/2 (f'u)(u'D u) / u_l^{3/2},  plus 1/nugget - (Sigma_kk + (z_k + mu~_k)^2) / nugget^2 for the nugget,
+ *   d loglik / d theta = -1/2 sum_k c_k.
+ * covType, covparms, nugget, grad and n_failed as for gpv_plan_loglik_grad ("matern" at 0.5, 1.5, 2.5 and "esqe").
+ *   loglik     out: gpv_loglik_from_sums of the sums of the evaluation this call makes (below)
+ *   col_terms  NULL, or out: Nlocs x (ncovparms + 1) row-major, row k = -1/2 c_k in the plan's ORDERED numbering, the nugget's
+ *              explicit terms included; the rows sum to grad.  NaN in a failed row.
+ * UNLIKE the 'z' entries this call evaluates the plan: it runs gpv_plan_eval(..., GPV_WANT_MEAN) at these parameters on the
+ * plan's own stream, then the selected inverse of that evaluation's factor (the pass of gpv_plan_selinv), then one pass over the
+ * conditioning sets.  Afterwards the plan's last evaluation IS that evaluation: gpv_plan_get_sums, gpv_plan_get_posterior_mean,
+ * gpv_plan_get_Lentries (if materialised), gpv_plan_factor_stamp and a following gpv_plan_selinv return what they return after
+ * such a gpv_plan_eval.  Blocking; bitwise reproducible from call to call.
+ * Arguments and state are validated before any of this; a refused call leaves every result of the plan as it was (the first
+ * call after gpv_plan_build_posterior builds the pass's index data from the plan's arrays, which reads the device).
+ * GPV_ERR_BAD_ARG as for gpv_plan_loglik_grad; GPV_ERR_COVTYPE; GPV_ERR_UNSUPPORTED_NU: another smoothness, and
+ * "matern_scaledim"; GPV_ERR_UNSUPPORTED_M: m + 1 > 64; GPV_ERR_STATE: no data set, no posterior structure
+ * (gpv_plan_build_posterior not called or refused), a filled structure (gpv_plan_build_posterior_fill), unobserved locations, a
+ * row shard or a communicator, a structure whose selected inverse drops terms (n_dropped > 0), or index data that do not match
+ * the structure.  A cond.yz = 'z' plan with a structure built is accepted: W is diagonal there and the result agrees with
+ * gpv_plan_loglik_grad. */
+int gpv_plan_loglik_grad_sgv(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms, double nugget,
+                             double *loglik, double *grad /* ncovparms + 1 */, int64_t *n_failed,
+                             double *col_terms /* NULL, or Nlocs x (ncovparms + 1), row-major */);
+
+/* The value and gradient of gpv_plan_loglik_grad together with the expected Fisher information of the 'z' likelihood, for standard errors and Fisher
  * scoring.  In the notation above, with t_i = D_i u (t = u for the nugget), a_i = u't_i and y_j = S'^-1 t_j, a row contributes
  *   F_k[i][j] = t_i'y_j / u_last - 1/2 a_i a_j / u_last^2
  *             = 1/2 tr(S'^-1 D_i S'^-1 D_j) - 1/2 tr(S'_c^-1 D_i,c S'_c^-1 D_j,c),   c: J without the row's own point,

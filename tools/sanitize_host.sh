@@ -31,6 +31,10 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   $HIPCC $CF -c $CSRC/gpv_grad.hip -o $B/grad.o & pids+=($!)
   $HIPCC $CF -c $CSRC/gpv_whiten.hip -o $B/whiten.o & pids+=($!)    # whitening and Gram passes: launchers only on the host
   $HIPCC $CF -c $CSRC/gpv_selinv.hip -o $B/selinv.o & pids+=($!)    # selected inverse: launchers only on the host
+  for pb in 16 32 64; do                         # gradient pass of the SGV likelihood: the same buckets, then its dispatcher
+    $HIPCC $CF -DGPV_SGV_PB=$pb -c $CSRC/gpv_grad_sgv.hip -o $B/grad_sgv_pb$pb.o & pids+=($!)
+  done
+  $HIPCC $CF -c $CSRC/gpv_grad_sgv.hip -o $B/grad_sgv.o & pids+=($!)
   for P in $PLIST; do
     $HIPCC $CF "-DGPV_P_LIST(X)=$plx" -DGPV_INST_P=$P -c $CSRC/gpv_sets_inst.hip -o $B/sets_p$P.o & pids+=($!)
     if [ $P -gt 16 ] && [ $P -lt 32 ]; then      # likelihood-only kernels: a unit of their own (gpvecchia_amd/build.py lik_p)
@@ -134,6 +138,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   rc=${PIPESTATUS[0]}
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_selinv.log; then
     echo "== $tag: selinv_driver FAILED (rc $rc)"; return 1
+  fi
+  # ... and under the driver of the gradient of the SGV likelihood (tests/sanitize/sgv_grad_driver.cpp)
+  mkdir -p $B/sgv_grad
+  $HIPCC $CF -c $ROOT/tests/sanitize/sgv_grad_driver.cpp -o $B/sgv_grad/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/sgv_grad/driver.o -o $B/sgv_grad_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./sgv_grad_driver ) 2>&1 | tee $B/run_sgv_grad.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_sgv_grad.log; then
+    echo "== $tag: sgv_grad_driver FAILED (rc $rc)"; return 1
   fi
   # ... and under the driver of the ordered nearest-neighbour search (tests/sanitize/nn_driver.cpp)
   mkdir -p $B/nn
