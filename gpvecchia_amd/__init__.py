@@ -7,7 +7,8 @@ from .api import (Comm, EsqeFun, MaternFun, MultiPlan, Plan, ReplicaPlans, U2V, 
                   loglik_z_from_sums, numerator_from_sums, vecchia_likelihood, vecchia_likelihood_U, vecchia_likelihood_grad,
                   vecchia_likelihood_fisher, vecchia_specify, profile_from_gram, vecchia_likelihood_replicates,
                   vecchia_profile_likelihood, vecchia_whiten, vecchia_likelihood_grad_replicates,
-                  vecchia_likelihood_fisher_replicates, vecchia_unwhiten, vecchia_simulate, vecchia_likelihood_grad_sgv)
+                  vecchia_likelihood_fisher_replicates, vecchia_unwhiten, vecchia_simulate, vecchia_likelihood_grad_sgv,
+                  vecchia_precision_multiply, vecchia_loo, loo_summary)
 
 from .laplace import (calculate_posterior_VL, vecchia_laplace_likelihood,  # noqa: F401,E402
                       vecchia_laplace_likelihood_from_posterior, vecchia_laplace_prediction, vecchia_prediction)

@@ -46,6 +46,7 @@ EXPORTS = [
     "gpv_whiten_max_cols", "gpv_plan_whiten",
     "gpv_unwhiten_narrow", "gpv_plan_unwhiten_levels", "gpv_plan_unwhiten", "gpv_plan_simulate",
     "gpv_plan_set_replicates", "gpv_plan_replicates", "gpv_plan_loglik_rep", "gpv_plan_loglik_rep_nu",
+    "gpv_loo_nscores", "gpv_plan_whiten_t", "gpv_plan_precision", "gpv_plan_loo", "gpv_plan_loo_index", "gpv_loo_index_host",
 ]
 
 
@@ -131,6 +132,14 @@ def lib():
     L.gpv_plan_unwhiten_levels.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gpv_plan_unwhiten.argtypes = [vp, dp, i64, C.c_int, dp, i64, C.POINTER(C.c_int64)]
     L.gpv_plan_simulate.argtypes = [vp, C.c_uint64, i64, i64, dp, i64, C.POINTER(C.c_int64)]
+    L.gpv_loo_nscores.restype = C.c_int
+    L.gpv_loo_nscores.argtypes = []
+    L.gpv_plan_whiten_t.argtypes = [vp, dp, i64, C.c_int, dp, i64, C.POINTER(C.c_int64)]
+    L.gpv_plan_precision.argtypes = [vp, dp, i64, C.c_int, dp, i64, dp, C.POINTER(C.c_int64)]
+    L.gpv_plan_loo.argtypes = [vp, dp, i64, C.c_int, dp, i64, dp, dp, C.POINTER(C.c_int64)]
+    L.gpv_plan_loo_index.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    i32p = C.POINTER(C.c_int32)
+    L.gpv_loo_index_host.argtypes = [i32p, i32p, i64, i64, C.c_int, i32p, i32p, i32p, i64, C.POINTER(C.c_int64)]
     L.gpv_plan_set_replicates.argtypes = [vp, dp, i64, C.c_int]
     L.gpv_plan_replicates.argtypes = [vp, ip]
     L.gpv_plan_loglik_rep.argtypes = L.gpv_plan_loglik_fisher.argtypes

@@ -25,6 +25,7 @@ from ._lib import GPV_WANT_DENOM, GPV_WANT_LOGLIK_Z, GPV_WANT_NUMERATOR, GPV_WAN
 
 
 WHITEN_MAX_COLS = 16                                  # gpv_whiten_max_cols(): columns per Plan.whiten call
+LOO_NSCORES = 6                                       # gpv_loo_nscores(): score sums per column of Plan.loo
 
 
 # ---------------------------------------------------------------------------
@@ -337,6 +338,61 @@ class Plan:
         L.check(L.lib().gpv_plan_unwhiten(self._h, L.dptr(E), self.Nlocs, ncols, L.dptr(B), self.Nlocs, C.byref(nf)),
                 "gpv_plan_unwhiten")
         return B, int(nf.value)
+
+    def _loo_columns(self, A_ord, what):
+        A = np.asarray(A_ord, dtype=np.float64)
+        if A.ndim == 1:
+            A = A[:, None]
+        if A.ndim != 2 or A.shape[0] != self.Nlocs:
+            raise ValueError(f"{what} must have one row per ordered location of the plan")
+        if A.shape[1] < 1 or A.shape[1] > WHITEN_MAX_COLS:
+            raise ValueError(f"{what}: 1 to {WHITEN_MAX_COLS} columns per call")
+        return np.asfortranarray(A), int(A.shape[1])
+
+    def whiten_t(self, E_ord):
+        """The TRANSPOSE of the whitening operator of the plan's latest evaluation (GPV_WANT_U) applied to the columns of E_ord,
+        (Nlocs, ncols) or (Nlocs,) in the ORDERED row numbering, ncols <= 16 (gpv_plan_whiten_t).  Returns (B_ord, n_failed):
+        <whiten(b), e> = <b, whiten_t(e)>.  All NaN with n_failed > 0.  The plan's last evaluation is left as it was."""
+        E, ncols = self._loo_columns(E_ord, "E_ord")
+        B = np.zeros((self.Nlocs, ncols), order="F")
+        nf = C.c_int64(0)
+        L.check(L.lib().gpv_plan_whiten_t(self._h, L.dptr(E), self.Nlocs, ncols, L.dptr(B), self.Nlocs, C.byref(nf)),
+                "gpv_plan_whiten_t")
+        return B, int(nf.value)
+
+    def precision(self, B_ord, want_diag=True):
+        """Q B for the precision matrix Q = T'T of the data vector under the plan's latest evaluation (GPV_WANT_U), T the
+        whitening operator; B_ord (Nlocs, ncols) or (Nlocs,) in the ORDERED row numbering, ncols <= 16 (gpv_plan_precision).
+        Returns (R_ord, qdiag, n_failed): qdiag = diag Q (Nlocs), None without want_diag.  All NaN with n_failed > 0."""
+        B, ncols = self._loo_columns(B_ord, "B_ord")
+        R = np.zeros((self.Nlocs, ncols), order="F")
+        q = np.zeros(self.Nlocs) if want_diag else None
+        nf = C.c_int64(0)
+        L.check(L.lib().gpv_plan_precision(self._h, L.dptr(B), self.Nlocs, ncols, L.dptr(R), self.Nlocs,
+                                           L.dptr(q) if want_diag else None, C.byref(nf)), "gpv_plan_precision")
+        return R, q, int(nf.value)
+
+    def loo(self, Z_ord, want_mean=True, want_var=True):
+        """Leave-one-out cross-validation of the columns of Z_ord, (Nlocs, ncols) or (Nlocs,) in the ORDERED row numbering,
+        ncols <= 16, under the plan's latest evaluation (GPV_WANT_U), without refitting (gpv_plan_loo): with Q the precision of
+        the data vector, mean_i = z_i - (Q z)_i / Q_ii and var_i = 1 / Q_ii.  Returns (mean (Nlocs, ncols) or None, var (Nlocs,)
+        or None, scores (ncols, 6), n_failed); scores per column: sum (z - mean)^2, sum |z - mean|, sum of squared standardised
+        residuals, sum log var, sum CRPS, count of |standardised residual| <= 1.96.  All NaN with n_failed > 0."""
+        Z, ncols = self._loo_columns(Z_ord, "Z_ord")
+        mean = np.zeros((self.Nlocs, ncols), order="F") if want_mean else None
+        var = np.zeros(self.Nlocs) if want_var else None
+        scores = np.zeros((ncols, LOO_NSCORES))
+        nf = C.c_int64(0)
+        L.check(L.lib().gpv_plan_loo(self._h, L.dptr(Z), self.Nlocs, ncols, L.dptr(mean) if want_mean else None, self.Nlocs,
+                                     L.dptr(var) if want_var else None, L.dptr(scores), C.byref(nf)), "gpv_plan_loo")
+        return mean, var, scores, int(nf.value)
+
+    def loo_index(self):
+        """(entries, longest column, empty columns) of the transposed index whiten_t / precision / loo gather through, built at
+        first use (gpv_plan_loo_index): for every location the stored entries that name it as a neighbour."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().gpv_plan_loo_index(self._h, C.byref(a), C.byref(b), C.byref(c)), "gpv_plan_loo_index")
+        return int(a.value), int(b.value), int(c.value)
 
     def unwhiten_levels(self):
         """(n_levels, n_launches) of the level schedule unwhiten and simulate sweep through, built at first use
@@ -1449,6 +1505,68 @@ def vecchia_simulate(vecchia_approx, covparms, nuggets, covmodel="matern", nsim=
     if mu is not None:
         Z += mu if mu.ndim == 0 else mu[:, None]
     return Z
+
+
+def vecchia_precision_multiply(B, vecchia_approx, covparms, nuggets, covmodel="matern", device=0):
+    """Q B and diag Q for the precision matrix Q = (C + tau I)^-1 of the data vector under the Vecchia approximation at these
+    parameters, everything in the CALLER's order of the locations: one evaluation (GPV_WANT_U), then ceil(c / 16)
+    Plan.precision calls.  B: n x c, or a vector.  Returns (QB (n x c), qdiag (n,)); all NaN when some block was not positive
+    definite at these parameters."""
+    va = vecchia_approx
+    B = _user_columns("vecchia_precision_multiply", B, va)
+    plan = _whiten_plan("vecchia_precision_multiply", va, covparms, nuggets, covmodel, device)
+    o = va["ord_z"] - 1
+    Bord = B[o]
+    Rord = np.empty(Bord.shape)
+    qord = None
+    for c0 in range(0, Bord.shape[1], WHITEN_MAX_COLS):
+        Rord[:, c0:c0 + WHITEN_MAX_COLS], q, _ = plan.precision(Bord[:, c0:c0 + WHITEN_MAX_COLS], want_diag=c0 == 0)
+        qord = q if c0 == 0 else qord
+    R, qdiag = np.empty(Bord.shape), np.empty(Bord.shape[0])
+    R[o] = Rord
+    qdiag[o] = qord
+    return R, qdiag
+
+
+def loo_summary(scores, n):
+    """The per-column summary of Plan.loo's score sums (ncols, 6) over n locations: rmse, mae, log_score (mean log predictive
+    density), crps (mean), coverage95, mean_sq_std_resid."""
+    s = np.atleast_2d(np.asarray(scores, dtype=np.float64))
+    return dict(rmse=np.sqrt(s[:, 0] / n), mae=s[:, 1] / n, log_score=-0.5 * (np.log(2.0 * np.pi) + (s[:, 3] + s[:, 2]) / n),
+                crps=s[:, 4] / n, coverage95=s[:, 5] / n, mean_sq_std_resid=s[:, 2] / n)
+
+
+def vecchia_loo(z, vecchia_approx, covparms, nuggets, covmodel="matern", mean=None, device=0):
+    """Leave-one-out cross-validation of the data under the Vecchia approximation of N(mean, C + tau I) at these parameters,
+    without refitting: one evaluation (GPV_WANT_U), then ceil(R / 16) Plan.loo calls.  z: a vector or n x R (R realisations),
+    in the CALLER's order of the locations; mean: None, a scalar or one value per location, subtracted before and added back.
+    Returns a dict, everything in the caller's order: mean (n x R: E[z_i | z_-i]), var (n,: Var[z_i | z_-i], the same for every
+    column), resid_std (n x R), and per column rmse, mae, log_score (mean log predictive density), crps (mean), coverage95,
+    mean_sq_std_resid (arrays of length R).  All NaN when some block was not positive definite at these parameters."""
+    va = vecchia_approx
+    Z = _user_columns("vecchia_loo", z, va)
+    n, R = Z.shape
+    mu = None
+    if mean is not None:
+        mu = np.asarray(mean, dtype=np.float64)
+        if mu.ndim > 1 or (mu.ndim == 1 and mu.size != n):
+            raise ValueError("vecchia_loo: mean must be a scalar or one value per location")
+        mu = mu if mu.ndim == 0 else mu[:, None]
+        Z = Z - mu
+    plan = _whiten_plan("vecchia_loo", va, covparms, nuggets, covmodel, device)
+    o = va["ord_z"] - 1
+    Zord = Z[o]
+    Mord, scores, vord = np.empty(Zord.shape), np.empty((R, LOO_NSCORES)), None
+    for c0 in range(0, R, WHITEN_MAX_COLS):
+        Mord[:, c0:c0 + WHITEN_MAX_COLS], v, scores[c0:c0 + WHITEN_MAX_COLS], _ = plan.loo(Zord[:, c0:c0 + WHITEN_MAX_COLS],
+                                                                                           want_var=c0 == 0)
+        vord = v if c0 == 0 else vord
+    M, var = np.empty(Zord.shape), np.empty(n)
+    M[o] = Mord
+    var[o] = vord
+    out = dict(mean=M if mu is None else M + mu, var=var, resid_std=(Z - M) / np.sqrt(var)[:, None])
+    out.update(loo_summary(scores, n))
+    return out
 
 
 def profile_from_gram(G, logdet, n):

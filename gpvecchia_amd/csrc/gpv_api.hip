@@ -13,6 +13,8 @@
 #include "gpv_whiten.h"
 #define GPV_UNWHITEN_LINKAGE __attribute__((weak))
 #include "gpv_unwhiten.h"
+#define GPV_LOO_LINKAGE __attribute__((weak))
+#include "gpv_loo.h"
 #define GPV_SELINV_LINKAGE __attribute__((weak))
 #include "gpv_selinv.h"
 #define GPV_GRAD_SGV_LINKAGE __attribute__((weak))
@@ -478,6 +480,21 @@ struct gpv_plan {
     DevBuf<unsigned> d_uw_nfail;
     int uw_cp_cap = 0, uw_cp_last = 0;
     int64_t uw_graph_eval[5] = {0, 0, 0, 0, 0};      // the evaluation whose addresses and nugget uw_graph[log2 cp] holds
+    // gpv_plan_whiten_t / gpv_plan_precision / gpv_plan_loo (gpv_loo.hip).  The transposed index is built from d_nn / d_rowid at
+    // first use (loo_index) and never changes: column starts, owners, flat offsets (LooArgs).  d_loo_g belongs to evaluation
+    // loo_g_eval (the scale pre-pass runs once per evaluation; loo_nfail is its count of failed rows).  The column buffers are
+    // allocated on first use and grown with the padded column count: the caller's columns as they arrive and the result on its
+    // way back [cp][Nlocs], B and R by internal position [Nlocs][cp], E by ordered row [Nlocs][cp]; q by internal position and
+    // in the ordered numbering, the variances, the score partials [16][loo_sgrid][6] and the scores [16][6].
+    bool loo_have_index = false;
+    int64_t loo_nnz = 0, loo_maxcol = 0, loo_empty = 0;
+    DevBuf<int32_t> d_loo_colptr, d_loo_owner, d_loo_col;
+    DevBuf<double> d_loo_g, d_loo_in, d_loo_out, d_loo_B, d_loo_E, d_loo_R, d_loo_q, d_loo_qord, d_loo_var, d_loo_part, d_loo_scores;
+    DevBuf<unsigned> d_loo_nfail;
+    int loo_cp_cap = 0, loo_grid = 0, loo_sgrid = 0;
+    int loo_last_mode = -1, loo_last_ncols = 0;      // what gpv_plan_debug_loo_ms repeats
+    int64_t loo_g_eval = 0;
+    unsigned loo_nfail = 0;
     // d_L and the nuggets on the device (d_nuggets / nug_scalar) belong to evaluation L_of_eval of the plan (evaluations are
     // counted from 1; 0: to none).  Set at the end of an evaluation that materialised U, cleared before anything of the two is
     // rewritten: an evaluation that starts, a Vecchia-Laplace step that writes its pseudo-nuggets, a rebuilt posterior structure.
@@ -2685,6 +2702,260 @@ extern "C" int gpv_plan_debug_unwhiten_ms(gpv_plan *pl, int reps, double *ms)
     for (int r = 0; r < reps && rc == GPV_OK; ++r) {
         float t = 0.f;
         if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(unwhiten_sweep(pl, pl->uw_cp_last, st)) ||
+            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
+            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
+            rc = GPV_ERR_HIP;
+        ms[r] = (double)t;
+    }
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// ---- the transposed whitening operator: precision products and leave-one-out cross-validation (gpv_loo.hip) ----------------
+int gpv_loo_nscores(void) { return kLooNScores; }
+
+// gpv_loo.hip is part of this link (see GPV_LOO_LINKAGE in gpv_loo.h)
+static bool loo_linked()
+{
+    return &loo_grid != nullptr && &loo_score_grid != nullptr && &loo_build_index != nullptr && &launch_loo_pack != nullptr &&
+           &launch_loo_unpack != nullptr && &launch_loo_scale != nullptr && &launch_loo_forward != nullptr &&
+           &launch_loo_transposed != nullptr && &launch_loo_scores != nullptr;
+}
+
+int gpv_loo_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t Nlocs, int P, int32_t *colptr, int32_t *owner,
+                       int32_t *col, int64_t col_cap, int64_t *nnz)
+{
+    if (!nnz || rows < 0 || Nlocs < 0 || P < 1) return GPV_ERR_BAD_ARG;
+    if (!loo_linked()) return GPV_ERR_STATE;
+    if (rows * (int64_t)P >= ((int64_t)1 << 31) || Nlocs >= ((int64_t)1 << 31) - 1) return GPV_ERR_INDEX;      // before any array is read
+    if (!nn || !rowid || !colptr || !owner) return GPV_ERR_BAD_ARG;
+    std::vector<int32_t> cptr, own, cl;
+    const int rc = loo_build_index(nn, rowid, rows, Nlocs, P, cptr, own, cl);
+    if (rc != 0) return rc == 1 ? GPV_ERR_INDEX : GPV_ERR_BAD_ARG;
+    *nnz = (int64_t)cl.size();
+    std::copy(cptr.begin(), cptr.end(), colptr);
+    std::copy(own.begin(), own.end(), owner);
+    if (col) {
+        if (col_cap < *nnz) return GPV_ERR_BAD_ARG;
+        std::copy(cl.begin(), cl.end(), col);
+    }
+    return GPV_OK;
+}
+
+// what the plan's structure must be for the index to mean anything / what gpv_plan_whiten asks of the latest evaluation
+static int loo_structure(const gpv_plan *pl)
+{
+    if (!loo_linked()) return GPV_ERR_STATE;
+    if (pl->rows != pl->Nlocs || pl->Nlocs < 1 || pl->latent_nb || !pl->d_nn || !pl->d_rowid) return GPV_ERR_STATE;
+    if ((int64_t)pl->rows * pl->P >= ((int64_t)1 << 31)) return GPV_ERR_INDEX;     // the flat offsets of the index are int32
+    return GPV_OK;
+}
+static int loo_state(const gpv_plan *pl)
+{
+    if (!loo_linked()) return GPV_ERR_STATE;
+    if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L) return GPV_ERR_STATE;
+    if (pl->comm || pl->d_obs) return GPV_ERR_STATE;
+    return loo_structure(pl);
+}
+
+// The transposed index from the plan's own index arrays, read back once (the structure does not depend on the parameters).
+static int loo_index(gpv_plan *pl)
+{
+    if (pl->loo_have_index) return GPV_OK;
+    const int64_t rows = pl->rows, n = pl->Nlocs;
+    const int P = pl->P;
+    std::vector<int32_t> nn((size_t)rows * P), rowid((size_t)rows), colptr, owner, col;
+    GPV_HIP(hipMemcpy(nn.data(), pl->d_nn, nn.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(rowid.data(), pl->d_rowid, rowid.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    const int rc = loo_build_index(nn.data(), rowid.data(), rows, n, P, colptr, owner, col);
+    if (rc != 0) return rc == 1 ? GPV_ERR_INDEX : GPV_ERR_STATE;
+    int64_t maxcol = 0, empty = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t len = colptr[(size_t)i + 1] - colptr[(size_t)i];
+        maxcol = std::max(maxcol, len);
+        empty += len == 0;
+    }
+    GPV_BUF(pl->d_loo_colptr, upload(colptr.data(), colptr.size()));
+    GPV_BUF(pl->d_loo_owner, upload(owner.data(), owner.size()));
+    GPV_BUF(pl->d_loo_col, upload(col.data(), col.size()));
+    GPV_BUF(pl->d_loo_g, resize((size_t)rows));
+    GPV_BUF(pl->d_loo_nfail, resize(2));
+    GPV_BUF(pl->d_loo_q, resize((size_t)n));
+    GPV_BUF(pl->d_loo_qord, resize((size_t)n));
+    GPV_BUF(pl->d_loo_var, resize((size_t)n));
+    pl->loo_grid = loo_grid(rows, pl->cus);
+    pl->loo_sgrid = loo_score_grid(n, pl->cus);
+    GPV_BUF(pl->d_loo_part, resize((size_t)kLooMaxCols * pl->loo_sgrid * kLooNScores));
+    GPV_BUF(pl->d_loo_scores, resize((size_t)kLooMaxCols * kLooNScores));
+    pl->loo_nnz = (int64_t)col.size();
+    pl->loo_maxcol = maxcol;
+    pl->loo_empty = empty;
+    pl->loo_g_eval = 0;
+    pl->loo_have_index = true;
+    return GPV_OK;
+}
+
+int gpv_plan_loo_index(gpv_plan *pl, int64_t *n_entries, int64_t *max_column, int64_t *n_empty)
+{
+    if (!pl || !n_entries || !max_column || !n_empty) return GPV_ERR_BAD_ARG;
+    if (const int rc = loo_structure(pl)) return rc;
+    GPV_HIP(hipSetDevice(pl->device));
+    if (const int rc = loo_index(pl)) return rc;
+    *n_entries = pl->loo_nnz;
+    *max_column = pl->loo_maxcol;
+    *n_empty = pl->loo_empty;
+    return GPV_OK;
+}
+
+enum { kLooModeT = 0, kLooModeQ = 1, kLooModeCV = 2 };
+
+static LooArgs loo_args(gpv_plan *pl)
+{
+    LooArgs a;
+    a.L = pl->d_L; a.nn = pl->d_nn; a.rowid = pl->d_rowid;
+    a.nuggets = pl->nug_is_scalar ? nullptr : pl->d_nuggets.get();
+    a.nug_scalar = pl->nug_scalar;
+    a.colptr = pl->d_loo_colptr; a.owner = pl->d_loo_owner; a.col = pl->d_loo_col;
+    a.g = pl->d_loo_g; a.nfail = pl->d_loo_nfail;
+    a.B = pl->d_loo_B; a.E = pl->d_loo_E; a.R = pl->d_loo_R; a.q = pl->d_loo_q;
+    a.rows = pl->rows; a.n = pl->Nlocs; a.P = pl->P;
+    a.pmagic = loo_pmagic(pl->P);
+    return a;
+}
+
+// the device passes of one call on what is resident: d_loo_in -> d_loo_out (and d_loo_qord, d_loo_var, d_loo_scores)
+static hipError_t loo_enqueue(gpv_plan *pl, int mode, int ncols, bool want_q, hipStream_t st)
+{
+    const int cp = whiten_cp(ncols);
+    const int64_t n = pl->Nlocs;
+    const LooArgs a = loo_args(pl);
+    hipError_t e;
+    if (mode == kLooModeT) {
+        if ((e = launch_loo_pack(pl->d_loo_in, nullptr, n, ncols, cp, pl->d_loo_E, st)) != hipSuccess) return e;
+    } else {
+        if ((e = launch_loo_pack(pl->d_loo_in, pl->d_newpos, n, ncols, cp, pl->d_loo_B, st)) != hipSuccess) return e;
+        if ((e = launch_loo_forward(a, cp, pl->loo_grid, st)) != hipSuccess) return e;
+    }
+    if ((e = launch_loo_transposed(a, cp, pl->loo_grid, st)) != hipSuccess) return e;
+    if ((e = launch_loo_unpack(pl->d_loo_R, pl->d_newpos, n, ncols, cp, pl->d_loo_out, st)) != hipSuccess) return e;
+    if (want_q || mode == kLooModeCV)
+        if ((e = launch_loo_unpack(pl->d_loo_q, pl->d_newpos, n, 1, 1, pl->d_loo_qord, st)) != hipSuccess) return e;
+    if (mode == kLooModeCV)
+        return launch_loo_scores(pl->d_loo_in, pl->d_loo_out, pl->d_loo_qord, pl->d_loo_var, n, ncols, pl->loo_sgrid, pl->d_loo_part,
+                                 pl->d_loo_scores, st);
+    return hipSuccess;
+}
+
+// Reads d_L, the index arrays and the nuggets of the plan's latest evaluation and writes buffers of its own, so the sums, the U
+// entries, the posterior state, the factor stamp and what gpv_plan_whiten left on the device stay what they were.
+//   in / out: ncols columns; vec: qdiag (kLooModeQ) or var (kLooModeCV), NULL = not wanted; out may be NULL in kLooModeCV
+static int loo_run(gpv_plan *pl, int mode, const double *in, int64_t ldin, int ncols, double *out, int64_t ldout, double *vec,
+                   double *scores, int64_t *n_failed)
+{
+    if (const int rc = loo_state(pl)) return rc;
+    const int64_t n = pl->Nlocs;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));   // the evaluation's stream
+    if (const int rc = loo_index(pl)) return rc;
+    const int cp = whiten_cp(ncols);
+    if (cp > pl->loo_cp_cap) {
+        const size_t cnt = (size_t)n * cp;
+        pl->loo_cp_cap = 0;
+        GPV_BUF(pl->d_loo_in, resize(cnt));
+        GPV_BUF(pl->d_loo_out, resize(cnt));
+        GPV_BUF(pl->d_loo_B, resize(cnt));
+        GPV_BUF(pl->d_loo_E, resize(cnt));
+        GPV_BUF(pl->d_loo_R, resize(cnt));
+        pl->loo_cp_cap = cp;
+    }
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    if (pl->loo_g_eval != pl->eval_count) {            // the scale pre-pass: once per evaluation
+        pl->loo_g_eval = 0;
+        if (GPV_HIP_FAILED(hipMemsetAsync(pl->d_loo_nfail, 0, sizeof(unsigned), st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_loo_scale(loo_args(pl), pl->loo_grid, st))) return fail(GPV_ERR_HIP);
+        unsigned nf = 0;
+        if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_loo_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return GPV_ERR_HIP;
+        pl->loo_nfail = nf;
+        pl->loo_g_eval = pl->eval_count;
+    }
+    for (int j = 0; j < ncols; ++j)
+        if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_loo_in + (size_t)j * n, in + (int64_t)j * ldin, sizeof(double) * (size_t)n,
+                                          hipMemcpyHostToDevice, st)))
+            return fail(GPV_ERR_HIP);
+    pl->loo_last_mode = mode;
+    pl->loo_last_ncols = ncols;
+    if (GPV_HIP_FAILED(loo_enqueue(pl, mode, ncols, vec != nullptr, st))) return fail(GPV_ERR_HIP);
+    double sc[kLooMaxCols * kLooNScores];
+    if (mode == kLooModeCV &&
+        GPV_HIP_FAILED(hipMemcpyAsync(sc, pl->d_loo_scores, sizeof(double) * (size_t)ncols * kLooNScores, hipMemcpyDeviceToHost, st)))
+        return fail(GPV_ERR_HIP);
+    if (out)
+        for (int j = 0; j < ncols; ++j)                                               // (out may be in: the columns were read before)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(out + (int64_t)j * ldout, pl->d_loo_out + (size_t)j * n, sizeof(double) * (size_t)n,
+                                              hipMemcpyDeviceToHost, st)))
+                return fail(GPV_ERR_HIP);
+    if (vec && GPV_HIP_FAILED(hipMemcpyAsync(vec, mode == kLooModeCV ? pl->d_loo_var.get() : pl->d_loo_qord.get(),
+                                             sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st)))
+        return fail(GPV_ERR_HIP);
+    GPV_HIP(hipStreamSynchronize(st));
+    const bool bad = pl->loo_nfail > 0;
+    *n_failed = (int64_t)pl->loo_nfail;
+    if (scores)
+        for (int t = 0; t < ncols * kLooNScores; ++t) scores[t] = bad ? (double)NAN : sc[t];
+    if (bad) {                                         // a failed row's NaN reaches every location that names it: no entry is trusted
+        if (out)
+            for (int j = 0; j < ncols; ++j) std::fill_n(out + (int64_t)j * ldout, (size_t)n, (double)NAN);
+        if (vec) std::fill_n(vec, (size_t)n, (double)NAN);
+    }
+    return GPV_OK;
+}
+
+int gpv_plan_whiten_t(gpv_plan *pl, const double *E_ord, int64_t lde, int ncols, double *B_ord, int64_t ldb, int64_t *n_failed)
+{
+    if (!pl || !E_ord || !B_ord || !n_failed) return GPV_ERR_BAD_ARG;
+    if (ncols < 1 || ncols > kLooMaxCols) return GPV_ERR_BAD_ARG;
+    if (lde < pl->Nlocs || ldb < pl->Nlocs) return GPV_ERR_BAD_ARG;
+    return loo_run(pl, kLooModeT, E_ord, lde, ncols, B_ord, ldb, nullptr, nullptr, n_failed);
+}
+
+int gpv_plan_precision(gpv_plan *pl, const double *B_ord, int64_t ldb, int ncols, double *R_ord, int64_t ldr, double *qdiag,
+                       int64_t *n_failed)
+{
+    if (!pl || !B_ord || !R_ord || !n_failed) return GPV_ERR_BAD_ARG;
+    if (ncols < 1 || ncols > kLooMaxCols) return GPV_ERR_BAD_ARG;
+    if (ldb < pl->Nlocs || ldr < pl->Nlocs) return GPV_ERR_BAD_ARG;
+    return loo_run(pl, kLooModeQ, B_ord, ldb, ncols, R_ord, ldr, qdiag, nullptr, n_failed);
+}
+
+int gpv_plan_loo(gpv_plan *pl, const double *Z_ord, int64_t ldz, int ncols, double *mean, int64_t ldm, double *var, double *scores,
+                 int64_t *n_failed)
+{
+    if (!pl || !Z_ord || !scores || !n_failed) return GPV_ERR_BAD_ARG;
+    if (ncols < 1 || ncols > kLooMaxCols) return GPV_ERR_BAD_ARG;
+    if (ldz < pl->Nlocs || (mean && ldm < pl->Nlocs)) return GPV_ERR_BAD_ARG;
+    return loo_run(pl, kLooModeCV, Z_ord, ldz, ncols, mean, ldm, var, scores, n_failed);
+}
+
+// developer aid (tools/loo_timing.py; not part of the public header): device time of `reps` runs of the device passes of the
+// latest gpv_plan_whiten_t / gpv_plan_precision / gpv_plan_loo over the columns it left on the device, by a pair of events
+// around them alone: no copies to or from the host
+extern "C" int gpv_plan_debug_loo_ms(gpv_plan *pl, int reps, double *ms)
+{
+    if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
+    if (const int rc = loo_state(pl)) return rc;
+    if (pl->loo_last_mode < 0 || !pl->loo_have_index || pl->loo_g_eval != pl->eval_count) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    Event a, b;
+    GPV_HIP(hipEventCreate(a.put()));
+    GPV_HIP(hipEventCreate(b.put()));
+    int rc = GPV_OK;
+    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
+        float t = 0.f;
+        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(loo_enqueue(pl, pl->loo_last_mode, pl->loo_last_ncols, true, st)) ||
             GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
             GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
             rc = GPV_ERR_HIP;

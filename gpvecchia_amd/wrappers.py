@@ -175,8 +175,11 @@ def profile_negloglik_grad(lg, data, X, va, covmodel="matern", smoothness=None):
 
 def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini=None, output_level=1,
                      reltol=np.sqrt(np.finfo(float).eps), seed=0, maxit=300, smoothness=None, method="Nelder-Mead",
-                     trend="ols", smoothness_grad=False, reneighbor=False, **specify_args):
-    """trend: "ols" (the reference, R/vecchia_wrappers.R:32-51: coefficients by ordinary least squares once, the covariance
+                     trend="ols", smoothness_grad=False, reneighbor=False, loo=False, **specify_args):
+    """loo=True (needs cond_yz='z' and a named family; the default changes nothing): the result gains `loo`, the leave-one-out
+    cross-validation summary of vecchia_loo at the estimate on the detrended data z (with trend="gls" the GLS residual): per
+    column rmse, mae, log_score, crps, coverage95, mean_sq_std_resid.
+    trend: "ols" (the reference, R/vecchia_wrappers.R:32-51: coefficients by ordinary least squares once, the covariance
     fitted to their residuals) or "gls": generalised least squares with the coefficients profiled out of the likelihood
     (vecchia_profile_likelihood: beta_hat(theta) under the Vecchia precision at every step), for X given or the constant
     column; needs cond_yz='z'.  Nelder-Mead then minimises the negative profile likelihood; "L-BFGS-B" and "fisher" take value and
@@ -222,6 +225,8 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     if trend not in ("ols", "gls"):
         raise ValueError(f"trend='{trend}' not defined")
     gls = trend == "gls"
+    if loo and (specify_args.get("cond_yz") != "z" or not isinstance(covmodel, str)):
+        raise ValueError("loo=True needs cond_yz='z' and a named covariance family (the fit vecchia_loo cross-validates)")
     if smoothness_grad and gls:
         raise ValueError("smoothness_grad=True is not available with trend='gls'")
     if smoothness_grad and covmodel != "matern":
@@ -449,6 +454,10 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     if gls:
         out["beta_cov"] = prof["beta_cov"]
         out["beta_se"] = np.sqrt(np.diag(prof["beta_cov"]))
+    if loo:
+        cp_hat, nug_hat = full(theta_hat)
+        cv = A.vecchia_loo(z, va, cp_hat, nug_hat, covmodel=covmodel)
+        out["loo"] = {k: cv[k] for k in ("rmse", "mae", "log_score", "crps", "coverage95", "mean_sq_std_resid")}
     return out
 
 

@@ -491,6 +491,52 @@ int gpv_plan_unwhiten(gpv_plan *plan, const double *E_ord, int64_t lde, int ncol
 int gpv_plan_simulate(gpv_plan *plan, uint64_t seed, int64_t col0, int64_t ncols, double *Z_ord, int64_t ldz,
                       int64_t *n_failed);
 
+/* The TRANSPOSE of the whitening operator, precision products and leave-one-out cross-validation.  With T the whitening
+ * operator of gpv_plan_whiten (row k: T_kk = 1/s_k, T_kj = L_kj / (d_k s_k), s_k = sqrt(tau_k + 1/d_k^2)) the precision matrix of
+ * the data vector under the cond.yz='z' likelihood is Q = T^T T, and for a Gaussian model no refitting is needed:
+ *   E[z_i | z_-i] = z_i - (Q z)_i / Q_ii,        Var[z_i | z_-i] = 1 / Q_ii.
+ * T^T reads the factor by column; the transposed index (for every location the stored entries that name it: 4 bytes per stored
+ * entry plus 8 bytes per location) is built on the host from the plan's index arrays at first use, kept with the plan and never
+ * rebuilt.  The passes gather, nothing is scattered and there are no floating-point atomics: results are bitwise reproducible
+ * from call to call, and a column's bits do not depend on the other columns of the call.  Everything is in the ORDERED row
+ * numbering, column-major with the given leading dimensions.
+ *   gpv_plan_whiten_t    B = T^T E
+ *   gpv_plan_precision   R = Q B = T^T (T B); qdiag: NULL, or out: diag Q (Nlocs)
+ *   gpv_plan_loo         from r = Q z and q = diag Q per column: mean (NULL, or Nlocs x ncols, leading dimension ldm) the
+ *             leave-one-out predictive means z_i - r_i / q_i; var (NULL, or Nlocs) the leave-one-out variances 1 / q_i, the same
+ *             for every column; scores (ncols x GPV_LOO_NSCORES, row-major) per column, with s_i = r_i / sqrt(q_i):
+ *               [0] sum (z_i - mean_i)^2   [1] sum |z_i - mean_i|   [2] sum s_i^2   [3] sum log var_i
+ *               [4] sum CRPS_i, CRPS_i = sqrt(var_i) [s_i (2 Phi(s_i) - 1) + 2 phi(s_i) - 1/sqrt(pi)]
+ *               [5] the count of |s_i| <= 1.959963984540054
+ *             the log predictive density is -(Nlocs log(2 pi) + [3] + [2]) / 2.
+ *   gpv_plan_loo_index   builds the transposed index if it is absent; out: its entries (own entries are not listed), the longest
+ *             column and the number of empty columns.  Needs no evaluation.
+ *   gpv_loo_index_host   the builder itself on host arrays, a plan's layout: nn [rows][P] internal positions, valid entries
+ *             right-aligned, -1 = missing, the own point last; rowid [rows] the output row of each stored set.  Out: colptr
+ *             (Nlocs + 1 starts), owner (Nlocs: flat offset output row x P + left-aligned slot of the own entry of the first set
+ *             that ends in the position, -1: none), col (NULL, or col_cap entries: the flat offsets of the entries that name
+ *             each position, ascending in stored-set order; a further set that ends in an owned position lists its own entry
+ *             here), *nnz their number.  GPV_ERR_INDEX for rows x P >= 2^31 (tested before any array is read).
+ * 1 <= ncols <= gpv_whiten_max_cols().  n_failed: rows whose block was not positive definite in that evaluation; with
+ * n_failed > 0 every output is NaN.  Blocking, on the plan's own stream; buffers are allocated on first use and belong to the
+ * plan.  The plan's last evaluation and what gpv_plan_whiten left on the device stay as they were (sums, Lentries, posterior
+ * state, factor stamp).  Arguments and state are validated before the device is touched, with the statuses of gpv_plan_whiten:
+ * GPV_ERR_BAD_ARG for a null pointer (the optional outputs excepted), a column count out of range or a leading dimension
+ * < Nlocs; GPV_ERR_STATE where gpv_plan_whiten returns it; GPV_ERR_INDEX for a plan with rows x P >= 2^31 (the flat offsets of the
+ * index are 32-bit). */
+#define GPV_LOO_NSCORES 6
+int gpv_loo_nscores(void);             /* GPV_LOO_NSCORES */
+int gpv_plan_whiten_t(gpv_plan *plan, const double *E_ord, int64_t lde, int ncols, double *B_ord, int64_t ldb,
+                      int64_t *n_failed);
+int gpv_plan_precision(gpv_plan *plan, const double *B_ord, int64_t ldb, int ncols, double *R_ord, int64_t ldr,
+                       double *qdiag /* NULL, or Nlocs */, int64_t *n_failed);
+int gpv_plan_loo(gpv_plan *plan, const double *Z_ord, int64_t ldz, int ncols,
+                 double *mean /* NULL, or Nlocs x ncols, leading dimension ldm */, int64_t ldm, double *var /* NULL, or Nlocs */,
+                 double *scores /* ncols x GPV_LOO_NSCORES, row-major */, int64_t *n_failed);
+int gpv_plan_loo_index(gpv_plan *plan, int64_t *n_entries, int64_t *max_column, int64_t *n_empty);
+int gpv_loo_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t Nlocs, int P, int32_t *colptr,
+                       int32_t *owner, int32_t *col /* NULL, or col_cap entries */, int64_t col_cap, int64_t *nnz);
+
 /* Vecchia-Laplace Newton-Raphson with the state on the device: calculate_posterior_VL of R/vecchia_laplace_NR.R:31-155
  * for fully observed data.  model: position in the reference's family list (:32): 0 gaussian, 1 logistic, 2 poisson,
  * 3 gamma, 4 beta, 5 gamma_alt.  likparms = {alpha, sigma} (:33), for beta {alpha, sigma, beta}.
