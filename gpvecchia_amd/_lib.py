@@ -47,6 +47,7 @@ EXPORTS = [
     "gpv_unwhiten_narrow", "gpv_plan_unwhiten_levels", "gpv_plan_unwhiten", "gpv_plan_simulate",
     "gpv_plan_set_replicates", "gpv_plan_replicates", "gpv_plan_loglik_rep", "gpv_plan_loglik_rep_nu",
     "gpv_loo_nscores", "gpv_plan_whiten_t", "gpv_plan_precision", "gpv_plan_loo", "gpv_plan_loo_index", "gpv_loo_index_host",
+    "gpv_blockcv_nscores", "gpv_blockcv_max_block", "gpv_plan_set_blocks", "gpv_plan_block_cv", "gpv_blocks_index_host",
 ]
 
 
@@ -140,6 +141,14 @@ def lib():
     L.gpv_plan_loo_index.argtypes = [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     i32p = C.POINTER(C.c_int32)
     L.gpv_loo_index_host.argtypes = [i32p, i32p, i64, i64, C.c_int, i32p, i32p, i32p, i64, C.POINTER(C.c_int64)]
+    L.gpv_blockcv_nscores.restype = C.c_int
+    L.gpv_blockcv_nscores.argtypes = []
+    L.gpv_blockcv_max_block.restype = C.c_int
+    L.gpv_blockcv_max_block.argtypes = []
+    L.gpv_plan_set_blocks.argtypes = [vp, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), ip, C.POINTER(C.c_int64)]
+    L.gpv_plan_block_cv.argtypes = [vp, dp, i64, C.c_int, dp, i64, dp, dp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+    L.gpv_blocks_index_host.argtypes = [i32p, i32p, i64, i64, C.c_int, i32p, i32p, C.POINTER(C.c_int64), C.POINTER(C.c_int64), ip,
+                                        C.POINTER(C.c_int64), i32p, i32p, i32p, i32p, i64, i32p]
     L.gpv_plan_set_replicates.argtypes = [vp, dp, i64, C.c_int]
     L.gpv_plan_replicates.argtypes = [vp, ip]
     L.gpv_plan_loglik_rep.argtypes = L.gpv_plan_loglik_fisher.argtypes

@@ -26,6 +26,8 @@ from ._lib import GPV_WANT_DENOM, GPV_WANT_LOGLIK_Z, GPV_WANT_NUMERATOR, GPV_WAN
 
 WHITEN_MAX_COLS = 16                                  # gpv_whiten_max_cols(): columns per Plan.whiten call
 LOO_NSCORES = 6                                       # gpv_loo_nscores(): score sums per column of Plan.loo
+BLOCKCV_NSCORES = 8                                   # gpv_blockcv_nscores(): score sums per column of Plan.block_cv
+BLOCKCV_MAX_BLOCK = 64                                # gpv_blockcv_max_block(): members of a held-out block
 
 
 # ---------------------------------------------------------------------------
@@ -393,6 +395,40 @@ class Plan:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         L.check(L.lib().gpv_plan_loo_index(self._h, C.byref(a), C.byref(b), C.byref(c)), "gpv_plan_loo_index")
         return int(a.value), int(b.value), int(c.value)
+
+    def set_blocks(self, block_of_ord):
+        """The held-out blocks of Plan.block_cv (gpv_plan_set_blocks): block_of_ord[i], i the ORDERED row, is -1 (never held
+        out: stays in the conditioning data) or a block id in [0, Nlocs); a block has at most 64 members of any shape.  Builds
+        the block index on the host (structure only: no evaluation needed, kept until the labels are replaced).  Returns
+        (n_blocks, n_heldout, max_size, n_set_refs).  A refused call leaves the plan's current blocks as they were."""
+        lab = np.asarray(block_of_ord)
+        if lab.ndim != 1 or lab.shape[0] != self.Nlocs or not np.issubdtype(lab.dtype, np.integer):
+            raise ValueError("block_of_ord must be one integer label per ordered location of the plan")
+        if lab.size and (lab.min() < np.iinfo(np.int32).min or lab.max() > np.iinfo(np.int32).max):
+            raise ValueError("block_of_ord: labels are -1 or a block id in [0, Nlocs)")
+        lab = np.ascontiguousarray(lab, dtype=np.int32)
+        nb, nh, nr, ms = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int(0)
+        L.check(L.lib().gpv_plan_set_blocks(self._h, lab.ctypes.data_as(C.POINTER(C.c_int32)), C.byref(nb), C.byref(nh), C.byref(ms),
+                                            C.byref(nr)), "gpv_plan_set_blocks")
+        return int(nb.value), int(nh.value), int(ms.value), int(nr.value)
+
+    def block_cv(self, Z_ord, want_mean=True, want_var=True):
+        """Leave-block-out cross-validation of the columns of Z_ord, (Nlocs, ncols) or (Nlocs,) in the ORDERED row numbering,
+        ncols <= 16, for the blocks of Plan.set_blocks under the plan's latest evaluation (GPV_WANT_U), without refitting
+        (gpv_plan_block_cv): with Q the precision of the data vector, z_B | z_-B ~ N(z_B - Q_BB^-1 (Q z)_B, Q_BB^-1) for every
+        block B.  Returns (mean (Nlocs, ncols) or None, var (Nlocs,) or None, scores (ncols, 8), n_failed, n_bad_blocks); mean
+        and var are NaN where the location is not held out.  scores per column over the held-out locations: [0] .. [5] as
+        Plan.loo, [6] the sum over the blocks of r_B' Q_BB^-1 r_B, [7] minus the sum of log det Q_BB.  All NaN with
+        n_failed > 0."""
+        Z, ncols = self._loo_columns(Z_ord, "Z_ord")
+        mean = np.zeros((self.Nlocs, ncols), order="F") if want_mean else None
+        var = np.zeros(self.Nlocs) if want_var else None
+        scores = np.zeros((ncols, BLOCKCV_NSCORES))
+        nf, nbad = C.c_int64(0), C.c_int64(0)
+        L.check(L.lib().gpv_plan_block_cv(self._h, L.dptr(Z), self.Nlocs, ncols, L.dptr(mean) if want_mean else None, self.Nlocs,
+                                          L.dptr(var) if want_var else None, L.dptr(scores), C.byref(nf), C.byref(nbad)),
+                "gpv_plan_block_cv")
+        return mean, var, scores, int(nf.value), int(nbad.value)
 
     def unwhiten_levels(self):
         """(n_levels, n_launches) of the level schedule unwhiten and simulate sweep through, built at first use
@@ -1566,6 +1602,104 @@ def vecchia_loo(z, vecchia_approx, covparms, nuggets, covmodel="matern", mean=No
     var[o] = vord
     out = dict(mean=M if mu is None else M + mu, var=var, resid_std=(Z - M) / np.sqrt(var)[:, None])
     out.update(loo_summary(scores, n))
+    return out
+
+
+def spatial_blocks(locs, max_size=BLOCKCV_MAX_BLOCK):
+    """Spatial blocks for vecchia_block_cv (host numpy, deterministic): recursive bisection of the locations (n x d) along
+    cycling coordinates, each cell split at the middle of a STABLE sort of its points on the coordinate (by rank, not by value:
+    duplicated points cannot stall it), until every cell holds <= max_size points.  Returns integer labels 0 .. n_cells - 1 in
+    the caller's order, cells numbered left first."""
+    locs = np.asarray(locs, dtype=np.float64)
+    if locs.ndim == 1:
+        locs = locs[:, None]
+    if locs.ndim != 2 or locs.shape[0] < 1 or locs.shape[1] < 1:
+        raise ValueError("spatial_blocks: locs must be n x d with n >= 1")
+    if int(max_size) != max_size or int(max_size) < 1:
+        raise ValueError("spatial_blocks: max_size must be an integer >= 1")
+    n, d = locs.shape
+    labels = np.empty(n, dtype=np.int64)
+    stack, nxt = [(np.arange(n), 0)], 0
+    while stack:
+        idx, axis = stack.pop()
+        if idx.size <= max_size:
+            labels[idx] = nxt
+            nxt += 1
+            continue
+        srt = idx[np.argsort(locs[idx, axis], kind="stable")]
+        half = (idx.size + 1) // 2
+        stack.append((np.sort(srt[half:]), (axis + 1) % d))            # (popped second: the left half is numbered first)
+        stack.append((np.sort(srt[:half]), (axis + 1) % d))
+    return labels
+
+
+def block_cv_summary(scores, n_heldout):
+    """The per-column summary of Plan.block_cv's score sums (ncols, 8) over n_heldout held-out locations: the keys of
+    loo_summary (with the block predictive means and variances), and joint_log_score, the joint log predictive density of all
+    blocks per held-out location."""
+    s = np.atleast_2d(np.asarray(scores, dtype=np.float64))
+    out = loo_summary(s[:, :LOO_NSCORES], n_heldout)
+    out["joint_log_score"] = -0.5 * (np.log(2.0 * np.pi) + (s[:, 7] + s[:, 6]) / n_heldout)
+    return out
+
+
+def _block_ids(name, blocks, locs, n):
+    """labels in the caller's order (None: spatial_blocks of the locations; -1: keep) -> block ids 0 .. through np.unique"""
+    if blocks is None:
+        return spatial_blocks(locs).astype(np.int32)
+    lab = np.asarray(blocks)
+    if lab.ndim != 1 or lab.shape[0] != n or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"{name}: blocks must be one integer label per location (-1: never held out)")
+    if np.any(lab < -1):
+        raise ValueError(f"{name}: block labels are -1 (never held out) or >= 0")
+    ids = np.full(n, -1, dtype=np.int32)
+    held = lab >= 0
+    if not held.any():
+        raise ValueError(f"{name}: no location is held out")
+    uniq, inv = np.unique(lab[held], return_inverse=True)
+    if np.bincount(inv).max() > BLOCKCV_MAX_BLOCK:
+        raise ValueError(f"{name}: a block has more than {BLOCKCV_MAX_BLOCK} members")
+    ids[held] = inv.astype(np.int32)
+    return ids
+
+
+def vecchia_block_cv(z, vecchia_approx, covparms, nuggets, covmodel="matern", blocks=None, mean=None, device=0):
+    """Leave-block-out cross-validation of the data under the Vecchia approximation of N(mean, C + tau I) at these parameters,
+    without refitting: one evaluation (GPV_WANT_U), Plan.set_blocks, then ceil(R / 16) Plan.block_cv calls.  z: a vector or
+    n x R (R realisations), in the CALLER's order of the locations; blocks: None (spatial_blocks of the locations: cells of at
+    most 64 points) or integer labels in the caller's order, -1 = never held out, at most 64 locations to a label; mean: None, a
+    scalar or one value per location, subtracted before and added back.  Returns a dict, everything in the caller's order and NaN
+    where a location is not held out: mean (n x R: E[z_i | the data outside i's block]), var (n,), resid_std (n x R), per column
+    the keys of block_cv_summary (arrays of length R), and n_blocks, n_heldout.  All NaN when some block of the approximation
+    was not positive definite at these parameters."""
+    va = vecchia_approx
+    Z = _user_columns("vecchia_block_cv", z, va)
+    n, R = Z.shape
+    mu = None
+    if mean is not None:
+        mu = np.asarray(mean, dtype=np.float64)
+        if mu.ndim > 1 or (mu.ndim == 1 and mu.size != n):
+            raise ValueError("vecchia_block_cv: mean must be a scalar or one value per location")
+        mu = mu if mu.ndim == 0 else mu[:, None]
+        Z = Z - mu
+    o = va["ord_z"] - 1
+    locs = np.empty(va["locsord"].shape)
+    locs[o] = va["locsord"]
+    ids = _block_ids("vecchia_block_cv", blocks, locs, n)
+    plan = _whiten_plan("vecchia_block_cv", va, covparms, nuggets, covmodel, device)
+    n_blocks, n_heldout, _, _ = plan.set_blocks(ids[o])
+    Zord = Z[o]
+    Mord, scores, vord = np.empty(Zord.shape), np.empty((R, BLOCKCV_NSCORES)), None
+    for c0 in range(0, R, WHITEN_MAX_COLS):
+        Mord[:, c0:c0 + WHITEN_MAX_COLS], v, scores[c0:c0 + WHITEN_MAX_COLS], _, _ = plan.block_cv(Zord[:, c0:c0 + WHITEN_MAX_COLS],
+                                                                                                  want_var=c0 == 0)
+        vord = v if c0 == 0 else vord
+    M, var = np.empty(Zord.shape), np.empty(n)
+    M[o] = Mord
+    var[o] = vord
+    out = dict(mean=M if mu is None else M + mu, var=var, resid_std=(Z - M) / np.sqrt(var)[:, None])
+    out.update(block_cv_summary(scores, n_heldout))
+    out.update(n_blocks=n_blocks, n_heldout=n_heldout)
     return out
 
 

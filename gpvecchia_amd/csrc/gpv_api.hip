@@ -15,6 +15,8 @@
 #include "gpv_unwhiten.h"
 #define GPV_LOO_LINKAGE __attribute__((weak))
 #include "gpv_loo.h"
+#define GPV_BLOCKCV_LINKAGE __attribute__((weak))
+#include "gpv_blockcv.h"
 #define GPV_SELINV_LINKAGE __attribute__((weak))
 #include "gpv_selinv.h"
 #define GPV_GRAD_SGV_LINKAGE __attribute__((weak))
@@ -495,6 +497,19 @@ struct gpv_plan {
     int loo_last_mode = -1, loo_last_ncols = 0;      // what gpv_plan_debug_loo_ms repeats
     int64_t loo_g_eval = 0;
     unsigned loo_nfail = 0;
+    // gpv_plan_set_blocks / gpv_plan_block_cv (gpv_blockcv.hip).  The block index (BlockIndex) stays until the labels are
+    // replaced.  The calls use the transposed index and d_loo_g above and column buffers of their OWN, so what gpv_plan_loo left
+    // on the device stays: the caller's columns and the means on their way back [cp][Nlocs], B, R, delta and y^2 by internal
+    // position [Nlocs][cp], E by ordered row, q, the variances and the -log pivots by internal position and ordered, the score
+    // partials [16][bcv_sgrid][8] and the scores [16][8]; d_bcv_nbad: the call's counter of bad blocks.
+    bool bcv_have = false;
+    int64_t bcv_nblocks = 0, bcv_nheld = 0, bcv_nrefs = 0;
+    int bcv_maxsize = 0;
+    DevBuf<int32_t> d_bcv_memptr, d_bcv_members, d_bcv_setptr, d_bcv_sets, d_bcv_blkloc;
+    DevBuf<double> d_bcv_in, d_bcv_out, d_bcv_B, d_bcv_E, d_bcv_R, d_bcv_q, d_bcv_D, d_bcv_Y2, d_bcv_y2ord, d_bcv_var, d_bcv_nlp,
+        d_bcv_varord, d_bcv_nlpord, d_bcv_part, d_bcv_scores;
+    DevBuf<unsigned> d_bcv_nbad;
+    int bcv_cp_cap = 0, bcv_grid = 0, bcv_sgrid = 0, bcv_last_ncols = 0;
     // d_L and the nuggets on the device (d_nuggets / nug_scalar) belong to evaluation L_of_eval of the plan (evaluations are
     // counted from 1; 0: to none).  Set at the end of an evaluation that materialised U, cleared before anything of the two is
     // rewritten: an evaluation that starts, a Vecchia-Laplace step that writes its pseudo-nuggets, a rebuilt posterior structure.
@@ -2846,6 +2861,22 @@ static hipError_t loo_enqueue(gpv_plan *pl, int mode, int ncols, bool want_q, hi
     return hipSuccess;
 }
 
+// the scale pre-pass: once per evaluation (needs loo_index)
+static int loo_scale_once(gpv_plan *pl, hipStream_t st)
+{
+    if (pl->loo_g_eval == pl->eval_count) return GPV_OK;
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    pl->loo_g_eval = 0;
+    if (GPV_HIP_FAILED(hipMemsetAsync(pl->d_loo_nfail, 0, sizeof(unsigned), st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_loo_scale(loo_args(pl), pl->loo_grid, st))) return fail(GPV_ERR_HIP);
+    unsigned nf = 0;
+    if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_loo_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return GPV_ERR_HIP;
+    pl->loo_nfail = nf;
+    pl->loo_g_eval = pl->eval_count;
+    return GPV_OK;
+}
+
 // Reads d_L, the index arrays and the nuggets of the plan's latest evaluation and writes buffers of its own, so the sums, the U
 // entries, the posterior state, the factor stamp and what gpv_plan_whiten left on the device stay what they were.
 //   in / out: ncols columns; vec: qdiag (kLooModeQ) or var (kLooModeCV), NULL = not wanted; out may be NULL in kLooModeCV
@@ -2870,16 +2901,7 @@ static int loo_run(gpv_plan *pl, int mode, const double *in, int64_t ldin, int n
         pl->loo_cp_cap = cp;
     }
     auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
-    if (pl->loo_g_eval != pl->eval_count) {            // the scale pre-pass: once per evaluation
-        pl->loo_g_eval = 0;
-        if (GPV_HIP_FAILED(hipMemsetAsync(pl->d_loo_nfail, 0, sizeof(unsigned), st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(launch_loo_scale(loo_args(pl), pl->loo_grid, st))) return fail(GPV_ERR_HIP);
-        unsigned nf = 0;
-        if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_loo_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return GPV_ERR_HIP;
-        pl->loo_nfail = nf;
-        pl->loo_g_eval = pl->eval_count;
-    }
+    if (const int rc = loo_scale_once(pl, st)) return rc;
     for (int j = 0; j < ncols; ++j)
         if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_loo_in + (size_t)j * n, in + (int64_t)j * ldin, sizeof(double) * (size_t)n,
                                           hipMemcpyHostToDevice, st)))
@@ -2956,6 +2978,233 @@ extern "C" int gpv_plan_debug_loo_ms(gpv_plan *pl, int reps, double *ms)
     for (int r = 0; r < reps && rc == GPV_OK; ++r) {
         float t = 0.f;
         if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(loo_enqueue(pl, pl->loo_last_mode, pl->loo_last_ncols, true, st)) ||
+            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
+            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
+            rc = GPV_ERR_HIP;
+        ms[r] = (double)t;
+    }
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// ---- leave-block-out cross-validation: per-block precision solves (gpv_blockcv.hip) ----------------------------------------
+int gpv_blockcv_nscores(void) { return kBcvNScores; }
+int gpv_blockcv_max_block(void) { return kBcvMaxBlock; }
+
+// gpv_blockcv.hip is part of this link (see GPV_BLOCKCV_LINKAGE in gpv_blockcv.h)
+static bool blockcv_linked()
+{
+    return &blockcv_grid != nullptr && &blockcv_score_grid != nullptr && &blockcv_check_labels != nullptr &&
+           &blockcv_build_index != nullptr && &launch_blockcv_blocks != nullptr && &launch_blockcv_scores != nullptr;
+}
+
+static int blockcv_status(int rc) { return rc == 0 ? GPV_OK : rc == 1 ? GPV_ERR_INDEX : GPV_ERR_BAD_ARG; }
+
+int gpv_blocks_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t Nlocs, int P, const int32_t *newpos,
+                          const int32_t *block_of_ord, int64_t *n_blocks, int64_t *n_heldout, int *max_size, int64_t *n_set_refs,
+                          int32_t *memptr, int32_t *members, int32_t *setptr, int32_t *sets, int64_t sets_cap, int32_t *blkloc)
+{
+    if (!n_blocks || !n_heldout || !max_size || !n_set_refs || rows < 0 || Nlocs < 0 || P < 1) return GPV_ERR_BAD_ARG;
+    if (!blockcv_linked()) return GPV_ERR_STATE;
+    if (rows * (int64_t)P >= ((int64_t)1 << 31) || Nlocs >= ((int64_t)1 << 31) - 1) return GPV_ERR_INDEX;      // before any array is read
+    if (!nn || !rowid || !block_of_ord) return GPV_ERR_BAD_ARG;
+    BlockIndex ix;
+    if (const int rc = blockcv_build_index(nn, rowid, rows, Nlocs, P, newpos, block_of_ord, ix)) return blockcv_status(rc);
+    *n_blocks = ix.n_blocks;
+    *n_heldout = ix.n_heldout;
+    *max_size = ix.max_size;
+    *n_set_refs = ix.n_set_refs;
+    if (memptr) std::copy(ix.memptr.begin(), ix.memptr.end(), memptr);
+    if (members) std::copy(ix.members.begin(), ix.members.end(), members);
+    if (setptr) std::copy(ix.setptr.begin(), ix.setptr.end(), setptr);
+    if (blkloc) std::copy(ix.blkloc.begin(), ix.blkloc.end(), blkloc);
+    if (sets) {
+        if (sets_cap < ix.n_set_refs) return GPV_ERR_BAD_ARG;
+        std::copy(ix.sets.begin(), ix.sets.end(), sets);
+    }
+    return GPV_OK;
+}
+
+int gpv_plan_set_blocks(gpv_plan *pl, const int32_t *block_of_ord, int64_t *n_blocks, int64_t *n_heldout, int *max_size,
+                        int64_t *n_set_refs)
+{
+    if (!pl || !block_of_ord || !n_blocks || !n_heldout || !max_size || !n_set_refs) return GPV_ERR_BAD_ARG;
+    if (!blockcv_linked()) return GPV_ERR_STATE;
+    if (const int rc = loo_structure(pl)) return rc;
+    const int64_t rows = pl->rows, n = pl->Nlocs;
+    const int P = pl->P;
+    if (pl->h_newpos.size() != (size_t)n) return GPV_ERR_STATE;
+    {                                                  // the labels by themselves, before the device is touched
+        std::vector<int32_t> ids, sizes;
+        if (blockcv_check_labels(block_of_ord, n, ids, sizes) != 0) return GPV_ERR_BAD_ARG;
+    }
+    GPV_HIP(hipSetDevice(pl->device));
+    std::vector<int32_t> nn((size_t)rows * P), rowid((size_t)rows);
+    GPV_HIP(hipMemcpy(nn.data(), pl->d_nn, nn.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    GPV_HIP(hipMemcpy(rowid.data(), pl->d_rowid, rowid.size() * sizeof(int32_t), hipMemcpyDeviceToHost));
+    BlockIndex ix;
+    if (const int rc = blockcv_build_index(nn.data(), rowid.data(), rows, n, P, pl->h_newpos.data(), block_of_ord, ix))
+        return rc == 2 ? GPV_ERR_STATE : blockcv_status(rc);
+    // the new index goes to buffers of its own first: a failure leaves the plan's current blocks as they were
+    DevBuf<int32_t> memptr, members, setptr, sets, blkloc;
+    GPV_BUF(memptr, upload(ix.memptr.data(), ix.memptr.size()));
+    GPV_BUF(members, upload(ix.members.data(), ix.members.size()));
+    GPV_BUF(setptr, upload(ix.setptr.data(), ix.setptr.size()));
+    GPV_BUF(sets, upload(ix.sets.data(), ix.sets.size()));
+    GPV_BUF(blkloc, upload(ix.blkloc.data(), ix.blkloc.size()));
+    GPV_HIP(hipStreamSynchronize(pl->stream));         // nothing of an earlier call still reads the index that is about to go
+    pl->d_bcv_memptr = std::move(memptr);
+    pl->d_bcv_members = std::move(members);
+    pl->d_bcv_setptr = std::move(setptr);
+    pl->d_bcv_sets = std::move(sets);
+    pl->d_bcv_blkloc = std::move(blkloc);
+    pl->bcv_nblocks = *n_blocks = ix.n_blocks;
+    pl->bcv_nheld = *n_heldout = ix.n_heldout;
+    pl->bcv_maxsize = *max_size = ix.max_size;
+    pl->bcv_nrefs = *n_set_refs = ix.n_set_refs;
+    pl->bcv_grid = blockcv_grid(ix.n_blocks, pl->cus);
+    pl->bcv_last_ncols = 0;
+    pl->bcv_have = true;
+    return GPV_OK;
+}
+
+// back to the ordered numbering, column-major, and the scores
+static hipError_t bcv_epilogue(gpv_plan *pl, int ncols, int cp, hipStream_t st)
+{
+    const int64_t n = pl->Nlocs;
+    hipError_t e;
+    if ((e = launch_loo_unpack(pl->d_bcv_D, pl->d_newpos, n, ncols, cp, pl->d_bcv_out, st)) != hipSuccess) return e;
+    if ((e = launch_loo_unpack(pl->d_bcv_Y2, pl->d_newpos, n, ncols, cp, pl->d_bcv_y2ord, st)) != hipSuccess) return e;
+    if ((e = launch_loo_unpack(pl->d_bcv_var, pl->d_newpos, n, 1, 1, pl->d_bcv_varord, st)) != hipSuccess) return e;
+    if ((e = launch_loo_unpack(pl->d_bcv_nlp, pl->d_newpos, n, 1, 1, pl->d_bcv_nlpord, st)) != hipSuccess) return e;
+    return launch_blockcv_scores(pl->d_bcv_in, pl->d_bcv_out, pl->d_bcv_y2ord, pl->d_bcv_varord, pl->d_bcv_nlpord, n, ncols,
+                                 pl->bcv_sgrid, pl->d_bcv_part, pl->d_bcv_scores, st);
+}
+
+// the device passes of one call on what is resident: d_bcv_in -> d_bcv_out, d_bcv_varord, d_bcv_scores, d_bcv_nbad.
+// parts (gpv_plan_debug_blockcv_ms): 1 = r = Q z (pack, forward, transposed), 2 = the fills and the block pass, 4 = unpack and scores
+static hipError_t bcv_enqueue(gpv_plan *pl, int ncols, hipStream_t st, int parts = 7)
+{
+    const int cp = whiten_cp(ncols);
+    const int64_t n = pl->Nlocs;
+    LooArgs a = loo_args(pl);
+    a.B = pl->d_bcv_B; a.E = pl->d_bcv_E; a.R = pl->d_bcv_R; a.q = pl->d_bcv_q;
+    hipError_t e;
+    if (parts & 1) {
+        if ((e = launch_loo_pack(pl->d_bcv_in, pl->d_newpos, n, ncols, cp, pl->d_bcv_B, st)) != hipSuccess) return e;
+        if ((e = launch_loo_forward(a, cp, pl->loo_grid, st)) != hipSuccess) return e;
+        if ((e = launch_loo_transposed(a, cp, pl->loo_grid, st)) != hipSuccess) return e;
+    }
+    if (!(parts & 2)) return parts & 4 ? bcv_epilogue(pl, ncols, cp, st) : hipSuccess;
+    // every byte 0xFF is a NaN: what a kept location and a bad block return
+    const size_t colbytes = sizeof(double) * (size_t)n * cp, vecbytes = sizeof(double) * (size_t)n;
+    if ((e = hipMemsetAsync(pl->d_bcv_D, 0xFF, colbytes, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(pl->d_bcv_Y2, 0xFF, colbytes, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(pl->d_bcv_var, 0xFF, vecbytes, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(pl->d_bcv_nlp, 0xFF, vecbytes, st)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(pl->d_bcv_nbad, 0, sizeof(unsigned), st)) != hipSuccess) return e;
+    BlockCvArgs b;
+    b.L = pl->d_L; b.nn = pl->d_nn; b.rowid = pl->d_rowid; b.g = pl->d_loo_g;
+    b.memptr = pl->d_bcv_memptr; b.members = pl->d_bcv_members; b.setptr = pl->d_bcv_setptr; b.sets = pl->d_bcv_sets;
+    b.blkloc = reinterpret_cast<const int2 *>(pl->d_bcv_blkloc.get());
+    b.B = pl->d_bcv_B; b.R = pl->d_bcv_R; b.D = pl->d_bcv_D; b.Y2 = pl->d_bcv_Y2; b.var = pl->d_bcv_var; b.nlp = pl->d_bcv_nlp;
+    b.nbad = pl->d_bcv_nbad;
+    b.n_blocks = pl->bcv_nblocks; b.P = pl->P;
+    if ((e = launch_blockcv_blocks(b, cp, pl->bcv_grid, st)) != hipSuccess) return e;
+    return parts & 4 ? bcv_epilogue(pl, ncols, cp, st) : hipSuccess;
+}
+
+// Reads what gpv_plan_loo reads (d_L, the index arrays, the nuggets, the transposed index, the scale of the evaluation) and
+// writes buffers of its own: the plan's last evaluation and what gpv_plan_whiten and gpv_plan_loo left on the device stay.
+int gpv_plan_block_cv(gpv_plan *pl, const double *Z_ord, int64_t ldz, int ncols, double *mean, int64_t ldm, double *var, double *scores,
+                      int64_t *n_failed, int64_t *n_bad_blocks)
+{
+    if (!pl || !Z_ord || !scores || !n_failed || !n_bad_blocks) return GPV_ERR_BAD_ARG;
+    if (ncols < 1 || ncols > kBcvMaxCols) return GPV_ERR_BAD_ARG;
+    if (ldz < pl->Nlocs || (mean && ldm < pl->Nlocs)) return GPV_ERR_BAD_ARG;
+    if (!blockcv_linked()) return GPV_ERR_STATE;
+    if (const int rc = loo_state(pl)) return rc;
+    if (!pl->bcv_have) return GPV_ERR_STATE;
+    const int64_t n = pl->Nlocs;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));   // the evaluation's stream
+    if (const int rc = loo_index(pl)) return rc;
+    const int cp = whiten_cp(ncols);
+    if (cp > pl->bcv_cp_cap) {
+        const size_t cnt = (size_t)n * cp;
+        pl->bcv_cp_cap = 0;
+        GPV_BUF(pl->d_bcv_in, resize(cnt));
+        GPV_BUF(pl->d_bcv_out, resize(cnt));
+        GPV_BUF(pl->d_bcv_B, resize(cnt));
+        GPV_BUF(pl->d_bcv_E, resize(cnt));
+        GPV_BUF(pl->d_bcv_R, resize(cnt));
+        GPV_BUF(pl->d_bcv_D, resize(cnt));
+        GPV_BUF(pl->d_bcv_Y2, resize(cnt));
+        GPV_BUF(pl->d_bcv_y2ord, resize(cnt));
+        GPV_BUF(pl->d_bcv_q, ensure((size_t)n));
+        GPV_BUF(pl->d_bcv_var, ensure((size_t)n));
+        GPV_BUF(pl->d_bcv_nlp, ensure((size_t)n));
+        GPV_BUF(pl->d_bcv_varord, ensure((size_t)n));
+        GPV_BUF(pl->d_bcv_nlpord, ensure((size_t)n));
+        GPV_BUF(pl->d_bcv_nbad, ensure(2));
+        pl->bcv_sgrid = blockcv_score_grid(n, pl->cus);
+        GPV_BUF(pl->d_bcv_part, ensure((size_t)kBcvMaxCols * pl->bcv_sgrid * kBcvNScores));
+        GPV_BUF(pl->d_bcv_scores, ensure((size_t)kBcvMaxCols * kBcvNScores));
+        pl->bcv_cp_cap = cp;
+    }
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    if (const int rc = loo_scale_once(pl, st)) return rc;
+    for (int j = 0; j < ncols; ++j)
+        if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_bcv_in + (size_t)j * n, Z_ord + (int64_t)j * ldz, sizeof(double) * (size_t)n,
+                                          hipMemcpyHostToDevice, st)))
+            return fail(GPV_ERR_HIP);
+    pl->bcv_last_ncols = ncols;
+    if (GPV_HIP_FAILED(bcv_enqueue(pl, ncols, st))) return fail(GPV_ERR_HIP);
+    double sc[kBcvMaxCols * kBcvNScores];
+    unsigned nbad = 0;
+    if (GPV_HIP_FAILED(hipMemcpyAsync(sc, pl->d_bcv_scores, sizeof(double) * (size_t)ncols * kBcvNScores, hipMemcpyDeviceToHost, st)))
+        return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(&nbad, pl->d_bcv_nbad, sizeof(nbad), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+    if (mean)
+        for (int j = 0; j < ncols; ++j)                                               // (mean may be Z_ord: the columns were read before)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(mean + (int64_t)j * ldm, pl->d_bcv_out + (size_t)j * n, sizeof(double) * (size_t)n,
+                                              hipMemcpyDeviceToHost, st)))
+                return fail(GPV_ERR_HIP);
+    if (var && GPV_HIP_FAILED(hipMemcpyAsync(var, pl->d_bcv_varord, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st)))
+        return fail(GPV_ERR_HIP);
+    GPV_HIP(hipStreamSynchronize(st));
+    const bool bad = pl->loo_nfail > 0;
+    *n_failed = (int64_t)pl->loo_nfail;
+    *n_bad_blocks = (int64_t)nbad;
+    for (int t = 0; t < ncols * kBcvNScores; ++t) scores[t] = bad ? (double)NAN : sc[t];
+    if (bad) {                                         // a failed row's NaN reaches every block that names it: no entry is trusted
+        if (mean)
+            for (int j = 0; j < ncols; ++j) std::fill_n(mean + (int64_t)j * ldm, (size_t)n, (double)NAN);
+        if (var) std::fill_n(var, (size_t)n, (double)NAN);
+    }
+    return GPV_OK;
+}
+
+// developer aid (tools/blockcv_timing.py; not part of the public header): device time of `reps` runs of the device passes of
+// the latest gpv_plan_block_cv over the columns it left on the device, by a pair of events around them alone; parts: 7 = all,
+// or 1 / 2 / 4 = one part of bcv_enqueue on what the other parts left
+extern "C" int gpv_plan_debug_blockcv_ms(gpv_plan *pl, int reps, int parts, double *ms)
+{
+    if (!pl || reps <= 0 || !ms || parts < 1 || parts > 7) return GPV_ERR_BAD_ARG;
+    if (!blockcv_linked()) return GPV_ERR_STATE;
+    if (const int rc = loo_state(pl)) return rc;
+    if (!pl->bcv_have || pl->bcv_last_ncols < 1 || !pl->loo_have_index || pl->loo_g_eval != pl->eval_count) return GPV_ERR_STATE;
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    Event a, b;
+    GPV_HIP(hipEventCreate(a.put()));
+    GPV_HIP(hipEventCreate(b.put()));
+    int rc = GPV_OK;
+    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
+        float t = 0.f;
+        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(bcv_enqueue(pl, pl->bcv_last_ncols, st, parts)) ||
             GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
             GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
             rc = GPV_ERR_HIP;

@@ -175,8 +175,12 @@ def profile_negloglik_grad(lg, data, X, va, covmodel="matern", smoothness=None):
 
 def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini=None, output_level=1,
                      reltol=np.sqrt(np.finfo(float).eps), seed=0, maxit=300, smoothness=None, method="Nelder-Mead",
-                     trend="ols", smoothness_grad=False, reneighbor=False, loo=False, **specify_args):
-    """loo=True (needs cond_yz='z' and a named family; the default changes nothing): the result gains `loo`, the leave-one-out
+                     trend="ols", smoothness_grad=False, reneighbor=False, loo=False, block_cv=False, **specify_args):
+    """block_cv=True or an array of integer block labels in the caller's order, -1 = never held out (needs cond_yz='z' and a
+    named family; the default changes nothing): the result gains `block_cv`, the leave-block-out cross-validation summary of
+    vecchia_block_cv at the estimate on the detrended data z, for the cells of spatial_blocks(locs) (True) or the given blocks:
+    per column rmse, mae, log_score, crps, coverage95, mean_sq_std_resid, joint_log_score, and n_blocks, n_heldout.
+    loo=True (needs cond_yz='z' and a named family; the default changes nothing): the result gains `loo`, the leave-one-out
     cross-validation summary of vecchia_loo at the estimate on the detrended data z (with trend="gls" the GLS residual): per
     column rmse, mae, log_score, crps, coverage95, mean_sq_std_resid.
     trend: "ols" (the reference, R/vecchia_wrappers.R:32-51: coefficients by ordinary least squares once, the covariance
@@ -227,6 +231,9 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     gls = trend == "gls"
     if loo and (specify_args.get("cond_yz") != "z" or not isinstance(covmodel, str)):
         raise ValueError("loo=True needs cond_yz='z' and a named covariance family (the fit vecchia_loo cross-validates)")
+    want_bcv = block_cv is not False and block_cv is not None
+    if want_bcv and (specify_args.get("cond_yz") != "z" or not isinstance(covmodel, str)):
+        raise ValueError("block_cv needs cond_yz='z' and a named covariance family (the fit vecchia_block_cv cross-validates)")
     if smoothness_grad and gls:
         raise ValueError("smoothness_grad=True is not available with trend='gls'")
     if smoothness_grad and covmodel != "matern":
@@ -458,6 +465,11 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
         cp_hat, nug_hat = full(theta_hat)
         cv = A.vecchia_loo(z, va, cp_hat, nug_hat, covmodel=covmodel)
         out["loo"] = {k: cv[k] for k in ("rmse", "mae", "log_score", "crps", "coverage95", "mean_sq_std_resid")}
+    if want_bcv:
+        cp_hat, nug_hat = full(theta_hat)
+        cv = A.vecchia_block_cv(z, va, cp_hat, nug_hat, covmodel=covmodel, blocks=None if block_cv is True else block_cv)
+        out["block_cv"] = {k: cv[k] for k in ("rmse", "mae", "log_score", "crps", "coverage95", "mean_sq_std_resid",
+                                              "joint_log_score", "n_blocks", "n_heldout")}
     return out
 
 

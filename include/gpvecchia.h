@@ -537,6 +537,51 @@ int gpv_plan_loo_index(gpv_plan *plan, int64_t *n_entries, int64_t *max_column, 
 int gpv_loo_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t Nlocs, int P, int32_t *colptr,
                        int32_t *owner, int32_t *col /* NULL, or col_cap entries */, int64_t col_cap, int64_t *nnz);
 
+/* Leave-BLOCK-out cross-validation: hold a whole set B of locations out and predict it from the rest.  With Q = T^T T as above,
+ * exactly and without refitting,
+ *   z_B | z_-B  ~  N( z_B - Q_BB^-1 (Q z)_B ,  Q_BB^-1 ).
+ * A block is any set of at most gpv_blockcv_max_block() = 64 locations (a spatial tile, scattered points, a coincident pair); a
+ * block of one is leave-one-out, and one block of every location returns the prior mean and the plan's log-likelihood as its
+ * joint density.  For each block the device assembles the dense Q_BB (Q_ab = sum over the conditioning sets that hold both a and
+ * b of T_ka T_kb), factors it and solves, one wavefront per block; r = Q z comes from the passes of gpv_plan_precision.  It
+ * gathers, nothing is scattered, there are no floating-point atomics: calls repeat bit for bit, a column's bits do not depend
+ * on the call's other columns, and the mean and variance of a block depend on its own members only, not on which other blocks
+ * exist or how they are labelled.  Scope and statuses are those of gpv_plan_loo.
+ *   gpv_plan_set_blocks  block_of_ord[i], i the ORDERED row: -1 = never held out (stays in the conditioning data), or a block
+ *             id in [0, Nlocs); ids without a member are skipped, the members of a block are taken in ascending ordered row.
+ *             Builds the block index on the host (structure only: it needs no evaluation and stays with the plan until the
+ *             labels are replaced) and reports the number of blocks, of held-out locations, the largest block and the length of
+ *             the set lists (per block the stored sets with at least one member in it: 4 bytes each, plus 12 bytes per location).
+ *             GPV_ERR_BAD_ARG for a label out of range, a block of more than 64 or no block at all, decided before the device is
+ *             touched; a refused call leaves the plan's current blocks as they were.
+ *   gpv_plan_block_cv    mean (NULL, or Nlocs x ncols, leading dimension ldm) the predictive means, var (NULL, or Nlocs)
+ *             diag(Q_BB^-1), the same for every column: both NaN at a location labelled -1.  scores (ncols x
+ *             GPV_BLOCKCV_NSCORES, row-major), sums over the N_h held-out locations only, with s = (z - mean) / sqrt(var):
+ *               [0] .. [5] as gpv_plan_loo with this mean and variance
+ *               [6] sum over the blocks of r_B' Q_BB^-1 r_B      [7] - sum over the blocks of log det Q_BB (the same in every column)
+ *             the joint log predictive density of all blocks is -(N_h log(2 pi) + [7] + [6]) / 2.  A block with a pivot that is
+ *             not > 0 is counted in n_bad_blocks, returns NaN and stays out of the sums.  GPV_ERR_STATE without blocks; n_failed
+ *             as gpv_plan_loo: with n_failed > 0 every output is NaN.  The plan's last evaluation and what gpv_plan_whiten and
+ *             gpv_plan_loo left on the device stay as they were.
+ *   gpv_blocks_index_host   the builder itself on host arrays (nn, rowid as gpv_loo_index_host; newpos: the internal position of
+ *             each ordered row, NULL = the identity).  Out, each NULL or of the documented size: memptr (n_blocks + 1; Nlocs + 1
+ *             always suffices), members (n_heldout internal positions), setptr (n_blocks + 1), sets (sets_cap >= n_set_refs stored
+ *             sets, ascending per block), blkloc (Nlocs x 2 by internal position: block and local index, -1 -1 = kept). */
+#define GPV_BLOCKCV_NSCORES 8
+int gpv_blockcv_nscores(void);         /* GPV_BLOCKCV_NSCORES */
+int gpv_blockcv_max_block(void);       /* 64 */
+int gpv_plan_set_blocks(gpv_plan *plan, const int32_t *block_of_ord /* Nlocs: -1 or id in [0, Nlocs) */,
+                        int64_t *n_blocks, int64_t *n_heldout, int *max_size, int64_t *n_set_refs);
+int gpv_plan_block_cv(gpv_plan *plan, const double *Z_ord, int64_t ldz, int ncols,
+                      double *mean /* NULL, or Nlocs x ncols */, int64_t ldm, double *var /* NULL, or Nlocs */,
+                      double *scores /* ncols x GPV_BLOCKCV_NSCORES, row-major */,
+                      int64_t *n_failed, int64_t *n_bad_blocks);
+int gpv_blocks_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t Nlocs, int P,
+                          const int32_t *newpos /* NULL, or Nlocs */, const int32_t *block_of_ord,
+                          int64_t *n_blocks, int64_t *n_heldout, int *max_size, int64_t *n_set_refs,
+                          int32_t *memptr, int32_t *members, int32_t *setptr,
+                          int32_t *sets /* NULL, or sets_cap entries */, int64_t sets_cap, int32_t *blkloc);
+
 /* Vecchia-Laplace Newton-Raphson with the state on the device: calculate_posterior_VL of R/vecchia_laplace_NR.R:31-155
  * for fully observed data.  model: position in the reference's family list (:32): 0 gaussian, 1 logistic, 2 poisson,
  * 3 gamma, 4 beta, 5 gamma_alt.  likparms = {alpha, sigma} (:33), for beta {alpha, sigma, beta}.

@@ -32,6 +32,7 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   $HIPCC $CF -c $CSRC/gpv_whiten.hip -o $B/whiten.o & pids+=($!)    # whitening and Gram passes: launchers only on the host
   $HIPCC $CF -c $CSRC/gpv_selinv.hip -o $B/selinv.o & pids+=($!)    # selected inverse: launchers only on the host
   $HIPCC $CF -c $CSRC/gpv_loo.hip -o $B/loo.o & pids+=($!)          # transposed whitening: launchers and the index builder
+  $HIPCC $CF -c $CSRC/gpv_blockcv.hip -o $B/blockcv.o & pids+=($!)  # leave-block-out: launchers and the block index builder
   for pb in 16 32 64; do                         # gradient pass of the SGV likelihood: the same buckets, then its dispatcher
     $HIPCC $CF -DGPV_SGV_PB=$pb -c $CSRC/gpv_grad_sgv.hip -o $B/grad_sgv_pb$pb.o & pids+=($!)
   done
@@ -169,6 +170,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   rc=${PIPESTATUS[0]}
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_loo.log; then
     echo "== $tag: loo_driver FAILED (rc $rc)"; return 1
+  fi
+  # ... and under the driver of the leave-block-out entries (tests/sanitize/blockcv_driver.cpp)
+  mkdir -p $B/blockcv
+  $HIPCC $CF -c $ROOT/tests/sanitize/blockcv_driver.cpp -o $B/blockcv/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/blockcv/driver.o -o $B/blockcv_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./blockcv_driver ) 2>&1 | tee $B/run_blockcv.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_blockcv.log; then
+    echo "== $tag: blockcv_driver FAILED (rc $rc)"; return 1
   fi
   echo "== $tag: clean"
 }
