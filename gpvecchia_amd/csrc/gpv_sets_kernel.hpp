@@ -92,6 +92,12 @@
 #ifndef GPV_OPT_XYSOA
 #define GPV_OPT_XYSOA 1       // three dimensions: staged coordinates coordinate-major (conflict-free partner reads)
 #endif
+#ifndef GPV_OPT_XYWIDE
+#define GPV_OPT_XYWIDE 1      // two dimensions, closed forms: the partner's (x, y) in one 16-byte LDS read from a bank-checked layout (SetsLdsDims)
+#endif
+#ifndef GPV_OPT_ROWB64
+#define GPV_OPT_ROWB64 1      // 2-D lean kernels: matrix rows into registers one column per LDS read (ds_read_b64: 2 LDS cycles per double, twice
+#endif                        // the instructions) instead of two (ds_read2_b64: 4 cycles per double); measured on its own, DESIGN.md section 5
 #ifndef GPV_OPT_GEN_NOLIVE
 #define GPV_OPT_GEN_NOLIVE 1  // general nu: no select on dist == 0 in the rounds; coincident points have s below every table segment,
 #endif                        // are flagged like any pair outside the table and get sigma^2 from the out-of-line pass
@@ -329,8 +335,9 @@ __device__ __forceinline__ KSetArgs *kargs_now()
     return k;
 }
 
+// Sizes and strides of a wavefront's LDS (SetsLds below; tools/lds_bank_model.py repeats these formulas: keep them equal)
 template <int P, int D, int COV>
-struct SetsLds {
+struct SetsLdsDims {
     using G = Geo<P>;
     static constexpr int SPW = G::SPW;
     static constexpr int TRI = (P * (P + 1) / 2 + 1) & ~1;   // doubles, even => 16 B aligned slices
@@ -340,26 +347,64 @@ struct SetsLds {
     // two sets do not collide (with a 256-B-aligned stride every pivot-row read paid a 2-way conflict)
     static constexpr int COLS0 = (G::SLOTS + 2) & ~1;
     static constexpr int COLS = ((COLS0 * 8) % 256 == 0) ? COLS0 + 2 : COLS0;
-    double tri[SPW][TRI];        // packed lower triangle (diagonal included): (hi,lo) at hi(hi+1)/2+lo
     static constexpr int NCOL = G::DPP ? 1 : 2;
-    double col[NCOL][SPW][COLS]; // LDS sweep: pivot-row exchange, double buffered; the last one doubles as the data-row staging
     // staged coordinates; with XYEXT rows P .. P+P/2-1 repeat rows 0 .. P/2-1, so that the circulant partner (r + s) mod P
     // of the covariance rounds is simply row r + s
     // (not for the general-nu variant: there every spare byte of LDS holds rows of the Matern table)
     static constexpr bool XYEXT = GPV_OPT_XYEXT != 0 && D != 0 && COV != COV_DENSE && COV != COV_MATERN_GEN;
-    static constexpr int XYROWS = XYEXT ? P + P / 2 : P;
     // D = 3: coordinate-major (x[rows], y[rows], z[rows]).  Row-major rows of 4 doubles put consecutive rows 32 bytes apart:
     // the rounds' partner reads (lane r reads row r + s) were 2-way (b128) and 4-way (b64) bank conflicts, two thirds of the
     // LDS-active cycles at P = 61, where ONE wavefront per SIMD hides nothing.  Coordinate-major: consecutive lanes read
-    // consecutive doubles (ds_read2_b64 + ds_read_b64, conflict free).  D = 2 keeps its 16-byte rows (one ds_read_b128).
+    // consecutive doubles (ds_read2_b64 + ds_read_b64, conflict free).
     static constexpr bool XYSOA = GPV_OPT_XYSOA != 0 && D == 3 && COV != COV_DENSE;
+    // D = 2 with extended rows (XYWIDE): the partner's (x, y) is ONE 16-byte read (ds_read_b128).  hipcc emits it only for an
+    // address it knows to be 16-byte aligned; from a pointer to double it issues ds_read2_b64 offset0:2k offset1:2k+1, whose
+    // two accesses each serve 16 contiguous lanes reading 8 B at a 16-B stride over 32 banks: lanes k and k + 8 collide, a
+    // 2-way conflict on every fetch.  A ds_read_b128 lane group, {0-3, 12-15, 20-27}, mixes two sets, so the layout is:
+    //   * the coordinates 256-B aligned with a per-set stride that is a multiple of 256 B (P = 31: 94 -> 96 doubles): the
+    //     two sets of a lane group then cover disjoint banks;
+    //   * a row slot that owns no row (slot r >= P) shadows row r - P, not row 0, and reads it and its partners from their
+    //     COPIES, rows r and r + s: every lane then reads the bank column of its own position in the set, whatever it owns
+    //     (row 0 + s and row 16 + s share their banks: shadowing row 0 was a 2-way conflict in every group of the second
+    //     slot).  So the copies go on to row SLOTS - 1 + P/2 (P = 31: one more row, P = 21: all of them);
+    //   * the coordinates directly behind the triangles, so that the padding fits the LDS of two workgroups per CU
+    //     (P = 31: 4 x 20 480 B = 81 920 B, exactly half of a CU's 160 KiB).
+    // One and three dimensions keep the layout they had.
+    static constexpr bool XYWIDE = GPV_OPT_XYWIDE != 0 && XYEXT && D == 2;
+    static constexpr int XEXT = XYEXT ? P / 2 + (XYWIDE ? G::SLOTS - P : 0) : 0;   // copied rows behind row P - 1
+    static_assert(XEXT <= P && G::SLOTS - P <= G::LPS, "every copied row is a row, every shadowed row one of the first slot");
+    static constexpr int XYROWS = P + XEXT;
     static constexpr int XS_ROW = XYSOA ? 1 : DS, XS_DIM = XYSOA ? XYROWS : 1;   // strides (doubles) of row and coordinate
-    double xy[SPW][XYSOA ? 3 * XYROWS : XYROWS * DS];
-    __device__ __forceinline__ double &xyat(int sub, int row, int t) { return xy[sub][row * XS_ROW + t * XS_DIM]; }
+    static constexpr int XYLEN0 = XYSOA ? 3 * XYROWS : XYROWS * DS;
+    static constexpr int XYLEN = XYWIDE ? ((XYLEN0 + 31) & ~31) : XYLEN0;        // per-set stride (doubles)
     static constexpr bool NEEDZERO = G::SLOTS > P + (G::ZROW ? 1 : 0);
-    double zero[NEEDZERO ? COLS : 2];   // source of the padding rows beyond the data row
-    double acc[SPW][kNSums];     // per-set running partial sums
-    int ix[COV == COV_DENSE ? SPW : 1][COV == COV_DENSE ? COLS : 2];   // staged neighbour indices (dense-covariance variant)
+};
+// the members in the order they always had ...
+template <class M, bool DENSE>
+struct SetsLdsPacked {
+    double tri[M::SPW][M::TRI];        // packed lower triangle (diagonal included): (hi,lo) at hi(hi+1)/2+lo
+    double col[M::NCOL][M::SPW][M::COLS]; // LDS sweep: pivot-row exchange, double buffered; the last one doubles as the data-row staging
+    double xy[M::SPW][M::XYLEN];       // staged coordinates
+    double zero[M::NEEDZERO ? M::COLS : 2];   // source of the padding rows beyond the data row
+    double acc[M::SPW][kNSums];        // per-set running partial sums
+    int ix[DENSE ? M::SPW : 1][DENSE ? M::COLS : 2];   // staged neighbour indices (dense-covariance variant)
+};
+// ... and for XYWIDE: 256-B aligned as a whole, the coordinates behind the triangles on a 256-B boundary
+template <class M>
+struct alignas(256) SetsLdsWide {
+    double tri[M::SPW][M::TRI];
+    alignas(256) double xy[M::SPW][M::XYLEN];
+    double col[M::NCOL][M::SPW][M::COLS];
+    double zero[M::NEEDZERO ? M::COLS : 2];
+    double acc[M::SPW][kNSums];
+    int ix[1][2];
+};
+template <int P, int D, int COV>
+struct SetsLds : SetsLdsDims<P, D, COV>,
+                 std::conditional_t<SetsLdsDims<P, D, COV>::XYWIDE, SetsLdsWide<SetsLdsDims<P, D, COV>>,
+                                    SetsLdsPacked<SetsLdsDims<P, D, COV>, COV == COV_DENSE>> {
+    using M = SetsLdsDims<P, D, COV>;
+    __device__ __forceinline__ double &xyat(int sub, int row, int t) { return this->xy[sub][row * M::XS_ROW + t * M::XS_DIM]; }
 };
 
 // waves per workgroup: 4 when two 4-wave workgroups fit the 160 KiB of LDS of a CU, else single-wave workgroups
@@ -547,6 +592,10 @@ __device__ __forceinline__ unsigned lds_addr(const void *p)
 }
 __device__ __forceinline__ lds_cdouble *lds_ptr(unsigned a) { return (lds_cdouble *)(uintptr_t)a; }
 __device__ __forceinline__ lds_wdouble *lds_wptr(unsigned a) { return (lds_wdouble *)(uintptr_t)a; }
+// a pair of doubles at a 16-byte aligned address (hipcc reads through a pointer to double with 8-byte instructions only)
+typedef double lds_double2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) const lds_double2 lds_cdouble2;
+__device__ __forceinline__ lds_cdouble2 *lds_ptr2(unsigned a) { return (lds_cdouble2 *)(uintptr_t)a; }
 
 // scale * exp(-t) for the closed-form Matern families, two instructions shorter per value than scale * exp_neg(t):
 //   * the Horner coefficients are multiplied by scale (= sigma^2) once per wavefront and kept in SGPRs, so the value
@@ -1103,7 +1152,8 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
         const unsigned tr0 = lds_addr(&L.tri[sub][0]);
 #pragma unroll
         for (int q = 0; q < RPL; ++q) {
-            const unsigned r = (lane_on && i_const + q * LPS < P) ? (unsigned)(i_const + q * LPS) : 0u;   // as rq[q] of the rounds
+            const int r0 = i_const + q * LPS;                    // as rq[q] of the rounds
+            const unsigned r = (lane_on && r0 < P) ? (unsigned)r0 : ((Lds::XYWIDE && lane_on) ? (unsigned)(r0 - P) : 0u);
             const unsigned rt8 = tr0 + __umul24(r, r + 1) * 4;
 #pragma unroll
             for (int s = 1; s <= P / 2; ++s) {
@@ -1121,7 +1171,7 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
     // an eleven-way bank conflict per store, which cost the short launches of m = 20 more than the masks had (kernel +3.4 %
     // at n = 1e5, measured); there, and for three coordinates in their coordinate-major layout, which do not fit the two
     // cells, a negative address marks such a slot and the store keeps one compare.
-    //   st_xy / st_xyx  staged coordinates of the slot's row and their copy behind row P - 1 (rows below P / 2)
+    //   st_xy / st_xyx  staged coordinates of the slot's row and their copy behind row P - 1 (rows below Lds::XEXT)
     //   st_xo           the row whose coordinates the slot's rounds use: its own, or row 0 (the shadow rows of the rounds)
     //   st_dg / st_z    the row's diagonal cell of the triangle and its cell of the data row; row P - 1 has no cell of the
     //                   data row (it is the point itself): that cell is cleared here, once, and every task leaves it at 0
@@ -1140,9 +1190,10 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
             const bool own = lane_on && r < P;
             const unsigned rc = own ? (unsigned)r : 0u;
             const unsigned nowhere = XYDUMP ? dump : 0x80000000u;
-            st_xo[q] = xy0 + rc * (Lds::XS_ROW * 8);
+            // (XYWIDE: a slot without a row shadows row r - P and reads its copy, row r)
+            st_xo[q] = xy0 + ((own || (Lds::XYWIDE && lane_on)) ? (unsigned)r : 0u) * (Lds::XS_ROW * 8);
             st_xy[q] = own ? st_xo[q] : nowhere;
-            st_xyx[q] = (lane_on && r < P / 2) ? st_xo[q] + P * Lds::XS_ROW * 8 : nowhere;
+            st_xyx[q] = (lane_on && r < Lds::XEXT) ? st_xo[q] + P * Lds::XS_ROW * 8 : nowhere;
             st_dg[q] = own ? tr0 + (__umul24(rc, rc + 1) * 4 + rc * 8) : (DUMP ? dump : 0x80000000u);
             st_z[q] = (own && r != P - 1) ? zr0 + rc * 8 : (DUMP ? dump : 0x80000000u);
             st_row[q] = own ? tr0 + __umul24(rc, rc + 1) * 4 : ((lane_on && r == P) ? zr0 : lds_addr(&L.zero[0]));
@@ -1204,7 +1255,7 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
 #pragma unroll
                         for (int t = 0; t < D; ++t) p[t * Lds::XS_DIM] = xi[q][t];
                     }
-                    if (q * LPS < P / 2) {
+                    if (q * LPS < Lds::XEXT) {
                         if (XYDUMP || (int)st_xyx[q] >= 0) {
                             lds_wdouble *const p = lds_wptr(st_xyx[q]);
 #pragma unroll
@@ -1273,8 +1324,8 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
 #pragma unroll
                     for (int t = 0; t < D; ++t) L.xyat(sub, row[q], t) = xi[q][t];
                 }
-                if (Lds::XYEXT && q * LPS < P / 2) {            // rows 0 .. P/2-1 once more behind row P-1 (folds after unrolling)
-                    if (lane_on && row[q] < P / 2) {
+                if (Lds::XYEXT && q * LPS < Lds::XEXT) {            // rows 0 .. XEXT-1 once more behind row P-1 (folds after unrolling)
+                    if (lane_on && row[q] < Lds::XEXT) {
 #pragma unroll
                         for (int t = 0; t < D; ++t) L.xyat(sub, row[q] + P, t) = xi[q][t];
                     }
@@ -1387,17 +1438,18 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
 #pragma unroll
             for (int q = 0; q < RPL; ++q) {
                 const bool own = lane_on && row[q] < P;
-                rq[q] = own ? row[q] : 0;                               // shadows row 0 of the set
+                // a slot without a row shadows row 0 of the set (XYWIDE: row r - P, read from its copy, row r: SetsLdsDims)
+                rq[q] = own ? row[q] : ((Lds::XYWIDE && lane_on) ? row[q] - P : 0);
 #pragma unroll
                 for (int t = 0; t < D; ++t) {
                     // (lean: a slot whose rows all lie below P keeps its registers; the last one reads back what its row, or the
                     // row it shadows, staged: the same bits without a select)
                     if constexpr (LEAN) xq[q][t] = ((q + 1) * LPS <= P) ? xi[q][t] : lds_ptr(st_xo[q])[t * Lds::XS_DIM];
-                    else xq[q][t] = own ? xi[q][t] : L.xyat(sub, 0, t);
+                    else xq[q][t] = own ? xi[q][t] : L.xyat(sub, Lds::XYWIDE ? rq[q] : 0, t);
                 }
-                vq[q] = own ? valid[q] : (bool)((vmask[0] >> (sub * LPS)) & 1ull);
+                vq[q] = own ? valid[q] : (bool)((vmask[0] >> (sub * LPS + (Lds::XYWIDE ? rq[q] : 0))) & 1ull);
                 if constexpr (LEAN) xoA[q] = st_xo[q];
-                else xoA[q] = xy0 + __umul24(rq[q], Lds::XS_ROW * 8);
+                else xoA[q] = xy0 + __umul24((Lds::XYWIDE && lane_on) ? row[q] : rq[q], Lds::XS_ROW * 8);
                 xoB[q] = xoA[q] - P * Lds::XS_ROW * 8;                  // (used by the lanes with row + s >= P only)
                 rq8[q] = rq[q] * 8;
                 // slot of the pair (r, r+s), minus 8 s: r+s < P: tri + 8 (rt + r (s+1) + s(s+1)/2 - s), kept incrementally;
@@ -1417,6 +1469,12 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
                 }
             };
             auto fetch = [&](int q, int s, double (&dst)[DD]) {
+                if constexpr (Lds::XYWIDE) {                             // 16-byte aligned by layout: one ds_read_b128
+                    const lds_double2 p = *lds_ptr2(xoA[q] + s * 16);
+                    dst[0] = p.x;
+                    dst[DD - 1] = p.y;
+                    return;
+                }
                 const lds_cdouble *xj = Lds::XYEXT ? lds_ptr(xoA[q] + s * Lds::XS_ROW * 8)
                                                    : lds_ptr(((rq[q] < P - s) ? xoA[q] : xoB[q]) + s * Lds::XS_ROW * 8);
 #pragma unroll
@@ -1581,7 +1639,9 @@ __global__ void __launch_bounds__((wpb<P, D, (COVX & (kCovLean - 1))>() * 64), G
             // (r,c) lives at r(r+1)/2 + c for c <= r and at c(c+1)/2 + r above the diagonal: one select per column;
             // slot P reads the staged data row, slots beyond read zeros
             if constexpr (LEAN) {                                 // the same cells from the wavefront's row address
-                lds_cdouble *const rowL = lds_ptr(st_row[q]);
+                // (GPV_OPT_ROWB64, 2-D: one ds_read_b64 per column -- a volatile load is not merged with its neighbour into the
+                // ds_read2_b64 hipcc otherwise makes of two columns)
+                std::conditional_t<GPV_OPT_ROWB64 != 0 && Lds::XYWIDE, volatile lds_cdouble, lds_cdouble> *const rowL = lds_ptr(st_row[q]);
                 static_for<0, P>([&](auto cc) __attribute__((always_inline)) {
                     constexpr int c = decltype(cc)::value;
                     if (c <= lik_maxcol<P>(q)) a[q][c] = rowL[c];
