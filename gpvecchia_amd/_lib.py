@@ -48,6 +48,7 @@ EXPORTS = [
     "gpv_plan_set_replicates", "gpv_plan_replicates", "gpv_plan_loglik_rep", "gpv_plan_loglik_rep_nu",
     "gpv_loo_nscores", "gpv_plan_whiten_t", "gpv_plan_precision", "gpv_plan_loo", "gpv_plan_loo_index", "gpv_loo_index_host",
     "gpv_blockcv_nscores", "gpv_blockcv_max_block", "gpv_plan_set_blocks", "gpv_plan_block_cv", "gpv_blocks_index_host",
+    "gpv_find_query_nn", "gpv_krige_max_cols", "gpv_plan_krige",
 ]
 
 
@@ -175,6 +176,12 @@ def lib():
     L.gpv_order_maxmin_exact.argtypes = [dp, i64, C.c_int, ip]
     L.gpv_ic0.argtypes = [i64, ip, ip, dp, C.POINTER(C.c_int64)]
     L.gpv_find_ordered_nn.argtypes = [C.c_int, dp, i64, C.c_int, C.c_int, i64, i64, ip]
+    u8p = C.POINTER(C.c_uint8)
+    L.gpv_find_query_nn.argtypes = [C.c_int, dp, i64, C.c_int, u8p, dp, i64, C.c_int, ip]
+    L.gpv_krige_max_cols.restype = C.c_int
+    L.gpv_krige_max_cols.argtypes = []
+    L.gpv_plan_krige.argtypes = [vp, C.c_char_p, dp, C.c_int, dp, i64, dp, i64, C.c_int, dp, i64, C.c_int, ip, dp, u8p, i64,
+                                 dp, i64, dp, C.POINTER(C.c_int64)]
     L.gpv_nn_max_m.restype = C.c_int
     L.gpv_nn_max_m.argtypes = []
     L.gpv_whichCondOnLatent.argtypes = [ip, i64, C.c_int, i64, ip]

@@ -28,6 +28,7 @@ WHITEN_MAX_COLS = 16                                  # gpv_whiten_max_cols(): c
 LOO_NSCORES = 6                                       # gpv_loo_nscores(): score sums per column of Plan.loo
 BLOCKCV_NSCORES = 8                                   # gpv_blockcv_nscores(): score sums per column of Plan.block_cv
 BLOCKCV_MAX_BLOCK = 64                                # gpv_blockcv_max_block(): members of a held-out block
+KRIGE_MAX_COLS = 16                                   # gpv_krige_max_cols(): data columns per Plan.krige call
 
 
 # ---------------------------------------------------------------------------
@@ -429,6 +430,50 @@ class Plan:
                                           L.dptr(var) if want_var else None, L.dptr(scores), C.byref(nf), C.byref(nbad)),
                 "gpv_plan_block_cv")
         return mean, var, scores, int(nf.value), int(nbad.value)
+
+    def krige(self, covmodel, covparms, nuggets_ord, qlocs, m, Z_ord=None, NNq=None, scale=None, eligible_ord=None, chunk=0):
+        """Local kriging at the prediction locations qlocs (nq, dim) under the cond.yz='z' model of this plan (gpv_plan_krige):
+        every location conditions on its m nearest observations (m + 1 <= 64), one independent solve each; needs no evaluation
+        and disturbs none.  nuggets_ord: one value or Nlocs in the ORDERED layout; Z_ord: None (the plan's data) or
+        (Nlocs[, ncols <= 16]) in the ORDERED layout; NNq: None (searched on the device, on the coordinates divided by `scale`
+        when given, skipping the locations whose eligible_ord is False) or (nq, m) ORDERED ids, 1-based, 0 = none; chunk:
+        locations per pass (0: the default), which changes no bit of the result.  Returns (mean (nq, ncols), var (nq,), n_failed):
+        the predictive mean of every column and the variance of the latent field; NaN where the location's block was not
+        positive definite (counted in n_failed)."""
+        q = np.asfortranarray(np.asarray(qlocs, dtype=np.float64).reshape(-1, self.dim))
+        nq = q.shape[0]
+        cp = np.ascontiguousarray(covparms, dtype=np.float64).reshape(-1)
+        nug = np.ascontiguousarray(np.atleast_1d(np.asarray(nuggets_ord, dtype=np.float64)))
+        Z, ncols = None, 1
+        if Z_ord is not None:
+            Z = np.asarray(Z_ord, dtype=np.float64)
+            Z = np.asfortranarray(Z[:, None] if Z.ndim == 1 else Z)
+            if Z.ndim != 2 or Z.shape[0] != self.Nlocs:
+                raise ValueError("Z_ord must have one row per ordered location of the plan")
+            ncols = Z.shape[1]
+        nn = None
+        if NNq is not None:
+            nn = np.asfortranarray(NNq, dtype=np.int32)
+            if nn.shape != (nq, int(m)):
+                raise ValueError("NNq must be (nq, m)")
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+        if sc is not None and sc.size != self.dim:
+            raise ValueError("scale must hold one number per coordinate")
+        el = None
+        if eligible_ord is not None:
+            el = np.ascontiguousarray(np.asarray(eligible_ord).astype(bool).reshape(-1), dtype=np.uint8)
+            if el.shape[0] != self.Nlocs:
+                raise ValueError("eligible_ord must hold one flag per ordered location of the plan")
+        mean = np.zeros((nq, ncols), order="F")
+        var = np.zeros(nq)
+        nf = C.c_int64(0)
+        u8 = C.POINTER(C.c_uint8)
+        L.check(L.lib().gpv_plan_krige(self._h, str(covmodel).encode(), L.dptr(cp), cp.size, L.dptr(nug), nug.size,
+                                       None if Z is None else L.dptr(Z), self.Nlocs, ncols, L.dptr(q), nq, int(m),
+                                       None if nn is None else L.iptr(nn), None if sc is None else L.dptr(sc),
+                                       None if el is None else el.ctypes.data_as(u8), int(chunk), L.dptr(mean), max(nq, 1),
+                                       L.dptr(var), C.byref(nf)), "gpv_plan_krige")
+        return mean, var, int(nf.value)
 
     def unwhiten_levels(self):
         """(n_levels, n_launches) of the level schedule unwhiten and simulate sweep through, built at first use
@@ -1701,6 +1746,69 @@ def vecchia_block_cv(z, vecchia_approx, covparms, nuggets, covmodel="matern", bl
     out.update(block_cv_summary(scores, n_heldout))
     out.update(n_blocks=n_blocks, n_heldout=n_heldout)
     return out
+
+
+def vecchia_krige(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="matern", m=None, mean=None, mean_pred=None,
+                  predict="y", nugget_pred=None, scale=None, device=0):
+    """Prediction at new locations under the cond.yz='z' Vecchia model, the one vecchia_likelihood scores and
+    vecchia_estimate(method="L-BFGS-B" | "fisher") fits: every prediction location is ordered last and conditions on its m
+    nearest observations, so its predictive distribution is local kriging, one independent solve per location on the GPU
+    (Plan.krige), streamed in chunks: the size of the map is not bounded by device memory.
+    z: (n,) or (n, R <= 16) in the CALLER's order; NaN entries of a single column are missing data and never enter a
+    conditioning set (NaN in several columns is refused).  vecchia_approx: a cond_yz='z' specification without prediction
+    locations; m=None takes its m.  mean / mean_pred: subtracted from z / added to the predictions (a scalar, or one value per
+    location[, column]).  predict='y' returns the variance of the latent field, 'z' adds nugget_pred (a scalar or one value
+    per prediction location).  scale: what vecchia_specify(scale=) was given ('matern_scaledim': the neighbours are searched
+    on locs / scale).  Returns dict(mean_pred (n_p[, R]), var_pred (n_p,), n_failed); a location whose block is not positive
+    definite (it coincides with an observation that has no nugget) is NaN."""
+    va = vecchia_approx
+    name = "vecchia_krige"
+    if va["cond_yz"] != "z":
+        raise ValueError(f"{name} needs cond_yz='z' (the other modes predict through the posterior factor: vecchia_prediction)")
+    n = va["locsord"].shape[0]
+    if int(np.sum(va["obs"])) != n:
+        raise ValueError(f"{name} does not take plans with prediction locations")
+    if not isinstance(covmodel, str):
+        raise ValueError(f"{name} needs a named covariance family ('matern', 'matern_scaledim' or 'esqe'), not a function or matrix")
+    if predict not in ("y", "z"):
+        raise ValueError(f"{name}: predict must be 'y' or 'z'")
+    Z = np.array(z, dtype=np.float64)
+    vector = Z.ndim == 1
+    if vector:
+        Z = Z[:, None]
+    if Z.ndim != 2 or Z.shape[0] != n or not 1 <= Z.shape[1] <= KRIGE_MAX_COLS:
+        raise ValueError(f"{name}: z must be (n,) or (n, R) with R <= {KRIGE_MAX_COLS}")
+    if mean is not None:
+        mu = np.asarray(mean, dtype=np.float64)
+        Z = Z - (mu if mu.ndim == 0 else mu.reshape(n, -1))
+    miss = np.isnan(Z)
+    eligible = None
+    if miss.any():
+        if Z.shape[1] > 1:
+            raise ValueError(f"{name}: missing values (NaN) are taken in a single column only")
+        eligible = ~miss[:, 0]
+        Z = np.where(miss, 0.0, Z)
+    if not np.all(np.isfinite(Z)):
+        raise ValueError(f"{name}: z must be finite (NaN marks a missing value)")
+    nug = np.atleast_1d(np.asarray(nuggets, dtype=np.float64))
+    if nug.size not in (1, n):
+        raise ValueError(f"{name}: nuggets must be one value or one per location")
+    lp = np.asarray(locs_pred, dtype=np.float64).reshape(-1, va["locsord"].shape[1])
+    n_p = lp.shape[0]
+    if m is None:
+        m = va["U_prep"]["revNNarray"].shape[1] - 1
+    ordz = va["ord_z"] - 1
+    plan = _plan_for(va, device)
+    mu_p, var_p, n_failed = plan.krige(covmodel, covparms, nug if nug.size == 1 else nug[ordz], lp, int(m), Z_ord=Z[ordz],
+                                       scale=scale, eligible_ord=None if eligible is None else eligible[ordz])
+    if mean_pred is not None:
+        mp = np.asarray(mean_pred, dtype=np.float64)
+        mu_p = mu_p + (mp if mp.ndim == 0 else mp.reshape(n_p, -1))
+    if predict == "z":
+        if nugget_pred is None:
+            raise ValueError(f"{name}: predict='z' needs nugget_pred")
+        var_p = var_p + np.asarray(nugget_pred, dtype=np.float64)
+    return dict(mean_pred=mu_p[:, 0] if vector else mu_p, var_pred=var_p, n_failed=n_failed)
 
 
 def profile_from_gram(G, logdet, n):

@@ -102,7 +102,7 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
                  kern + H("gpv_plist.h"), force))
     work.append((os.path.join(CSRC, "gpv_api.hip"), os.path.join(BUILD, "api.o"), list(extra_flags),
                  internal + [pub] + H("gpv_laplace.h", "gpv_generic.h", "gpv_posterior_ext.h", "gpv_philox.hpp", "gpv_grad.h",
-                                      "gpv_whiten.h", "gpv_unwhiten.h", "gpv_loo.h", "gpv_blockcv.h", "gpv_selinv.h", "gpv_grad_sgv.h", "gpv_hip_raii.hpp"), force))
+                                      "gpv_whiten.h", "gpv_unwhiten.h", "gpv_loo.h", "gpv_blockcv.h", "gpv_krige.h", "gpv_selinv.h", "gpv_grad_sgv.h", "gpv_hip_raii.hpp"), force))
     work.append((os.path.join(CSRC, "gpv_posterior.hip"), os.path.join(BUILD, "posterior.o"), list(extra_flags),
                  internal + H("gpv_posterior_ext.h"), force))
     work.append((os.path.join(CSRC, "gpv_lincomb.hip"), os.path.join(BUILD, "lincomb.o"), list(extra_flags),
@@ -125,9 +125,10 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
                  H("gpv_unwhiten.h", "gpv_philox.hpp"), force))
     work.append((os.path.join(CSRC, "gpv_loo.hip"), os.path.join(BUILD, "loo.o"), list(extra_flags), H("gpv_loo.h"), force))
     work.append((os.path.join(CSRC, "gpv_blockcv.hip"), os.path.join(BUILD, "blockcv.o"), list(extra_flags), H("gpv_blockcv.h"), force))
+    work.append((os.path.join(CSRC, "gpv_krige.hip"), os.path.join(BUILD, "krige.o"), list(extra_flags), internal + H("gpv_krige.h"), force))
     work.append((os.path.join(CSRC, "gpv_selinv.hip"), os.path.join(BUILD, "selinv.o"), list(extra_flags), H("gpv_selinv.h"), force))
     work.append((os.path.join(CSRC, "gpv_order.cpp"), os.path.join(BUILD, "order.o"), ["-x", "c++"], [pub], force))
-    work.append((os.path.join(CSRC, "gpv_nn.hip"), os.path.join(BUILD, "nn.o"), ["-ffp-contract=off"], internal + [pub], force))
+    work.append((os.path.join(CSRC, "gpv_nn.hip"), os.path.join(BUILD, "nn.o"), ["-ffp-contract=off"], internal + [pub] + H("gpv_krige.h"), force))
     jobs = jobs or min(8, os.cpu_count() or 1)
     with ThreadPoolExecutor(jobs) as ex:
         res = list(ex.map(_compile, work))

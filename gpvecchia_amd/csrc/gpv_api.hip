@@ -17,6 +17,8 @@
 #include "gpv_loo.h"
 #define GPV_BLOCKCV_LINKAGE __attribute__((weak))
 #include "gpv_blockcv.h"
+#define GPV_KRIGE_LINKAGE __attribute__((weak))
+#include "gpv_krige.h"
 #define GPV_SELINV_LINKAGE __attribute__((weak))
 #include "gpv_selinv.h"
 #define GPV_GRAD_SGV_LINKAGE __attribute__((weak))
@@ -510,6 +512,9 @@ struct gpv_plan {
         d_bcv_varord, d_bcv_nlpord, d_bcv_part, d_bcv_scores;
     DevBuf<unsigned> d_bcv_nbad;
     int bcv_cp_cap = 0, bcv_grid = 0, bcv_sgrid = 0, bcv_last_ncols = 0;
+    // gpv_plan_krige (gpv_krige.hip): device time of the latest call's searches and passes, summed over its chunks
+    // (gpv_plan_debug_krige_ms).  Its buffers live for the call.
+    double kr_search_ms = 0.0, kr_pass_ms = 0.0;
     // d_L and the nuggets on the device (d_nuggets / nug_scalar) belong to evaluation L_of_eval of the plan (evaluations are
     // counted from 1; 0: to none).  Set at the end of an evaluation that materialised U, cleared before anything of the two is
     // rewritten: an evaluation that starts, a Vecchia-Laplace step that writes its pseudo-nuggets, a rebuilt posterior structure.
@@ -3212,6 +3217,174 @@ extern "C" int gpv_plan_debug_blockcv_ms(gpv_plan *pl, int reps, int parts, doub
     }
     (void)hipStreamSynchronize(st);
     return rc;
+}
+
+// ---- local kriging of a cond.yz='z' plan at new locations (gpv_krige.hip; the search: gpv_nn.hip) --------------------------
+int gpv_krige_max_cols(void) { return kKrigeMaxCols; }
+
+// gpv_krige.hip is part of this link (see GPV_KRIGE_LINKAGE in gpv_krige.h)
+static bool krige_linked() { return &krige_grid != nullptr && &launch_krige != nullptr; }
+
+// Reads the plan's records, its data and newpos, and writes buffers that live for the call only (and d_gmt, the table of a
+// general smoothness, which the blocking gradient calls share): no evaluation is needed and none is disturbed.  Every refusal
+// comes before the device is touched and before anything is written.
+int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, const double *nuggets, int64_t n_nuggets,
+                   const double *Z_ord, int64_t ldz, int ncols, const double *qlocs, int64_t nq, int m, const int *NNq,
+                   const double *scale, const unsigned char *eligible_ord, int64_t chunk, double *mean, int64_t ldm, double *var,
+                   int64_t *n_failed)
+{
+    if (!pl || !covType || !covparms || !nuggets || !n_failed || nq < 0 || chunk < 0 || m < 1) return GPV_ERR_BAD_ARG;
+    if (nq > 0 && (!qlocs || !mean || !var)) return GPV_ERR_BAD_ARG;
+    const int64_t n = pl->Nlocs;
+    if ((n_nuggets != 1 && n_nuggets != n) || ncols < 1 || ncols > kKrigeMaxCols || ldm < nq) return GPV_ERR_BAD_ARG;
+    if (Z_ord ? ldz < n : ncols != 1) return GPV_ERR_BAD_ARG;
+    for (int64_t i = 0; i < n_nuggets; ++i)
+        if (!(nuggets[i] >= 0.0) || !std::isfinite(nuggets[i])) return GPV_ERR_BAD_ARG;
+    const bool matern = std::strcmp(covType, "matern") == 0, scaled = std::strcmp(covType, "matern_scaledim") == 0;
+    if (!matern && !scaled && std::strcmp(covType, "esqe") != 0) return GPV_ERR_COVTYPE;
+    if (ncovparms != (matern ? 3 : (scaled ? pl->dim + 2 : 4))) return GPV_ERR_BAD_ARG;
+    CovSetup cs;
+    if (const int rc = cov_setup(covType, covparms, ncovparms, pl->dim, cs)) return rc;
+    if (scale)
+        for (int t = 0; t < pl->dim; ++t)
+            if (!(scale[t] > 0.0) || !std::isfinite(scale[t])) return GPV_ERR_BAD_ARG;
+    if (m + 1 > kKrigeMaxP) return GPV_ERR_UNSUPPORTED_M;
+    if (!krige_linked() || pl->dim > kMaxDimGeneric || !pl->d_locs || !pl->d_newpos) return GPV_ERR_STATE;
+    // a row shard, unobserved locations, a neighbour conditioned on as latent (not a 'z' plan), no data to predict from
+    if (pl->comm || pl->rows != n || pl->d_obs || pl->latent_nb || (!Z_ord && !pl->has_z) || (int64_t)pl->h_newpos.size() != n)
+        return GPV_ERR_STATE;
+    if (NNq)
+        for (int64_t i = 0; i < nq * m; ++i)
+            if (NNq[i] < 0 || NNq[i] > n) return GPV_ERR_INDEX;
+    *n_failed = 0;
+    if (nq == 0) return GPV_OK;
+
+    GPV_HIP(hipSetDevice(pl->device));
+    hipStream_t st = pl->stream;
+    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    const int dim = pl->dim;
+    const bool packed = dim <= 3;
+    KrigeArgs a{};
+    a.rec = pl->d_locs; a.z = pl->d_z; a.newpos = pl->d_newpos;
+    a.m = m; a.dim = dim; a.locs_ld = pl->locs_ld; a.ncols = ncols;
+    a.cov = cs.cov; a.nscale = cs.nscale;
+    a.sA = cs.sA; a.cA = cs.cA; a.sB = cs.sB; a.cB = cs.cB; a.nug = nuggets[0];
+    for (int t = 0; t < 8; ++t) a.inv[t] = (cs.nscale && t < dim) ? cs.inv[t] : 1.0;
+    a.gen = MaternDerivConst{0.0, 0.0, 0.0};
+    if (cs.cov == COV_MATERN_GEN) {
+        // (cov_setup's sA is the normalised constant of the set kernel's value path: the tables hold C / sigma^2)
+        a.sA = covparms[0];
+        a.gen = matern_deriv_const(covparms[ncovparms - 1]);
+        int e_lo = 0, base = 0, nseg = 0;
+        const double lo = cs.nscale ? cs.inv_min : a.cA, hi = cs.nscale ? cs.inv_max : a.cA;
+        if (getenv("GPV_NO_MATERN_TABLE") == nullptr && pl->dist_min > 0.0 && pl->dist_max >= pl->dist_min &&
+            matern_dtab_range(0.5 * pl->dist_min * lo, 4.0 * pl->dist_max * hi, &e_lo, &base, &nseg)) {
+            GPV_BUF(pl->d_gmt, ensure((size_t)MaternDTab::MAX_SEG * MaternDTab::ROW));
+            GPV_HIP(launch_matern_dtab(a.gen, e_lo, nseg, pl->d_gmt, st));
+            a.gmt = pl->d_gmt; a.gmt_base = base; a.gmt_nseg = nseg;
+        }
+    }
+    // the call's nuggets and columns
+    DevBuf<double> d_nug, d_in, d_Z;
+    if (n_nuggets > 1) {
+        GPV_BUF(d_nug, upload(nuggets, (size_t)n));
+        a.nuggets = d_nug;
+    }
+    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
+    if (Z_ord) {
+        a.zld = (ncols + 3) / 4 * 4;
+        GPV_BUF(d_in, resize((size_t)n * ncols));
+        GPV_BUF(d_Z, resize((size_t)n * a.zld));
+        for (int j = 0; j < ncols; ++j)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(d_in + (size_t)j * n, Z_ord + (int64_t)j * ldz, sizeof(double) * (size_t)n,
+                                              hipMemcpyHostToDevice, st)))
+                return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_rep_pack(d_in, pl->d_newpos, n, ncols, a.zld, d_Z, st))) return fail(GPV_ERR_HIP);
+        a.Z = d_Z;
+    }
+    // the search over the plan's locations in the ORDERED numbering, on the coordinates divided by `scale`
+    struct Index { QnnIndex ix; ~Index() { qnn_free(ix); } } index;
+    if (!NNq) {
+        const int ld = packed ? 4 : pl->locs_ld;
+        std::vector<double> rec((size_t)n * ld), lc((size_t)n * dim);
+        if (GPV_HIP_FAILED(hipMemcpyAsync(rec.data(), pl->d_locs, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, st)) ||
+            GPV_HIP_FAILED(hipStreamSynchronize(st)))
+            return fail(GPV_ERR_HIP);
+        for (int t = 0; t < dim; ++t)
+            for (int64_t i = 0; i < n; ++i) {
+                const double x = rec[(size_t)pl->h_newpos[(size_t)i] * ld + t];
+                lc[(size_t)i + (size_t)t * n] = scale ? x / scale[t] : x;
+            }
+        if (GPV_HIP_FAILED(qnn_build(lc.data(), n, dim, eligible_ord, index.ix))) return fail(GPV_ERR_HIP);
+    }
+    // the chunks: queries up, search or neighbours up, the pass, results back
+    const int64_t cap = std::min<int64_t>(chunk > 0 ? chunk : kKrigeChunk, nq);
+    DevBuf<double> d_q, d_qs, d_mean, d_var;
+    DevBuf<int32_t> d_nn;
+    DevBuf<unsigned> d_nfail;
+    GPV_BUF(d_q, resize((size_t)cap * dim));
+    if (!NNq && scale) GPV_BUF(d_qs, resize((size_t)cap * dim));
+    GPV_BUF(d_mean, resize((size_t)cap * ncols));
+    GPV_BUF(d_var, resize((size_t)cap));
+    GPV_BUF(d_nn, resize((size_t)cap * m));
+    GPV_BUF(d_nfail, resize(2));
+    if (GPV_HIP_FAILED(hipMemsetAsync(d_nfail, 0, sizeof(unsigned), st))) return fail(GPV_ERR_HIP);
+    a.nnq = d_nn; a.q = d_q; a.mean = d_mean; a.var = d_var; a.nfail = d_nfail;
+    Event ev[3];                                           // around the search and the pass of a chunk
+    for (auto &e : ev) GPV_HIP(hipEventCreate(e.put()));
+    pl->kr_search_ms = pl->kr_pass_ms = 0.0;
+    std::vector<double> hq((size_t)cap * dim), hqs(d_qs ? (size_t)cap * dim : 0);
+    std::vector<int32_t> hnn(NNq ? (size_t)cap * m : 0);
+    for (int64_t c0 = 0; c0 < nq; c0 += cap) {
+        const int64_t cn = std::min(cap, nq - c0);
+        for (int t = 0; t < dim; ++t)
+            for (int64_t i = 0; i < cn; ++i) {
+                const double x = qlocs[c0 + i + (int64_t)t * nq];
+                hq[(size_t)i * dim + t] = x;
+                if (d_qs) hqs[(size_t)i * dim + t] = x / scale[t];
+            }
+        if (GPV_HIP_FAILED(hipMemcpyAsync(d_q, hq.data(), sizeof(double) * (size_t)cn * dim, hipMemcpyHostToDevice, st)))
+            return fail(GPV_ERR_HIP);
+        if (NNq) {
+            for (int s = 0; s < m; ++s)
+                for (int64_t i = 0; i < cn; ++i) hnn[(size_t)i * m + s] = NNq[c0 + i + (int64_t)s * nq];
+            if (GPV_HIP_FAILED(hipMemcpyAsync(d_nn, hnn.data(), sizeof(int32_t) * (size_t)cn * m, hipMemcpyHostToDevice, st)))
+                return fail(GPV_ERR_HIP);
+        } else {
+            if (d_qs && GPV_HIP_FAILED(hipMemcpyAsync(d_qs, hqs.data(), sizeof(double) * (size_t)cn * dim, hipMemcpyHostToDevice, st)))
+                return fail(GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return fail(GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(qnn_search(index.ix, d_qs ? d_qs.get() : d_q.get(), cn, m, d_nn, st))) return fail(GPV_ERR_HIP);
+        }
+        a.nq = cn;
+        if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_krige(a, krige_grid(cn, pl->cus), st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipEventRecord(ev[2], st))) return fail(GPV_ERR_HIP);
+        for (int j = 0; j < ncols; ++j)
+            if (GPV_HIP_FAILED(hipMemcpyAsync(mean + (int64_t)j * ldm + c0, d_mean + (size_t)j * cn, sizeof(double) * (size_t)cn,
+                                              hipMemcpyDeviceToHost, st)))
+                return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipMemcpyAsync(var + c0, d_var, sizeof(double) * (size_t)cn, hipMemcpyDeviceToHost, st)))
+            return fail(GPV_ERR_HIP);
+        GPV_HIP(hipStreamSynchronize(st));                 // (the staging vectors and the chunk buffers are reused)
+        float t = 0.f;
+        if (!NNq && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) pl->kr_search_ms += (double)t;
+        if (hipEventElapsedTime(&t, ev[1], ev[2]) == hipSuccess) pl->kr_pass_ms += (double)t;
+    }
+    unsigned nbad = 0;
+    GPV_HIP(hipMemcpy(&nbad, d_nfail, sizeof(nbad), hipMemcpyDeviceToHost));
+    *n_failed = (int64_t)nbad;
+    return GPV_OK;
+}
+
+// developer aid (tools/krige_timing.py; not part of the public header): device time of the searches and of the passes of the
+// latest gpv_plan_krige, each summed over the call's chunks, by event pairs around them alone
+extern "C" int gpv_plan_debug_krige_ms(gpv_plan *pl, double *ms)
+{
+    if (!pl || !ms) return GPV_ERR_BAD_ARG;
+    ms[0] = pl->kr_search_ms;
+    ms[1] = pl->kr_pass_ms;
+    return GPV_OK;
 }
 
 // LincombArgs::lrec from the plan's structure as it lives on the device (built on the first gpv_plan_lincomb after a

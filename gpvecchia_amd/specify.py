@@ -205,6 +205,68 @@ def find_ordered_nn_gpu(locs, m, rows=None, device=0):
     return np.ascontiguousarray(out)
 
 
+def find_query_nn(locs, qlocs, m, eligible=None, workers=-1):
+    """Nearest observations of query points, on the host, exact by the definition of gpv_find_query_nn: row q lists the
+    min(m, #eligible) eligible points of locs closest to qlocs[q] by ascending distance (the arithmetic of _canon_dist), lower
+    index first among equal distances.  eligible: None or n booleans, False = the point enters no list.  A point with a NaN or
+    infinite coordinate enters no list, a query with one gets a row of zeros.  Returns int32 (nq, m), 1-based, 0-padded."""
+    from scipy.spatial import cKDTree
+    locs = np.ascontiguousarray(locs, dtype=np.float64)
+    q = np.ascontiguousarray(qlocs, dtype=np.float64).reshape(-1, locs.shape[1])
+    m = int(m)
+    if m < 1:
+        raise ValueError("find_query_nn needs m >= 1")
+    ok = np.all(np.isfinite(locs), axis=1)
+    if eligible is not None:
+        ok &= np.asarray(eligible).astype(bool).reshape(-1)
+    idx = np.nonzero(ok)[0]
+    NN = np.zeros((q.shape[0], m), dtype=np.int32)
+    pending = np.nonzero(np.all(np.isfinite(q), axis=1))[0]
+    if idx.size == 0 or pending.size == 0:
+        return NN
+    tree = cKDTree(locs[idx])
+    kk = min(idx.size, 2 * m + 2)
+    while pending.size:
+        dq, ind = tree.query(q[pending], k=kk, workers=workers)
+        dq, ind = dq.reshape(len(pending), -1), ind.reshape(len(pending), -1)
+        cand = idx[ind]
+        ssq = np.zeros(cand.shape)
+        for t in range(locs.shape[1]):
+            df = q[pending, t][:, None] - locs[cand, t]
+            ssq += df * df
+        d = np.sqrt(ssq)
+        o = np.lexsort((cand, d), axis=1)[:, :m]
+        ds = np.take_along_axis(d, o, axis=1)
+        # exact under ties: the last kept distance must lie strictly inside the queried ball, otherwise an equidistant point
+        # with a lower index may have been cut off by the k-NN query
+        done = (dq[:, -1] > ds[:, -1] * (1 + 1e-9)) if kk < idx.size else np.ones(len(pending), dtype=bool)
+        sel = np.nonzero(done)[0]
+        NN[pending[sel], :o.shape[1]] = np.where(np.isfinite(ds[sel]), np.take_along_axis(cand, o, axis=1)[sel] + 1, 0)
+        pending = pending[~done]
+        kk = min(idx.size, kk * 2)
+    return NN
+
+
+def find_query_nn_gpu(locs, qlocs, m, eligible=None, device=0):
+    """Same result as find_query_nn (bit-exact), computed on the GPU (gpv_find_query_nn): brute force, or in one to three
+    dimensions from 2048 searchable points on through a uniform grid.  Returns int32 (nq, m), 1-based, 0-padded."""
+    import ctypes as C
+    from . import _lib as L
+    locs = np.asfortranarray(locs, dtype=np.float64)
+    n, d = locs.shape
+    q = np.asfortranarray(np.asarray(qlocs, dtype=np.float64).reshape(-1, d))
+    nq = q.shape[0]
+    el = None
+    if eligible is not None:
+        el = np.ascontiguousarray(np.asarray(eligible).astype(bool).reshape(-1), dtype=np.uint8)
+        if el.shape[0] != n:
+            raise ValueError("eligible must hold one flag per point of locs")
+    out = np.zeros((nq, int(m)), dtype=np.int32, order="F")
+    L.check(L.lib().gpv_find_query_nn(int(device), L.dptr(locs), n, d, None if el is None else el.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                      L.dptr(q), nq, int(m), L.iptr(out)), "gpv_find_query_nn")
+    return np.ascontiguousarray(out)
+
+
 def whichCondOnLatent(NNarray, firstind_pred=None, native=True):
     """R/whichCondOnLatent.R:2-26 (SGV rule).  NNarray int (n, m+1), 1-based, 0 = NA.
     Returns int8 (n, m+1): 1 TRUE (latent), 0 FALSE (observed), -1 NA.

@@ -473,16 +473,30 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     return out
 
 
-def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, **specify_args):
+def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, local=False, **specify_args):
     """R/vecchia_wrappers.R:134-161: spatial prediction at new locations from the result of vecchia_estimate, with the
     exact prediction variances of the latent field (vecchia_prediction(..., return_values='meanvar')).  With prediction locations in two or more dimensions vecchia_specify defaults to
-    cond.yz='zy' (R/vecchia_specify.R:92-96), whose posterior mean is one triangular solve on the GPU."""
+    cond.yz='zy' (R/vecchia_specify.R:92-96), whose posterior mean is one triangular solve on the GPU.
+    local=True (the default changes nothing): the prediction of the cond_yz='z' model itself, the one vecchia_estimate fits with
+    cond_yz='z', by local kriging on the m nearest observations of every location (vecchia_krige): no posterior pass, any
+    number of prediction locations.  The observations are specified again with cond_yz='z' (specify_args as for
+    vecchia_estimate); the trend is added back as below."""
     import warnings
-    from .laplace import vecchia_prediction
-    va = A.vecchia_specify(vecchia_est["locs"], m, locs_pred=np.asarray(locs_pred, dtype=np.float64), **specify_args)   # :137
     theta_hat = np.asarray(vecchia_est["theta_hat"], dtype=np.float64)                               # :140-143
-    preds = vecchia_prediction(vecchia_est["z"], va, theta_hat[:-1], theta_hat[-1],
-                               covmodel=vecchia_est.get("covmodel", "matern"), return_values="meanvar", device=device)
+    if local:
+        if specify_args.setdefault("cond_yz", "z") != "z":
+            raise ValueError("local=True predicts the cond_yz='z' model")
+        if np.asarray(vecchia_est["z"]).ndim != 1:
+            raise ValueError("local=True takes the result of an estimation from one data vector")
+        va = A.vecchia_specify(vecchia_est["locs"], m, **specify_args)
+        kr = A.vecchia_krige(vecchia_est["z"], va, locs_pred, theta_hat[:-1], theta_hat[-1],
+                             covmodel=vecchia_est.get("covmodel", "matern"), scale=specify_args.get("scale"), device=device)
+        preds = dict(mu_pred=kr["mean_pred"], var_pred=kr["var_pred"])
+    else:
+        from .laplace import vecchia_prediction
+        va = A.vecchia_specify(vecchia_est["locs"], m, locs_pred=np.asarray(locs_pred, dtype=np.float64), **specify_args)   # :137
+        preds = vecchia_prediction(vecchia_est["z"], va, theta_hat[:-1], theta_hat[-1],
+                                   covmodel=vecchia_est.get("covmodel", "matern"), return_values="meanvar", device=device)
     if X_pred is not None:                                                                           # :146-147
         mu_pred = preds["mu_pred"] + np.asarray(X_pred, dtype=np.float64) @ vecchia_est["beta_hat"]
     elif vecchia_est["trend"] == "none":                                                             # :148-149

@@ -746,6 +746,60 @@ int gpv_nn_max_m(void);                /* 212 */
 int gpv_find_ordered_nn(int device, const double *locs, int64_t n, int dim, int m, int64_t row_begin, int64_t row_end,
                         int *NNarray);
 
+/* Nearest observations of QUERY points that are not plan points, on the GPU, bit-exact: for each query the
+ * min(m, #eligible) eligible points of locs closest to it, by ascending distance in the arithmetic of gpv_find_ordered_nn
+ * (separately rounded products and sums accumulated left to right, compared on the correctly rounded square root), ties
+ * towards the lower index.  locs: n x dim, qlocs: nq x dim, NN: nq x m, all column-major; NN is 1-based and 0-padded.
+ * eligible: NULL (every point) or n bytes, 0 = the point enters no list (how missing data stay out of conditioning sets).
+ * Two routes give the same arrays bit for bit: brute force, and in one to three dimensions from 2048 searchable points on a
+ * uniform grid walked in shells (queries outside the bounding box of the points included); GPV_NN_BRUTE=1 in the environment
+ * forces the first.  A point with a NaN or infinite coordinate enters no list; a query with one gets a row of zeros.
+ * Limits: 1 <= dim <= 8, 1 <= m <= gpv_nn_max_m(), 0 < n < 2^31, 0 <= nq < 2^31 - 64.
+ * Statuses: GPV_ERR_BAD_ARG for a NULL pointer (eligible excepted) or anything outside these limits, checked before the
+ * device is touched; GPV_ERR_NO_DEVICE; GPV_ERR_HIP.  NN is written only by a call that returns GPV_OK; nq == 0 is GPV_OK. */
+int gpv_find_query_nn(int device, const double *locs, int64_t n, int dim, const unsigned char *eligible, const double *qlocs,
+                      int64_t nq, int m, int *NN);
+
+/* Local kriging: the predictive distribution of a cond.yz='z' model at new locations (gpv_krige.hip).  Under that model a
+ * prediction location ordered last conditions on its m nearest observations J and on nothing else; with the location as the
+ * last row of S = C(J u q, J u q) + diag(tau_J, 0) and u = S^-1 e_last,
+ *     var[q] = 1 / u_last (of the latent field y; add the nugget of the location for z),
+ *     mean[q, c] = -(sum_{j in J} u_j z_{j,c}) / u_last,
+ * one independent solve per location, one wavefront each.  Appending the location to the plan as its last row gives
+ * loglik([z; z0]) = loglik(z) + log N(z0; mean, var + tau_0): it is the prediction of the model the likelihood scores.
+ *   covType, covparms, ncovparms   "matern" (any smoothness in (0, 60]), "esqe", "matern_scaledim" (up to 8 coordinates)
+ *   nuggets, n_nuggets             1 value, or Nlocs in the ORDERED layout; finite and >= 0
+ *   Z_ord, ldz, ncols              ncols <= gpv_krige_max_cols() = 16 data columns in the ORDERED layout, ldz >= Nlocs apart;
+ *                                  NULL (ncols = 1): the plan's data (gpv_plan_set_data)
+ *   qlocs, nq, m                   nq x dim column-major prediction locations; m + 1 <= 64 neighbours each
+ *   NNq                            NULL: the search of gpv_find_query_nn on the device, over the plan's locations; else nq x m
+ *                                  column-major ORDERED ids, 1-based, 0 = none (eligible_ord and scale are then not used)
+ *   scale                          NULL, or one positive number per coordinate: the search runs on the coordinates divided by
+ *                                  it, the covariance on the true ones (vecchia_specify(scale=) for "matern_scaledim")
+ *   eligible_ord                   NULL, or Nlocs bytes in the ORDERED layout: 0 = never a neighbour (missing data)
+ *   chunk                          prediction locations per pass, 0: 262144.  The call streams nq in chunks (queries up, search
+ *                                  or neighbours up, the pass, results back), so device memory does not grow with nq; a
+ *                                  location's bits do not depend on the chunking, a column's not on the other columns
+ *   mean, ldm, var, n_failed       nq x ncols column-major (ldm >= nq), nq, and the count of locations whose block was not
+ *                                  positive definite ("pivot <= 0 or NaN", e.g. a location on an observation that has no
+ *                                  nugget): their mean and var are NaN
+ * Needs no evaluation and disturbs none; whatever it allocates lives for the call or is freed with the plan.
+ * Arguments and state are validated before the device is touched, and a refused call writes nothing.  GPV_ERR_BAD_ARG: a null
+ * pointer (Z_ord, NNq, scale, eligible_ord excepted), n_nuggets not 1 or Nlocs, a nugget < 0 or not finite, ncols outside
+ * [1, 16] (or not 1 with Z_ord NULL), ldz < Nlocs, ldm < nq, nq < 0, m < 1, chunk < 0, a scale <= 0, ncovparms not 3 / 4 /
+ * dim + 2; GPV_ERR_COVTYPE; GPV_ERR_UNSUPPORTED_NU; GPV_ERR_UNSUPPORTED_M: m + 1 > 64; GPV_ERR_INDEX: an entry of NNq outside
+ * [0, Nlocs]; GPV_ERR_STATE: a row shard, a communicator attached, unobserved locations (gpv_plan_set_observed), latent
+ * conditioning (not a cond.yz='z' plan), Z_ord NULL and no data set, a plan without coordinates, a library linked without
+ * gpv_krige.hip.  nq == 0 is GPV_OK. */
+int gpv_krige_max_cols(void);          /* 16 */
+int gpv_plan_krige(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms,
+                   const double *nuggets, int64_t n_nuggets,          /* 1 or Nlocs, ORDERED */
+                   const double *Z_ord, int64_t ldz, int ncols,        /* NULL: the plan's data; ncols <= 16 */
+                   const double *qlocs, int64_t nq, int m,             /* nq x dim column-major */
+                   const int *NNq,                                     /* NULL: search on the device; else nq x m, ORDERED ids */
+                   const double *scale, const unsigned char *eligible_ord, int64_t chunk /* 0: default */,
+                   double *mean, int64_t ldm, double *var, int64_t *n_failed);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,7 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   $HIPCC $CF -c $CSRC/gpv_selinv.hip -o $B/selinv.o & pids+=($!)    # selected inverse: launchers only on the host
   $HIPCC $CF -c $CSRC/gpv_loo.hip -o $B/loo.o & pids+=($!)          # transposed whitening: launchers and the index builder
   $HIPCC $CF -c $CSRC/gpv_blockcv.hip -o $B/blockcv.o & pids+=($!)  # leave-block-out: launchers and the block index builder
+  $HIPCC $CF -c $CSRC/gpv_krige.hip -o $B/krige.o & pids+=($!)      # local kriging: the launcher of the predict pass
   for pb in 16 32 64; do                         # gradient pass of the SGV likelihood: the same buckets, then its dispatcher
     $HIPCC $CF -DGPV_SGV_PB=$pb -c $CSRC/gpv_grad_sgv.hip -o $B/grad_sgv_pb$pb.o & pids+=($!)
   done
@@ -180,6 +181,16 @@ build_and_run() {   # $1 = tag, $2 = sanitizer flags, $3 = driver args
   rc=${PIPESTATUS[0]}
   if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_blockcv.log; then
     echo "== $tag: blockcv_driver FAILED (rc $rc)"; return 1
+  fi
+  # ... and under the driver of the local kriging entries (tests/sanitize/krige_driver.cpp)
+  mkdir -p $B/krige
+  $HIPCC $CF -c $ROOT/tests/sanitize/krige_driver.cpp -o $B/krige/driver.o
+  $CLANGXX $san -g $(ls $B/*.o | grep -v "/driver\.o$") $B/krige/driver.o -o $B/krige_driver -lpthread -ldl -lm
+  ( cd $B && ASAN_OPTIONS=detect_leaks=1:abort_on_error=0:halt_on_error=1 UBSAN_OPTIONS=print_stacktrace=1:halt_on_error=1 \
+      TSAN_OPTIONS=halt_on_error=1 timeout 600 ./krige_driver ) 2>&1 | tee $B/run_krige.log
+  rc=${PIPESTATUS[0]}
+  if [ $rc -ne 0 ] || grep -q "runtime error\|ERROR: AddressSanitizer\|WARNING: ThreadSanitizer\|ERROR: LeakSanitizer" $B/run_krige.log; then
+    echo "== $tag: krige_driver FAILED (rc $rc)"; return 1
   fi
   echo "== $tag: clean"
 }
