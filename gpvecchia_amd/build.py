@@ -63,6 +63,55 @@ def _compile(args):
     return obj, time.time() - t0
 
 
+def units(plist, extra_flags=()):
+    """The library as data: one record (source file name under csrc/, object name, unit-specific flags, header dependencies) per
+    object, in compile order (the longest first).  Every recipe reads this list: build() below for the product, and
+    tests/_host_driver_build.py for the host-only sanitizer programs.  extra_flags are those of a tuning build; the header
+    dependencies are paths relative to csrc/, kept by hand and checked against the #include lines by tests/test_build_units.py."""
+    x = list(extra_flags)
+    pub = "../../include/gpvecchia.h"
+    internal = ["gpv_internal.h", "gpv_bessel.hpp"]
+    kern = internal + ["gpv_sets_kernel.hpp", "gpv_reduce_tail.hpp", "gpv_plist.h"]   # what the conditioning-set kernel TUs include
+    grad = internal + ["gpv_grad.h", "gpv_grad_set_pass.inc", "gpv_rep_kernel.hpp"]
+    sgv = internal + ["gpv_grad.h", "gpv_grad_sgv.h"]
+    inst = "gpv_sets_inst.hip"
+    u = []
+    for P in sorted(plist, reverse=True):            # longest compiles first
+        if P >= SPLIT_FROM_P:                        # one TU per spatial dimension + the function that picks among them
+            for d in (3, 2, 1, 0):
+                u.append((inst, f"sets_p{P}_d{d}.o", [f"-DGPV_INST_P={P}", f"-DGPV_INST_DIM={d}"] + x, kern))
+            u.append((inst, f"sets_p{P}.o", [f"-DGPV_INST_P={P}", "-DGPV_INST_DISPATCH"] + x, kern))
+        else:
+            u.append((inst, f"sets_p{P}.o", [f"-DGPV_INST_P={P}"] + x, kern))
+        if lik_p(P):
+            u.append((inst, f"sets_p{P}_lik.o", [f"-DGPV_INST_P={P}", "-DGPV_INST_LIK"] + x, kern))
+        if lean_p(P):
+            u.append((inst, f"sets_p{P}_lean.o", [f"-DGPV_INST_P={P}", "-DGPV_INST_LEAN"] + x, kern))
+    u.append(("gpv_aux_kernels.hip", "aux.o", list(x), kern))
+    u.append(("gpv_api.hip", "api.o", list(x), internal + [pub, "gpv_laplace.h", "gpv_generic.h", "gpv_posterior_ext.h", "gpv_philox.hpp",
+                                                     "gpv_grad.h", "gpv_whiten.h", "gpv_unwhiten.h", "gpv_loo.h", "gpv_blockcv.h",
+                                                     "gpv_krige.h", "gpv_selinv.h", "gpv_grad_sgv.h", "gpv_hip_raii.hpp"]))
+    u.append(("gpv_posterior.hip", "posterior.o", list(x), internal + ["gpv_posterior_ext.h"]))
+    u.append(("gpv_lincomb.hip", "lincomb.o", list(x), internal + ["gpv_posterior_ext.h", "gpv_philox.hpp"]))
+    u.append(("gpv_laplace.hip", "laplace.o", [], ["gpv_laplace.h"]))            # no extra_flags: nothing in it is tuned
+    u.append(("gpv_sets_generic.hip", "generic.o", list(x), kern + ["gpv_generic.h"]))
+    for pb in (64, 32, 16):                          # value + gradient (+ information) kernels: one object per row-length bucket
+        u.append(("gpv_grad.hip", f"grad_pb{pb}.o", [f"-DGPV_GRAD_PB={pb}"] + x, grad))
+    u.append(("gpv_grad.hip", "grad.o", list(x), grad))
+    for pb in (64, 32, 16):                          # gradient pass of the SGV likelihood: the same buckets
+        u.append(("gpv_grad_sgv.hip", f"grad_sgv_pb{pb}.o", [f"-DGPV_SGV_PB={pb}"] + x, sgv))
+    u.append(("gpv_grad_sgv.hip", "grad_sgv.o", list(x), sgv))
+    u.append(("gpv_whiten.hip", "whiten.o", list(x), ["gpv_whiten.h"]))
+    u.append(("gpv_unwhiten.hip", "unwhiten.o", list(x), ["gpv_unwhiten.h", "gpv_philox.hpp"]))
+    u.append(("gpv_loo.hip", "loo.o", list(x), ["gpv_loo.h"]))
+    u.append(("gpv_blockcv.hip", "blockcv.o", list(x), ["gpv_blockcv.h"]))
+    u.append(("gpv_krige.hip", "krige.o", list(x), internal + ["gpv_krige.h"]))
+    u.append(("gpv_selinv.hip", "selinv.o", list(x), ["gpv_selinv.h"]))
+    u.append(("gpv_order.cpp", "order.o", ["-x", "c++"], [pub]))
+    u.append(("gpv_nn.hip", "nn.o", ["-ffp-contract=off"], internal + [pub, "gpv_krige.h"]))
+    return u
+
+
 def build(force: bool = False, jobs: int | None = None, verbose: bool = False, tag: str = "",
           extra_flags: list[str] | None = None, only: list[int] | None = None) -> str:
     """tag/extra_flags build a tuning variant (libgpvecchia_hip<tag>.so, objects under build<tag>/);
@@ -77,58 +126,8 @@ def build(force: bool = False, jobs: int | None = None, verbose: bool = False, t
             raise ValueError("a shortened row-length list is for tagged tuning builds only")
         extra_flags.append("-DGPV_P_LIST(X)=" + " ".join(f"X({p})" for p in sorted(only)))
     os.makedirs(BUILD, exist_ok=True)
-    H = lambda *names: [os.path.join(CSRC, f) for f in names]
-    pub = os.path.join(os.path.dirname(HERE), "include", "gpvecchia.h")
-    internal = H("gpv_internal.h", "gpv_bessel.hpp")
-    kern = internal + H("gpv_sets_kernel.hpp", "gpv_reduce_tail.hpp", "gpv_plist.h")   # what the conditioning-set kernel TUs include
-    work = []
-    inst = os.path.join(CSRC, "gpv_sets_inst.hip")
-    for P in sorted(only or plist(), reverse=True):          # longest compiles first
-        if P >= SPLIT_FROM_P:                        # one TU per spatial dimension + the function that picks among them
-            for d in (3, 2, 1, 0):
-                work.append((inst, os.path.join(BUILD, f"sets_p{P}_d{d}.o"),
-                             [f"-DGPV_INST_P={P}", f"-DGPV_INST_DIM={d}"] + extra_flags, kern, force))
-            work.append((inst, os.path.join(BUILD, f"sets_p{P}.o"), [f"-DGPV_INST_P={P}", "-DGPV_INST_DISPATCH"] + extra_flags,
-                         kern, force))
-        else:
-            work.append((inst, os.path.join(BUILD, f"sets_p{P}.o"), [f"-DGPV_INST_P={P}"] + extra_flags, kern, force))
-        if lik_p(P):
-            work.append((inst, os.path.join(BUILD, f"sets_p{P}_lik.o"), [f"-DGPV_INST_P={P}", "-DGPV_INST_LIK"] + extra_flags,
-                         kern, force))
-        if lean_p(P):
-            work.append((inst, os.path.join(BUILD, f"sets_p{P}_lean.o"), [f"-DGPV_INST_P={P}", "-DGPV_INST_LEAN"] + extra_flags,
-                         kern, force))
-    work.append((os.path.join(CSRC, "gpv_aux_kernels.hip"), os.path.join(BUILD, "aux.o"), list(extra_flags),
-                 kern + H("gpv_plist.h"), force))
-    work.append((os.path.join(CSRC, "gpv_api.hip"), os.path.join(BUILD, "api.o"), list(extra_flags),
-                 internal + [pub] + H("gpv_laplace.h", "gpv_generic.h", "gpv_posterior_ext.h", "gpv_philox.hpp", "gpv_grad.h",
-                                      "gpv_whiten.h", "gpv_unwhiten.h", "gpv_loo.h", "gpv_blockcv.h", "gpv_krige.h", "gpv_selinv.h", "gpv_grad_sgv.h", "gpv_hip_raii.hpp"), force))
-    work.append((os.path.join(CSRC, "gpv_posterior.hip"), os.path.join(BUILD, "posterior.o"), list(extra_flags),
-                 internal + H("gpv_posterior_ext.h"), force))
-    work.append((os.path.join(CSRC, "gpv_lincomb.hip"), os.path.join(BUILD, "lincomb.o"), list(extra_flags),
-                 internal + H("gpv_posterior_ext.h", "gpv_philox.hpp"), force))
-    work.append((os.path.join(CSRC, "gpv_laplace.hip"), os.path.join(BUILD, "laplace.o"), [], H("gpv_laplace.h"), force))
-    work.append((os.path.join(CSRC, "gpv_sets_generic.hip"), os.path.join(BUILD, "generic.o"), list(extra_flags),
-                 kern + H("gpv_generic.h"), force))
-    grad = os.path.join(CSRC, "gpv_grad.hip")                # value + gradient (+ information) kernels: one object per row-length bucket
-    for pb in (64, 32, 16):
-        work.append((grad, os.path.join(BUILD, f"grad_pb{pb}.o"), [f"-DGPV_GRAD_PB={pb}"] + extra_flags,
-                     internal + H("gpv_grad.h", "gpv_grad_set_pass.inc", "gpv_rep_kernel.hpp"), force))
-    work.append((grad, os.path.join(BUILD, "grad.o"), list(extra_flags), internal + H("gpv_grad.h", "gpv_grad_set_pass.inc", "gpv_rep_kernel.hpp"), force))
-    sgv = os.path.join(CSRC, "gpv_grad_sgv.hip")             # gradient pass of the SGV likelihood: the same buckets
-    for pb in (64, 32, 16):
-        work.append((sgv, os.path.join(BUILD, f"grad_sgv_pb{pb}.o"), [f"-DGPV_SGV_PB={pb}"] + extra_flags,
-                     internal + H("gpv_grad.h", "gpv_grad_sgv.h"), force))
-    work.append((sgv, os.path.join(BUILD, "grad_sgv.o"), list(extra_flags), internal + H("gpv_grad.h", "gpv_grad_sgv.h"), force))
-    work.append((os.path.join(CSRC, "gpv_whiten.hip"), os.path.join(BUILD, "whiten.o"), list(extra_flags), H("gpv_whiten.h"), force))
-    work.append((os.path.join(CSRC, "gpv_unwhiten.hip"), os.path.join(BUILD, "unwhiten.o"), list(extra_flags),
-                 H("gpv_unwhiten.h", "gpv_philox.hpp"), force))
-    work.append((os.path.join(CSRC, "gpv_loo.hip"), os.path.join(BUILD, "loo.o"), list(extra_flags), H("gpv_loo.h"), force))
-    work.append((os.path.join(CSRC, "gpv_blockcv.hip"), os.path.join(BUILD, "blockcv.o"), list(extra_flags), H("gpv_blockcv.h"), force))
-    work.append((os.path.join(CSRC, "gpv_krige.hip"), os.path.join(BUILD, "krige.o"), list(extra_flags), internal + H("gpv_krige.h"), force))
-    work.append((os.path.join(CSRC, "gpv_selinv.hip"), os.path.join(BUILD, "selinv.o"), list(extra_flags), H("gpv_selinv.h"), force))
-    work.append((os.path.join(CSRC, "gpv_order.cpp"), os.path.join(BUILD, "order.o"), ["-x", "c++"], [pub], force))
-    work.append((os.path.join(CSRC, "gpv_nn.hip"), os.path.join(BUILD, "nn.o"), ["-ffp-contract=off"], internal + [pub] + H("gpv_krige.h"), force))
+    work = [(os.path.join(CSRC, src), os.path.join(BUILD, obj), flags, [os.path.join(CSRC, h) for h in deps], force)
+            for src, obj, flags, deps in units(only or plist(), extra_flags)]
     jobs = jobs or min(8, os.cpu_count() or 1)
     with ThreadPoolExecutor(jobs) as ex:
         res = list(ex.map(_compile, work))

@@ -9,19 +9,12 @@
 #include "gpv_posterior_ext.h"
 #include "gpv_philox.hpp"
 #include "gpv_grad.h"
-#define GPV_WHITEN_LINKAGE __attribute__((weak))
 #include "gpv_whiten.h"
-#define GPV_UNWHITEN_LINKAGE __attribute__((weak))
 #include "gpv_unwhiten.h"
-#define GPV_LOO_LINKAGE __attribute__((weak))
 #include "gpv_loo.h"
-#define GPV_BLOCKCV_LINKAGE __attribute__((weak))
 #include "gpv_blockcv.h"
-#define GPV_KRIGE_LINKAGE __attribute__((weak))
 #include "gpv_krige.h"
-#define GPV_SELINV_LINKAGE __attribute__((weak))
 #include "gpv_selinv.h"
-#define GPV_GRAD_SGV_LINKAGE __attribute__((weak))
 #include "gpv_grad_sgv.h"
 #include "gpv_hip_raii.hpp"
 
@@ -2379,13 +2372,6 @@ int gpv_plan_loglik_rep_nu(gpv_plan *pl, const char *covType, const double *covp
 // ---- the whitening operator of the plan's latest evaluation applied to a block of columns (gpv_whiten.hip) -----------------
 int gpv_whiten_max_cols(void) { return kWhitenMaxCols; }
 
-// gpv_whiten.hip is part of this link (see GPV_WHITEN_LINKAGE in gpv_whiten.h)
-static bool whiten_linked()
-{
-    return &launch_whiten != nullptr && &launch_whiten_gram != nullptr && &launch_whiten_pack != nullptr &&
-           &launch_whiten_unpack != nullptr && &whiten_grid != nullptr && &whiten_gram_grid != nullptr;
-}
-
 // the two passes on what is resident: d_wh_B -> d_wh_E, partials, totals
 static hipError_t whiten_enqueue(gpv_plan *pl, int cp, hipStream_t st)
 {
@@ -2409,7 +2395,6 @@ int gpv_plan_whiten(gpv_plan *pl, const double *B_ord, int64_t ldb, int ncols, d
     if (ncols < 1 || ncols > kWhitenMaxCols) return GPV_ERR_BAD_ARG;
     const int64_t n = pl->Nlocs;
     if (ldb < n || (E_ord && lde < n)) return GPV_ERR_BAD_ARG;
-    if (!whiten_linked()) return GPV_ERR_STATE;
     if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L) return GPV_ERR_STATE;
     if (pl->comm || pl->rows != n || n < 1 || pl->d_obs || pl->latent_nb) return GPV_ERR_STATE;
     GPV_HIP(hipSetDevice(pl->device));
@@ -2462,7 +2447,6 @@ int gpv_plan_whiten(gpv_plan *pl, const double *B_ord, int64_t ldb, int ncols, d
 extern "C" int gpv_plan_debug_whiten_ms(gpv_plan *pl, int reps, double *ms)
 {
     if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
-    if (!whiten_linked()) return GPV_ERR_STATE;
     if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || pl->wh_cp_last == 0 || !pl->d_wh_tot) return GPV_ERR_STATE;
     GPV_HIP(hipSetDevice(pl->device));
     hipStream_t st = pl->stream;
@@ -2486,17 +2470,9 @@ extern "C" int gpv_plan_debug_whiten_ms(gpv_plan *pl, int reps, double *ms)
 // ---- the colouring operator, the inverse of the whitening operator: simulation from the Vecchia model (gpv_unwhiten.hip) ----
 int gpv_unwhiten_narrow(void) { return kUnwhitenNarrow; }
 
-// gpv_unwhiten.hip is part of this link (see GPV_UNWHITEN_LINKAGE in gpv_unwhiten.h)
-static bool unwhiten_linked()
-{
-    return &launch_unwhiten_pack != nullptr && &launch_unwhiten_unpack != nullptr && &launch_unwhiten_normals != nullptr &&
-           &launch_unwhiten_wide != nullptr && &launch_unwhiten_narrow != nullptr;
-}
-
 // what the plan's structure must be for the schedule to mean anything / what gpv_plan_whiten asks of the latest evaluation
 static int unwhiten_structure(const gpv_plan *pl)
 {
-    if (!unwhiten_linked()) return GPV_ERR_STATE;
     if (pl->rows != pl->Nlocs || pl->Nlocs < 1 || pl->latent_nb || !pl->d_nn || !pl->d_rowid) return GPV_ERR_STATE;
     return GPV_OK;
 }
@@ -2734,19 +2710,10 @@ extern "C" int gpv_plan_debug_unwhiten_ms(gpv_plan *pl, int reps, double *ms)
 // ---- the transposed whitening operator: precision products and leave-one-out cross-validation (gpv_loo.hip) ----------------
 int gpv_loo_nscores(void) { return kLooNScores; }
 
-// gpv_loo.hip is part of this link (see GPV_LOO_LINKAGE in gpv_loo.h)
-static bool loo_linked()
-{
-    return &loo_grid != nullptr && &loo_score_grid != nullptr && &loo_build_index != nullptr && &launch_loo_pack != nullptr &&
-           &launch_loo_unpack != nullptr && &launch_loo_scale != nullptr && &launch_loo_forward != nullptr &&
-           &launch_loo_transposed != nullptr && &launch_loo_scores != nullptr;
-}
-
 int gpv_loo_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t Nlocs, int P, int32_t *colptr, int32_t *owner,
                        int32_t *col, int64_t col_cap, int64_t *nnz)
 {
     if (!nnz || rows < 0 || Nlocs < 0 || P < 1) return GPV_ERR_BAD_ARG;
-    if (!loo_linked()) return GPV_ERR_STATE;
     if (rows * (int64_t)P >= ((int64_t)1 << 31) || Nlocs >= ((int64_t)1 << 31) - 1) return GPV_ERR_INDEX;      // before any array is read
     if (!nn || !rowid || !colptr || !owner) return GPV_ERR_BAD_ARG;
     std::vector<int32_t> cptr, own, cl;
@@ -2765,14 +2732,12 @@ int gpv_loo_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, in
 // what the plan's structure must be for the index to mean anything / what gpv_plan_whiten asks of the latest evaluation
 static int loo_structure(const gpv_plan *pl)
 {
-    if (!loo_linked()) return GPV_ERR_STATE;
     if (pl->rows != pl->Nlocs || pl->Nlocs < 1 || pl->latent_nb || !pl->d_nn || !pl->d_rowid) return GPV_ERR_STATE;
     if ((int64_t)pl->rows * pl->P >= ((int64_t)1 << 31)) return GPV_ERR_INDEX;     // the flat offsets of the index are int32
     return GPV_OK;
 }
 static int loo_state(const gpv_plan *pl)
 {
-    if (!loo_linked()) return GPV_ERR_STATE;
     if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L) return GPV_ERR_STATE;
     if (pl->comm || pl->d_obs) return GPV_ERR_STATE;
     return loo_structure(pl);
@@ -2996,13 +2961,6 @@ extern "C" int gpv_plan_debug_loo_ms(gpv_plan *pl, int reps, double *ms)
 int gpv_blockcv_nscores(void) { return kBcvNScores; }
 int gpv_blockcv_max_block(void) { return kBcvMaxBlock; }
 
-// gpv_blockcv.hip is part of this link (see GPV_BLOCKCV_LINKAGE in gpv_blockcv.h)
-static bool blockcv_linked()
-{
-    return &blockcv_grid != nullptr && &blockcv_score_grid != nullptr && &blockcv_check_labels != nullptr &&
-           &blockcv_build_index != nullptr && &launch_blockcv_blocks != nullptr && &launch_blockcv_scores != nullptr;
-}
-
 static int blockcv_status(int rc) { return rc == 0 ? GPV_OK : rc == 1 ? GPV_ERR_INDEX : GPV_ERR_BAD_ARG; }
 
 int gpv_blocks_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t Nlocs, int P, const int32_t *newpos,
@@ -3010,7 +2968,6 @@ int gpv_blocks_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows,
                           int32_t *memptr, int32_t *members, int32_t *setptr, int32_t *sets, int64_t sets_cap, int32_t *blkloc)
 {
     if (!n_blocks || !n_heldout || !max_size || !n_set_refs || rows < 0 || Nlocs < 0 || P < 1) return GPV_ERR_BAD_ARG;
-    if (!blockcv_linked()) return GPV_ERR_STATE;
     if (rows * (int64_t)P >= ((int64_t)1 << 31) || Nlocs >= ((int64_t)1 << 31) - 1) return GPV_ERR_INDEX;      // before any array is read
     if (!nn || !rowid || !block_of_ord) return GPV_ERR_BAD_ARG;
     BlockIndex ix;
@@ -3034,7 +2991,6 @@ int gpv_plan_set_blocks(gpv_plan *pl, const int32_t *block_of_ord, int64_t *n_bl
                         int64_t *n_set_refs)
 {
     if (!pl || !block_of_ord || !n_blocks || !n_heldout || !max_size || !n_set_refs) return GPV_ERR_BAD_ARG;
-    if (!blockcv_linked()) return GPV_ERR_STATE;
     if (const int rc = loo_structure(pl)) return rc;
     const int64_t rows = pl->rows, n = pl->Nlocs;
     const int P = pl->P;
@@ -3127,7 +3083,6 @@ int gpv_plan_block_cv(gpv_plan *pl, const double *Z_ord, int64_t ldz, int ncols,
     if (!pl || !Z_ord || !scores || !n_failed || !n_bad_blocks) return GPV_ERR_BAD_ARG;
     if (ncols < 1 || ncols > kBcvMaxCols) return GPV_ERR_BAD_ARG;
     if (ldz < pl->Nlocs || (mean && ldm < pl->Nlocs)) return GPV_ERR_BAD_ARG;
-    if (!blockcv_linked()) return GPV_ERR_STATE;
     if (const int rc = loo_state(pl)) return rc;
     if (!pl->bcv_have) return GPV_ERR_STATE;
     const int64_t n = pl->Nlocs;
@@ -3197,7 +3152,6 @@ int gpv_plan_block_cv(gpv_plan *pl, const double *Z_ord, int64_t ldz, int ncols,
 extern "C" int gpv_plan_debug_blockcv_ms(gpv_plan *pl, int reps, int parts, double *ms)
 {
     if (!pl || reps <= 0 || !ms || parts < 1 || parts > 7) return GPV_ERR_BAD_ARG;
-    if (!blockcv_linked()) return GPV_ERR_STATE;
     if (const int rc = loo_state(pl)) return rc;
     if (!pl->bcv_have || pl->bcv_last_ncols < 1 || !pl->loo_have_index || pl->loo_g_eval != pl->eval_count) return GPV_ERR_STATE;
     GPV_HIP(hipSetDevice(pl->device));
@@ -3221,9 +3175,6 @@ extern "C" int gpv_plan_debug_blockcv_ms(gpv_plan *pl, int reps, int parts, doub
 
 // ---- local kriging of a cond.yz='z' plan at new locations (gpv_krige.hip; the search: gpv_nn.hip) --------------------------
 int gpv_krige_max_cols(void) { return kKrigeMaxCols; }
-
-// gpv_krige.hip is part of this link (see GPV_KRIGE_LINKAGE in gpv_krige.h)
-static bool krige_linked() { return &krige_grid != nullptr && &launch_krige != nullptr; }
 
 // Reads the plan's records, its data and newpos, and writes buffers that live for the call only (and d_gmt, the table of a
 // general smoothness, which the blocking gradient calls share): no evaluation is needed and none is disturbed.  Every refusal
@@ -3249,7 +3200,7 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
         for (int t = 0; t < pl->dim; ++t)
             if (!(scale[t] > 0.0) || !std::isfinite(scale[t])) return GPV_ERR_BAD_ARG;
     if (m + 1 > kKrigeMaxP) return GPV_ERR_UNSUPPORTED_M;
-    if (!krige_linked() || pl->dim > kMaxDimGeneric || !pl->d_locs || !pl->d_newpos) return GPV_ERR_STATE;
+    if (pl->dim > kMaxDimGeneric || !pl->d_locs || !pl->d_newpos) return GPV_ERR_STATE;
     // a row shard, unobserved locations, a neighbour conditioned on as latent (not a 'z' plan), no data to predict from
     if (pl->comm || pl->rows != n || pl->d_obs || pl->latent_nb || (!Z_ord && !pl->has_z) || (int64_t)pl->h_newpos.size() != n)
         return GPV_ERR_STATE;
@@ -3589,16 +3540,9 @@ extern "C" int gpv_plan_debug_solve_t_ms(gpv_plan *pl, int reps, double *ms)
 }
 
 // ---- the selected inverse of the factor: every posterior variance in one pass (gpv_selinv.hip) -------------------------------
-// gpv_selinv.hip is part of this link (see GPV_SELINV_LINKAGE in gpv_selinv.h)
-static bool selinv_linked()
-{
-    return &selinv_tile != nullptr && &launch_selinv_top != nullptr && &launch_selinv_level != nullptr && &launch_selinv_out != nullptr;
-}
-
 // what gpv_plan_lincomb and gpv_plan_solve_t ask of the plan
 static int selinv_state(const gpv_plan *pl)
 {
-    if (!selinv_linked()) return GPV_ERR_STATE;
     if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
     if (pl->post_ld > 64 || !pl->d_meanrec) return GPV_ERR_STATE;
     return GPV_OK;
@@ -3759,9 +3703,6 @@ extern "C" int gpv_plan_debug_selinv_ms(gpv_plan *pl, int reps, double *ms)
 }
 
 // ---- value and analytic gradient of the cond.yz='SGV' log-likelihood (gpv_grad_sgv.hip) ---------------------------------------
-// gpv_grad_sgv.hip is part of this link (see GPV_GRAD_SGV_LINKAGE in gpv_grad_sgv.h)
-static bool grad_sgv_linked() { return &grad_sgv_grid != nullptr && &launch_grad_sgv != nullptr; }
-
 // The index data of the pass from the plan's arrays as they live on the device (built on the first call after a
 // gpv_plan_build_posterior): for every stored set the record of its posterior column, and for every entry of the set the
 // position of its point among the column's entries.  Every position is found in the column itself and checked against it:
@@ -3831,7 +3772,6 @@ int gpv_plan_loglik_grad_sgv(gpv_plan *pl, const char *covType, const double *co
     CovSetup cs;
     int rc = grad_args_checked(pl, covType, covparms, ncovparms, nugget, false, matern, a, cs, false, true);
     if (rc != GPV_OK) return rc;
-    if (!grad_sgv_linked() || !selinv_linked()) return GPV_ERR_STATE;
     if (!pl->have_post || pl->post_filled || pl->post_ld > 64 || !pl->d_meanrec || pl->row_begin != 0) return GPV_ERR_STATE;
     // the structure's own facts, established once: the terms its selected inverse drops (none for SGV) and the index data.
     // They read the plan's arrays and write buffers of their own; a refusal here leaves every result of the plan as it was.

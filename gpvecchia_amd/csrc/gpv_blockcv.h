@@ -52,28 +52,22 @@ struct BlockCvArgs {
     int P;
 };
 
-// Linkage of the launchers as the including unit sees them: weak in gpv_api.hip, as GPV_LOO_LINKAGE (gpv_loo.h); a link
-// without gpv_blockcv.hip resolves and the entries refuse with GPV_ERR_STATE (blockcv_linked()).
-#ifndef GPV_BLOCKCV_LINKAGE
-#define GPV_BLOCKCV_LINKAGE
-#endif
-
-GPV_BLOCKCV_LINKAGE int blockcv_grid(int64_t n_blocks, int cus);
-GPV_BLOCKCV_LINKAGE int blockcv_score_grid(int64_t n, int cus);
+int blockcv_grid(int64_t n_blocks, int cus);
+int blockcv_score_grid(int64_t n, int cus);
 // The labels alone (nothing of the plan is read): 0, or 3 (a label < -1 or >= n, a block of more than kBcvMaxBlock members,
 // no block at all).  ids: [n] the block number of each ORDERED location (-1: kept); sizes: [n_blocks].
-GPV_BLOCKCV_LINKAGE int blockcv_check_labels(const int32_t *block_of_ord, int64_t n, std::vector<int32_t> &ids,
+int blockcv_check_labels(const int32_t *block_of_ord, int64_t n, std::vector<int32_t> &ids,
                                              std::vector<int32_t> &sizes);
 // The index.  newpos: [n] internal position of each ordered location, nullptr = the identity.  Returns 0, 1 (rows x P >= 2^31),
 // 2 (an index out of range, a missing entry behind a valid one, newpos not a permutation) or 3 (blockcv_check_labels).
-GPV_BLOCKCV_LINKAGE int blockcv_build_index(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t n, int P,
+int blockcv_build_index(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t n, int P,
                                             const int32_t *newpos, const int32_t *block_of_ord, BlockIndex &out);
 // assembly of Q_BB, factor, solves, variances: cp = 1, 2, 4, 8, 16 columns
-GPV_BLOCKCV_LINKAGE hipError_t launch_blockcv_blocks(const BlockCvArgs &a, int cp, int grid, hipStream_t s);
+hipError_t launch_blockcv_blocks(const BlockCvArgs &a, int cp, int grid, hipStream_t s);
 // the epilogue on ORDERED column-major data: Z, DM, Y2 [ncols][n], var, nlp [n].  DM holds delta on entry and the predictive
 // mean z - delta on return; a location whose var is not > 0 (kept, or of a bad block) enters no sum.
 // part: [ncols][grid][kBcvNScores]; scores: [ncols][kBcvNScores]
-GPV_BLOCKCV_LINKAGE hipError_t launch_blockcv_scores(const double *Z, double *DM, const double *Y2, const double *var, const double *nlp,
+hipError_t launch_blockcv_scores(const double *Z, double *DM, const double *Y2, const double *var, const double *nlp,
                                                      int64_t n, int ncols, int grid, double *part, double *scores, hipStream_t s);
 
 }  // namespace gpv

@@ -26,15 +26,9 @@ struct SgvGradArgs {
     const double *mu;        // [Nlocs] W^-1 z2 by ordered index (the mean sweep's u; the posterior mean is its negative)
 };
 
-// Linkage as the including unit sees it: gpv_api.hip declares the launchers weak, like those of gpv_selinv.h, so that a link of
-// the library's host code without this unit resolves and gpv_plan_loglik_grad_sgv refuses loudly there.
-#ifndef GPV_GRAD_SGV_LINKAGE
-#define GPV_GRAD_SGV_LINKAGE
-#endif
-
 // workgroups of the launch: the wavefront cap of grad_grid (the bucket of 64 runs one wavefront per workgroup, the others four)
-GPV_GRAD_SGV_LINKAGE int grad_sgv_grid(int p, int64_t rows, int cus);
+int grad_sgv_grid(int p, int64_t rows, int cus);
 // both launches (the set pass, then the fixed-order sum of its partials) on `stream`; p: entries per row (m + 1)
-GPV_GRAD_SGV_LINKAGE hipError_t launch_grad_sgv(int p, const SgvGradArgs &a, int grid, hipStream_t stream);
+hipError_t launch_grad_sgv(int p, const SgvGradArgs &a, int grid, hipStream_t stream);
 
 }  // namespace gpv

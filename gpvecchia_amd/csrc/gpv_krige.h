@@ -66,12 +66,7 @@ struct KrigeArgs {
     int gmt_base, gmt_nseg;
 };
 
-#ifndef GPV_KRIGE_LINKAGE
-#define GPV_KRIGE_LINKAGE
-#endif
-// (weak in gpv_api.hip, as GPV_BLOCKCV_LINKAGE: a link without gpv_krige.hip resolves and gpv_plan_krige refuses with
-// GPV_ERR_STATE)
-GPV_KRIGE_LINKAGE int krige_grid(int64_t nq, int cus);
-GPV_KRIGE_LINKAGE hipError_t launch_krige(const KrigeArgs &a, int grid, hipStream_t s);
+int krige_grid(int64_t nq, int cus);
+hipError_t launch_krige(const KrigeArgs &a, int grid, hipStream_t s);
 
 }  // namespace gpv

@@ -43,32 +43,26 @@ struct LooArgs {
     double nug_scalar;
 };
 
-// Linkage of the launchers as the including unit sees them: weak in gpv_api.hip, as GPV_WHITEN_LINKAGE (gpv_whiten.h); a link
-// without gpv_loo.hip resolves and the entries refuse with GPV_ERR_STATE (loo_linked()).
-#ifndef GPV_LOO_LINKAGE
-#define GPV_LOO_LINKAGE
-#endif
-
 inline uint64_t loo_pmagic(int P) { return P <= 1 ? 0 : ~(uint64_t)0 / (uint64_t)P + 1; }
-GPV_LOO_LINKAGE int loo_grid(int64_t items, int cus);
-GPV_LOO_LINKAGE int loo_score_grid(int64_t n, int cus);
+int loo_grid(int64_t items, int cus);
+int loo_score_grid(int64_t n, int cus);
 // The transposed index of a plan's index arrays (host).  Returns 0, 1 (rows x P >= 2^31: the flat offsets are int32) or 2 (an
 // index out of range, a missing entry behind a valid one).  colptr: n + 1 starts; owner: n; col: colptr[n] offsets.
-GPV_LOO_LINKAGE int loo_build_index(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t n, int P,
+int loo_build_index(const int32_t *nn, const int32_t *rowid, int64_t rows, int64_t n, int P,
                                     std::vector<int32_t> &colptr, std::vector<int32_t> &owner, std::vector<int32_t> &col);
 // in: ncols columns of length n, n apart -> out[map ? map[i] : i][cp], zeros in the columns ncols .. cp - 1
-GPV_LOO_LINKAGE hipError_t launch_loo_pack(const double *in, const int32_t *map, int64_t n, int ncols, int cp, double *out, hipStream_t s);
+hipError_t launch_loo_pack(const double *in, const int32_t *map, int64_t n, int ncols, int cp, double *out, hipStream_t s);
 // in[map ? map[i] : i][cp] -> out: ncols columns of length n, n apart
-GPV_LOO_LINKAGE hipError_t launch_loo_unpack(const double *in, const int32_t *map, int64_t n, int ncols, int cp, double *out, hipStream_t s);
+hipError_t launch_loo_unpack(const double *in, const int32_t *map, int64_t n, int ncols, int cp, double *out, hipStream_t s);
 // the scale pre-pass: g and the counter of failed rows (cleared by the caller)
-GPV_LOO_LINKAGE hipError_t launch_loo_scale(const LooArgs &a, int grid, hipStream_t s);
+hipError_t launch_loo_scale(const LooArgs &a, int grid, hipStream_t s);
 // E = T B
-GPV_LOO_LINKAGE hipError_t launch_loo_forward(const LooArgs &a, int cp, int grid, hipStream_t s);
+hipError_t launch_loo_forward(const LooArgs &a, int cp, int grid, hipStream_t s);
 // R = T^T E, q = diag(T^T T)
-GPV_LOO_LINKAGE hipError_t launch_loo_transposed(const LooArgs &a, int cp, int grid, hipStream_t s);
+hipError_t launch_loo_transposed(const LooArgs &a, int cp, int grid, hipStream_t s);
 // the leave-one-out epilogue on ORDERED column-major data: Z, RM [ncols][n], q [n].  RM holds r = Q z on entry and the
 // leave-one-out mean on return; var[i] = 1 / q[i]; part: [ncols][grid][kLooNScores]; scores: [ncols][kLooNScores]
-GPV_LOO_LINKAGE hipError_t launch_loo_scores(const double *Z, double *RM, const double *q, double *var, int64_t n, int ncols, int grid,
+hipError_t launch_loo_scores(const double *Z, double *RM, const double *q, double *var, int64_t n, int ncols, int grid,
                                              double *part, double *scores, hipStream_t s);
 
 }  // namespace gpv

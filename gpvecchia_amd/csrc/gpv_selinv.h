@@ -23,21 +23,14 @@ struct SelinvArgs {
 
 constexpr int kSelinvTopMax = 128;     // columns the top kernel takes at most (kTopMax of gpv_posterior_ext.h)
 
-// Linkage of the launchers as the including unit sees them.  gpv_api.hip declares them weak: a link of the library's host code
-// that lists its units and has no gpv_selinv.hip among them still resolves, and gpv_plan_selinv then refuses loudly
-// (selinv_linked()); the library itself always links this unit (gpvecchia_amd/build.py).
-#ifndef GPV_SELINV_LINKAGE
-#define GPV_SELINV_LINKAGE
-#endif
-
 // the tile a level's kernel keeps per column: the smallest of 16, 32, 64 that holds max_entries entries (0: none does)
-GPV_SELINV_LINKAGE int selinv_tile(int max_entries);
+int selinv_tile(int max_entries);
 // the records [0, K) (the dense top block, closed: the rows of its columns are among its columns), one after the other in ONE
 // workgroup; toprows[j][e], 64 per column: the index inside the block of the row of entry e of column j
-GPV_SELINV_LINKAGE hipError_t launch_selinv_top(const SelinvArgs &a, int K, const uint8_t *toprows, hipStream_t s);
+hipError_t launch_selinv_top(const SelinvArgs &a, int K, const uint8_t *toprows, hipStream_t s);
 // the records [first, first + count): one level of the schedule, every column at most `tile` entries long
-GPV_SELINV_LINKAGE hipError_t launch_selinv_level(const SelinvArgs &a, int first, int count, int tile, hipStream_t s);
+hipError_t launch_selinv_level(const SelinvArgs &a, int first, int count, int tile, hipStream_t s);
 // out[k] = k < skip_front ? 0 : vars[k]
-GPV_SELINV_LINKAGE hipError_t launch_selinv_out(const double *vars, int64_t n, int64_t skip_front, double *out, hipStream_t s);
+hipError_t launch_selinv_out(const double *vars, int64_t n, int64_t skip_front, double *out, hipStream_t s);
 
 }  // namespace gpv

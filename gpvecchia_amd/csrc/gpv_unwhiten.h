@@ -33,22 +33,16 @@ struct UnwhitenArgs {
     double nug_scalar;
 };
 
-// Linkage of the launchers as the including unit sees them: weak in gpv_api.hip, as GPV_WHITEN_LINKAGE (gpv_whiten.h); a link
-// without gpv_unwhiten.hip resolves and the entries refuse with GPV_ERR_STATE.
-#ifndef GPV_UNWHITEN_LINKAGE
-#define GPV_UNWHITEN_LINKAGE
-#endif
-
 // in: ncols columns of length n, n apart (ORDERED layout) -> E[k][cp], zeros in the columns ncols .. cp - 1
-GPV_UNWHITEN_LINKAGE hipError_t launch_unwhiten_pack(const double *in, int64_t n, int ncols, int cp, double *E, hipStream_t s);
+hipError_t launch_unwhiten_pack(const double *in, int64_t n, int ncols, int cp, double *E, hipStream_t s);
 // B[newpos[i]][cp] -> out: ncols columns of length n, n apart (ORDERED layout)
-GPV_UNWHITEN_LINKAGE hipError_t launch_unwhiten_unpack(const double *B, const int32_t *newpos, int64_t n, int ncols, int cp,
+hipError_t launch_unwhiten_unpack(const double *B, const int32_t *newpos, int64_t n, int ncols, int cp,
                                                        double *out, hipStream_t s);
 // E[k][16] <- the standard normals of ordered location k, draws draw0 .. draw0 + 15 (gpv_philox.hpp); draw0 a multiple of 16
-GPV_UNWHITEN_LINKAGE hipError_t launch_unwhiten_normals(double *E, int64_t n, uint64_t seed, int64_t draw0, hipStream_t s);
+hipError_t launch_unwhiten_normals(double *E, int64_t n, uint64_t seed, int64_t draw0, hipStream_t s);
 // one wide level: the sets order[lo .. hi)
-GPV_UNWHITEN_LINKAGE hipError_t launch_unwhiten_wide(const UnwhitenArgs &a, int cp, int64_t lo, int64_t hi, hipStream_t s);
+hipError_t launch_unwhiten_wide(const UnwhitenArgs &a, int cp, int64_t lo, int64_t hi, hipStream_t s);
 // one run of narrow levels lev0 .. lev1 - 1 in ONE workgroup
-GPV_UNWHITEN_LINKAGE hipError_t launch_unwhiten_narrow(const UnwhitenArgs &a, int cp, int lev0, int lev1, hipStream_t s);
+hipError_t launch_unwhiten_narrow(const UnwhitenArgs &a, int cp, int lev0, int lev1, hipStream_t s);
 
 }  // namespace gpv

@@ -34,26 +34,19 @@ struct WhitenArgs {
     double nug_scalar;
 };
 
-// Linkage of the launchers as the including unit sees them.  gpv_api.hip declares them weak: a link of the library's host code
-// that lists its units and has no gpv_whiten.hip among them still resolves, and gpv_plan_whiten then refuses loudly
-// (whiten_linked()); the library itself always links this unit (gpvecchia_amd/build.py).
-#ifndef GPV_WHITEN_LINKAGE
-#define GPV_WHITEN_LINKAGE
-#endif
-
 // padded column count of a call with ncols columns: the next power of two
 inline int whiten_cp(int ncols) { int cp = 1; while (cp < ncols) cp <<= 1; return cp; }
-GPV_WHITEN_LINKAGE int whiten_grid(int64_t rows, int cus);
-GPV_WHITEN_LINKAGE int whiten_gram_grid(int64_t rows, int cus);
+int whiten_grid(int64_t rows, int cus);
+int whiten_gram_grid(int64_t rows, int cus);
 // in: ncols columns of length n, n apart (ORDERED layout) -> B[newpos[i]][cp], zeros in the columns ncols .. cp - 1
-GPV_WHITEN_LINKAGE hipError_t launch_whiten_pack(const double *in, const int32_t *newpos, int64_t n, int ncols, int cp, double *B, hipStream_t s);
+hipError_t launch_whiten_pack(const double *in, const int32_t *newpos, int64_t n, int ncols, int cp, double *B, hipStream_t s);
 // E[n][cp] -> out: ncols columns of length n, n apart
-GPV_WHITEN_LINKAGE hipError_t launch_whiten_unpack(const double *E, int64_t n, int ncols, int cp, double *out, hipStream_t s);
+hipError_t launch_whiten_unpack(const double *E, int64_t n, int ncols, int cp, double *out, hipStream_t s);
 // the whitening pass (one launch): E and the per-workgroup partials
-GPV_WHITEN_LINKAGE hipError_t launch_whiten(const WhitenArgs &a, int cp, int grid, hipStream_t s);
+hipError_t launch_whiten(const WhitenArgs &a, int cp, int grid, hipStream_t s);
 // the Gram pass: per-workgroup partial tiles of E^T E (gpart: [ggrid][kGramTile]), then ONE workgroup that adds the tiles and the
 // whitening pass's partials (wpart: [wgrid][kWhitenNV]) in workgroup order into totals[kWhitenTotals]
-GPV_WHITEN_LINKAGE hipError_t launch_whiten_gram(const double *E, int64_t n, int cp, int ggrid, double *gpart, const double *wpart, int wgrid,
+hipError_t launch_whiten_gram(const double *E, int64_t n, int cp, int ggrid, double *gpart, const double *wpart, int wgrid,
                               double *totals, hipStream_t s);
 
 }  // namespace gpv

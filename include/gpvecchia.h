@@ -789,8 +789,8 @@ int gpv_find_query_nn(int device, const double *locs, int64_t n, int dim, const 
  * [1, 16] (or not 1 with Z_ord NULL), ldz < Nlocs, ldm < nq, nq < 0, m < 1, chunk < 0, a scale <= 0, ncovparms not 3 / 4 /
  * dim + 2; GPV_ERR_COVTYPE; GPV_ERR_UNSUPPORTED_NU; GPV_ERR_UNSUPPORTED_M: m + 1 > 64; GPV_ERR_INDEX: an entry of NNq outside
  * [0, Nlocs]; GPV_ERR_STATE: a row shard, a communicator attached, unobserved locations (gpv_plan_set_observed), latent
- * conditioning (not a cond.yz='z' plan), Z_ord NULL and no data set, a plan without coordinates, a library linked without
- * gpv_krige.hip.  nq == 0 is GPV_OK. */
+ * conditioning (not a cond.yz='z' plan), Z_ord NULL and no data set, a plan without coordinates.
+ * nq == 0 is GPV_OK. */
 int gpv_krige_max_cols(void);          /* 16 */
 int gpv_plan_krige(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms,
                    const double *nuggets, int64_t n_nuggets,          /* 1 or Nlocs, ORDERED */

@@ -7,8 +7,8 @@
 // entries and the padding of the leading dimensions stay untouched), buffer growth across column counts, replaced blocks, and
 // that nothing is left allocated — never numbers.
 //
-//   build: every .hip of the library --offload-host-only with -fsanitize=address,undefined (gpv_loo.hip and gpv_blockcv.hip
-//          among them), this file in place of host_driver.cpp: tests/test_blockcv_driver.py.
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_blockcv_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <algorithm>

@@ -7,8 +7,8 @@
 // (grid and brute route, an eligibility mask, non-finite coordinates), that the plan's evaluation stays what it was, and
 // that nothing is left allocated — never numbers.
 //
-//   build: every .hip of the library --offload-host-only with -fsanitize=address,undefined (gpv_krige.hip among them), this
-//          file in place of host_driver.cpp: tests/test_krige_driver.py.
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_krige_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <climits>

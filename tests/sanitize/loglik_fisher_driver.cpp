@@ -5,8 +5,8 @@
 // fisher and row_terms stay untouched, fisher is symmetric), that the plan's last evaluation is left alone and that nothing is
 // left allocated — never numbers.
 //
-//   build: tests/test_loglik_fisher_driver.py (every .hip of the library --offload-host-only with
-//          -fsanitize=address,undefined, this file as the program).
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_loglik_fisher_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <climits>

@@ -4,8 +4,8 @@
 // (guard entries behind grad and row_terms stay untouched), that the plan's last evaluation is left alone and that nothing is
 // left allocated — never numbers.
 //
-//   build: every .hip of the library --offload-host-only with -fsanitize=address,undefined as tools/sanitize_host.sh does,
-//          this file in place of host_driver.cpp.
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_host_drivers.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <climits>

@@ -7,8 +7,8 @@
 // last evaluation is left alone and that nothing is left allocated.  The pair functions run on the host: their values at the ends
 // of the argument range are checked for what they must be exactly.
 //
-//   build: tests/test_loglik_grad_nu_driver.py (every .hip of the library --offload-host-only with
-//          -fsanitize=address,undefined, this file as the program).
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_loglik_grad_nu_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <climits>

@@ -6,8 +6,8 @@
 // sanitizer report), the shape of what is written (guard entries behind grad, fisher and row_terms stay untouched, fisher may be
 // NULL), that the plan's data column and last evaluation are left alone and that nothing is left allocated — never numbers.
 //
-//   build: tests/test_loglik_rep_driver.py and tools/sanitize_host.sh (every .hip of the library --offload-host-only with
-//          -fsanitize=address,undefined, this file as the program).
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_loglik_rep_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <climits>

@@ -6,8 +6,8 @@
 // 32-bit guard, buffers of exactly the documented sizes), the shape of what is written (guard entries and the padding of the
 // leading dimensions stay untouched), buffer growth across column counts, and that nothing is left allocated — never numbers.
 //
-//   build: every .hip of the library --offload-host-only with -fsanitize=address,undefined (gpv_whiten.hip and gpv_loo.hip
-//          among them), this file in place of host_driver.cpp: tests/test_loo_driver.py.
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_loo_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <algorithm>

@@ -6,7 +6,8 @@
 // lifetimes and leaks, never indices: after a good call the rows of the shard hold 0 and every other entry of the caller's
 // array still holds the sentinel it was filled with.
 //
-//   build: gpv_nn.hip --offload-host-only with -fsanitize=address,undefined, the mock runtime, this file (tests/test_nn_driver.py).
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_nn_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <cmath>

@@ -7,8 +7,8 @@
 // copy) at EVERY evaluation, the shape of what the gradient-type entries write in 1, 2 and 3 dimensions (NaN exactly in the
 // smoothness slots, guard entries behind grad, fisher and row_terms untouched), and that nothing is left allocated — never numbers.
 //
-//   build: tests/test_scaledim_driver.py and tools/sanitize_host.sh (every .hip of the library --offload-host-only with
-//          -fsanitize=address,undefined, this file as the program).
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_scaledim_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <climits>

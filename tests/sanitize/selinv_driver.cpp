@@ -5,8 +5,8 @@
 // loop over the pattern here), the shape of what is written (guard entries stay), the rebuild after a new structure, one graph
 // replay per call, and that nothing is left allocated — never numbers.
 //
-//   build: every .hip of the library --offload-host-only with -fsanitize=address,undefined (gpv_selinv.hip among them), this file
-//          in place of host_driver.cpp: tests/test_selinv_driver.py.
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_selinv_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <algorithm>

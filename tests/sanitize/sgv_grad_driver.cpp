@@ -5,8 +5,8 @@
 // entries stay), the evaluation the call makes (factor stamp), a repeat after gpv_plan_build_posterior, and that nothing is
 // left allocated — never numbers.
 //
-//   build: every .hip of the library --offload-host-only with -fsanitize=address,undefined (gpv_selinv.hip and gpv_grad_sgv.hip
-//          among them), this file in place of host_driver.cpp: tests/test_sgv_grad_driver.py.
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_sgv_grad_driver.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <climits>

@@ -3,8 +3,8 @@
 // the HIP runtime.  Kernels do not run, so this checks statuses, the strided copies of E and X (guard columns stay
 // untouched), batching, in-place use, graph lifetime across a rebuild, and that nothing is left allocated — never numbers.
 //
-//   build: every .hip of the library --offload-host-only with -fsanitize=address,undefined as tools/sanitize_host.sh does,
-//          this file in place of host_driver.cpp.
+//   build: tests/_host_driver_build.py (every unit of gpvecchia_amd/build.py units() --offload-host-only with the sanitizers, the
+//          mock runtime, this file as the program); run by tests/test_host_drivers.py and tools/sanitize_host.sh.
 #include "../../include/gpvecchia.h"
 
 #include <algorithm>

@@ -9,19 +9,17 @@ import pytest
 
 import _host_driver_build as H
 
-DRIVER = "scaledim_driver"
+DRIVERS = {"scaledim_driver": []}
 
 
 @pytest.fixture(scope="module")
-def programs(tmp_path_factory):
-    if not H.have_toolchain():
-        pytest.skip("no hipcc on this machine")
-    return H.build_programs(str(tmp_path_factory.mktemp(DRIVER)), [DRIVER])
+def programs():
+    return H.programs_or_skip(DRIVERS)
 
 
 def test_scaledim_driver_is_clean(programs):
     """The driver ends with status 0 (no failed expectation) and neither sanitizer nor LeakSanitizer has anything to say."""
-    rc, log = H.run_driver(programs, DRIVER)
+    rc, log = H.run_driver(programs, "scaledim_driver", DRIVERS["scaledim_driver"])
     print(log[-4000:])
     assert rc == 0 and not H.BAD.search(log), log[-4000:]
     assert "0 failed expectation(s)" in log
