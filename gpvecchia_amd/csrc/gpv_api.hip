@@ -544,6 +544,117 @@ struct gpv_plan {
     }
 };
 
+// ---- what the operators on a resident factor share: every entry below is made of these, none keeps a copy ------------------
+// An entry's first step on the device: the plan's device, then a wait for the stream of the plan's latest evaluation (the
+// plan's own or a caller's), which may still be writing what the entry reads.  enter() leaves the plan's own stream alone: what
+// the entry enqueues there is ordered behind the evaluation anyway.  enter_final() waits for it as well: the factor must be
+// final, since the entry reads the structure back with blocking copies or makes the plan's stream the latest one.
+static int enter(gpv_plan *pl)
+{
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream && pl->last_stream != pl->stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    return GPV_OK;
+}
+static int enter_final(gpv_plan *pl)
+{
+    GPV_HIP(hipSetDevice(pl->device));
+    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    return GPV_OK;
+}
+
+// How an entry leaves after a failure past its first enqueue: nothing in flight on `st` still reads the caller's arrays or the
+// buffers that live for the call when they go.
+static int drain_fail(hipStream_t st, int rc)
+{
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
+// `ncols` columns of `n` doubles between a host array of leading dimension `ld` and a device buffer that holds them back to
+// back, one copy per column on `st`; a failed copy is recorded here, under its own name.  cols_fill_nan(): what a caller gets in
+// place of columns that a failed row has reached.
+static int cols_to_device(double *dev, const double *host, int64_t ld, int64_t n, int64_t ncols, hipStream_t st)
+{
+    for (int64_t j = 0; j < ncols; ++j)
+        GPV_HIP(hipMemcpyAsync(dev + (size_t)j * n, host + j * ld, sizeof(double) * (size_t)n, hipMemcpyHostToDevice, st));
+    return GPV_OK;
+}
+static int cols_to_host(double *host, int64_t ld, const double *dev, int64_t n, int64_t ncols, hipStream_t st)
+{
+    for (int64_t j = 0; j < ncols; ++j)
+        GPV_HIP(hipMemcpyAsync(host + j * ld, dev + (size_t)j * n, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st));
+    return GPV_OK;
+}
+static void cols_fill_nan(double *host, int64_t ld, int64_t n, int64_t ncols)
+{
+    for (int64_t j = 0; j < ncols; ++j) std::fill_n(host + j * ld, (size_t)n, (double)NAN);
+}
+
+// The factor of the plan's latest evaluation as the operators' kernels see it (WhitenArgs, UnwhitenArgs, LooArgs): the U
+// entries, the index arrays, and the nuggets as a vector or as one value.
+template <class Args>
+static void factor_view(const gpv_plan *pl, Args &a)
+{
+    a.L = pl->d_L; a.nn = pl->d_nn; a.rowid = pl->d_rowid;
+    a.nuggets = pl->nug_is_scalar ? nullptr : pl->d_nuggets.get();
+    a.nug_scalar = pl->nug_scalar;
+}
+
+// d_L and the nuggets on the device are those of the plan's latest evaluation
+static bool factor_current(const gpv_plan *pl) { return !(pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L); }
+// What the plan's structure must be for a level schedule or a transposed index to mean anything, evaluation or not: every row
+// on this device and no neighbour conditioned on as latent.  (plan_fill uploads both index arrays of every plan.)
+static int z_structure(const gpv_plan *pl)
+{
+    if (pl->rows != pl->Nlocs || pl->Nlocs < 1 || pl->latent_nb || !pl->d_nn || !pl->d_rowid) return GPV_ERR_STATE;
+    return GPV_OK;
+}
+// What every operator on the resident factor asks: the latest evaluation left its factor, and this is a plain 'z' plan (no row
+// shard, no unobserved location).
+static int factor_state(const gpv_plan *pl)
+{
+    if (!factor_current(pl) || pl->comm || pl->d_obs) return GPV_ERR_STATE;
+    return z_structure(pl);
+}
+
+// What every entry that sweeps with the posterior factor asks of the plan (gpv_plan_solve_t, gpv_plan_selinv, the draws): a
+// structure, a factor of its own (no row shard), and columns no longer than the sweeps' tiles (no structure is built with longer).
+static int posterior_factor_state(const gpv_plan *pl)
+{
+    if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
+    if (pl->post_ld > 64 || !pl->d_meanrec) return GPV_ERR_STATE;
+    return GPV_OK;
+}
+
+// The body of the gpv_plan_debug_*_ms entries, which have checked their arguments and their state: the plan's device (and,
+// with wait_eval, enter()'s wait), then `reps` runs of `body` on the plan's stream, each between a pair of events and waited
+// for: ms[r] = the device time of run r.  `before` is enqueued ahead of each run's first event, untimed.
+static hipError_t nothing_before() { return hipSuccess; }
+template <class Body, class Before = hipError_t (*)()>
+static int timed_reps(gpv_plan *pl, bool wait_eval, int reps, double *ms, Body body, Before before = nothing_before)
+{
+    if (wait_eval) {
+        if (const int rc = enter(pl)) return rc;
+    } else {
+        GPV_HIP(hipSetDevice(pl->device));
+    }
+    hipStream_t st = pl->stream;
+    Event a, b;
+    GPV_HIP(hipEventCreate(a.put()));
+    GPV_HIP(hipEventCreate(b.put()));
+    int rc = GPV_OK;
+    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
+        float t = 0.f;
+        if (GPV_HIP_FAILED(before()) || GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(body()) ||
+            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
+            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
+            rc = GPV_ERR_HIP;
+        ms[r] = (double)t;
+    }
+    (void)hipStreamSynchronize(st);
+    return rc;
+}
+
 extern "C" {
 
 const char *gpv_status_string(int status)
@@ -889,9 +1000,8 @@ static int plan_fill(gpv_plan *pl, int device, int64_t Nlocs, int dim, int ncolN
 int gpv_plan_set_data(gpv_plan *pl, const double *z_ord)
 {
     if (!pl || !z_ord) return GPV_ERR_BAD_ARG;
-    GPV_HIP(hipSetDevice(pl->device));
     // an evaluation enqueued earlier on a caller stream may still be reading the records / d_zuser this call rewrites
-    if (pl->last_stream && pl->last_stream != pl->stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (const int rc = enter(pl)) return rc;
     GPV_HIP(hipMemcpyAsync(pl->d_stage, z_ord, sizeof(double) * (size_t)pl->Nlocs, hipMemcpyHostToDevice, pl->stream));
     if (pl->dim <= 3) {
         GPV_HIP(launch_scatter(pl->d_stage, pl->d_newpos, pl->Nlocs, pl->d_locs, 4, 3, pl->stream));   // rec[.][3] = datum
@@ -909,8 +1019,7 @@ int gpv_plan_set_data(gpv_plan *pl, const double *z_ord)
 int gpv_plan_set_observed(gpv_plan *pl, const int *obs_ord)
 {
     if (!pl) return GPV_ERR_BAD_ARG;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (const int rc = enter_final(pl)) return rc;
     for (auto &g : pl->pgraph) g.exec.reset();        // the captured passes hold the address of the nuggets they read
     std::vector<uint8_t> h((size_t)pl->Nlocs);
     bool all = true;
@@ -1844,8 +1953,7 @@ static int vl_begin_impl(gpv_plan *pl, int model, const double *likparms, const 
     if (model < 0 || model > 5) return GPV_ERR_BAD_ARG;
     if (!pl->have_post) return GPV_ERR_STATE;                       // every step is a posterior-mean evaluation
     if (user_layout && !pl->d_user_ord) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream && pl->last_stream != pl->stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (const int rc = enter(pl)) return rc;
     const size_t nb = sizeof(double) * (size_t)pl->Nlocs;
     DevBuf<double> *bufs[] = {&pl->d_vl_z, &pl->d_vl_pm, &pl->d_vl_y[0], &pl->d_vl_y[1], &pl->d_vl_y0, &pl->d_nug_user, &pl->d_zuser};
     for (DevBuf<double> *b : bufs) GPV_BUF(*b, ensure((size_t)pl->Nlocs));
@@ -1919,8 +2027,7 @@ int gpv_plan_vl_restart(gpv_plan *pl, const double *likparms)
     // the same data, prior mean and start value as the last gpv_plan_vl_begin*: nothing crosses PCIe
     if (!pl) return GPV_ERR_BAD_ARG;
     if (pl->vl_model < 0 || !pl->d_vl_y0) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream && pl->last_stream != pl->stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (const int rc = enter(pl)) return rc;
     GPV_HIP(hipMemcpyAsync(pl->d_vl_y[0], pl->d_vl_y0, sizeof(double) * (size_t)pl->Nlocs, hipMemcpyDeviceToDevice, pl->stream));
     if (likparms) {
         pl->vl_alpha = likparms[0];
@@ -2339,12 +2446,8 @@ int gpv_plan_set_replicates(gpv_plan *pl, const double *Z_ord, int64_t ldz, int 
     DevBuf<double> d_in;
     GPV_BUF(d_in, resize((size_t)n * R));
     GPV_BUF(pl->d_rep_Z, resize((size_t)n * rp));
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
-    for (int j = 0; j < R; ++j)
-        if (GPV_HIP_FAILED(hipMemcpyAsync(d_in + (size_t)j * n, Z_ord + (int64_t)j * ldz, sizeof(double) * (size_t)n,
-                                          hipMemcpyHostToDevice, st)))
-            return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(launch_rep_pack(d_in, pl->d_newpos, n, R, rp, pl->d_rep_Z, st))) return fail(GPV_ERR_HIP);
+    if (cols_to_device(d_in, Z_ord, ldz, n, R, st)) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_rep_pack(d_in, pl->d_newpos, n, R, rp, pl->d_rep_Z, st))) return drain_fail(st, GPV_ERR_HIP);
     GPV_HIP(hipStreamSynchronize(st));
     pl->rep_R = R; pl->rep_RP = rp;
     return GPV_OK;
@@ -2376,9 +2479,7 @@ int gpv_whiten_max_cols(void) { return kWhitenMaxCols; }
 static hipError_t whiten_enqueue(gpv_plan *pl, int cp, hipStream_t st)
 {
     WhitenArgs a;
-    a.L = pl->d_L; a.nn = pl->d_nn; a.rowid = pl->d_rowid;
-    a.nuggets = pl->nug_is_scalar ? nullptr : pl->d_nuggets.get();
-    a.nug_scalar = pl->nug_scalar;
+    factor_view(pl, a);
     a.B = pl->d_wh_B; a.E = pl->d_wh_E; a.part = pl->d_wh_wpart;
     a.rows = pl->rows; a.P = pl->P;
     const hipError_t e = launch_whiten(a, cp, pl->wh_wgrid, st);
@@ -2395,11 +2496,9 @@ int gpv_plan_whiten(gpv_plan *pl, const double *B_ord, int64_t ldb, int ncols, d
     if (ncols < 1 || ncols > kWhitenMaxCols) return GPV_ERR_BAD_ARG;
     const int64_t n = pl->Nlocs;
     if (ldb < n || (E_ord && lde < n)) return GPV_ERR_BAD_ARG;
-    if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L) return GPV_ERR_STATE;
-    if (pl->comm || pl->rows != n || n < 1 || pl->d_obs || pl->latent_nb) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
+    if (const int rc = factor_state(pl)) return rc;
+    if (const int rc = enter(pl)) return rc;
     hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));   // the evaluation's stream
     const int cp = whiten_cp(ncols);
     if (cp > pl->wh_cp_cap) {
         pl->wh_cp_cap = 0;
@@ -2415,22 +2514,15 @@ int gpv_plan_whiten(gpv_plan *pl, const double *B_ord, int64_t ldb, int ncols, d
         GPV_BUF(pl->d_wh_gpart, resize((size_t)pl->wh_ggrid * kGramTile));
         GPV_BUF(pl->d_wh_tot, resize(kWhitenTotals));
     }
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
-    for (int j = 0; j < ncols; ++j)
-        if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_wh_in + (size_t)j * n, B_ord + (int64_t)j * ldb, sizeof(double) * (size_t)n,
-                                          hipMemcpyHostToDevice, st)))
-            return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(launch_whiten_pack(pl->d_wh_in, pl->d_newpos, n, ncols, cp, pl->d_wh_B, st))) return fail(GPV_ERR_HIP);
+    if (cols_to_device(pl->d_wh_in, B_ord, ldb, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_whiten_pack(pl->d_wh_in, pl->d_newpos, n, ncols, cp, pl->d_wh_B, st))) return drain_fail(st, GPV_ERR_HIP);
     pl->wh_cp_last = cp;
-    if (GPV_HIP_FAILED(whiten_enqueue(pl, cp, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(whiten_enqueue(pl, cp, st))) return drain_fail(st, GPV_ERR_HIP);
     double tot[kWhitenTotals];
-    if (GPV_HIP_FAILED(hipMemcpyAsync(tot, pl->d_wh_tot, sizeof(tot), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(tot, pl->d_wh_tot, sizeof(tot), hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
     if (E_ord) {
-        if (GPV_HIP_FAILED(launch_whiten_unpack(pl->d_wh_E, n, ncols, cp, pl->d_wh_in, st))) return fail(GPV_ERR_HIP);
-        for (int j = 0; j < ncols; ++j)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(E_ord + (int64_t)j * lde, pl->d_wh_in + (size_t)j * n, sizeof(double) * (size_t)n,
-                                              hipMemcpyDeviceToHost, st)))
-                return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_whiten_unpack(pl->d_wh_E, n, ncols, cp, pl->d_wh_in, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (cols_to_host(E_ord, lde, pl->d_wh_in, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
     }
     GPV_HIP(hipStreamSynchronize(st));
     const bool bad = tot[kGramTile + 1] > 0.0;
@@ -2447,42 +2539,12 @@ int gpv_plan_whiten(gpv_plan *pl, const double *B_ord, int64_t ldb, int ncols, d
 extern "C" int gpv_plan_debug_whiten_ms(gpv_plan *pl, int reps, double *ms)
 {
     if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
-    if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || pl->wh_cp_last == 0 || !pl->d_wh_tot) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
-    Event a, b;
-    GPV_HIP(hipEventCreate(a.put()));
-    GPV_HIP(hipEventCreate(b.put()));
-    int rc = GPV_OK;
-    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
-        float t = 0.f;
-        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(whiten_enqueue(pl, pl->wh_cp_last, st)) ||
-            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
-            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
-            rc = GPV_ERR_HIP;
-        ms[r] = (double)t;
-    }
-    (void)hipStreamSynchronize(st);
-    return rc;
+    if (!factor_current(pl) || pl->wh_cp_last == 0 || !pl->d_wh_tot) return GPV_ERR_STATE;   // (d_L lives as long as the plan)
+    return timed_reps(pl, true, reps, ms, [&] { return whiten_enqueue(pl, pl->wh_cp_last, pl->stream); });
 }
 
 // ---- the colouring operator, the inverse of the whitening operator: simulation from the Vecchia model (gpv_unwhiten.hip) ----
 int gpv_unwhiten_narrow(void) { return kUnwhitenNarrow; }
-
-// what the plan's structure must be for the schedule to mean anything / what gpv_plan_whiten asks of the latest evaluation
-static int unwhiten_structure(const gpv_plan *pl)
-{
-    if (pl->rows != pl->Nlocs || pl->Nlocs < 1 || pl->latent_nb || !pl->d_nn || !pl->d_rowid) return GPV_ERR_STATE;
-    return GPV_OK;
-}
-static int unwhiten_state(const gpv_plan *pl)
-{
-    if (const int rc = unwhiten_structure(pl)) return rc;
-    if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L) return GPV_ERR_STATE;
-    if (pl->comm || pl->d_obs) return GPV_ERR_STATE;
-    return GPV_OK;
-}
 
 // The level schedule from the plan's own index arrays, read back once: level(k) = 0 for a row without neighbours, else
 // 1 + max_j level(j), taken in the ordered row sequence (every neighbour precedes its row); the stored sets sorted by level,
@@ -2553,7 +2615,7 @@ static int unwhiten_schedule(gpv_plan *pl)
 int gpv_plan_unwhiten_levels(gpv_plan *pl, int64_t *n_levels, int64_t *n_launches)
 {
     if (!pl || !n_levels || !n_launches) return GPV_ERR_BAD_ARG;
-    if (const int rc = unwhiten_structure(pl)) return rc;
+    if (const int rc = z_structure(pl)) return rc;             // (the schedule needs no evaluation)
     GPV_HIP(hipSetDevice(pl->device));
     if (const int rc = unwhiten_schedule(pl)) return rc;
     *n_levels = (int64_t)pl->uw_levptr.size() - 1;
@@ -2565,9 +2627,7 @@ int gpv_plan_unwhiten_levels(gpv_plan *pl, int64_t *n_levels, int64_t *n_launche
 static hipError_t unwhiten_enqueue(gpv_plan *pl, int cp, hipStream_t st)
 {
     UnwhitenArgs a;
-    a.L = pl->d_L; a.nn = pl->d_nn; a.rowid = pl->d_rowid;
-    a.nuggets = pl->nug_is_scalar ? nullptr : pl->d_nuggets.get();
-    a.nug_scalar = pl->nug_scalar;
+    factor_view(pl, a);
     a.E = pl->d_uw_E; a.B = pl->d_uw_B; a.order = pl->d_uw_order; a.levptr = pl->d_uw_levptr; a.nfail = pl->d_uw_nfail;
     a.P = pl->P;
     for (const gpv_plan::UwLaunch &u : pl->uw_launches) {
@@ -2598,8 +2658,7 @@ static hipError_t unwhiten_sweep(gpv_plan *pl, int cp, hipStream_t st)
 // device, schedule and the column buffers at the padded column count cp
 static int unwhiten_prepare(gpv_plan *pl, int cp)
 {
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream && pl->last_stream != pl->stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));   // the evaluation's stream
+    if (const int rc = enter(pl)) return rc;
     if (const int rc = unwhiten_schedule(pl)) return rc;
     if (cp > pl->uw_cp_cap) {
         const size_t cnt = (size_t)pl->Nlocs * cp;
@@ -2621,29 +2680,21 @@ int gpv_plan_unwhiten(gpv_plan *pl, const double *E_ord, int64_t lde, int ncols,
     if (ncols < 1 || ncols > kUnwhitenMaxCols) return GPV_ERR_BAD_ARG;
     const int64_t n = pl->Nlocs;
     if (lde < n || ldb < n) return GPV_ERR_BAD_ARG;
-    if (const int rc = unwhiten_state(pl)) return rc;
+    if (const int rc = factor_state(pl)) return rc;
     const int cp = whiten_cp(ncols);
     if (const int rc = unwhiten_prepare(pl, cp)) return rc;
     hipStream_t st = pl->stream;
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
-    for (int j = 0; j < ncols; ++j)
-        if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_uw_in + (size_t)j * n, E_ord + (int64_t)j * lde, sizeof(double) * (size_t)n,
-                                          hipMemcpyHostToDevice, st)))
-            return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(launch_unwhiten_pack(pl->d_uw_in, n, ncols, cp, pl->d_uw_E, st))) return fail(GPV_ERR_HIP);
+    if (cols_to_device(pl->d_uw_in, E_ord, lde, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_unwhiten_pack(pl->d_uw_in, n, ncols, cp, pl->d_uw_E, st))) return drain_fail(st, GPV_ERR_HIP);
     pl->uw_cp_last = cp;
-    if (GPV_HIP_FAILED(unwhiten_sweep(pl, cp, st))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(launch_unwhiten_unpack(pl->d_uw_B, pl->d_newpos, n, ncols, cp, pl->d_uw_in, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(unwhiten_sweep(pl, cp, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_unwhiten_unpack(pl->d_uw_B, pl->d_newpos, n, ncols, cp, pl->d_uw_in, st))) return drain_fail(st, GPV_ERR_HIP);
     unsigned nf = 0;
-    if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_uw_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
-    for (int j = 0; j < ncols; ++j)                                               // (B_ord may be E_ord: the columns were read before)
-        if (GPV_HIP_FAILED(hipMemcpyAsync(B_ord + (int64_t)j * ldb, pl->d_uw_in + (size_t)j * n, sizeof(double) * (size_t)n,
-                                          hipMemcpyDeviceToHost, st)))
-            return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_uw_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (cols_to_host(B_ord, ldb, pl->d_uw_in, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);   // (B_ord may be E_ord: read before)
     GPV_HIP(hipStreamSynchronize(st));
     *n_failed = (int64_t)nf;
-    if (nf > 0)                                                                   // the recursion hands a failed row's NaN on: no entry is trusted
-        for (int j = 0; j < ncols; ++j) std::fill_n(B_ord + (int64_t)j * ldb, (size_t)n, (double)NAN);
+    if (nf > 0) cols_fill_nan(B_ord, ldb, n, ncols);                              // the recursion hands a failed row's NaN on: no entry is trusted
     return GPV_OK;
 }
 
@@ -2655,28 +2706,25 @@ int gpv_plan_simulate(gpv_plan *pl, uint64_t seed, int64_t col0, int64_t ncols, 
     if (!pl || !Z_ord || !n_failed || col0 < 0 || ncols < 1) return GPV_ERR_BAD_ARG;
     const int64_t n = pl->Nlocs;
     if (ldz < n || col0 > INT64_MAX - ncols) return GPV_ERR_BAD_ARG;
-    if (const int rc = unwhiten_state(pl)) return rc;
+    if (const int rc = factor_state(pl)) return rc;
     if (const int rc = unwhiten_prepare(pl, NB)) return rc;
     hipStream_t st = pl->stream;
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     const int64_t end = col0 + ncols;
     unsigned nf = 0;
     pl->uw_cp_last = NB;
     for (int64_t b = col0 / NB; b * NB < end; ++b) {
         const int64_t base = b * NB;
-        if (GPV_HIP_FAILED(launch_unwhiten_normals(pl->d_uw_E, n, seed, base, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(unwhiten_sweep(pl, NB, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(launch_unwhiten_unpack(pl->d_uw_B, pl->d_newpos, n, NB, NB, pl->d_uw_in, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_uw_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
-        for (int64_t j = std::max(base, col0); j < std::min(base + NB, end); ++j)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(Z_ord + (j - col0) * ldz, pl->d_uw_in + (size_t)(j - base) * n, sizeof(double) * (size_t)n,
-                                              hipMemcpyDeviceToHost, st)))
-                return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_unwhiten_normals(pl->d_uw_E, n, seed, base, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(unwhiten_sweep(pl, NB, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_unwhiten_unpack(pl->d_uw_B, pl->d_newpos, n, NB, NB, pl->d_uw_in, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_uw_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
+        const int64_t j0 = std::max(base, col0), j1 = std::min(base + NB, end);        // the batch's share of the call's columns
+        if (cols_to_host(Z_ord + (j0 - col0) * ldz, ldz, pl->d_uw_in + (size_t)(j0 - base) * n, n, j1 - j0, st))
+            return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
     }
     *n_failed = (int64_t)nf;
-    if (nf > 0)
-        for (int64_t j = 0; j < ncols; ++j) std::fill_n(Z_ord + j * ldz, (size_t)n, (double)NAN);
+    if (nf > 0) cols_fill_nan(Z_ord, ldz, n, ncols);
     return GPV_OK;
 }
 
@@ -2686,25 +2734,9 @@ int gpv_plan_simulate(gpv_plan *pl, uint64_t seed, int64_t col0, int64_t ncols, 
 extern "C" int gpv_plan_debug_unwhiten_ms(gpv_plan *pl, int reps, double *ms)
 {
     if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
-    if (const int rc = unwhiten_state(pl)) return rc;
+    if (const int rc = factor_state(pl)) return rc;
     if (pl->uw_cp_last == 0 || !pl->uw_sched) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
-    Event a, b;
-    GPV_HIP(hipEventCreate(a.put()));
-    GPV_HIP(hipEventCreate(b.put()));
-    int rc = GPV_OK;
-    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
-        float t = 0.f;
-        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(unwhiten_sweep(pl, pl->uw_cp_last, st)) ||
-            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
-            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
-            rc = GPV_ERR_HIP;
-        ms[r] = (double)t;
-    }
-    (void)hipStreamSynchronize(st);
-    return rc;
+    return timed_reps(pl, true, reps, ms, [&] { return unwhiten_sweep(pl, pl->uw_cp_last, pl->stream); });
 }
 
 // ---- the transposed whitening operator: precision products and leave-one-out cross-validation (gpv_loo.hip) ----------------
@@ -2729,17 +2761,16 @@ int gpv_loo_index_host(const int32_t *nn, const int32_t *rowid, int64_t rows, in
     return GPV_OK;
 }
 
-// what the plan's structure must be for the index to mean anything / what gpv_plan_whiten asks of the latest evaluation
+// z_structure() and the index's own limit / factor_state() and that limit, after every state error
 static int loo_structure(const gpv_plan *pl)
 {
-    if (pl->rows != pl->Nlocs || pl->Nlocs < 1 || pl->latent_nb || !pl->d_nn || !pl->d_rowid) return GPV_ERR_STATE;
+    if (const int rc = z_structure(pl)) return rc;
     if ((int64_t)pl->rows * pl->P >= ((int64_t)1 << 31)) return GPV_ERR_INDEX;     // the flat offsets of the index are int32
     return GPV_OK;
 }
 static int loo_state(const gpv_plan *pl)
 {
-    if (pl->L_of_eval == 0 || pl->L_of_eval != pl->eval_count || !pl->d_L) return GPV_ERR_STATE;
-    if (pl->comm || pl->d_obs) return GPV_ERR_STATE;
+    if (const int rc = factor_state(pl)) return rc;
     return loo_structure(pl);
 }
 
@@ -2797,9 +2828,7 @@ enum { kLooModeT = 0, kLooModeQ = 1, kLooModeCV = 2 };
 static LooArgs loo_args(gpv_plan *pl)
 {
     LooArgs a;
-    a.L = pl->d_L; a.nn = pl->d_nn; a.rowid = pl->d_rowid;
-    a.nuggets = pl->nug_is_scalar ? nullptr : pl->d_nuggets.get();
-    a.nug_scalar = pl->nug_scalar;
+    factor_view(pl, a);
     a.colptr = pl->d_loo_colptr; a.owner = pl->d_loo_owner; a.col = pl->d_loo_col;
     a.g = pl->d_loo_g; a.nfail = pl->d_loo_nfail;
     a.B = pl->d_loo_B; a.E = pl->d_loo_E; a.R = pl->d_loo_R; a.q = pl->d_loo_q;
@@ -2835,12 +2864,11 @@ static hipError_t loo_enqueue(gpv_plan *pl, int mode, int ncols, bool want_q, hi
 static int loo_scale_once(gpv_plan *pl, hipStream_t st)
 {
     if (pl->loo_g_eval == pl->eval_count) return GPV_OK;
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     pl->loo_g_eval = 0;
-    if (GPV_HIP_FAILED(hipMemsetAsync(pl->d_loo_nfail, 0, sizeof(unsigned), st))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(launch_loo_scale(loo_args(pl), pl->loo_grid, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemsetAsync(pl->d_loo_nfail, 0, sizeof(unsigned), st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_loo_scale(loo_args(pl), pl->loo_grid, st))) return drain_fail(st, GPV_ERR_HIP);
     unsigned nf = 0;
-    if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_loo_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(&nf, pl->d_loo_nfail, sizeof(nf), hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
     if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return GPV_ERR_HIP;
     pl->loo_nfail = nf;
     pl->loo_g_eval = pl->eval_count;
@@ -2855,9 +2883,8 @@ static int loo_run(gpv_plan *pl, int mode, const double *in, int64_t ldin, int n
 {
     if (const int rc = loo_state(pl)) return rc;
     const int64_t n = pl->Nlocs;
-    GPV_HIP(hipSetDevice(pl->device));
+    if (const int rc = enter(pl)) return rc;
     hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));   // the evaluation's stream
     if (const int rc = loo_index(pl)) return rc;
     const int cp = whiten_cp(ncols);
     if (cp > pl->loo_cp_cap) {
@@ -2870,35 +2897,26 @@ static int loo_run(gpv_plan *pl, int mode, const double *in, int64_t ldin, int n
         GPV_BUF(pl->d_loo_R, resize(cnt));
         pl->loo_cp_cap = cp;
     }
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     if (const int rc = loo_scale_once(pl, st)) return rc;
-    for (int j = 0; j < ncols; ++j)
-        if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_loo_in + (size_t)j * n, in + (int64_t)j * ldin, sizeof(double) * (size_t)n,
-                                          hipMemcpyHostToDevice, st)))
-            return fail(GPV_ERR_HIP);
+    if (cols_to_device(pl->d_loo_in, in, ldin, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
     pl->loo_last_mode = mode;
     pl->loo_last_ncols = ncols;
-    if (GPV_HIP_FAILED(loo_enqueue(pl, mode, ncols, vec != nullptr, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(loo_enqueue(pl, mode, ncols, vec != nullptr, st))) return drain_fail(st, GPV_ERR_HIP);
     double sc[kLooMaxCols * kLooNScores];
     if (mode == kLooModeCV &&
         GPV_HIP_FAILED(hipMemcpyAsync(sc, pl->d_loo_scores, sizeof(double) * (size_t)ncols * kLooNScores, hipMemcpyDeviceToHost, st)))
-        return fail(GPV_ERR_HIP);
-    if (out)
-        for (int j = 0; j < ncols; ++j)                                               // (out may be in: the columns were read before)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(out + (int64_t)j * ldout, pl->d_loo_out + (size_t)j * n, sizeof(double) * (size_t)n,
-                                              hipMemcpyDeviceToHost, st)))
-                return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
+    if (out && cols_to_host(out, ldout, pl->d_loo_out, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);   // (out may be in: read before)
     if (vec && GPV_HIP_FAILED(hipMemcpyAsync(vec, mode == kLooModeCV ? pl->d_loo_var.get() : pl->d_loo_qord.get(),
                                              sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st)))
-        return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
     GPV_HIP(hipStreamSynchronize(st));
     const bool bad = pl->loo_nfail > 0;
     *n_failed = (int64_t)pl->loo_nfail;
     if (scores)
         for (int t = 0; t < ncols * kLooNScores; ++t) scores[t] = bad ? (double)NAN : sc[t];
     if (bad) {                                         // a failed row's NaN reaches every location that names it: no entry is trusted
-        if (out)
-            for (int j = 0; j < ncols; ++j) std::fill_n(out + (int64_t)j * ldout, (size_t)n, (double)NAN);
+        if (out) cols_fill_nan(out, ldout, n, ncols);
         if (vec) std::fill_n(vec, (size_t)n, (double)NAN);
     }
     return GPV_OK;
@@ -2938,23 +2956,7 @@ extern "C" int gpv_plan_debug_loo_ms(gpv_plan *pl, int reps, double *ms)
     if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
     if (const int rc = loo_state(pl)) return rc;
     if (pl->loo_last_mode < 0 || !pl->loo_have_index || pl->loo_g_eval != pl->eval_count) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
-    Event a, b;
-    GPV_HIP(hipEventCreate(a.put()));
-    GPV_HIP(hipEventCreate(b.put()));
-    int rc = GPV_OK;
-    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
-        float t = 0.f;
-        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(loo_enqueue(pl, pl->loo_last_mode, pl->loo_last_ncols, true, st)) ||
-            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
-            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
-            rc = GPV_ERR_HIP;
-        ms[r] = (double)t;
-    }
-    (void)hipStreamSynchronize(st);
-    return rc;
+    return timed_reps(pl, true, reps, ms, [&] { return loo_enqueue(pl, pl->loo_last_mode, pl->loo_last_ncols, true, pl->stream); });
 }
 
 // ---- leave-block-out cross-validation: per-block precision solves (gpv_blockcv.hip) ----------------------------------------
@@ -3065,7 +3067,7 @@ static hipError_t bcv_enqueue(gpv_plan *pl, int ncols, hipStream_t st, int parts
     if ((e = hipMemsetAsync(pl->d_bcv_nlp, 0xFF, vecbytes, st)) != hipSuccess) return e;
     if ((e = hipMemsetAsync(pl->d_bcv_nbad, 0, sizeof(unsigned), st)) != hipSuccess) return e;
     BlockCvArgs b;
-    b.L = pl->d_L; b.nn = pl->d_nn; b.rowid = pl->d_rowid; b.g = pl->d_loo_g;
+    b.L = a.L; b.nn = a.nn; b.rowid = a.rowid; b.g = a.g;     // the factor's view and the scale, as the two passes above had them
     b.memptr = pl->d_bcv_memptr; b.members = pl->d_bcv_members; b.setptr = pl->d_bcv_setptr; b.sets = pl->d_bcv_sets;
     b.blkloc = reinterpret_cast<const int2 *>(pl->d_bcv_blkloc.get());
     b.B = pl->d_bcv_B; b.R = pl->d_bcv_R; b.D = pl->d_bcv_D; b.Y2 = pl->d_bcv_Y2; b.var = pl->d_bcv_var; b.nlp = pl->d_bcv_nlp;
@@ -3086,9 +3088,8 @@ int gpv_plan_block_cv(gpv_plan *pl, const double *Z_ord, int64_t ldz, int ncols,
     if (const int rc = loo_state(pl)) return rc;
     if (!pl->bcv_have) return GPV_ERR_STATE;
     const int64_t n = pl->Nlocs;
-    GPV_HIP(hipSetDevice(pl->device));
+    if (const int rc = enter(pl)) return rc;
     hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));   // the evaluation's stream
     if (const int rc = loo_index(pl)) return rc;
     const int cp = whiten_cp(ncols);
     if (cp > pl->bcv_cp_cap) {
@@ -3113,34 +3114,25 @@ int gpv_plan_block_cv(gpv_plan *pl, const double *Z_ord, int64_t ldz, int ncols,
         GPV_BUF(pl->d_bcv_scores, ensure((size_t)kBcvMaxCols * kBcvNScores));
         pl->bcv_cp_cap = cp;
     }
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     if (const int rc = loo_scale_once(pl, st)) return rc;
-    for (int j = 0; j < ncols; ++j)
-        if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_bcv_in + (size_t)j * n, Z_ord + (int64_t)j * ldz, sizeof(double) * (size_t)n,
-                                          hipMemcpyHostToDevice, st)))
-            return fail(GPV_ERR_HIP);
+    if (cols_to_device(pl->d_bcv_in, Z_ord, ldz, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
     pl->bcv_last_ncols = ncols;
-    if (GPV_HIP_FAILED(bcv_enqueue(pl, ncols, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(bcv_enqueue(pl, ncols, st))) return drain_fail(st, GPV_ERR_HIP);
     double sc[kBcvMaxCols * kBcvNScores];
     unsigned nbad = 0;
     if (GPV_HIP_FAILED(hipMemcpyAsync(sc, pl->d_bcv_scores, sizeof(double) * (size_t)ncols * kBcvNScores, hipMemcpyDeviceToHost, st)))
-        return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemcpyAsync(&nbad, pl->d_bcv_nbad, sizeof(nbad), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
-    if (mean)
-        for (int j = 0; j < ncols; ++j)                                               // (mean may be Z_ord: the columns were read before)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(mean + (int64_t)j * ldm, pl->d_bcv_out + (size_t)j * n, sizeof(double) * (size_t)n,
-                                              hipMemcpyDeviceToHost, st)))
-                return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(&nbad, pl->d_bcv_nbad, sizeof(nbad), hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (mean && cols_to_host(mean, ldm, pl->d_bcv_out, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);   // (mean may be Z_ord: read before)
     if (var && GPV_HIP_FAILED(hipMemcpyAsync(var, pl->d_bcv_varord, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, st)))
-        return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
     GPV_HIP(hipStreamSynchronize(st));
     const bool bad = pl->loo_nfail > 0;
     *n_failed = (int64_t)pl->loo_nfail;
     *n_bad_blocks = (int64_t)nbad;
     for (int t = 0; t < ncols * kBcvNScores; ++t) scores[t] = bad ? (double)NAN : sc[t];
     if (bad) {                                         // a failed row's NaN reaches every block that names it: no entry is trusted
-        if (mean)
-            for (int j = 0; j < ncols; ++j) std::fill_n(mean + (int64_t)j * ldm, (size_t)n, (double)NAN);
+        if (mean) cols_fill_nan(mean, ldm, n, ncols);
         if (var) std::fill_n(var, (size_t)n, (double)NAN);
     }
     return GPV_OK;
@@ -3154,23 +3146,7 @@ extern "C" int gpv_plan_debug_blockcv_ms(gpv_plan *pl, int reps, int parts, doub
     if (!pl || reps <= 0 || !ms || parts < 1 || parts > 7) return GPV_ERR_BAD_ARG;
     if (const int rc = loo_state(pl)) return rc;
     if (!pl->bcv_have || pl->bcv_last_ncols < 1 || !pl->loo_have_index || pl->loo_g_eval != pl->eval_count) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
-    Event a, b;
-    GPV_HIP(hipEventCreate(a.put()));
-    GPV_HIP(hipEventCreate(b.put()));
-    int rc = GPV_OK;
-    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
-        float t = 0.f;
-        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(bcv_enqueue(pl, pl->bcv_last_ncols, st, parts)) ||
-            GPV_HIP_FAILED(hipEventRecord(b, st)) || GPV_HIP_FAILED(hipStreamSynchronize(st)) ||
-            GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
-            rc = GPV_ERR_HIP;
-        ms[r] = (double)t;
-    }
-    (void)hipStreamSynchronize(st);
-    return rc;
+    return timed_reps(pl, true, reps, ms, [&] { return bcv_enqueue(pl, pl->bcv_last_ncols, pl->stream, parts); });
 }
 
 // ---- local kriging of a cond.yz='z' plan at new locations (gpv_krige.hip; the search: gpv_nn.hip) --------------------------
@@ -3210,9 +3186,8 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
     *n_failed = 0;
     if (nq == 0) return GPV_OK;
 
-    GPV_HIP(hipSetDevice(pl->device));
+    if (const int rc = enter(pl)) return rc;
     hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
     const int dim = pl->dim;
     const bool packed = dim <= 3;
     KrigeArgs a{};
@@ -3241,16 +3216,12 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
         GPV_BUF(d_nug, upload(nuggets, (size_t)n));
         a.nuggets = d_nug;
     }
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     if (Z_ord) {
         a.zld = (ncols + 3) / 4 * 4;
         GPV_BUF(d_in, resize((size_t)n * ncols));
         GPV_BUF(d_Z, resize((size_t)n * a.zld));
-        for (int j = 0; j < ncols; ++j)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(d_in + (size_t)j * n, Z_ord + (int64_t)j * ldz, sizeof(double) * (size_t)n,
-                                              hipMemcpyHostToDevice, st)))
-                return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(launch_rep_pack(d_in, pl->d_newpos, n, ncols, a.zld, d_Z, st))) return fail(GPV_ERR_HIP);
+        if (cols_to_device(d_in, Z_ord, ldz, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_rep_pack(d_in, pl->d_newpos, n, ncols, a.zld, d_Z, st))) return drain_fail(st, GPV_ERR_HIP);
         a.Z = d_Z;
     }
     // the search over the plan's locations in the ORDERED numbering, on the coordinates divided by `scale`
@@ -3260,13 +3231,13 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
         std::vector<double> rec((size_t)n * ld), lc((size_t)n * dim);
         if (GPV_HIP_FAILED(hipMemcpyAsync(rec.data(), pl->d_locs, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, st)) ||
             GPV_HIP_FAILED(hipStreamSynchronize(st)))
-            return fail(GPV_ERR_HIP);
+            return drain_fail(st, GPV_ERR_HIP);
         for (int t = 0; t < dim; ++t)
             for (int64_t i = 0; i < n; ++i) {
                 const double x = rec[(size_t)pl->h_newpos[(size_t)i] * ld + t];
                 lc[(size_t)i + (size_t)t * n] = scale ? x / scale[t] : x;
             }
-        if (GPV_HIP_FAILED(qnn_build(lc.data(), n, dim, eligible_ord, index.ix))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(qnn_build(lc.data(), n, dim, eligible_ord, index.ix))) return drain_fail(st, GPV_ERR_HIP);
     }
     // the chunks: queries up, search or neighbours up, the pass, results back
     const int64_t cap = std::min<int64_t>(chunk > 0 ? chunk : kKrigeChunk, nq);
@@ -3279,7 +3250,7 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
     GPV_BUF(d_var, resize((size_t)cap));
     GPV_BUF(d_nn, resize((size_t)cap * m));
     GPV_BUF(d_nfail, resize(2));
-    if (GPV_HIP_FAILED(hipMemsetAsync(d_nfail, 0, sizeof(unsigned), st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemsetAsync(d_nfail, 0, sizeof(unsigned), st))) return drain_fail(st, GPV_ERR_HIP);
     a.nnq = d_nn; a.q = d_q; a.mean = d_mean; a.var = d_var; a.nfail = d_nfail;
     Event ev[3];                                           // around the search and the pass of a chunk
     for (auto &e : ev) GPV_HIP(hipEventCreate(e.put()));
@@ -3295,28 +3266,25 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
                 if (d_qs) hqs[(size_t)i * dim + t] = x / scale[t];
             }
         if (GPV_HIP_FAILED(hipMemcpyAsync(d_q, hq.data(), sizeof(double) * (size_t)cn * dim, hipMemcpyHostToDevice, st)))
-            return fail(GPV_ERR_HIP);
+            return drain_fail(st, GPV_ERR_HIP);
         if (NNq) {
             for (int s = 0; s < m; ++s)
                 for (int64_t i = 0; i < cn; ++i) hnn[(size_t)i * m + s] = NNq[c0 + i + (int64_t)s * nq];
             if (GPV_HIP_FAILED(hipMemcpyAsync(d_nn, hnn.data(), sizeof(int32_t) * (size_t)cn * m, hipMemcpyHostToDevice, st)))
-                return fail(GPV_ERR_HIP);
+                return drain_fail(st, GPV_ERR_HIP);
         } else {
             if (d_qs && GPV_HIP_FAILED(hipMemcpyAsync(d_qs, hqs.data(), sizeof(double) * (size_t)cn * dim, hipMemcpyHostToDevice, st)))
-                return fail(GPV_ERR_HIP);
-            if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return fail(GPV_ERR_HIP);
-            if (GPV_HIP_FAILED(qnn_search(index.ix, d_qs ? d_qs.get() : d_q.get(), cn, m, d_nn, st))) return fail(GPV_ERR_HIP);
+                return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(qnn_search(index.ix, d_qs ? d_qs.get() : d_q.get(), cn, m, d_nn, st))) return drain_fail(st, GPV_ERR_HIP);
         }
         a.nq = cn;
-        if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(launch_krige(a, krige_grid(cn, pl->cus), st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipEventRecord(ev[2], st))) return fail(GPV_ERR_HIP);
-        for (int j = 0; j < ncols; ++j)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(mean + (int64_t)j * ldm + c0, d_mean + (size_t)j * cn, sizeof(double) * (size_t)cn,
-                                              hipMemcpyDeviceToHost, st)))
-                return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_krige(a, krige_grid(cn, pl->cus), st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipEventRecord(ev[2], st))) return drain_fail(st, GPV_ERR_HIP);
+        if (cols_to_host(mean + c0, ldm, d_mean, cn, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
         if (GPV_HIP_FAILED(hipMemcpyAsync(var + c0, d_var, sizeof(double) * (size_t)cn, hipMemcpyDeviceToHost, st)))
-            return fail(GPV_ERR_HIP);
+            return drain_fail(st, GPV_ERR_HIP);
         GPV_HIP(hipStreamSynchronize(st));                 // (the staging vectors and the chunk buffers are reused)
         float t = 0.f;
         if (!NNq && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) pl->kr_search_ms += (double)t;
@@ -3409,8 +3377,7 @@ int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int
     }
     if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
     if (nrows == 0) return GPV_OK;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (const int rc = enter_final(pl)) return rc;
     if (!pl->lc_ready) {
         const int rc = lincomb_prepare(pl);
         if (rc != GPV_OK) return rc;
@@ -3419,14 +3386,13 @@ int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int
     DevBuf<int64_t> d_hptr;                                                   // this call's rows (freed when it returns)
     DevBuf<int32_t> d_hidx;
     DevBuf<double> d_hval;
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };   // nothing in flight reads them when they go
     std::vector<int64_t> hp((size_t)nrows + 1);
     for (int64_t r = 0; r <= nrows; ++r) hp[(size_t)r] = hptr[r] - h0;        // offsets into the uploaded slice
     if (GPV_BUF_FAILED(d_hptr, upload(hp.data(), hp.size())) || GPV_BUF_FAILED(d_hidx, upload(hnnz ? hidx + h0 : nullptr, (size_t)hnnz)) ||
         GPV_BUF_FAILED(d_hval, upload(hnnz ? hval + h0 : nullptr, (size_t)hnnz)))
-        return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
     if (cov && (GPV_BUF_FAILED(pl->d_lc_gpart, ensure((size_t)kLincombBlocks * NB * NB)) || GPV_BUF_FAILED(pl->d_lc_gram, ensure(NB * NB))))
-        return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
     LincombArgs la;
     la.colrec = pl->d_colrec; la.lrec = pl->d_lc_rec; la.C = pl->d_C; la.X = pl->d_lc_X;
     // the sweep: the factor pass's levels, leaves first, then the dense top block, then the column sums
@@ -3445,13 +3411,13 @@ int gpv_plan_lincomb(gpv_plan *pl, int64_t nrows, const int64_t *hptr, const int
         const int nb = (int)std::min<int64_t>(NB, nrows - row0);
         if (GPV_HIP_FAILED(launch_lincomb_init(pl->d_lc_X, pl->Nlocs, d_hptr, d_hidx, d_hval, row0, nb, bmax[(size_t)b],
                                                bserial[(size_t)b] != 0, st)))
-            return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(graph_replay(pl->lc_graph, st, enqueue))) return fail(GPV_ERR_HIP);
-        if (cov && GPV_HIP_FAILED(launch_lincomb_gram(pl->d_lc_X, pl->Nlocs, pl->d_lc_gpart, pl->d_lc_gram, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipMemcpyAsync(vb.data(), pl->d_lc_vars, sizeof(double) * NB, hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+            return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(graph_replay(pl->lc_graph, st, enqueue))) return drain_fail(st, GPV_ERR_HIP);
+        if (cov && GPV_HIP_FAILED(launch_lincomb_gram(pl->d_lc_X, pl->Nlocs, pl->d_lc_gpart, pl->d_lc_gram, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipMemcpyAsync(vb.data(), pl->d_lc_vars, sizeof(double) * NB, hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
         if (cov && GPV_HIP_FAILED(hipMemcpyAsync(gb.data(), pl->d_lc_gram, sizeof(double) * NB * NB, hipMemcpyDeviceToHost, st)))
-            return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+            return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
         for (int j = 0; j < nb; ++j) vars[row0 + j] = vb[(size_t)j];
         if (cov)
             for (int i = 0; i < nb; ++i)
@@ -3484,31 +3450,22 @@ int gpv_plan_solve_t(gpv_plan *pl, int64_t ncols, const double *E, int64_t lde, 
     if (!pl || ncols < 0 || !E || !X) return GPV_ERR_BAD_ARG;
     const int64_t n = pl->Nlocs;
     if (lde < n || ldx < n) return GPV_ERR_BAD_ARG;
-    if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
-    if (pl->post_ld > 64 || !pl->d_meanrec) return GPV_ERR_STATE;               // (no structure is built with longer columns)
+    if (const int rc = posterior_factor_state(pl)) return rc;
     if (ncols == 0) return GPV_OK;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (const int rc = enter_final(pl)) return rc;
     GPV_BUF(pl->d_lc_X, ensure((size_t)n * NB));
     GPV_BUF(pl->d_st_E, ensure((size_t)n * NB));
     hipStream_t st = pl->stream;
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     const int64_t nbatch = (ncols + NB - 1) / NB;
     for (int64_t b = 0; b < nbatch; ++b) {
         const int64_t col0 = b * NB;
         const int nb = (int)std::min<int64_t>(NB, ncols - col0);
-        for (int j = 0; j < nb; ++j)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(pl->d_st_E + (size_t)j * n, E + (col0 + j) * lde, sizeof(double) * (size_t)n,
-                                              hipMemcpyHostToDevice, st)))
-                return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(launch_solvet_pack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(solvet_sweep(pl, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(launch_solvet_unpack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return fail(GPV_ERR_HIP);
-        for (int j = 0; j < nb; ++j)                                              // (X may be E: the batch was read before)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(X + (col0 + j) * ldx, pl->d_st_E + (size_t)j * n, sizeof(double) * (size_t)n,
-                                              hipMemcpyDeviceToHost, st)))
-                return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+        if (cols_to_device(pl->d_st_E, E + col0 * lde, lde, n, nb, st)) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_solvet_pack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(solvet_sweep(pl, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_solvet_unpack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (cols_to_host(X + col0 * ldx, ldx, pl->d_st_E, n, nb, st)) return drain_fail(st, GPV_ERR_HIP);   // (X may be E: the batch was read before)
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
     }
     pl->last_stream = st;
     return GPV_OK;
@@ -3521,37 +3478,16 @@ extern "C" int gpv_plan_debug_solve_t_ms(gpv_plan *pl, int reps, double *ms)
 {
     if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
     if (!pl->have_post || !pl->have_factor || pl->comm || !pl->d_lc_X || !pl->d_st_E) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    hipStream_t st = pl->stream;
-    Event a, b;
-    GPV_HIP(hipEventCreate(a.put()));
-    GPV_HIP(hipEventCreate(b.put()));
-    int rc = GPV_OK;
-    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
-        float t = 0.f;
-        if (GPV_HIP_FAILED(launch_solvet_pack(pl->d_lc_X, pl->d_st_E, pl->Nlocs, pl->Nlocs, kLincombNB, st)) ||
-            GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(solvet_sweep(pl, st)) || GPV_HIP_FAILED(hipEventRecord(b, st)) ||
-            GPV_HIP_FAILED(hipStreamSynchronize(st)) || GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
-            rc = GPV_ERR_HIP;
-        ms[r] = (double)t;
-    }
-    (void)hipStreamSynchronize(st);
-    return rc;
+    // (the one timed entry that does not wait for the stream of the latest evaluation; the pack ahead of each run is untimed)
+    return timed_reps(pl, false, reps, ms, [&] { return solvet_sweep(pl, pl->stream); },
+                      [&] { return launch_solvet_pack(pl->d_lc_X, pl->d_st_E, pl->Nlocs, pl->Nlocs, kLincombNB, pl->stream); });
 }
 
 // ---- the selected inverse of the factor: every posterior variance in one pass (gpv_selinv.hip) -------------------------------
-// what gpv_plan_lincomb and gpv_plan_solve_t ask of the plan
-static int selinv_state(const gpv_plan *pl)
-{
-    if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
-    if (pl->post_ld > 64 || !pl->d_meanrec) return GPV_ERR_STATE;
-    return GPV_OK;
-}
-
 // The records of the pass from the plan's structure as it lives on the device (built on the first gpv_plan_selinv after a
-// gpv_plan_build_posterior, like lincomb_prepare): the row lists are rebuilt as build_posterior_impl lays them out, which gives
-// every entry of a column the row-list position of its pair and with it the pair's match records; the terms the pattern
-// drops are counted here, once: they depend on the structure alone.
+// gpv_plan_build_posterior: plans that never ask pay nothing): the row lists are rebuilt as build_posterior_impl lays them
+// out, which gives every entry of a column the row-list position of its pair and with it the pair's match records; the terms
+// the pattern drops are counted here, once: they depend on the structure alone.
 static int selinv_prepare(gpv_plan *pl)
 {
     const int64_t n = pl->Nlocs;
@@ -3660,17 +3596,15 @@ int gpv_plan_selinv(gpv_plan *pl, int64_t skip_front, double *vars_ord, int64_t 
 {
     if (!pl || !vars_ord || !n_dropped) return GPV_ERR_BAD_ARG;
     if (skip_front < 0 || skip_front >= pl->Nlocs) return GPV_ERR_BAD_ARG;
-    if (const int rc = selinv_state(pl)) return rc;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (const int rc = posterior_factor_state(pl)) return rc;
+    if (const int rc = enter_final(pl)) return rc;
     if (!pl->sel_ready)
         if (const int rc = selinv_prepare(pl)) return rc;
     hipStream_t st = pl->stream;
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
-    if (GPV_HIP_FAILED(selinv_sweep(pl, st))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(launch_selinv_out(pl->d_sel_vars, pl->Nlocs, skip_front, pl->d_sel_out, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(selinv_sweep(pl, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_selinv_out(pl->d_sel_vars, pl->Nlocs, skip_front, pl->d_sel_out, st))) return drain_fail(st, GPV_ERR_HIP);
     if (GPV_HIP_FAILED(hipMemcpyAsync(vars_ord, pl->d_sel_out, sizeof(double) * (size_t)pl->Nlocs, hipMemcpyDeviceToHost, st)))
-        return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
     GPV_HIP(hipStreamSynchronize(st));
     *n_dropped = pl->sel_dropped;
     pl->last_stream = st;
@@ -3682,24 +3616,9 @@ int gpv_plan_selinv(gpv_plan *pl, int64_t skip_front, double *vars_ord, int64_t 
 extern "C" int gpv_plan_debug_selinv_ms(gpv_plan *pl, int reps, double *ms)
 {
     if (!pl || reps <= 0 || !ms) return GPV_ERR_BAD_ARG;
-    if (const int rc = selinv_state(pl)) return rc;
+    if (const int rc = posterior_factor_state(pl)) return rc;
     if (!pl->sel_ready) return GPV_ERR_STATE;
-    GPV_HIP(hipSetDevice(pl->device));
-    hipStream_t st = pl->stream;
-    if (pl->last_stream && pl->last_stream != st) GPV_HIP(hipStreamSynchronize(pl->last_stream));
-    Event a, b;
-    GPV_HIP(hipEventCreate(a.put()));
-    GPV_HIP(hipEventCreate(b.put()));
-    int rc = GPV_OK;
-    for (int r = 0; r < reps && rc == GPV_OK; ++r) {
-        float t = 0.f;
-        if (GPV_HIP_FAILED(hipEventRecord(a, st)) || GPV_HIP_FAILED(selinv_sweep(pl, st)) || GPV_HIP_FAILED(hipEventRecord(b, st)) ||
-            GPV_HIP_FAILED(hipStreamSynchronize(st)) || GPV_HIP_FAILED(hipEventElapsedTime(&t, a, b)))
-            rc = GPV_ERR_HIP;
-        ms[r] = (double)t;
-    }
-    (void)hipStreamSynchronize(st);
-    return rc;
+    return timed_reps(pl, true, reps, ms, [&] { return selinv_sweep(pl, pl->stream); });
 }
 
 // ---- value and analytic gradient of the cond.yz='SGV' log-likelihood (gpv_grad_sgv.hip) ---------------------------------------
@@ -3775,8 +3694,7 @@ int gpv_plan_loglik_grad_sgv(gpv_plan *pl, const char *covType, const double *co
     if (!pl->have_post || pl->post_filled || pl->post_ld > 64 || !pl->d_meanrec || pl->row_begin != 0) return GPV_ERR_STATE;
     // the structure's own facts, established once: the terms its selected inverse drops (none for SGV) and the index data.
     // They read the plan's arrays and write buffers of their own; a refusal here leaves every result of the plan as it was.
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if ((rc = enter_final(pl)) != GPV_OK) return rc;
     if (!pl->sel_ready && (rc = selinv_prepare(pl)) != GPV_OK) return rc;
     if (pl->sel_dropped > 0) return GPV_ERR_STATE;
     if (!pl->sgv_ready && (rc = sgv_prepare(pl)) != GPV_OK) return rc;
@@ -3790,15 +3708,14 @@ int gpv_plan_loglik_grad_sgv(gpv_plan *pl, const char *covType, const double *co
     // the evaluation, on the plan's stream; its sums, mean, U entries and factor stamp are what the caller finds afterwards
     if ((rc = plan_eval_checked(pl, cs, &nugget, 1, GPV_WANT_MEAN, nullptr, nullptr)) != GPV_OK) return rc;
     hipStream_t st = pl->stream;
-    auto fail = [&](int rc2) { (void)hipStreamSynchronize(st); return rc2; };
-    if (GPV_HIP_FAILED(selinv_sweep(pl, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(selinv_sweep(pl, st))) return drain_fail(st, GPV_ERR_HIP);
     a.row_terms = col_terms ? pl->d_sgv_rows.get() : nullptr;
     a.block_part = pl->d_sgv_part; a.totals = pl->d_sgv_tot;
     sa.cpos = pl->d_sgv_cpos; sa.setrec = pl->d_sgv_rec; sa.crow = pl->d_crow;
     sa.pair = pl->d_sel_pair; sa.tp = pl->d_tp; sa.S = pl->d_sel_S; sa.vars = pl->d_sel_vars; sa.mu = pl->d_u;
     double tot[kSgvNV];
-    if (GPV_HIP_FAILED(launch_grad_sgv(pl->p, sa, grid, st))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemcpyAsync(tot, pl->d_sgv_tot, sizeof(tot), hipMemcpyDeviceToHost, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_grad_sgv(pl->p, sa, grid, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(tot, pl->d_sgv_tot, sizeof(tot), hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
     GPV_HIP(hipStreamSynchronize(st));
     double sums[kNSums];
     if ((rc = gpv_plan_get_sums(pl, sums)) != GPV_OK) return rc;
@@ -3843,39 +3760,28 @@ int gpv_draws_normals_host(uint64_t seed, int64_t k0, int64_t nk, int64_t col0, 
     return GPV_OK;
 }
 
-// the state every entry that sweeps with the factor asks for (gpv_plan_solve_t)
-static int draws_state(const gpv_plan *pl)
-{
-    if (!pl->have_post || !pl->have_factor || pl->comm) return GPV_ERR_STATE;
-    if (pl->post_ld > 64 || !pl->d_meanrec) return GPV_ERR_STATE;
-    return GPV_OK;
-}
-
 int gpv_plan_draws_normals(gpv_plan *pl, uint64_t seed, int64_t skip_front, int64_t col0, int64_t ncols, double *E, int64_t lde)
 {
     constexpr int NB = kLincombNB;
     if (!pl || !E || ncols < 0 || col0 < 0) return GPV_ERR_BAD_ARG;
     const int64_t n = pl->Nlocs;
     if (lde < n || skip_front < 0 || skip_front >= n) return GPV_ERR_BAD_ARG;
-    if (const int rc = draws_state(pl)) return rc;
+    if (const int rc = posterior_factor_state(pl)) return rc;
     if (ncols == 0) return GPV_OK;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (const int rc = enter_final(pl)) return rc;
     GPV_BUF(pl->d_lc_X, ensure((size_t)n * NB));
     GPV_BUF(pl->d_st_E, ensure((size_t)n * NB));
     hipStream_t st = pl->stream;
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     const int64_t end = col0 + ncols;
     for (int64_t b = col0 / NB; b * NB < end; ++b) {                       // the batches of gpv_plan_draws_summary that hold them
         const int64_t base = b * NB;
         const int nb = (int)std::min<int64_t>(NB, end - base);
-        if (GPV_HIP_FAILED(launch_draws_fill(pl->d_lc_X, n, seed, skip_front, base, nb, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(launch_solvet_unpack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return fail(GPV_ERR_HIP);
-        for (int64_t j = std::max(base, col0); j < base + nb; ++j)
-            if (GPV_HIP_FAILED(hipMemcpyAsync(E + (j - col0) * lde, pl->d_st_E + (size_t)(j - base) * n, sizeof(double) * (size_t)n,
-                                              hipMemcpyDeviceToHost, st)))
-                return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_draws_fill(pl->d_lc_X, n, seed, skip_front, base, nb, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_solvet_unpack(pl->d_lc_X, pl->d_st_E, n, n, nb, st))) return drain_fail(st, GPV_ERR_HIP);
+        const int64_t j0 = std::max(base, col0);                           // the batch's share of the call's columns
+        if (cols_to_host(E + (j0 - col0) * lde, lde, pl->d_st_E + (size_t)(j0 - base) * n, n, base + nb - j0, st))
+            return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
     }
     pl->last_stream = st;
     return GPV_OK;
@@ -3924,12 +3830,10 @@ int gpv_plan_draws_summary(gpv_plan *pl, int64_t ndraws, uint64_t seed, int64_t 
         for (int64_t k = skip_front; k < n; ++k) nsel += mask[k] != 0;
         if (nsel == 0) return GPV_ERR_BAD_ARG;
     }
-    if (const int rc = draws_state(pl)) return rc;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (const int rc = posterior_factor_state(pl)) return rc;
+    if (const int rc = enter_final(pl)) return rc;
     if (const int rc = draws_alloc(pl, ndraws)) return rc;
     hipStream_t st = pl->stream;
-    auto fail = [&](int rc) { (void)hipStreamSynchronize(st); return rc; };
     const DrawsBuf B = draws_buf(pl);
     DrawsArgs a{};
     a.X = pl->d_lc_X; a.mu = B.mu; a.mask = (mask && want_draw) ? pl->d_ds_mask : nullptr;
@@ -3939,30 +3843,30 @@ int gpv_plan_draws_summary(gpv_plan *pl, int64_t ndraws, uint64_t seed, int64_t 
     const size_t nbytes = sizeof(double) * (size_t)n;
     if (mu_ord ? GPV_HIP_FAILED(hipMemcpyAsync(B.mu, mu_ord, nbytes, hipMemcpyHostToDevice, st))
                : GPV_HIP_FAILED(hipMemsetAsync(B.mu, 0, nbytes, st)))
-        return fail(GPV_ERR_HIP);
-    if (a.mask && GPV_HIP_FAILED(hipMemcpyAsync(pl->d_ds_mask, mask, (size_t)n, hipMemcpyHostToDevice, st))) return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemsetAsync(B.S1, 0, 2 * nbytes, st))) return fail(GPV_ERR_HIP);                  // S1 and S2
+        return drain_fail(st, GPV_ERR_HIP);
+    if (a.mask && GPV_HIP_FAILED(hipMemcpyAsync(pl->d_ds_mask, mask, (size_t)n, hipMemcpyHostToDevice, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemsetAsync(B.S1, 0, 2 * nbytes, st))) return drain_fail(st, GPV_ERR_HIP);                  // S1 and S2
     if (nthr > 0 && GPV_HIP_FAILED(hipMemsetAsync(pl->d_ds_cnt, 0, sizeof(uint32_t) * (size_t)nthr * (size_t)n, st)))
-        return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
     double *d_max = pl->d_ds_draw, *d_mean = pl->d_ds_draw + ndraws;
     for (int64_t draw0 = 0; draw0 < ndraws; draw0 += NB) {
         const int nb = (int)std::min<int64_t>(NB, ndraws - draw0);
-        if (GPV_HIP_FAILED(launch_draws_fill(pl->d_lc_X, n, seed, skip_front, draw0, nb, st))) return fail(GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(solvet_sweep(pl, st))) return fail(GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_draws_fill(pl->d_lc_X, n, seed, skip_front, draw0, nb, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(solvet_sweep(pl, st))) return drain_fail(st, GPV_ERR_HIP);
         if (GPV_HIP_FAILED(launch_draws_accum(a, link, nb, draw0, (double)nsel, want_draw ? d_max : nullptr,
                                               want_draw ? d_mean : nullptr, st)))
-            return fail(GPV_ERR_HIP);
+            return drain_fail(st, GPV_ERR_HIP);
     }
-    if (GPV_HIP_FAILED(launch_draws_finish(a, link, ndraws, B.mean, B.var, B.exceed, st))) return fail(GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_draws_finish(a, link, ndraws, B.mean, B.var, B.exceed, st))) return drain_fail(st, GPV_ERR_HIP);
     if (GPV_HIP_FAILED(hipMemcpyAsync(mean, B.mean, nbytes, hipMemcpyDeviceToHost, st)) ||
         GPV_HIP_FAILED(hipMemcpyAsync(var, B.var, nbytes, hipMemcpyDeviceToHost, st)))
-        return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
     if (nthr > 0 && GPV_HIP_FAILED(hipMemcpyAsync(exceed, B.exceed, nbytes * (size_t)nthr, hipMemcpyDeviceToHost, st)))
-        return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
     if (want_draw && (GPV_HIP_FAILED(hipMemcpyAsync(draw_max, d_max, sizeof(double) * (size_t)ndraws, hipMemcpyDeviceToHost, st)) ||
                       GPV_HIP_FAILED(hipMemcpyAsync(draw_mean, d_mean, sizeof(double) * (size_t)ndraws, hipMemcpyDeviceToHost, st))))
-        return fail(GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return fail(GPV_ERR_HIP);
+        return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
     pl->last_stream = st;
     return GPV_OK;
 }
@@ -3973,10 +3877,9 @@ int gpv_plan_draws_summary(gpv_plan *pl, int64_t ndraws, uint64_t seed, int64_t 
 extern "C" int gpv_plan_debug_draws_ms(gpv_plan *pl, uint64_t seed, double *ms)
 {
     if (!pl || !ms) return GPV_ERR_BAD_ARG;
-    if (const int rc = draws_state(pl)) return rc;
+    if (const int rc = posterior_factor_state(pl)) return rc;
     if (!pl->d_lc_X || !pl->d_ds || pl->ds_draw_cap < kLincombNB) return GPV_ERR_STATE;   // (after a gpv_plan_draws_summary)
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));      // the factor is final
+    if (const int rc = enter_final(pl)) return rc;
     hipStream_t st = pl->stream;
     const DrawsBuf B = draws_buf(pl);
     DrawsArgs a{};
@@ -4049,8 +3952,7 @@ int gpv_plan_get_sums(gpv_plan *pl, double *sums)
 extern "C" int gpv_plan_debug_block_sums(gpv_plan *pl, int64_t offset, int64_t count, double *out, int *grid)
 {
     if (!pl || !out || offset < 0 || count < 0 || offset + count > (int64_t)kMaxGrid * kNSums) return GPV_ERR_BAD_ARG;
-    GPV_HIP(hipSetDevice(pl->device));
-    if (pl->last_stream) GPV_HIP(hipStreamSynchronize(pl->last_stream));
+    if (const int rc = enter_final(pl)) return rc;
     GPV_HIP(hipMemcpy(out, pl->d_block + offset, sizeof(double) * (size_t)count, hipMemcpyDeviceToHost));
     if (grid) *grid = pl->grid;
     return GPV_OK;

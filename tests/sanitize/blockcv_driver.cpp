@@ -22,6 +22,7 @@
 
 extern "C" long mockhip_launches(void);
 extern "C" long mockhip_live_allocations(void);
+extern "C" int gpv_plan_debug_blockcv_ms(gpv_plan *pl, int reps, int parts, double *ms);   // developer aid, not in the public header
 
 static int g_fail = 0;
 #define EXPECT(cond)                                                                           \
@@ -108,8 +109,15 @@ int main()
     EXPECT_ST(gpv_plan_block_cv(pl, A.data(), lda, 17, O.data(), ldo, q.data(), sc.data(), &nf, &nbad), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_block_cv(pl, A.data(), n - 1, 3, O.data(), ldo, q.data(), sc.data(), &nf, &nbad), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_block_cv(pl, A.data(), lda, 3, O.data(), n - 1, q.data(), sc.data(), &nf, &nbad), GPV_ERR_BAD_ARG);
+    double tms[3] = {guard, guard, guard};
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(nullptr, 2, 7, tms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 0, 7, tms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 2, 7, nullptr), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 2, 0, tms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 2, 8, tms), GPV_ERR_BAD_ARG);
     // ---- state: no evaluation and no blocks
     EXPECT_ST(gpv_plan_block_cv(pl, A.data(), lda, 3, O.data(), ldo, q.data(), sc.data(), &nf, &nbad), GPV_ERR_STATE);
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 2, 7, tms), GPV_ERR_STATE);
     EXPECT(nf == -1 && nbad == -1 && O[0] == guard && q[0] == guard && sc[0] == guard);        // a refused call writes nothing
     // labels are refused before the device is touched, and nothing is reported
     {
@@ -141,6 +149,9 @@ int main()
     int64_t stamp0 = -1, stamp1 = -1;
     EXPECT_ST(gpv_plan_get_sums(pl, sums0), GPV_OK);
     EXPECT_ST(gpv_plan_factor_stamp(pl, &stamp0), GPV_OK);
+    const long l0 = mockhip_launches();
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 2, 7, tms), GPV_ERR_STATE);                        // a factor and blocks, but no columns left by a call yet
+    EXPECT(mockhip_launches() == l0 && tms[0] == guard);
     // ---- buffer growth across column counts, shapes
     EXPECT_ST(gpv_plan_block_cv(pl, A.data(), lda, 3, O.data(), ldo, q.data(), sc.data(), &nf, &nbad), GPV_OK);
     EXPECT(nf == 0 && nbad == 0);                                                              // (no kernel ran: the counters were cleared)
@@ -183,6 +194,17 @@ int main()
     const long before = mockhip_launches();
     EXPECT_ST(gpv_plan_block_cv(pl, A.data(), lda, 2, O.data(), ldo, q.data(), sc.data(), &nf, &nbad), GPV_OK);
     const long per_call = mockhip_launches() - before;
+    // the timed repetitions on what that call left: its device passes (the scale is the evaluation's, made once), no copies
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 2, 7, tms), GPV_OK);
+    EXPECT(mockhip_launches() - before == per_call + 2 * per_call);
+    EXPECT(tms[0] == 0.125 && tms[1] == 0.125 && tms[2] == guard);                             // the mock's elapsed time, reps values
+    {                                                                                          // the three parts make up the whole
+        const long b1 = mockhip_launches();
+        EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 1, 1, tms), GPV_OK);
+        EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 1, 2, tms), GPV_OK);
+        EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 1, 4, tms), GPV_OK);
+        EXPECT(mockhip_launches() - b1 == per_call);
+    }
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, nugv.data(), n, GPV_WANT_U, nullptr, nullptr), GPV_OK);
     const long before2 = mockhip_launches();
     EXPECT_ST(gpv_plan_block_cv(pl, A.data(), lda, 2, O.data(), ldo, q.data(), sc.data(), &nf, &nbad), GPV_OK);  // the blocks outlive evaluations
@@ -190,6 +212,9 @@ int main()
     // the next evaluation leaves U alone: the resident one is stale
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, &tau, 1, GPV_WANT_LOGLIK_Z, nullptr, nullptr), GPV_OK);
     EXPECT_ST(gpv_plan_block_cv(pl, A.data(), lda, 2, O.data(), ldo, q.data(), sc.data(), &nf, &nbad), GPV_ERR_STATE);
+    const long l1 = mockhip_launches();
+    EXPECT_ST(gpv_plan_debug_blockcv_ms(pl, 2, 7, tms), GPV_ERR_STATE);                        // ... for the timed repetitions too
+    EXPECT(mockhip_launches() == l1);
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, &tau, 1, GPV_WANT_U, nullptr, nullptr), GPV_OK);
     // unobserved locations
     std::vector<int> obs((size_t)n, 1);

@@ -20,6 +20,7 @@
 
 extern "C" long mockhip_launches(void);
 extern "C" long mockhip_live_allocations(void);
+extern "C" int gpv_plan_debug_loo_ms(gpv_plan *pl, int reps, double *ms);          // developer aid, not in the public header
 
 static int g_fail = 0;
 #define EXPECT(cond)                                                                           \
@@ -121,10 +122,15 @@ int main()
     EXPECT_ST(gpv_plan_loo_index(pl, nullptr, &e1, &e2), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_loo_index(pl, &e0, nullptr, &e2), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_loo_index(pl, &e0, &e1, nullptr), GPV_ERR_BAD_ARG);
+    double ms[3] = {guard, guard, guard};
+    EXPECT_ST(gpv_plan_debug_loo_ms(nullptr, 2, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_loo_ms(pl, 0, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_loo_ms(pl, 2, nullptr), GPV_ERR_BAD_ARG);
     // ---- state: which evaluation the resident factor belongs to
     EXPECT_ST(gpv_plan_whiten_t(pl, A.data(), lda, 3, O.data(), ldo, &nf), GPV_ERR_STATE);                       // no evaluation
     EXPECT_ST(gpv_plan_precision(pl, A.data(), lda, 3, O.data(), ldo, q.data(), &nf), GPV_ERR_STATE);
     EXPECT_ST(gpv_plan_loo(pl, A.data(), lda, 3, O.data(), ldo, q.data(), sc.data(), &nf), GPV_ERR_STATE);
+    EXPECT_ST(gpv_plan_debug_loo_ms(pl, 2, ms), GPV_ERR_STATE);
     EXPECT(nf == -1 && O[0] == guard && q[0] == guard && sc[0] == guard);                      // a refused call writes nothing
     EXPECT(mockhip_launches() == 0);                                                           // ... and launches nothing
     // the index needs no evaluation: every location k is a neighbour of the rows k + 1 .. k + 10
@@ -141,6 +147,9 @@ int main()
     int64_t stamp0 = -1, stamp1 = -1;
     EXPECT_ST(gpv_plan_get_sums(pl, sums0), GPV_OK);
     EXPECT_ST(gpv_plan_factor_stamp(pl, &stamp0), GPV_OK);
+    const long l0 = mockhip_launches();
+    EXPECT_ST(gpv_plan_debug_loo_ms(pl, 2, ms), GPV_ERR_STATE);                                // a factor, but no columns left by a call yet
+    EXPECT(mockhip_launches() == l0 && ms[0] == guard);
     // ---- buffer growth across column counts, shapes
     EXPECT_ST(gpv_plan_whiten_t(pl, A.data(), lda, 3, O.data(), ldo, &nf), GPV_OK);
     EXPECT(nf == 0 && O[0] != guard && O[(size_t)2 * ldo + n - 1] != guard && O[(size_t)3 * ldo] == guard);      // 3 columns and no more
@@ -173,6 +182,10 @@ int main()
     const long before = mockhip_launches();
     EXPECT_ST(gpv_plan_loo(pl, A.data(), lda, 2, O.data(), ldo, q.data(), sc.data(), &nf), GPV_OK);
     const long per_call = mockhip_launches() - before;
+    // the timed repetitions on what that call left: its device passes (the scale is the evaluation's, made once), no copies
+    EXPECT_ST(gpv_plan_debug_loo_ms(pl, 2, ms), GPV_OK);
+    EXPECT(mockhip_launches() - before == per_call + 2 * per_call);
+    EXPECT(ms[0] == 0.125 && ms[1] == 0.125 && ms[2] == guard);                                // the mock's elapsed time, reps values
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, nugv.data(), n, GPV_WANT_U, nullptr, nullptr), GPV_OK);
     const long before2 = mockhip_launches();
     EXPECT_ST(gpv_plan_loo(pl, A.data(), lda, 2, O.data(), ldo, q.data(), sc.data(), &nf), GPV_OK);
@@ -182,6 +195,9 @@ int main()
     EXPECT_ST(gpv_plan_whiten_t(pl, A.data(), lda, 2, O.data(), ldo, &nf), GPV_ERR_STATE);
     EXPECT_ST(gpv_plan_precision(pl, A.data(), lda, 2, O.data(), ldo, q.data(), &nf), GPV_ERR_STATE);
     EXPECT_ST(gpv_plan_loo(pl, A.data(), lda, 2, O.data(), ldo, q.data(), sc.data(), &nf), GPV_ERR_STATE);
+    const long l1 = mockhip_launches();
+    EXPECT_ST(gpv_plan_debug_loo_ms(pl, 2, ms), GPV_ERR_STATE);                                // ... for the timed repetitions too
+    EXPECT(mockhip_launches() == l1);
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, &tau, 1, GPV_WANT_U, nullptr, nullptr), GPV_OK);
     // unobserved locations
     std::vector<int> obs((size_t)n, 1);

@@ -20,6 +20,7 @@
 extern "C" long mockhip_launches(void);
 extern "C" long mockhip_graph_launches(void);
 extern "C" long mockhip_live_allocations(void);
+extern "C" int gpv_plan_debug_selinv_ms(gpv_plan *pl, int reps, double *ms);       // developer aid, not in the public header
 
 static int g_fail = 0;
 #define EXPECT(cond)                                                                           \
@@ -92,8 +93,13 @@ int main()
     EXPECT_ST(gpv_plan_selinv(pl, 0, vars.data(), nullptr), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_selinv(pl, -1, vars.data(), &nd), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_selinv(pl, n, vars.data(), &nd), GPV_ERR_BAD_ARG);
+    double ms[3] = {guard, guard, guard};
+    EXPECT_ST(gpv_plan_debug_selinv_ms(nullptr, 2, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_selinv_ms(pl, 0, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_selinv_ms(pl, 2, nullptr), GPV_ERR_BAD_ARG);
     // state
     EXPECT_ST(gpv_plan_selinv(pl, 0, vars.data(), &nd), GPV_ERR_STATE);                      // no posterior structure
+    EXPECT_ST(gpv_plan_debug_selinv_ms(pl, 2, ms), GPV_ERR_STATE);
     EXPECT_ST(gpv_plan_build_posterior(pl, revNN.data(), revCond.data()), GPV_OK);
     EXPECT_ST(gpv_plan_selinv(pl, 0, vars.data(), &nd), GPV_ERR_STATE);                      // no factor yet
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, tau.data(), n, GPV_WANT_U, nullptr, nullptr), GPV_OK);
@@ -103,6 +109,8 @@ int main()
     EXPECT_ST(gpv_plan_factor_stamp(pl, &stamp0), GPV_OK);
     // the first call builds the records and allocates; the next ones do not
     const long l0 = mockhip_launches(), g0 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_selinv_ms(pl, 2, ms), GPV_ERR_STATE);                           // a factor, but no records built by a call yet
+    EXPECT(mockhip_launches() == l0 && mockhip_graph_launches() == g0 && ms[0] == guard);
     EXPECT_ST(gpv_plan_selinv(pl, 0, vars.data(), &nd), GPV_OK);
     EXPECT(nd == 0);
     EXPECT(vars[0] != guard && vars[(size_t)n - 1] != guard);
@@ -112,6 +120,16 @@ int main()
     EXPECT_ST(gpv_plan_selinv(pl, n - 1, vars.data(), &nd), GPV_OK);
     EXPECT_ST(gpv_plan_selinv(pl, 7, vars.data(), &nd), GPV_OK);
     EXPECT(mockhip_live_allocations() == a1 && mockhip_graph_launches() - g0 == 3);
+    // the timed repetitions: the pass alone (as the call replays or enqueues it), without the launch that writes the call's output
+    long l1 = mockhip_launches(), g1 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_selinv(pl, 7, vars.data(), &nd), GPV_OK);
+    const long rep_l = mockhip_launches() - l1 - 1, rep_g = mockhip_graph_launches() - g1;
+    EXPECT(rep_l >= 0 && rep_l + rep_g >= 1);
+    l1 = mockhip_launches(), g1 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_selinv_ms(pl, 2, ms), GPV_OK);
+    EXPECT(mockhip_launches() - l1 == 2 * rep_l && mockhip_graph_launches() - g1 == 2 * rep_g);
+    EXPECT(ms[0] == 0.125 && ms[1] == 0.125 && ms[2] == guard);                              // the mock's elapsed time, reps values
+    EXPECT(mockhip_live_allocations() == a1);
     EXPECT_ST(gpv_plan_factor_stamp(pl, &stamp1), GPV_OK);
     EXPECT(stamp0 != 0 && stamp1 == stamp0);                                                 // the factor is only read
     // the other sweeps of the plan beside it: buffers and graphs of their own
@@ -133,6 +151,9 @@ int main()
     // a rebuilt structure: refused until it holds a factor, then the records are built again
     EXPECT_ST(gpv_plan_build_posterior(pl, revNN.data(), revCond.data()), GPV_OK);
     EXPECT_ST(gpv_plan_selinv(pl, 0, vars.data(), &nd), GPV_ERR_STATE);
+    l1 = mockhip_launches(), g1 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_selinv_ms(pl, 2, ms), GPV_ERR_STATE);                           // ... and so are the timed repetitions
+    EXPECT(mockhip_launches() == l1 && mockhip_graph_launches() == g1);
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, tau.data(), n, GPV_WANT_MEAN, nullptr, nullptr), GPV_OK);
     EXPECT_ST(gpv_plan_selinv(pl, 0, vars.data(), &nd), GPV_OK);
     EXPECT(nd == 0);

@@ -18,6 +18,7 @@
 extern "C" long mockhip_launches(void);
 extern "C" long mockhip_graph_launches(void);
 extern "C" long mockhip_live_allocations(void);
+extern "C" int gpv_plan_debug_solve_t_ms(gpv_plan *pl, int reps, double *ms);      // developer aid, not in the public header
 
 static int g_fail = 0;
 #define EXPECT(cond)                                                                           \
@@ -88,18 +89,37 @@ int main()
     EXPECT_ST(gpv_plan_solve_t(pl, 1, E.data(), n - 1, X.data(), ld), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_solve_t(pl, 1, E.data(), ld, X.data(), n - 1), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_solve_t(pl, 0, E.data(), ld, X.data(), ld), GPV_OK);
+    // the timed repetitions: arguments, then the state (a factor, but no batch left by a call yet)
+    double ms[3] = {-7.0, -7.0, -7.0};
+    EXPECT_ST(gpv_plan_debug_solve_t_ms(nullptr, 2, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_solve_t_ms(pl, 0, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_solve_t_ms(pl, 2, nullptr), GPV_ERR_BAD_ARG);
+    long l1 = mockhip_launches(), g1 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_solve_t_ms(pl, 2, ms), GPV_ERR_STATE);
+    EXPECT(mockhip_launches() == l1 && mockhip_graph_launches() == g1 && ms[0] == -7.0);
     const long g0 = mockhip_graph_launches();
     EXPECT_ST(gpv_plan_solve_t(pl, ncols, E.data(), ld, X.data(), ld), GPV_OK);
     EXPECT(mockhip_graph_launches() - g0 == 3);                            // one replay per batch
     for (int64_t j = 0; j < ncols; ++j)
         for (int64_t k = n; k < ld; ++k) EXPECT(X[(size_t)(j * ld + k)] == -7.0);            // the guard columns are not written
     EXPECT_ST(gpv_plan_solve_t(pl, ncols, E.data(), ld, E.data(), ld), GPV_OK);              // in place
+    l1 = mockhip_launches(), g1 = mockhip_graph_launches();
     EXPECT_ST(gpv_plan_solve_t(pl, 1, E.data(), n, X.data(), n), GPV_OK);                    // tight strides, one column
+    // ... on what that call left: the untimed pack and the sweep (as the call replays or enqueues it), no unpacking, no copies
+    const long rep_l = mockhip_launches() - l1 - 1, rep_g = mockhip_graph_launches() - g1;
+    EXPECT(rep_l >= 1 && rep_l - 1 + rep_g >= 1);
+    l1 = mockhip_launches(), g1 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_solve_t_ms(pl, 2, ms), GPV_OK);
+    EXPECT(mockhip_launches() - l1 == 2 * rep_l && mockhip_graph_launches() - g1 == 2 * rep_g);
+    EXPECT(ms[0] == 0.125 && ms[1] == 0.125 && ms[2] == -7.0);             // the mock's elapsed time, reps values
     EXPECT_ST(gpv_plan_factor_stamp(pl, &stamp1), GPV_OK);
     EXPECT(stamp0 != 0 && stamp1 == stamp0);                               // the factor is only read
     // a rebuild destroys the captured sweep with the structure it names; the next solve needs a new evaluation first
     EXPECT_ST(gpv_plan_build_posterior(pl, revNN.data(), revCond.data()), GPV_OK);
     EXPECT_ST(gpv_plan_solve_t(pl, 1, E.data(), ld, X.data(), ld), GPV_ERR_STATE);
+    l1 = mockhip_launches(), g1 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_solve_t_ms(pl, 2, ms), GPV_ERR_STATE);                          // ... and so do the timed repetitions
+    EXPECT(mockhip_launches() == l1 && mockhip_graph_launches() == g1);
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, tau.data(), n, GPV_WANT_DENOM, nullptr, nullptr), GPV_OK);
     EXPECT_ST(gpv_plan_solve_t(pl, NB + 1, E.data(), ld, X.data(), ld), GPV_OK);
     EXPECT_ST(gpv_plan_destroy(pl), GPV_OK);

@@ -18,7 +18,9 @@
 #include <vector>
 
 extern "C" long mockhip_launches(void);
+extern "C" long mockhip_graph_launches(void);
 extern "C" long mockhip_live_allocations(void);
+extern "C" int gpv_plan_debug_unwhiten_ms(gpv_plan *pl, int reps, double *ms);     // developer aid, not in the public header
 
 static int g_fail = 0;
 #define EXPECT(cond)                                                                           \
@@ -126,9 +128,14 @@ int main()
     EXPECT_ST(gpv_plan_unwhiten_levels(nullptr, &nl, &nk), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_unwhiten_levels(pl, nullptr, &nk), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_unwhiten_levels(pl, &nl, nullptr), GPV_ERR_BAD_ARG);
+    double ms[3] = {guard, guard, guard};
+    EXPECT_ST(gpv_plan_debug_unwhiten_ms(nullptr, 2, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_unwhiten_ms(pl, 0, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_unwhiten_ms(pl, 2, nullptr), GPV_ERR_BAD_ARG);
     // ---- state: which evaluation the resident factor belongs to
     EXPECT_ST(gpv_plan_unwhiten(pl, E.data(), lde, 3, B.data(), ldb, &nf), GPV_ERR_STATE);                       // no evaluation
     EXPECT_ST(gpv_plan_simulate(pl, 1, 0, 3, Z.data(), ldb, &nf), GPV_ERR_STATE);
+    EXPECT_ST(gpv_plan_debug_unwhiten_ms(pl, 2, ms), GPV_ERR_STATE);
     EXPECT(nf == -1 && B[0] == guard && Z[0] == guard);                                        // a refused call writes nothing
     EXPECT(mockhip_launches() == 0);                                                           // ... and launches nothing
     // the schedule needs no evaluation: a chain, one row per level, all narrow: one launch
@@ -145,6 +152,9 @@ int main()
     int64_t stamp0 = -1, stamp1 = -1;
     EXPECT_ST(gpv_plan_get_sums(pl, sums0), GPV_OK);
     EXPECT_ST(gpv_plan_factor_stamp(pl, &stamp0), GPV_OK);
+    long l0 = mockhip_launches(), g0 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_unwhiten_ms(pl, 2, ms), GPV_ERR_STATE);                           // a factor, but no columns left by a call yet
+    EXPECT(mockhip_launches() == l0 && mockhip_graph_launches() == g0 && ms[0] == guard);
     // ---- buffer growth across column counts, shapes
     EXPECT_ST(gpv_plan_unwhiten(pl, E.data(), lde, 3, B.data(), ldb, &nf), GPV_OK);
     EXPECT(nf == 0 && B[0] != guard && B[(size_t)2 * ldb + n - 1] != guard && B[(size_t)3 * ldb] == guard);      // 3 columns and no more
@@ -155,6 +165,15 @@ int main()
     }
     for (size_t t = (size_t)ldb * nc; t < B.size(); ++t) EXPECT(B[t] == guard);
     EXPECT_ST(gpv_plan_unwhiten(pl, E.data(), lde, 5, B.data(), ldb, &nf), GPV_OK);                              // narrower again
+    // the timed repetitions on what that call left: the sweep alone (as the call replays or enqueues it), no packing, no copies
+    l0 = mockhip_launches(), g0 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_unwhiten(pl, E.data(), lde, 5, B.data(), ldb, &nf), GPV_OK);
+    const long sweep_l = mockhip_launches() - l0 - 2, sweep_g = mockhip_graph_launches() - g0;      // (less packing and unpacking)
+    EXPECT(sweep_l >= 0 && sweep_l + sweep_g >= 1);
+    l0 = mockhip_launches(), g0 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_unwhiten_ms(pl, 2, ms), GPV_OK);
+    EXPECT(mockhip_launches() - l0 == 2 * sweep_l && mockhip_graph_launches() - g0 == 2 * sweep_g);
+    EXPECT(ms[0] == 0.125 && ms[1] == 0.125 && ms[2] == guard);                                // the mock's elapsed time, reps values
     EXPECT_ST(gpv_plan_unwhiten(pl, E.data(), lde, 2, E.data(), lde, &nf), GPV_OK);                              // in place
     EXPECT_ST(gpv_plan_simulate(pl, 5, 13, 22, Z.data(), ldb, &nf), GPV_OK);                                     // draws 13 .. 34: three batches
     for (int j = 0; j < 22; ++j) {
@@ -181,6 +200,9 @@ int main()
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, &tau, 1, GPV_WANT_LOGLIK_Z, nullptr, nullptr), GPV_OK);
     EXPECT_ST(gpv_plan_unwhiten(pl, E.data(), lde, 2, B.data(), ldb, &nf), GPV_ERR_STATE);
     EXPECT_ST(gpv_plan_simulate(pl, 5, 0, 1, Z.data(), ldb, &nf), GPV_ERR_STATE);
+    l0 = mockhip_launches(), g0 = mockhip_graph_launches();
+    EXPECT_ST(gpv_plan_debug_unwhiten_ms(pl, 2, ms), GPV_ERR_STATE);                           // ... for the timed repetitions too
+    EXPECT(mockhip_launches() == l0 && mockhip_graph_launches() == g0);
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, &tau, 1, GPV_WANT_U, nullptr, nullptr), GPV_OK);
     // unobserved locations
     std::vector<int> obs((size_t)n, 1);

@@ -19,6 +19,7 @@
 
 extern "C" long mockhip_launches(void);
 extern "C" long mockhip_live_allocations(void);
+extern "C" int gpv_plan_debug_whiten_ms(gpv_plan *pl, int reps, double *ms);       // developer aid, not in the public header
 
 static int g_fail = 0;
 #define EXPECT(cond)                                                                           \
@@ -78,8 +79,13 @@ int main()
     EXPECT_ST(gpv_plan_whiten(pl, B.data(), ldb, 17, E.data(), lde, G.data(), &ld, &nf), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_whiten(pl, B.data(), n - 1, 3, E.data(), lde, G.data(), &ld, &nf), GPV_ERR_BAD_ARG);
     EXPECT_ST(gpv_plan_whiten(pl, B.data(), ldb, 3, E.data(), n - 1, G.data(), &ld, &nf), GPV_ERR_BAD_ARG);
+    double ms[3] = {guard, guard, guard};
+    EXPECT_ST(gpv_plan_debug_whiten_ms(nullptr, 2, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_whiten_ms(pl, 0, ms), GPV_ERR_BAD_ARG);
+    EXPECT_ST(gpv_plan_debug_whiten_ms(pl, 2, nullptr), GPV_ERR_BAD_ARG);
     // ---- state: which evaluation the resident factor belongs to
     EXPECT_ST(gpv_plan_whiten(pl, B.data(), ldb, 3, E.data(), lde, G.data(), &ld, &nf), GPV_ERR_STATE);          // no evaluation
+    EXPECT_ST(gpv_plan_debug_whiten_ms(pl, 2, ms), GPV_ERR_STATE);
     EXPECT(ld == guard && nf == -1 && G[0] == guard && E[0] == guard);                         // a refused call writes nothing
     EXPECT(mockhip_launches() == 0);                                                           // ... and launches nothing
     EXPECT_ST(gpv_plan_set_data(pl, z.data()), GPV_OK);
@@ -91,6 +97,8 @@ int main()
     EXPECT_ST(gpv_plan_get_sums(pl, sums0), GPV_OK);
     EXPECT_ST(gpv_plan_factor_stamp(pl, &stamp0), GPV_OK);
     long l0 = mockhip_launches();
+    EXPECT_ST(gpv_plan_debug_whiten_ms(pl, 2, ms), GPV_ERR_STATE);                             // a factor, but no columns left by a call yet
+    EXPECT(mockhip_launches() == l0 && ms[0] == guard);
     EXPECT_ST(gpv_plan_whiten(pl, B.data(), ldb, 3, nullptr, 0, G.data(), &ld, &nf), GPV_OK);                    // no E: lde unused
     EXPECT(mockhip_launches() - l0 == 4);                          // packing, the whitening pass, the Gram pass and its sum
     EXPECT(nf == 0 && G[8] == 0.0 && G[9] == guard && E[0] == guard);                          // 3 x 3 and no more
@@ -104,6 +112,11 @@ int main()
     for (size_t t = (size_t)lde * nc; t < E.size(); ++t) EXPECT(E[t] == guard);
     for (size_t t = (size_t)nc * nc; t < G.size(); ++t) EXPECT(G[t] == guard);
     EXPECT_ST(gpv_plan_whiten(pl, B.data(), ldb, 5, E.data(), lde, G.data(), &ld, &nf), GPV_OK);                 // narrower again
+    // the timed repetitions on what that call left: the two passes and the sum per repetition, no packing, no copies
+    l0 = mockhip_launches();
+    EXPECT_ST(gpv_plan_debug_whiten_ms(pl, 2, ms), GPV_OK);
+    EXPECT(mockhip_launches() - l0 == 2 * 3);
+    EXPECT(ms[0] == 0.125 && ms[1] == 0.125 && ms[2] == guard);                                // the mock's elapsed time, reps values
     EXPECT_ST(gpv_plan_get_sums(pl, sums1), GPV_OK);
     EXPECT_ST(gpv_plan_factor_stamp(pl, &stamp1), GPV_OK);
     for (int t = 0; t < GPV_NSUMS; ++t) EXPECT(sums0[t] == sums1[t]);
@@ -114,6 +127,9 @@ int main()
     // the next evaluation leaves U alone: the resident one is stale
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, &tau, 1, GPV_WANT_LOGLIK_Z, nullptr, nullptr), GPV_OK);
     EXPECT_ST(gpv_plan_whiten(pl, B.data(), ldb, 2, nullptr, 0, G.data(), &ld, &nf), GPV_ERR_STATE);
+    l0 = mockhip_launches();
+    EXPECT_ST(gpv_plan_debug_whiten_ms(pl, 2, ms), GPV_ERR_STATE);                             // ... for the timed repetitions too
+    EXPECT(mockhip_launches() == l0);
     // an evaluation that is refused (bad nugget count) after one with U: nothing is trusted
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, &tau, 1, GPV_WANT_U, nullptr, nullptr), GPV_OK);
     EXPECT_ST(gpv_plan_eval(pl, "matern", cp, 3, nugv.data(), n - 1, GPV_WANT_U, nullptr, nullptr), GPV_ERR_BAD_ARG);
