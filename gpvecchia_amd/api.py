@@ -29,6 +29,7 @@ LOO_NSCORES = 6                                       # gpv_loo_nscores(): score
 BLOCKCV_NSCORES = 8                                   # gpv_blockcv_nscores(): score sums per column of Plan.block_cv
 BLOCKCV_MAX_BLOCK = 64                                # gpv_blockcv_max_block(): members of a held-out block
 KRIGE_MAX_COLS = 16                                   # gpv_krige_max_cols(): data columns per Plan.krige call
+KRIGE_GROUPS_MAX_ROWS = 64                            # gpv_krige_groups_max_rows(): m + the size of a group of Plan.krige_groups
 
 
 # ---------------------------------------------------------------------------
@@ -474,6 +475,67 @@ class Plan:
                                        None if el is None else el.ctypes.data_as(u8), int(chunk), L.dptr(mean), max(nq, 1),
                                        L.dptr(var), C.byref(nf)), "gpv_plan_krige")
         return mean, var, int(nf.value)
+
+    def krige_groups(self, covmodel, covparms, nuggets_ord, qlocs, gptr, m, Z_ord=None, weights=None, NNg=None, scale=None,
+                     eligible_ord=None, chunk=0, want_cov=False):
+        """Grouped local kriging under the cond.yz='z' model of this plan (gpv_plan_krige_groups): group k is the rows
+        gptr[k] .. gptr[k + 1] - 1 of qlocs (nq, dim), its members share the conditioning set of the m observations nearest to
+        their mean (m + g <= 64) and are predicted jointly, one solve per group.  nuggets_ord, Z_ord, scale, eligible_ord: as
+        Plan.krige; weights: None (1 / g each) or nq numbers of any sign; NNg: None (searched at the groups' anchors) or
+        (ngroups, m) ORDERED ids, 1-based, 0 = none; chunk: groups per pass (0: the default), which changes no bit.  Returns
+        (mean (nq, ncols), var (nq,), gmean (ngroups, ncols), gvar (ngroups,), cov, n_failed): per location the predictive mean
+        and the variance of the latent field, per group the weighted mean, its variance w' Sigma_G w, and with want_cov the
+        packed lower triangles of the joint covariances Sigma_G (row-major, group after group; else None).  Everything of a
+        group that failed (a member on an observation that has no nugget) is NaN and it is counted in n_failed."""
+        q = np.asfortranarray(np.asarray(qlocs, dtype=np.float64).reshape(-1, self.dim))
+        nq = q.shape[0]
+        gp = np.ascontiguousarray(gptr, dtype=np.int64).reshape(-1)
+        if gp.size < 1:
+            raise ValueError("gptr must hold ngroups + 1 offsets")
+        ng = gp.size - 1
+        cp = np.ascontiguousarray(covparms, dtype=np.float64).reshape(-1)
+        nug = np.ascontiguousarray(np.atleast_1d(np.asarray(nuggets_ord, dtype=np.float64)))
+        Z, ncols = None, 1
+        if Z_ord is not None:
+            Z = np.asarray(Z_ord, dtype=np.float64)
+            Z = np.asfortranarray(Z[:, None] if Z.ndim == 1 else Z)
+            if Z.ndim != 2 or Z.shape[0] != self.Nlocs:
+                raise ValueError("Z_ord must have one row per ordered location of the plan")
+            ncols = Z.shape[1]
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64).reshape(-1)
+            if w.size != nq:
+                raise ValueError("weights must hold one number per prediction location")
+        nn = None
+        if NNg is not None:
+            nn = np.asfortranarray(NNg, dtype=np.int32)
+            if nn.shape != (ng, int(m)):
+                raise ValueError("NNg must be (ngroups, m)")
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+        if sc is not None and sc.size != self.dim:
+            raise ValueError("scale must hold one number per coordinate")
+        el = None
+        if eligible_ord is not None:
+            el = np.ascontiguousarray(np.asarray(eligible_ord).astype(bool).reshape(-1), dtype=np.uint8)
+            if el.shape[0] != self.Nlocs:
+                raise ValueError("eligible_ord must hold one flag per ordered location of the plan")
+        mean, var = np.zeros((nq, ncols), order="F"), np.zeros(nq)
+        gmean, gvar = np.zeros((ng, ncols), order="F"), np.zeros(ng)
+        cov = None
+        if want_cov:
+            g = np.diff(gp)
+            cov = np.zeros(max(int(np.sum(g * (g + 1) // 2)) if ng and np.all(g >= 0) else 0, 1))
+        nf = C.c_int64(0)
+        u8 = C.POINTER(C.c_uint8)
+        L.check(L.lib().gpv_plan_krige_groups(self._h, str(covmodel).encode(), L.dptr(cp), cp.size, L.dptr(nug), nug.size,
+                                              None if Z is None else L.dptr(Z), self.Nlocs, ncols, L.dptr(q), nq,
+                                              gp.ctypes.data_as(C.POINTER(C.c_int64)), ng, None if w is None else L.dptr(w), int(m),
+                                              None if nn is None else L.iptr(nn), None if sc is None else L.dptr(sc),
+                                              None if el is None else el.ctypes.data_as(u8), int(chunk), L.dptr(mean), max(nq, 1),
+                                              L.dptr(var), L.dptr(gmean), max(ng, 1), L.dptr(gvar),
+                                              None if cov is None else L.dptr(cov), C.byref(nf)), "gpv_plan_krige_groups")
+        return mean, var, gmean, gvar, cov, int(nf.value)
 
     def unwhiten_levels(self):
         """(n_levels, n_launches) of the level schedule unwhiten and simulate sweep through, built at first use
@@ -1748,21 +1810,9 @@ def vecchia_block_cv(z, vecchia_approx, covparms, nuggets, covmodel="matern", bl
     return out
 
 
-def vecchia_krige(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="matern", m=None, mean=None, mean_pred=None,
-                  predict="y", nugget_pred=None, scale=None, device=0):
-    """Prediction at new locations under the cond.yz='z' Vecchia model, the one vecchia_likelihood scores and
-    vecchia_estimate(method="L-BFGS-B" | "fisher") fits: every prediction location is ordered last and conditions on its m
-    nearest observations, so its predictive distribution is local kriging, one independent solve per location on the GPU
-    (Plan.krige), streamed in chunks: the size of the map is not bounded by device memory.
-    z: (n,) or (n, R <= 16) in the CALLER's order; NaN entries of a single column are missing data and never enter a
-    conditioning set (NaN in several columns is refused).  vecchia_approx: a cond_yz='z' specification without prediction
-    locations; m=None takes its m.  mean / mean_pred: subtracted from z / added to the predictions (a scalar, or one value per
-    location[, column]).  predict='y' returns the variance of the latent field, 'z' adds nugget_pred (a scalar or one value
-    per prediction location).  scale: what vecchia_specify(scale=) was given ('matern_scaledim': the neighbours are searched
-    on locs / scale).  Returns dict(mean_pred (n_p[, R]), var_pred (n_p,), n_failed); a location whose block is not positive
-    definite (it coincides with an observation that has no nugget) is NaN."""
-    va = vecchia_approx
-    name = "vecchia_krige"
+def _krige_inputs(name, z, va, locs_pred, nuggets, covmodel, m, mean, predict):
+    """what vecchia_krige and vecchia_krige_groups check and prepare alike: (Z (n, R) with the trend off and the missing values
+    zeroed, vector, eligible or None, nug, lp (n_p, dim), m, ordz)"""
     if va["cond_yz"] != "z":
         raise ValueError(f"{name} needs cond_yz='z' (the other modes predict through the posterior factor: vecchia_prediction)")
     n = va["locsord"].shape[0]
@@ -1794,10 +1844,29 @@ def vecchia_krige(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="mat
     if nug.size not in (1, n):
         raise ValueError(f"{name}: nuggets must be one value or one per location")
     lp = np.asarray(locs_pred, dtype=np.float64).reshape(-1, va["locsord"].shape[1])
-    n_p = lp.shape[0]
     if m is None:
         m = va["U_prep"]["revNNarray"].shape[1] - 1
     ordz = va["ord_z"] - 1
+    return Z, vector, eligible, nug, lp, int(m), ordz
+
+
+def vecchia_krige(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="matern", m=None, mean=None, mean_pred=None,
+                  predict="y", nugget_pred=None, scale=None, device=0):
+    """Prediction at new locations under the cond.yz='z' Vecchia model, the one vecchia_likelihood scores and
+    vecchia_estimate(method="L-BFGS-B" | "fisher") fits: every prediction location is ordered last and conditions on its m
+    nearest observations, so its predictive distribution is local kriging, one independent solve per location on the GPU
+    (Plan.krige), streamed in chunks: the size of the map is not bounded by device memory.
+    z: (n,) or (n, R <= 16) in the CALLER's order; NaN entries of a single column are missing data and never enter a
+    conditioning set (NaN in several columns is refused).  vecchia_approx: a cond_yz='z' specification without prediction
+    locations; m=None takes its m.  mean / mean_pred: subtracted from z / added to the predictions (a scalar, or one value per
+    location[, column]).  predict='y' returns the variance of the latent field, 'z' adds nugget_pred (a scalar or one value
+    per prediction location).  scale: what vecchia_specify(scale=) was given ('matern_scaledim': the neighbours are searched
+    on locs / scale).  Returns dict(mean_pred (n_p[, R]), var_pred (n_p,), n_failed); a location whose block is not positive
+    definite (it coincides with an observation that has no nugget) is NaN."""
+    va = vecchia_approx
+    name = "vecchia_krige"
+    Z, vector, eligible, nug, lp, m, ordz = _krige_inputs(name, z, va, locs_pred, nuggets, covmodel, m, mean, predict)
+    n_p = lp.shape[0]
     plan = _plan_for(va, device)
     mu_p, var_p, n_failed = plan.krige(covmodel, covparms, nug if nug.size == 1 else nug[ordz], lp, int(m), Z_ord=Z[ordz],
                                        scale=scale, eligible_ord=None if eligible is None else eligible[ordz])
@@ -1809,6 +1878,78 @@ def vecchia_krige(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="mat
             raise ValueError(f"{name}: predict='z' needs nugget_pred")
         var_p = var_p + np.asarray(nugget_pred, dtype=np.float64)
     return dict(mean_pred=mu_p[:, 0] if vector else mu_p, var_pred=var_p, n_failed=n_failed)
+
+
+def vecchia_krige_groups(z, vecchia_approx, locs_pred, groups, covparms, nuggets, covmodel="matern", m=None, weights=None, mean=None,
+                         mean_pred=None, predict="y", nugget_pred=None, scale=None, return_cov=False, device=0):
+    """Joint prediction of groups of new locations under the cond.yz='z' Vecchia model: the mean of a raster cell, a plot or a
+    footprint with its standard error (block kriging), a contrast between locations, the joint covariance of a few sites.  The
+    members of a group are ordered last and condition on the m observations nearest to their coordinate-wise mean and on the
+    members before them, so a group is one (m + g)-row solve on the GPU (Plan.krige_groups), m + g <= 64; the groups are streamed
+    in chunks.  A group of one location is the prediction of vecchia_krige there.
+    groups: one integer label per prediction location, in any order.  weights: None (1 / g: the group's average) or one number
+    per prediction location, any sign (+1, -1: a contrast).  z, vecchia_approx, m, mean / mean_pred, predict / nugget_pred,
+    scale and the refusals: as vecchia_krige.  Returns dict(mean_pred (n_p[, R]), var_pred (n_p,), group_ids (the distinct
+    labels, ascending), group_mean (n_groups[, R]) = sum_i w_i mean_i, group_var (n_groups,) = w' Sigma w, n_failed), all in the
+    caller's order of the locations, and with return_cov also group_cov: one symmetric g x g array per group, the joint
+    predictive covariance of its members in the caller's order.  predict='z' adds nugget_pred to var_pred and to the diagonals
+    of group_cov, and sum_i w_i^2 nugget_i to group_var.  Everything of a group that failed (a member on an observation that
+    has no nugget) is NaN; n_failed counts groups."""
+    va = vecchia_approx
+    name = "vecchia_krige_groups"
+    Z, vector, eligible, nug, lp, m, ordz = _krige_inputs(name, z, va, locs_pred, nuggets, covmodel, m, mean, predict)
+    n_p = lp.shape[0]
+    lab = np.asarray(groups)
+    if lab.ndim != 1 or lab.shape[0] != n_p or not np.issubdtype(lab.dtype, np.integer):
+        raise ValueError(f"{name}: groups must be one integer label per prediction location")
+    w = None
+    if weights is not None:
+        w = np.asarray(weights, dtype=np.float64).reshape(-1)
+        if w.size != n_p or not np.all(np.isfinite(w)):
+            raise ValueError(f"{name}: weights must be one finite number per prediction location")
+    tau_p = None
+    if predict == "z":
+        if nugget_pred is None:
+            raise ValueError(f"{name}: predict='z' needs nugget_pred")
+        tau_p = np.broadcast_to(np.asarray(nugget_pred, dtype=np.float64), (n_p,))
+    ids, inv = np.unique(lab, return_inverse=True)
+    o = np.argsort(inv, kind="stable")                       # the members of a group together, in the caller's order
+    size = np.bincount(inv, minlength=ids.size)
+    gptr = np.concatenate([[0], np.cumsum(size)]).astype(np.int64)
+    if size.size and m + int(size.max()) > KRIGE_GROUPS_MAX_ROWS:
+        raise ValueError(f"{name}: m + the size of a group must be <= {KRIGE_GROUPS_MAX_ROWS} (m = {m}, the largest group: {size.max()})")
+    plan = _plan_for(va, device)
+    mu_s, var_s, gmean, gvar, cov, n_failed = plan.krige_groups(
+        covmodel, covparms, nug if nug.size == 1 else nug[ordz], lp[o], gptr, m, Z_ord=Z[ordz], weights=None if w is None else w[o],
+        scale=scale, eligible_ord=None if eligible is None else eligible[ordz], want_cov=return_cov)
+    mu_p, var_p = np.empty(mu_s.shape), np.empty(n_p)
+    mu_p[o], var_p[o] = mu_s, var_s
+    ws = np.repeat(1.0 / np.maximum(size, 1), size) if w is None else w[o]
+    if mean_pred is not None:
+        mp = np.asarray(mean_pred, dtype=np.float64)
+        mp = np.broadcast_to(mp if mp.ndim == 0 else mp.reshape(n_p, -1), mu_p.shape)
+        mu_p = mu_p + mp
+        if ids.size:
+            gmean = gmean + np.add.reduceat(ws[:, None] * mp[o], gptr[:-1], axis=0)
+    if tau_p is not None:
+        var_p = var_p + tau_p
+        if ids.size:
+            gvar = gvar + np.add.reduceat(ws * ws * tau_p[o], gptr[:-1])
+    out = dict(mean_pred=mu_p[:, 0] if vector else mu_p, var_pred=var_p, group_ids=ids, group_mean=gmean[:, 0] if vector else gmean,
+               group_var=gvar, n_failed=n_failed)
+    if return_cov:
+        covs, at = [], 0
+        for k in range(ids.size):
+            g = int(size[k])
+            S = np.zeros((g, g))
+            S[np.tril_indices(g)] = cov[at:at + g * (g + 1) // 2]
+            S = S + np.tril(S, -1).T
+            if tau_p is not None:
+                S[np.diag_indices(g)] += tau_p[o[gptr[k]:gptr[k + 1]]]
+            covs.append(S)
+            at += g * (g + 1) // 2
+        out["group_cov"] = covs
+    return out
 
 
 def profile_from_gram(G, logdet, n):

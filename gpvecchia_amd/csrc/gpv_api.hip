@@ -14,6 +14,7 @@
 #include "gpv_loo.h"
 #include "gpv_blockcv.h"
 #include "gpv_krige.h"
+#include "gpv_krige_groups.h"
 #include "gpv_selinv.h"
 #include "gpv_grad_sgv.h"
 #include "gpv_hip_raii.hpp"
@@ -3152,45 +3153,61 @@ extern "C" int gpv_plan_debug_blockcv_ms(gpv_plan *pl, int reps, int parts, doub
 // ---- local kriging of a cond.yz='z' plan at new locations (gpv_krige.hip; the search: gpv_nn.hip) --------------------------
 int gpv_krige_max_cols(void) { return kKrigeMaxCols; }
 
-// Reads the plan's records, its data and newpos, and writes buffers that live for the call only (and d_gmt, the table of a
-// general smoothness, which the blocking gradient calls share): no evaluation is needed and none is disturbed.  Every refusal
-// comes before the device is touched and before anything is written.
-int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, const double *nuggets, int64_t n_nuggets,
-                   const double *Z_ord, int64_t ldz, int ncols, const double *qlocs, int64_t nq, int m, const int *NNq,
-                   const double *scale, const unsigned char *eligible_ord, int64_t chunk, double *mean, int64_t ldm, double *var,
-                   int64_t *n_failed)
+// ---- what gpv_plan_krige and gpv_plan_krige_groups share ----
+// the buffers that live for one call and the search index over the plan's locations
+namespace {
+struct KrigeCall {
+    CovSetup cs;
+    DevBuf<double> d_nug, d_in, d_Z;
+    QnnIndex ix;
+    KrigeCall() = default;
+    KrigeCall(const KrigeCall &) = delete;
+    KrigeCall &operator=(const KrigeCall &) = delete;
+    ~KrigeCall() { qnn_free(ix); }
+};
+}  // namespace
+
+// the arguments both entries take: the nuggets, the columns, the family and its parameters, the scale of the search
+static int krige_check_args(const gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, const double *nuggets,
+                            int64_t n_nuggets, const double *Z_ord, int64_t ldz, int ncols, const double *scale, CovSetup &cs)
 {
-    if (!pl || !covType || !covparms || !nuggets || !n_failed || nq < 0 || chunk < 0 || m < 1) return GPV_ERR_BAD_ARG;
-    if (nq > 0 && (!qlocs || !mean || !var)) return GPV_ERR_BAD_ARG;
     const int64_t n = pl->Nlocs;
-    if ((n_nuggets != 1 && n_nuggets != n) || ncols < 1 || ncols > kKrigeMaxCols || ldm < nq) return GPV_ERR_BAD_ARG;
+    if ((n_nuggets != 1 && n_nuggets != n) || ncols < 1 || ncols > kKrigeMaxCols) return GPV_ERR_BAD_ARG;
     if (Z_ord ? ldz < n : ncols != 1) return GPV_ERR_BAD_ARG;
     for (int64_t i = 0; i < n_nuggets; ++i)
         if (!(nuggets[i] >= 0.0) || !std::isfinite(nuggets[i])) return GPV_ERR_BAD_ARG;
     const bool matern = std::strcmp(covType, "matern") == 0, scaled = std::strcmp(covType, "matern_scaledim") == 0;
     if (!matern && !scaled && std::strcmp(covType, "esqe") != 0) return GPV_ERR_COVTYPE;
     if (ncovparms != (matern ? 3 : (scaled ? pl->dim + 2 : 4))) return GPV_ERR_BAD_ARG;
-    CovSetup cs;
     if (const int rc = cov_setup(covType, covparms, ncovparms, pl->dim, cs)) return rc;
     if (scale)
         for (int t = 0; t < pl->dim; ++t)
             if (!(scale[t] > 0.0) || !std::isfinite(scale[t])) return GPV_ERR_BAD_ARG;
-    if (m + 1 > kKrigeMaxP) return GPV_ERR_UNSUPPORTED_M;
+    return GPV_OK;
+}
+
+// the plan both entries take; NN: nn given ids (or nullptr), each in [0, Nlocs]
+static int krige_check_state(const gpv_plan *pl, bool plan_data, const int *NN, int64_t nn)
+{
+    const int64_t n = pl->Nlocs;
     if (pl->dim > kMaxDimGeneric || !pl->d_locs || !pl->d_newpos) return GPV_ERR_STATE;
     // a row shard, unobserved locations, a neighbour conditioned on as latent (not a 'z' plan), no data to predict from
-    if (pl->comm || pl->rows != n || pl->d_obs || pl->latent_nb || (!Z_ord && !pl->has_z) || (int64_t)pl->h_newpos.size() != n)
+    if (pl->comm || pl->rows != n || pl->d_obs || pl->latent_nb || (plan_data && !pl->has_z) || (int64_t)pl->h_newpos.size() != n)
         return GPV_ERR_STATE;
-    if (NNq)
-        for (int64_t i = 0; i < nq * m; ++i)
-            if (NNq[i] < 0 || NNq[i] > n) return GPV_ERR_INDEX;
-    *n_failed = 0;
-    if (nq == 0) return GPV_OK;
+    if (NN)
+        for (int64_t i = 0; i < nn; ++i)
+            if (NN[i] < 0 || NN[i] > n) return GPV_ERR_INDEX;
+    return GPV_OK;
+}
 
-    if (const int rc = enter(pl)) return rc;
-    hipStream_t st = pl->stream;
+// what a pass reads of the plan and of the call, but the chunks: the records, the covariance (the table of a general
+// smoothness included), the call's nuggets and columns on the device
+static int krige_resident(gpv_plan *pl, const double *covparms, int ncovparms, const double *nuggets, int64_t n_nuggets,
+                          const double *Z_ord, int64_t ldz, int ncols, int m, KrigeCall &kc, KrigeArgs &a, hipStream_t st)
+{
+    const CovSetup &cs = kc.cs;
+    const int64_t n = pl->Nlocs;
     const int dim = pl->dim;
-    const bool packed = dim <= 3;
-    KrigeArgs a{};
     a.rec = pl->d_locs; a.z = pl->d_z; a.newpos = pl->d_newpos;
     a.m = m; a.dim = dim; a.locs_ld = pl->locs_ld; a.ncols = ncols;
     a.cov = cs.cov; a.nscale = cs.nscale;
@@ -3211,34 +3228,65 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
         }
     }
     // the call's nuggets and columns
-    DevBuf<double> d_nug, d_in, d_Z;
     if (n_nuggets > 1) {
-        GPV_BUF(d_nug, upload(nuggets, (size_t)n));
-        a.nuggets = d_nug;
+        GPV_BUF(kc.d_nug, upload(nuggets, (size_t)n));
+        a.nuggets = kc.d_nug;
     }
     if (Z_ord) {
         a.zld = (ncols + 3) / 4 * 4;
-        GPV_BUF(d_in, resize((size_t)n * ncols));
-        GPV_BUF(d_Z, resize((size_t)n * a.zld));
-        if (cols_to_device(d_in, Z_ord, ldz, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
-        if (GPV_HIP_FAILED(launch_rep_pack(d_in, pl->d_newpos, n, ncols, a.zld, d_Z, st))) return drain_fail(st, GPV_ERR_HIP);
-        a.Z = d_Z;
+        GPV_BUF(kc.d_in, resize((size_t)n * ncols));
+        GPV_BUF(kc.d_Z, resize((size_t)n * a.zld));
+        if (cols_to_device(kc.d_in, Z_ord, ldz, n, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_rep_pack(kc.d_in, pl->d_newpos, n, ncols, a.zld, kc.d_Z, st))) return drain_fail(st, GPV_ERR_HIP);
+        a.Z = kc.d_Z;
     }
-    // the search over the plan's locations in the ORDERED numbering, on the coordinates divided by `scale`
-    struct Index { QnnIndex ix; ~Index() { qnn_free(ix); } } index;
-    if (!NNq) {
-        const int ld = packed ? 4 : pl->locs_ld;
-        std::vector<double> rec((size_t)n * ld), lc((size_t)n * dim);
-        if (GPV_HIP_FAILED(hipMemcpyAsync(rec.data(), pl->d_locs, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, st)) ||
-            GPV_HIP_FAILED(hipStreamSynchronize(st)))
-            return drain_fail(st, GPV_ERR_HIP);
-        for (int t = 0; t < dim; ++t)
-            for (int64_t i = 0; i < n; ++i) {
-                const double x = rec[(size_t)pl->h_newpos[(size_t)i] * ld + t];
-                lc[(size_t)i + (size_t)t * n] = scale ? x / scale[t] : x;
-            }
-        if (GPV_HIP_FAILED(qnn_build(lc.data(), n, dim, eligible_ord, index.ix))) return drain_fail(st, GPV_ERR_HIP);
-    }
+    return GPV_OK;
+}
+
+// the search index over the plan's locations in the ORDERED numbering, on the coordinates divided by `scale`
+static int krige_index(gpv_plan *pl, const double *scale, const unsigned char *eligible_ord, KrigeCall &kc, hipStream_t st)
+{
+    const int64_t n = pl->Nlocs;
+    const int dim = pl->dim;
+    const int ld = dim <= 3 ? 4 : pl->locs_ld;
+    std::vector<double> rec((size_t)n * ld), lc((size_t)n * dim);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(rec.data(), pl->d_locs, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, st)) ||
+        GPV_HIP_FAILED(hipStreamSynchronize(st)))
+        return drain_fail(st, GPV_ERR_HIP);
+    for (int t = 0; t < dim; ++t)
+        for (int64_t i = 0; i < n; ++i) {
+            const double x = rec[(size_t)pl->h_newpos[(size_t)i] * ld + t];
+            lc[(size_t)i + (size_t)t * n] = scale ? x / scale[t] : x;
+        }
+    if (GPV_HIP_FAILED(qnn_build(lc.data(), n, dim, eligible_ord, kc.ix))) return drain_fail(st, GPV_ERR_HIP);
+    return GPV_OK;
+}
+
+// Reads the plan's records, its data and newpos, and writes buffers that live for the call only (and d_gmt, the table of a
+// general smoothness, which the blocking gradient calls share): no evaluation is needed and none is disturbed.  Every refusal
+// comes before the device is touched and before anything is written.
+int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, const double *nuggets, int64_t n_nuggets,
+                   const double *Z_ord, int64_t ldz, int ncols, const double *qlocs, int64_t nq, int m, const int *NNq,
+                   const double *scale, const unsigned char *eligible_ord, int64_t chunk, double *mean, int64_t ldm, double *var,
+                   int64_t *n_failed)
+{
+    if (!pl || !covType || !covparms || !nuggets || !n_failed || nq < 0 || chunk < 0 || m < 1) return GPV_ERR_BAD_ARG;
+    if (nq > 0 && (!qlocs || !mean || !var)) return GPV_ERR_BAD_ARG;
+    if (ldm < nq) return GPV_ERR_BAD_ARG;
+    KrigeCall kc;
+    if (const int rc = krige_check_args(pl, covType, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, scale, kc.cs)) return rc;
+    if (m + 1 > kKrigeMaxP) return GPV_ERR_UNSUPPORTED_M;
+    if (const int rc = krige_check_state(pl, !Z_ord, NNq, nq * m)) return rc;
+    *n_failed = 0;
+    if (nq == 0) return GPV_OK;
+
+    if (const int rc = enter(pl)) return rc;
+    hipStream_t st = pl->stream;
+    const int dim = pl->dim;
+    KrigeArgs a{};
+    if (const int rc = krige_resident(pl, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, m, kc, a, st)) return rc;
+    if (!NNq)
+        if (const int rc = krige_index(pl, scale, eligible_ord, kc, st)) return rc;
     // the chunks: queries up, search or neighbours up, the pass, results back
     const int64_t cap = std::min<int64_t>(chunk > 0 ? chunk : kKrigeChunk, nq);
     DevBuf<double> d_q, d_qs, d_mean, d_var;
@@ -3276,7 +3324,7 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
             if (d_qs && GPV_HIP_FAILED(hipMemcpyAsync(d_qs, hqs.data(), sizeof(double) * (size_t)cn * dim, hipMemcpyHostToDevice, st)))
                 return drain_fail(st, GPV_ERR_HIP);
             if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return drain_fail(st, GPV_ERR_HIP);
-            if (GPV_HIP_FAILED(qnn_search(index.ix, d_qs ? d_qs.get() : d_q.get(), cn, m, d_nn, st))) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(qnn_search(kc.ix, d_qs ? d_qs.get() : d_q.get(), cn, m, d_nn, st))) return drain_fail(st, GPV_ERR_HIP);
         }
         a.nq = cn;
         if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return drain_fail(st, GPV_ERR_HIP);
@@ -3296,8 +3344,160 @@ int gpv_plan_krige(gpv_plan *pl, const char *covType, const double *covparms, in
     return GPV_OK;
 }
 
-// developer aid (tools/krige_timing.py; not part of the public header): device time of the searches and of the passes of the
-// latest gpv_plan_krige, each summed over the call's chunks, by event pairs around them alone
+// ---- grouped local kriging (gpv_krige_groups.hip): joint predictions of groups of locations that share a conditioning set ----
+int gpv_krige_groups_max_rows(void) { return kKrigeGroupMaxRows; }
+
+// The contract of gpv_plan_krige: buffers that live for the call, no evaluation needed and none disturbed, every refusal before
+// the device is touched and before anything is written.  The groups are streamed `chunk` at a time; the groups of a chunk are
+// binned by their row bucket (a function of m + g alone) and each bucket is one launch, so a group's bits depend neither on the
+// chunking nor on the other groups.
+int gpv_plan_krige_groups(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, const double *nuggets,
+                          int64_t n_nuggets, const double *Z_ord, int64_t ldz, int ncols, const double *qlocs, int64_t nq,
+                          const int64_t *gptr, int64_t ngroups, const double *weights, int m, const int *NNg, const double *scale,
+                          const unsigned char *eligible_ord, int64_t chunk, double *mean, int64_t ldm, double *var, double *gmean,
+                          int64_t ldg, double *gvar, double *cov, int64_t *n_failed)
+{
+    if (!pl || !covType || !covparms || !nuggets || !n_failed || nq < 0 || ngroups < 0 || chunk < 0 || m < 1) return GPV_ERR_BAD_ARG;
+    if (ngroups > 0 && (!gptr || !qlocs || !mean || !var || !gmean || !gvar)) return GPV_ERR_BAD_ARG;
+    if (ldm < nq || ldg < ngroups) return GPV_ERR_BAD_ARG;
+    KrigeCall kc;
+    if (const int rc = krige_check_args(pl, covType, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, scale, kc.cs)) return rc;
+    // the groups: gptr non-decreasing from 0 to nq, no group empty
+    if (ngroups == 0 ? nq != 0 : (gptr[0] != 0 || gptr[ngroups] != nq)) return GPV_ERR_BAD_ARG;
+    int64_t gmax = 0;
+    for (int64_t k = 0; k < ngroups; ++k) {
+        if (gptr[k + 1] <= gptr[k] || gptr[k + 1] > nq) return GPV_ERR_BAD_ARG;
+        gmax = std::max(gmax, gptr[k + 1] - gptr[k]);
+    }
+    if (weights)
+        for (int64_t i = 0; i < nq; ++i)
+            if (!std::isfinite(weights[i])) return GPV_ERR_BAD_ARG;
+    if (m + 1 > kKrigeGroupMaxRows || m + gmax > kKrigeGroupMaxRows) return GPV_ERR_UNSUPPORTED_M;
+    if (const int rc = krige_check_state(pl, !Z_ord, NNg, ngroups * m)) return rc;
+    *n_failed = 0;
+    if (ngroups == 0) return GPV_OK;
+
+    if (const int rc = enter(pl)) return rc;
+    hipStream_t st = pl->stream;
+    const int dim = pl->dim;
+    KrigeGroupArgs a{};
+    if (const int rc = krige_resident(pl, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, m, kc, a.k, st)) return rc;
+    if (!NNg)
+        if (const int rc = krige_index(pl, scale, eligible_ord, kc, st)) return rc;
+    // the chunks, by groups; what the largest of them holds
+    const int64_t cap = std::min<int64_t>(std::min<int64_t>(chunk > 0 ? chunk : kKrigeGroupChunk, ngroups), (int64_t)1 << 24);
+    int64_t maxq = 0, maxc = 0;
+    const auto tri = [](int64_t g) { return g * (g + 1) / 2; };
+    for (int64_t k0 = 0; k0 < ngroups; k0 += cap) {
+        const int64_t k1 = std::min(k0 + cap, ngroups);
+        int64_t c = 0;
+        for (int64_t k = k0; k < k1; ++k) c += tri(gptr[k + 1] - gptr[k]);
+        maxq = std::max(maxq, gptr[k1] - gptr[k0]);
+        maxc = std::max(maxc, c);
+    }
+    DevBuf<double> d_q, d_anc, d_w, d_mean, d_var, d_gmean, d_gvar, d_cov;
+    DevBuf<int32_t> d_nn, d_gptr, d_list;
+    DevBuf<int64_t> d_coff;
+    DevBuf<unsigned> d_nfail;
+    GPV_BUF(d_q, resize((size_t)maxq * dim));
+    if (!NNg) GPV_BUF(d_anc, resize((size_t)cap * dim));
+    GPV_BUF(d_w, resize((size_t)maxq));
+    GPV_BUF(d_mean, resize((size_t)maxq * ncols));
+    GPV_BUF(d_var, resize((size_t)maxq));
+    GPV_BUF(d_gmean, resize((size_t)cap * ncols));
+    GPV_BUF(d_gvar, resize((size_t)cap));
+    if (cov) {
+        GPV_BUF(d_cov, resize((size_t)maxc));
+        GPV_BUF(d_coff, resize((size_t)cap));
+    }
+    GPV_BUF(d_nn, resize((size_t)cap * m));
+    GPV_BUF(d_gptr, resize((size_t)cap + 1));
+    GPV_BUF(d_list, resize((size_t)cap));
+    GPV_BUF(d_nfail, resize(2));
+    if (GPV_HIP_FAILED(hipMemsetAsync(d_nfail, 0, sizeof(unsigned), st))) return drain_fail(st, GPV_ERR_HIP);
+    a.k.nnq = d_nn; a.k.q = d_q; a.k.mean = d_mean; a.k.var = d_var; a.k.nfail = d_nfail;
+    a.gptr = d_gptr; a.w = d_w; a.coff = d_coff; a.gmean = d_gmean; a.gvar = d_gvar; a.cov = cov ? d_cov.get() : nullptr;
+    Event ev[3];                                           // around the search and the passes of a chunk
+    for (auto &e : ev) GPV_HIP(hipEventCreate(e.put()));
+    pl->kr_search_ms = pl->kr_pass_ms = 0.0;
+    std::vector<double> hq((size_t)maxq * dim), hanc(NNg ? 0 : (size_t)cap * dim), hw((size_t)maxq);
+    std::vector<int32_t> hnn(NNg ? (size_t)cap * m : 0), hgptr((size_t)cap + 1), hlist((size_t)cap);
+    std::vector<int64_t> hcoff(cov ? (size_t)cap : 0);
+    int64_t cov0 = 0;                                      // where the chunk's triangles start in `cov`
+    for (int64_t k0 = 0; k0 < ngroups; k0 += cap) {
+        const int64_t cg = std::min(cap, ngroups - k0), q0 = gptr[k0], cn = gptr[k0 + cg] - q0;
+        int64_t nb[kKrigeGroupBuckets] = {0, 0, 0}, at[kKrigeGroupBuckets], clen = 0;
+        for (int64_t k = 0; k < cg; ++k) {
+            const int64_t g0 = gptr[k0 + k] - q0, g = gptr[k0 + k + 1] - gptr[k0 + k];
+            hgptr[(size_t)k] = (int32_t)g0;
+            ++nb[krige_group_bucket(m + (int)g)];
+            if (cov) hcoff[(size_t)k] = clen;
+            clen += tri(g);
+            for (int64_t i = 0; i < g; ++i) hw[(size_t)(g0 + i)] = weights ? weights[q0 + g0 + i] : 1.0 / (double)g;
+            if (!NNg)                                      // the anchor: the members' mean, summed in member order, then the scale
+                for (int t = 0; t < dim; ++t) {
+                    double s = qlocs[q0 + g0 + (int64_t)t * nq];
+                    for (int64_t i = 1; i < g; ++i) s += qlocs[q0 + g0 + i + (int64_t)t * nq];
+                    const double anchor = s / (double)g;
+                    hanc[(size_t)k * dim + t] = scale ? anchor / scale[t] : anchor;
+                }
+        }
+        hgptr[(size_t)cg] = (int32_t)cn;
+        at[0] = 0; at[1] = nb[0]; at[2] = nb[0] + nb[1];
+        {
+            int64_t fill[kKrigeGroupBuckets] = {at[0], at[1], at[2]};
+            for (int64_t k = 0; k < cg; ++k) hlist[(size_t)fill[krige_group_bucket(m + (int)(gptr[k0 + k + 1] - gptr[k0 + k]))]++] = (int32_t)k;
+        }
+        for (int t = 0; t < dim; ++t)
+            for (int64_t i = 0; i < cn; ++i) hq[(size_t)i * dim + t] = qlocs[q0 + i + (int64_t)t * nq];
+        if (GPV_HIP_FAILED(hipMemcpyAsync(d_q, hq.data(), sizeof(double) * (size_t)cn * dim, hipMemcpyHostToDevice, st)) ||
+            GPV_HIP_FAILED(hipMemcpyAsync(d_w, hw.data(), sizeof(double) * (size_t)cn, hipMemcpyHostToDevice, st)) ||
+            GPV_HIP_FAILED(hipMemcpyAsync(d_gptr, hgptr.data(), sizeof(int32_t) * (size_t)(cg + 1), hipMemcpyHostToDevice, st)) ||
+            GPV_HIP_FAILED(hipMemcpyAsync(d_list, hlist.data(), sizeof(int32_t) * (size_t)cg, hipMemcpyHostToDevice, st)))
+            return drain_fail(st, GPV_ERR_HIP);
+        if (cov && GPV_HIP_FAILED(hipMemcpyAsync(d_coff, hcoff.data(), sizeof(int64_t) * (size_t)cg, hipMemcpyHostToDevice, st)))
+            return drain_fail(st, GPV_ERR_HIP);
+        if (NNg) {
+            for (int s = 0; s < m; ++s)
+                for (int64_t k = 0; k < cg; ++k) hnn[(size_t)k * m + s] = NNg[k0 + k + (int64_t)s * ngroups];
+            if (GPV_HIP_FAILED(hipMemcpyAsync(d_nn, hnn.data(), sizeof(int32_t) * (size_t)cg * m, hipMemcpyHostToDevice, st)))
+                return drain_fail(st, GPV_ERR_HIP);
+        } else {
+            if (GPV_HIP_FAILED(hipMemcpyAsync(d_anc, hanc.data(), sizeof(double) * (size_t)cg * dim, hipMemcpyHostToDevice, st)))
+                return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(qnn_search(kc.ix, d_anc, cg, m, d_nn, st))) return drain_fail(st, GPV_ERR_HIP);
+        }
+        a.k.nq = cn; a.ng = cg;
+        if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return drain_fail(st, GPV_ERR_HIP);
+        for (int b = 0; b < kKrigeGroupBuckets; ++b) {
+            if (nb[b] == 0) continue;
+            a.list = d_list.get() + at[b]; a.nlist = nb[b];
+            if (GPV_HIP_FAILED(launch_krige_groups(a, b, krige_grid(nb[b], pl->cus), st))) return drain_fail(st, GPV_ERR_HIP);
+        }
+        if (GPV_HIP_FAILED(hipEventRecord(ev[2], st))) return drain_fail(st, GPV_ERR_HIP);
+        if (cols_to_host(mean + q0, ldm, d_mean, cn, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
+        if (cols_to_host(gmean + k0, ldg, d_gmean, cg, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipMemcpyAsync(var + q0, d_var, sizeof(double) * (size_t)cn, hipMemcpyDeviceToHost, st)) ||
+            GPV_HIP_FAILED(hipMemcpyAsync(gvar + k0, d_gvar, sizeof(double) * (size_t)cg, hipMemcpyDeviceToHost, st)))
+            return drain_fail(st, GPV_ERR_HIP);
+        if (cov && GPV_HIP_FAILED(hipMemcpyAsync(cov + cov0, d_cov, sizeof(double) * (size_t)clen, hipMemcpyDeviceToHost, st)))
+            return drain_fail(st, GPV_ERR_HIP);
+        cov0 += clen;
+        GPV_HIP(hipStreamSynchronize(st));                 // (the staging vectors and the chunk buffers are reused)
+        float t = 0.f;
+        if (!NNg && hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) pl->kr_search_ms += (double)t;
+        if (hipEventElapsedTime(&t, ev[1], ev[2]) == hipSuccess) pl->kr_pass_ms += (double)t;
+    }
+    unsigned nbad = 0;
+    GPV_HIP(hipMemcpy(&nbad, d_nfail, sizeof(nbad), hipMemcpyDeviceToHost));
+    *n_failed = (int64_t)nbad;
+    return GPV_OK;
+}
+
+// developer aid (tools/krige_timing.py, tools/krige_groups_timing.py; not part of the public header): device time of the
+// searches and of the passes of the latest gpv_plan_krige or gpv_plan_krige_groups, each summed over the call's chunks, by
+// event pairs around them alone
 extern "C" int gpv_plan_debug_krige_ms(gpv_plan *pl, double *ms)
 {
     if (!pl || !ms) return GPV_ERR_BAD_ARG;

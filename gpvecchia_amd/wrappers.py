@@ -473,31 +473,53 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
     return out
 
 
-def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, local=False, **specify_args):
+def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, local=False, groups=None, weights=None, return_cov=False,
+                 **specify_args):
     """R/vecchia_wrappers.R:134-161: spatial prediction at new locations from the result of vecchia_estimate, with the
     exact prediction variances of the latent field (vecchia_prediction(..., return_values='meanvar')).  With prediction locations in two or more dimensions vecchia_specify defaults to
     cond.yz='zy' (R/vecchia_specify.R:92-96), whose posterior mean is one triangular solve on the GPU.
     local=True (the default changes nothing): the prediction of the cond_yz='z' model itself, the one vecchia_estimate fits with
     cond_yz='z', by local kriging on the m nearest observations of every location (vecchia_krige): no posterior pass, any
     number of prediction locations.  The observations are specified again with cond_yz='z' (specify_args as for
-    vecchia_estimate); the trend is added back as below."""
+    vecchia_estimate); the trend is added back as below.
+    groups (with local=True): one integer label per prediction location; the members of a group are predicted jointly
+    (vecchia_krige_groups, with weights and return_cov), and group_ids, group_mean (the trend included), group_var, n_failed
+    and, with return_cov, group_cov join what is returned.  Without groups it is the call it was."""
     import warnings
     theta_hat = np.asarray(vecchia_est["theta_hat"], dtype=np.float64)                               # :140-143
+    if groups is not None and not local:
+        raise ValueError("groups are predicted by local kriging: local=True")
+    extra = {}
     if local:
         if specify_args.setdefault("cond_yz", "z") != "z":
             raise ValueError("local=True predicts the cond_yz='z' model")
         if np.asarray(vecchia_est["z"]).ndim != 1:
             raise ValueError("local=True takes the result of an estimation from one data vector")
         va = A.vecchia_specify(vecchia_est["locs"], m, **specify_args)
-        kr = A.vecchia_krige(vecchia_est["z"], va, locs_pred, theta_hat[:-1], theta_hat[-1],
-                             covmodel=vecchia_est.get("covmodel", "matern"), scale=specify_args.get("scale"), device=device)
+        if groups is None:
+            kr = A.vecchia_krige(vecchia_est["z"], va, locs_pred, theta_hat[:-1], theta_hat[-1],
+                                 covmodel=vecchia_est.get("covmodel", "matern"), scale=specify_args.get("scale"), device=device)
+        else:                                            # the trend joins the locations' and the groups' means alike
+            trend = None
+            if X_pred is not None:
+                trend = np.asarray(X_pred, dtype=np.float64) @ vecchia_est["beta_hat"]
+            elif vecchia_est["trend"] == "constant":
+                trend = np.asarray(vecchia_est["beta_hat"][0], dtype=np.float64)
+            kr = A.vecchia_krige_groups(vecchia_est["z"], va, locs_pred, groups, theta_hat[:-1], theta_hat[-1],
+                                        covmodel=vecchia_est.get("covmodel", "matern"), weights=weights, mean_pred=trend,
+                                        scale=specify_args.get("scale"), return_cov=return_cov, device=device)
+            if vecchia_est["trend"] not in ("none", "constant") and X_pred is None:
+                warnings.warn("X.pred was not specified, so no trend was added back to the predictions")
+            extra = {k: kr[k] for k in ("group_ids", "group_mean", "group_var", "n_failed", "group_cov") if k in kr}
         preds = dict(mu_pred=kr["mean_pred"], var_pred=kr["var_pred"])
     else:
         from .laplace import vecchia_prediction
         va = A.vecchia_specify(vecchia_est["locs"], m, locs_pred=np.asarray(locs_pred, dtype=np.float64), **specify_args)   # :137
         preds = vecchia_prediction(vecchia_est["z"], va, theta_hat[:-1], theta_hat[-1],
                                    covmodel=vecchia_est.get("covmodel", "matern"), return_values="meanvar", device=device)
-    if X_pred is not None:                                                                           # :146-147
+    if extra:
+        mu_pred = preds["mu_pred"]
+    elif X_pred is not None:                                                                         # :146-147
         mu_pred = preds["mu_pred"] + np.asarray(X_pred, dtype=np.float64) @ vecchia_est["beta_hat"]
     elif vecchia_est["trend"] == "none":                                                             # :148-149
         mu_pred = preds["mu_pred"]
@@ -506,4 +528,4 @@ def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, local=Fals
     else:                                                                                            # :152-156
         mu_pred = preds["mu_pred"]
         warnings.warn("X.pred was not specified, so no trend was added back to the predictions")
-    return dict(mean_pred=mu_pred, var_pred=preds["var_pred"])                                                    # :159
+    return dict(mean_pred=mu_pred, var_pred=preds["var_pred"], **extra)                                           # :159

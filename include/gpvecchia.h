@@ -800,6 +800,47 @@ int gpv_plan_krige(gpv_plan *plan, const char *covType, const double *covparms, 
                    const double *scale, const unsigned char *eligible_ord, int64_t chunk /* 0: default */,
                    double *mean, int64_t ldm, double *var, int64_t *n_failed);
 
+/* Grouped local kriging: joint predictions of groups of locations under a cond.yz='z' model (gpv_krige_groups.hip).  A group G
+ * of g locations is ordered last; member i conditions on one shared set J of observations and on the members before it, which
+ * is a valid Vecchia model.  With S = C(J u G, J u G) + diag(tau_J, 0_G), J in front, and the J pivots eliminated,
+ *     Sigma_G = K_GG - K_GJ (K_JJ + tau_J)^-1 K_JG    the joint predictive covariance of the latent field y on G,
+ *     mean[i, c] = K_iJ (K_JJ + tau_J)^-1 z_{J,c},    var[i] = (Sigma_G)_ii,
+ *     gmean[k, c] = sum_i w_i mean[i, c],             gvar[k] = w' Sigma_G w     (an areal average, a contrast, ...).
+ * J = the min(m, #eligible) eligible observations nearest (gpv_find_query_nn) to the group's anchor, the coordinate-wise mean
+ * of its members (summed in member order in double precision, then divided by g; with `scale`, then divided by it), or NNg.
+ * A group of one location is the prediction of gpv_plan_krige there.
+ *   covType ... ncols, scale, eligible_ord   as gpv_plan_krige
+ *   qlocs, nq                      nq x dim column-major, the members of a group contiguous
+ *   gptr, ngroups                  group k = rows gptr[k] .. gptr[k + 1] - 1; gptr[0] = 0, gptr[ngroups] = nq, no group empty
+ *   weights                        NULL: 1 / g each; else nq finite values of any sign
+ *   m, NNg                         m + g <= gpv_krige_groups_max_rows() = 64 for every group; NNg: NULL (searched at the anchors)
+ *                                  or ngroups x m column-major ORDERED ids, 1-based, 0 = none
+ *   chunk                          groups per pass, 0: 65536.  Device memory does not grow with nq.  A group's bits depend on
+ *                                  neither the chunking, nor the other groups of the call, nor the other columns
+ *   mean, ldm, var                 per location: nq x ncols column-major (ldm >= nq), nq
+ *   gmean, ldg, gvar               per group: ngroups x ncols column-major (ldg >= ngroups), ngroups
+ *   cov                            NULL, or sum_k g_k (g_k + 1) / 2 doubles: the lower triangle of group k's Sigma_G, row-major,
+ *                                  at the running offset
+ *   n_failed                       groups that failed: a J pivot not > 0 (or NaN) or a diagonal entry of Sigma_G not > 0 (a
+ *                                  member on an observation that has no nugget).  Everything of a failed group is NaN.
+ *                                  Duplicate members are legal: Sigma_G is singular there
+ * Statuses as gpv_plan_krige, and GPV_ERR_BAD_ARG: gptr not increasing from 0 to nq (an empty group included), a weight that
+ * is not finite, ldg < ngroups; GPV_ERR_UNSUPPORTED_M: m + g > 64 in any group; GPV_ERR_INDEX: an entry of NNg outside
+ * [0, Nlocs].  A refused call writes nothing.  ngroups == 0 is GPV_OK. */
+int gpv_krige_groups_max_rows(void);   /* 64: m + g */
+int gpv_plan_krige_groups(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms,
+                          const double *nuggets, int64_t n_nuggets,
+                          const double *Z_ord, int64_t ldz, int ncols,
+                          const double *qlocs, int64_t nq,            /* nq x dim column-major, members of a group contiguous */
+                          const int64_t *gptr, int64_t ngroups,       /* group k = rows gptr[k] .. gptr[k+1]-1 */
+                          const double *weights,                      /* NULL: 1/g; else nq values, any sign */
+                          int m, const int *NNg,                      /* NULL: search at the anchors; else ngroups x m ORDERED ids */
+                          const double *scale, const unsigned char *eligible_ord, int64_t chunk /* groups per pass, 0: default */,
+                          double *mean, int64_t ldm, double *var,     /* per location */
+                          double *gmean, int64_t ldg, double *gvar,   /* per group */
+                          double *cov,                                /* NULL, or the packed lower triangles */
+                          int64_t *n_failed);
+
 #ifdef __cplusplus
 }
 #endif
