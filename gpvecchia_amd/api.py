@@ -476,6 +476,66 @@ class Plan:
                                        L.dptr(var), C.byref(nf)), "gpv_plan_krige")
         return mean, var, int(nf.value)
 
+    def cond_sim(self, covmodel, covparms, nuggets_ord, qlocs, m, Z_ord=None, NNq=None, scale=None, eligible_ord=None, E=None,
+                 seed=0, col0=0, nsim=0, chunk=0):
+        """Conditional simulation over the prediction locations qlocs (nq, dim), taken in the order given (the sweep order), under
+        the cond.yz='z' model of this plan (gpv_plan_cond_sim): location i conditions on its m nearest points among the
+        observations and the locations before it (m + 1 <= 64); needs no evaluation and disturbs none.  nuggets_ord, Z_ord,
+        scale, eligible_ord: as Plan.krige; NNq: None (the library's ordered search) or (nq, m) ids, 1-based, 0 = none:
+        1 .. Nlocs an ORDERED observation, Nlocs + 1 + p the sweep row p (before the own row).  E: None (nsim draws col0 ..
+        col0 + nsim - 1 of the library's generator under `seed`) or the caller's (nq, nsim) standard normals.  chunk: rows per
+        launch of the factor pass (0: the default), which changes no bit.  Returns dict(mean (nq, ncols), dev (nq, nsim): the
+        draw (c, s) is mean[:, c] + dev[:, s]; sd (nq,): the conditional standard deviation given the neighbours; n_levels,
+        n_launches, n_failed); NaN at a location whose block was not positive definite (counted) and at those that depend on
+        it."""
+        q = np.asfortranarray(np.asarray(qlocs, dtype=np.float64).reshape(-1, self.dim))
+        nq = q.shape[0]
+        cp = np.ascontiguousarray(covparms, dtype=np.float64).reshape(-1)
+        nug = np.ascontiguousarray(np.atleast_1d(np.asarray(nuggets_ord, dtype=np.float64)))
+        Z, ncols = None, 1
+        if Z_ord is not None:
+            Z = np.asarray(Z_ord, dtype=np.float64)
+            Z = np.asfortranarray(Z[:, None] if Z.ndim == 1 else Z)
+            if Z.ndim != 2 or Z.shape[0] != self.Nlocs:
+                raise ValueError("Z_ord must have one row per ordered location of the plan")
+            ncols = Z.shape[1]
+        nn = None
+        if NNq is not None:
+            nn = np.asfortranarray(NNq, dtype=np.int32)
+            if nn.shape != (nq, int(m)):
+                raise ValueError("NNq must be (nq, m)")
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+        if sc is not None and sc.size != self.dim:
+            raise ValueError("scale must hold one number per coordinate")
+        el = None
+        if eligible_ord is not None:
+            el = np.ascontiguousarray(np.asarray(eligible_ord).astype(bool).reshape(-1), dtype=np.uint8)
+            if el.shape[0] != self.Nlocs:
+                raise ValueError("eligible_ord must hold one flag per ordered location of the plan")
+        Ef = None
+        if E is not None:
+            Ef = np.asfortranarray(np.asarray(E, dtype=np.float64).reshape(nq, -1))
+            nsim = Ef.shape[1]
+        nsim = int(nsim)
+        mean = np.zeros((nq, ncols), order="F")
+        dev = np.zeros((nq, max(nsim, 0)), order="F")
+        sd = np.zeros(nq)
+        nlev, nlaunch, nf = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        u8 = C.POINTER(C.c_uint8)
+        lib = L.lib()
+        L.check(lib.gpv_plan_debug_csim_chunk(self._h, int(chunk)), "gpv_plan_debug_csim_chunk")
+        try:
+            L.check(lib.gpv_plan_cond_sim(self._h, str(covmodel).encode(), L.dptr(cp), cp.size, L.dptr(nug), nug.size,
+                                          None if Z is None else L.dptr(Z), self.Nlocs, ncols, L.dptr(q), nq, int(m),
+                                          None if nn is None else L.iptr(nn), None if sc is None else L.dptr(sc),
+                                          None if el is None else el.ctypes.data_as(u8),
+                                          None if Ef is None else L.dptr(Ef), max(nq, 1), int(seed), int(col0), nsim,
+                                          L.dptr(mean), max(nq, 1), L.dptr(dev), max(nq, 1), L.dptr(sd),
+                                          C.byref(nlev), C.byref(nlaunch), C.byref(nf)), "gpv_plan_cond_sim")
+        finally:
+            lib.gpv_plan_debug_csim_chunk(self._h, 0)
+        return dict(mean=mean, dev=dev, sd=sd, n_levels=int(nlev.value), n_launches=int(nlaunch.value), n_failed=int(nf.value))
+
     def krige_groups(self, covmodel, covparms, nuggets_ord, qlocs, gptr, m, Z_ord=None, weights=None, NNg=None, scale=None,
                      eligible_ord=None, chunk=0, want_cov=False):
         """Grouped local kriging under the cond.yz='z' model of this plan (gpv_plan_krige_groups): group k is the rows
@@ -1878,6 +1938,63 @@ def vecchia_krige(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="mat
             raise ValueError(f"{name}: predict='z' needs nugget_pred")
         var_p = var_p + np.asarray(nugget_pred, dtype=np.float64)
     return dict(mean_pred=mu_p[:, 0] if vector else mu_p, var_pred=var_p, n_failed=n_failed)
+
+
+_COND_SIM_NOISE_KEY = 0x9E3779B97F4A7C15              # added to the seed (mod 2^64): the key of the predict='z' noise
+
+
+def vecchia_cond_sim(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="matern", m=None, nsim=1, seed=0, order="maxmin",
+                     mean=None, mean_pred=None, predict="y", nugget_pred=None, scale=None, eps=None, device=0):
+    """Spatially coherent conditional draws over a map under the cond.yz='z' Vecchia model (Plan.cond_sim): the prediction
+    locations are ordered after all observations, in a sweep order, and each conditions on its m nearest points among the
+    observations and the prediction locations before it (the reference's ordering.pred='obspred' with pred.cond='general',
+    for a 'z' model).  One factor pass and one level-scheduled sweep per 16 draws on the GPU.
+    z, vecchia_approx, m, mean, mean_pred, scale, nuggets and the missing values: as vecchia_krige.  order: "maxmin" (the exact
+    max-min ordering of the prediction locations), "given", or a permutation of range(n_p) (position k of the sweep takes
+    location order[k]); everything comes back in the CALLER's order.  nsim, seed: draws of the library's generator; eps: the
+    caller's (n_p, nsim) standard normals instead, row i for location i.  predict='z' adds independent N(0, nugget_pred) noise
+    to the draws, from the same generator under a key of its own.
+    Returns dict(mean (n_p[, R]), draws (n_p, nsim) with one data column, else dev (n_p, nsim): draw (c, s) = mean[:, c] +
+    dev[:, s]; sd_cond (n_p,): the conditional standard deviation given the neighbours, NOT the marginal one; order (the sweep
+    order, 0-based), n_levels, n_failed).  A location that coincides with an earlier one of the sweep, or with an observation
+    that has no nugget, fails: it and every location that depends on it are NaN."""
+    va = vecchia_approx
+    name = "vecchia_cond_sim"
+    Z, vector, eligible, nug, lp, m, ordz = _krige_inputs(name, z, va, locs_pred, nuggets, covmodel, m, mean, predict)
+    n_p = lp.shape[0]
+    if isinstance(order, str):
+        if order not in ("maxmin", "given"):
+            raise ValueError(f"{name}: order must be 'maxmin', 'given' or a permutation")
+        o = (S.order_maxmin_exact(lp) - 1) if (order == "maxmin" and n_p > 1) else np.arange(n_p, dtype=np.int64)
+    else:
+        o = np.asarray(order, dtype=np.int64).reshape(-1)
+        if o.size != n_p or not np.array_equal(np.sort(o), np.arange(n_p)):
+            raise ValueError(f"{name}: order must be a permutation of range(n_p)")
+    E = None
+    if eps is not None:
+        E = np.asarray(eps, dtype=np.float64).reshape(n_p, -1)[o]
+        nsim = E.shape[1]
+    nsim = int(nsim)
+    if predict == "z" and nugget_pred is None:
+        raise ValueError(f"{name}: predict='z' needs nugget_pred")
+    plan = _plan_for(va, device)
+    r = plan.cond_sim(covmodel, covparms, nug if nug.size == 1 else nug[ordz], lp[o], int(m), Z_ord=Z[ordz], scale=scale,
+                      eligible_ord=None if eligible is None else eligible[ordz], E=E, seed=seed, nsim=nsim)
+    mu_p, dev, sd = np.empty_like(r["mean"]), np.empty_like(r["dev"]), np.empty(n_p)
+    mu_p[o], dev[o], sd[o] = r["mean"], r["dev"], r["sd"]
+    if mean_pred is not None:
+        mp = np.asarray(mean_pred, dtype=np.float64)
+        mu_p = mu_p + (mp if mp.ndim == 0 else mp.reshape(n_p, -1))
+    if predict == "z" and nsim > 0:
+        from .lincomb import draws_normals_host
+        noise = draws_normals_host((int(seed) + _COND_SIM_NOISE_KEY) % (1 << 64), 0, n_p, 0, nsim).T
+        dev = dev + np.sqrt(np.broadcast_to(np.asarray(nugget_pred, dtype=np.float64), (n_p,)))[:, None] * noise
+    out = dict(mean=mu_p[:, 0] if vector else mu_p, sd_cond=sd, order=o, n_levels=r["n_levels"], n_failed=r["n_failed"])
+    if Z.shape[1] == 1:
+        out["draws"] = mu_p[:, :1] + dev
+    else:
+        out["dev"] = dev
+    return out
 
 
 def vecchia_krige_groups(z, vecchia_approx, locs_pred, groups, covparms, nuggets, covmodel="matern", m=None, weights=None, mean=None,

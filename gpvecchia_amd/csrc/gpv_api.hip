@@ -15,6 +15,7 @@
 #include "gpv_blockcv.h"
 #include "gpv_krige.h"
 #include "gpv_krige_groups.h"
+#include "gpv_csim.h"
 #include "gpv_selinv.h"
 #include "gpv_grad_sgv.h"
 #include "gpv_hip_raii.hpp"
@@ -509,6 +510,11 @@ struct gpv_plan {
     // gpv_plan_krige (gpv_krige.hip): device time of the latest call's searches and passes, summed over its chunks
     // (gpv_plan_debug_krige_ms).  Its buffers live for the call.
     double kr_search_ms = 0.0, kr_pass_ms = 0.0;
+    // gpv_plan_cond_sim (gpv_csim.hip): the rows per launch of its factor pass (0: the default; gpv_plan_debug_csim_chunk) and
+    // the latest call's times (gpv_plan_debug_csim_ms): the search by the host's clock, then device time of the factor pass,
+    // of all sweeps and of the last sweep.  Its buffers live for the call.
+    int64_t cs_chunk = 0;
+    double cs_search_ms = 0.0, cs_factor_ms = 0.0, cs_sweep_ms = 0.0, cs_last_sweep_ms = 0.0;
     // d_L and the nuggets on the device (d_nuggets / nug_scalar) belong to evaluation L_of_eval of the plan (evaluations are
     // counted from 1; 0: to none).  Set at the end of an evaluation that materialised U, cleared before anything of the two is
     // rewritten: an evaluation that starts, a Vecchia-Laplace step that writes its pseudo-nuggets, a rebuilt posterior structure.
@@ -3503,6 +3509,287 @@ extern "C" int gpv_plan_debug_krige_ms(gpv_plan *pl, double *ms)
     if (!pl || !ms) return GPV_ERR_BAD_ARG;
     ms[0] = pl->kr_search_ms;
     ms[1] = pl->kr_pass_ms;
+    return GPV_OK;
+}
+
+// ---- conditional simulation of a map (gpv_csim.hip): the sequential kriging sweep over the prediction locations -------------
+namespace {
+struct CsimLaunch { int lev0, lev1; bool narrow; };
+}  // namespace
+
+// The level schedule of a mixed neighbour list: entry (i, s) at NN[i * rs + s * cs]; an id in (Nlocs, Nlocs + i] names sweep row
+// id - Nlocs - 1.  level(i) = 0 without such an id, else 1 + the largest level among them; the rows counting-sorted by level,
+// ascending inside a level.  (The schedule of gpv_plan_unwhiten is built from the plan's index arrays, where rows may share
+// their last entry and positions may have no owner: it keeps its own loop and its bits.)  Returns GPV_ERR_INDEX for an id
+// outside [0, Nlocs + own row].
+static int csim_levels_core(const int32_t *NN, int64_t rs, int64_t cs, int64_t nq, int m, int64_t Nlocs, std::vector<int32_t> &level,
+                            std::vector<int32_t> &order, std::vector<int64_t> &levptr)
+{
+    level.assign((size_t)nq, 0);
+    int32_t top = 0;
+    for (int64_t i = 0; i < nq; ++i) {
+        int32_t lv = 0;
+        for (int s = 0; s < m; ++s) {
+            const int64_t id = NN[i * rs + (int64_t)s * cs];
+            if (id < 0 || id > Nlocs + i) return GPV_ERR_INDEX;
+            if (id > Nlocs) lv = std::max(lv, level[(size_t)(id - Nlocs - 1)] + 1);
+        }
+        level[(size_t)i] = lv;
+        top = std::max(top, lv);
+    }
+    const int64_t nlev = nq > 0 ? (int64_t)top + 1 : 0;
+    levptr.assign((size_t)nlev + 1, 0);
+    order.assign((size_t)nq, 0);
+    for (int64_t i = 0; i < nq; ++i) levptr[(size_t)level[(size_t)i] + 1]++;
+    for (int64_t l = 0; l < nlev; ++l) levptr[(size_t)l + 1] += levptr[(size_t)l];
+    std::vector<int64_t> fill(levptr.begin(), levptr.end() - 1);
+    for (int64_t i = 0; i < nq; ++i) order[(size_t)fill[(size_t)level[(size_t)i]]++] = (int32_t)i;
+    return GPV_OK;
+}
+
+int gpv_csim_levels_host(const int32_t *NN, int64_t nq, int m, int64_t Nlocs, int32_t *level, int32_t *order, int64_t *levptr,
+                         int64_t *n_levels)
+{
+    if (!n_levels || nq < 0 || m < 1 || Nlocs < 0) return GPV_ERR_BAD_ARG;
+    if (Nlocs + nq >= ((int64_t)1 << 31) - 1) return GPV_ERR_INDEX;                      // before any array is read
+    if (nq > 0 && (!NN || !level || !order)) return GPV_ERR_BAD_ARG;
+    if (!levptr) return GPV_ERR_BAD_ARG;
+    std::vector<int32_t> lv, ord;
+    std::vector<int64_t> lp;
+    if (const int rc = csim_levels_core(NN, 1, nq, nq, m, Nlocs, lv, ord, lp)) return rc;
+    std::copy(lv.begin(), lv.end(), level);
+    std::copy(ord.begin(), ord.end(), order);
+    std::copy(lp.begin(), lp.end(), levptr);
+    *n_levels = (int64_t)lp.size() - 1;
+    return GPV_OK;
+}
+
+// The neighbour lists of the sweep rows by the library's ordered search (gpv_nn.hip) on [the eligible ORDERED observations ;
+// the prediction locations], each coordinate divided by `scale` when given: row Nlocs' + i of that search lists the m + 1
+// closest among its predecessors and itself; the row's own entry is dropped (a row that does not list itself, being one of
+// more than m + 1 coincident points, loses its last entry) and the ids go back to the call's numbering.  hnn: [nq][m] row-major.
+static int csim_search(gpv_plan *pl, const double *qlocs, int64_t nq, int m, const double *scale, const unsigned char *eligible_ord,
+                       std::vector<int32_t> &hnn, hipStream_t st)
+{
+    const int64_t n = pl->Nlocs;
+    const int dim = pl->dim;
+    const int ld = dim <= 3 ? 4 : pl->locs_ld;
+    std::vector<double> rec((size_t)n * ld);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(rec.data(), pl->d_locs, sizeof(double) * rec.size(), hipMemcpyDeviceToHost, st)) ||
+        GPV_HIP_FAILED(hipStreamSynchronize(st)))
+        return drain_fail(st, GPV_ERR_HIP);
+    std::vector<int32_t> back;                              // compact index -> ORDERED id - 1
+    back.reserve((size_t)n);
+    for (int64_t i = 0; i < n; ++i)
+        if (!eligible_ord || eligible_ord[i]) back.push_back((int32_t)i);
+    const int64_t ne = (int64_t)back.size(), nt = ne + nq;
+    std::vector<double> lc((size_t)nt * dim);
+    for (int t = 0; t < dim; ++t) {
+        const double sc = scale ? scale[t] : 1.0;
+        for (int64_t i = 0; i < ne; ++i) {
+            const double x = rec[(size_t)pl->h_newpos[(size_t)back[(size_t)i]] * ld + t];
+            lc[(size_t)i + (size_t)t * nt] = scale ? x / sc : x;
+        }
+        for (int64_t i = 0; i < nq; ++i) {
+            const double x = qlocs[i + (int64_t)t * nq];
+            lc[(size_t)(ne + i) + (size_t)t * nt] = scale ? x / sc : x;
+        }
+    }
+    std::vector<int> found((size_t)nq * (m + 1));
+    if (const int rc = ordered_nn_rows(pl->device, lc.data(), nt, dim, m, ne, nt, found.data(), nq)) return rc;
+    hnn.assign((size_t)nq * m, 0);
+    for (int64_t i = 0; i < nq; ++i) {
+        const int64_t self = ne + i + 1;
+        int w = 0;
+        for (int s = 0; s <= m && w < m; ++s) {
+            const int64_t id = found[(size_t)(i + (int64_t)s * nq)];
+            if (id <= 0 || id == self) continue;
+            if (id > self) return GPV_ERR_STATE;
+            hnn[(size_t)i * m + w++] = id <= ne ? back[(size_t)(id - 1)] + 1 : (int32_t)(n + (id - ne));
+        }
+    }
+    return GPV_OK;
+}
+
+// The contract of gpv_plan_krige: buffers that live for the call, no evaluation needed and none disturbed, every refusal before
+// the device is touched and before anything is written.  The factor pass may be chunked over the rows (the locations stay
+// resident: a row reads those of its list); the sweeps run on what it left.
+int gpv_plan_cond_sim(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, const double *nuggets, int64_t n_nuggets,
+                      const double *Z_ord, int64_t ldz, int ncols, const double *qlocs, int64_t nq, int m, const int *NNq,
+                      const double *scale, const unsigned char *eligible_ord, const double *E, int64_t lde, uint64_t seed, int64_t col0,
+                      int64_t nsim, double *mean, int64_t ldm, double *dev, int64_t ldd, double *sd, int64_t *n_levels,
+                      int64_t *n_launches, int64_t *n_failed)
+{
+    constexpr int NB = kCsimMaxCols;
+    if (!pl || !covType || !covparms || !nuggets || !n_levels || !n_launches || !n_failed || nq < 0 || m < 1) return GPV_ERR_BAD_ARG;
+    if (nsim < 0 || col0 < 0 || col0 > INT64_MAX - nsim) return GPV_ERR_BAD_ARG;
+    if (nq > 0 && (!qlocs || !mean || !sd || (nsim > 0 && !dev))) return GPV_ERR_BAD_ARG;
+    if (ldm < nq || (nsim > 0 && (ldd < nq || (E && lde < nq)))) return GPV_ERR_BAD_ARG;
+    KrigeCall kc;
+    if (const int rc = krige_check_args(pl, covType, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, scale, kc.cs)) return rc;
+    if (m + 1 > kKrigeMaxP) return GPV_ERR_UNSUPPORTED_M;
+    if (const int rc = krige_check_state(pl, !Z_ord, nullptr, 0)) return rc;
+    const int64_t n = pl->Nlocs;
+    if (n + nq >= ((int64_t)1 << 31) - 1) return GPV_ERR_INDEX;
+    if (NNq)
+        for (int64_t i = 0; i < nq; ++i)
+            for (int s = 0; s < m; ++s) {
+                const int64_t id = NNq[i + (int64_t)s * nq];
+                if (id < 0 || id > n + i) return GPV_ERR_INDEX;
+            }
+    *n_failed = 0;
+    *n_levels = 0;
+    *n_launches = 0;
+    if (nq == 0) return GPV_OK;
+
+    if (const int rc = enter(pl)) return rc;
+    hipStream_t st = pl->stream;
+    const int dim = pl->dim;
+    CsimFactorArgs f{};
+    if (const int rc = krige_resident(pl, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, m, kc, f.k, st)) return rc;
+    pl->cs_search_ms = pl->cs_factor_ms = pl->cs_sweep_ms = pl->cs_last_sweep_ms = 0.0;
+    // the lists, row-major, and the schedule
+    std::vector<int32_t> hnn;
+    if (NNq) {
+        hnn.resize((size_t)nq * m);
+        for (int s = 0; s < m; ++s)
+            for (int64_t i = 0; i < nq; ++i) hnn[(size_t)i * m + s] = NNq[i + (int64_t)s * nq];
+    } else {
+        const auto t0 = std::chrono::steady_clock::now();
+        if (const int rc = csim_search(pl, qlocs, nq, m, scale, eligible_ord, hnn, st)) return rc;
+        pl->cs_search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    }
+    std::vector<int32_t> level, order;
+    std::vector<int64_t> levptr;
+    if (csim_levels_core(hnn.data(), m, 1, nq, m, n, level, order, levptr)) return GPV_ERR_STATE;   // (given lists were checked above)
+    const int nlev = (int)levptr.size() - 1;
+    std::vector<int32_t> levptr32(levptr.begin(), levptr.end());
+    std::vector<CsimLaunch> launches;
+    for (int l = 0; l < nlev; ++l) {
+        const bool narrow = levptr[(size_t)l + 1] - levptr[(size_t)l] <= kCsimNarrow;
+        if (narrow && !launches.empty() && launches.back().narrow) launches.back().lev1 = l + 1;
+        else launches.push_back(CsimLaunch{l, l + 1, narrow});
+    }
+    // what stays resident for the call
+    const int cpm = whiten_cp(ncols);
+    const int cpx = nsim > 0 ? (E ? std::max(cpm, whiten_cp((int)std::min<int64_t>(nsim, NB))) : NB) : cpm;
+    DevBuf<double> d_q, d_coef, d_sd, d_a, d_X, d_io;
+    DevBuf<int32_t> d_nn, d_order, d_levptr;
+    DevBuf<unsigned> d_nfail;
+    {
+        std::vector<double> hq((size_t)nq * dim);
+        for (int t = 0; t < dim; ++t)
+            for (int64_t i = 0; i < nq; ++i) hq[(size_t)i * dim + t] = qlocs[i + (int64_t)t * nq];
+        GPV_BUF(d_q, upload(hq.data(), hq.size()));
+    }
+    GPV_BUF(d_nn, upload(hnn.data(), hnn.size()));
+    GPV_BUF(d_order, upload(order.data(), order.size()));
+    GPV_BUF(d_levptr, upload(levptr32.data(), levptr32.size()));
+    GPV_BUF(d_coef, resize((size_t)nq * m));
+    GPV_BUF(d_sd, resize((size_t)nq));
+    GPV_BUF(d_a, resize((size_t)nq * ncols));
+    GPV_BUF(d_X, resize((size_t)nq * cpx));
+    GPV_BUF(d_io, resize((size_t)nq * std::max(cpx, ncols)));
+    GPV_BUF(d_nfail, resize(2));
+    if (GPV_HIP_FAILED(hipMemsetAsync(d_nfail, 0, sizeof(unsigned), st))) return drain_fail(st, GPV_ERR_HIP);
+    Event ev[2];
+    for (auto &e : ev) GPV_HIP(hipEventCreate(e.put()));
+    // ---- the factor pass
+    f.k.nnq = d_nn; f.k.nfail = d_nfail;
+    f.qall = d_q; f.nrows = nq; f.Nlocs = n; f.coef = d_coef; f.sd = d_sd; f.a = d_a;
+    const int64_t cap = std::min<int64_t>(pl->cs_chunk > 0 ? pl->cs_chunk : kCsimChunk, nq);
+    if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return drain_fail(st, GPV_ERR_HIP);
+    for (int64_t c0 = 0; c0 < nq; c0 += cap) {
+        f.row0 = c0;
+        f.k.nq = std::min(cap, nq - c0);
+        if (GPV_HIP_FAILED(launch_csim_factor(f, krige_grid(f.k.nq, pl->cus), st))) return drain_fail(st, GPV_ERR_HIP);
+    }
+    if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(sd, d_sd, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
+    {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) pl->cs_factor_ms = (double)t;
+    }
+    // ---- the sweeps: d_X holds the right-hand sides, then the solution
+    CsimSweepArgs w{};
+    w.coef = d_coef; w.nn = d_nn; w.X = d_X; w.order = d_order; w.levptr = d_levptr; w.Nlocs = n; w.m = m;
+    const auto sweep = [&](int cp) -> int {
+        if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return GPV_ERR_HIP;
+        for (const CsimLaunch &u : launches)
+            if (GPV_HIP_FAILED(u.narrow ? launch_csim_narrow(w, cp, u.lev0, u.lev1, st)
+                                        : launch_csim_wide(w, cp, levptr[(size_t)u.lev0], levptr[(size_t)u.lev1], st)))
+                return GPV_ERR_HIP;
+        if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return GPV_ERR_HIP;
+        return GPV_OK;
+    };
+    const auto sweep_time = [&] {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) {
+            pl->cs_sweep_ms += (double)t;
+            pl->cs_last_sweep_ms = (double)t;
+        }
+    };
+    // the means: (I - B)^-1 A
+    if (GPV_HIP_FAILED(launch_csim_pack(d_a, nq, nullptr, nq, ncols, cpm, d_X, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (sweep(cpm)) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_csim_unpack(d_X, nq, ncols, cpm, d_io, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (cols_to_host(mean, ldm, d_io, nq, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
+    sweep_time();
+    // the deviation fields: (I - B)^-1 D E, sixteen columns at a time
+    if (nsim > 0 && E) {
+        for (int64_t b0 = 0; b0 < nsim; b0 += NB) {
+            const int nb = (int)std::min<int64_t>(NB, nsim - b0), cp = whiten_cp(nb);
+            if (cols_to_device(d_io, E + b0 * lde, lde, nq, nb, st)) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(launch_csim_pack(d_io, nq, d_sd, nq, nb, cp, d_X, st))) return drain_fail(st, GPV_ERR_HIP);
+            if (sweep(cp)) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(launch_csim_unpack(d_X, nq, nb, cp, d_io, st))) return drain_fail(st, GPV_ERR_HIP);
+            if (cols_to_host(dev + b0 * ldd, ldd, d_io, nq, nb, st)) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
+            sweep_time();
+        }
+    } else if (nsim > 0) {
+        // draw j is always made in the batch [16 floor(j / 16), + 16) at CP = 16: its bits depend on (seed, j) alone; the normals
+        // of sweep row i are those of the id Nlocs + i, apart from what gpv_plan_simulate draws for the observations
+        const int64_t end = col0 + nsim;
+        for (int64_t b = col0 / NB; b * NB < end; ++b) {
+            const int64_t base = b * NB;
+            if (GPV_HIP_FAILED(launch_csim_normals(d_X, d_sd, nq, seed, n, base, st))) return drain_fail(st, GPV_ERR_HIP);
+            if (sweep(NB)) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(launch_csim_unpack(d_X, nq, NB, NB, d_io, st))) return drain_fail(st, GPV_ERR_HIP);
+            const int64_t j0 = std::max(base, col0), j1 = std::min(base + NB, end);
+            if (cols_to_host(dev + (j0 - col0) * ldd, ldd, d_io + (size_t)(j0 - base) * nq, nq, j1 - j0, st)) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
+            sweep_time();
+        }
+    }
+    unsigned nbad = 0;
+    GPV_HIP(hipMemcpy(&nbad, d_nfail, sizeof(nbad), hipMemcpyDeviceToHost));
+    *n_failed = (int64_t)nbad;
+    *n_levels = nlev;
+    *n_launches = (int64_t)launches.size();
+    return GPV_OK;
+}
+
+// developer aids (tools/cond_sim_timing.py and the tests; not part of the public header): the rows per launch of the factor
+// pass of the plan's following gpv_plan_cond_sim calls (0: the default), which changes no bit of a result; and the times of the
+// latest call: {search (host clock), factor pass, all sweeps, the last sweep} in milliseconds, the last three device time by
+// event pairs
+extern "C" int gpv_plan_debug_csim_chunk(gpv_plan *pl, int64_t chunk)
+{
+    if (!pl || chunk < 0) return GPV_ERR_BAD_ARG;
+    pl->cs_chunk = chunk;
+    return GPV_OK;
+}
+
+extern "C" int gpv_plan_debug_csim_ms(gpv_plan *pl, double *ms)
+{
+    if (!pl || !ms) return GPV_ERR_BAD_ARG;
+    ms[0] = pl->cs_search_ms;
+    ms[1] = pl->cs_factor_ms;
+    ms[2] = pl->cs_sweep_ms;
+    ms[3] = pl->cs_last_sweep_ms;
     return GPV_OK;
 }
 

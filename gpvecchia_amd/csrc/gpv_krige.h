@@ -36,6 +36,10 @@ void qnn_free(QnnIndex &ix);
 // d_q: [nq][dim] row-major queries on the device; d_out: [nq][m] 1-based indices by ascending distance, 0-padded
 hipError_t qnn_search(const QnnIndex &ix, const double *d_q, int64_t nq, int m, int32_t *d_out, hipStream_t s);
 
+// ---- ordered search (gpv_nn.hip): gpv_find_ordered_nn with the shard's rows written from `out` on, ld apart ------------------
+// Statuses and arithmetic: those of gpv_find_ordered_nn.  out[r - row_begin + s * ld], s = 0 .. m; ld >= row_end - row_begin.
+int ordered_nn_rows(int device, const double *locs, int64_t n, int dim, int m, int64_t row_begin, int64_t row_end, int *out, int64_t ld);
+
 // ---- the predict pass (gpv_krige.hip) ---------------------------------------------------------------------------------------
 constexpr int kKrigeMaxP = 64;         // m + 1: the neighbours and the query, one lane each
 constexpr int kKrigeMaxCols = 16;

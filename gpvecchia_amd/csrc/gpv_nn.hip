@@ -229,6 +229,15 @@ extern "C" int gpv_nn_max_m(void) { return kNnMaxM; }
 extern "C" int gpv_find_ordered_nn(int device, const double *locs, int64_t n, int dim, int m, int64_t row_begin,
                                    int64_t row_end, int *NNarray)
 {
+    if (!NNarray || row_begin < 0 || row_begin > row_end) return GPV_ERR_BAD_ARG;
+    return ordered_nn_rows(device, locs, n, dim, m, row_begin, row_end, NNarray + row_begin, n);
+}
+
+// the search itself; row r of the shard goes to out[r - row_begin + s * ld], s = 0 .. m (gpv_krige.h: gpv_plan_cond_sim asks for
+// the rows of its prediction locations alone and has no use for an array of n rows)
+int gpv::ordered_nn_rows(int device, const double *locs, int64_t n, int dim, int m, int64_t row_begin, int64_t row_end, int *NNarray,
+                         int64_t ld)
+{
     if (!locs || !NNarray || n <= 0 || dim < 1 || dim > kMaxDimGeneric || m < 0 || m > kNnMaxM) return GPV_ERR_BAD_ARG;
     if (row_begin < 0 || row_end > n || row_begin > row_end || n >= ((int64_t)1 << 31)) return GPV_ERR_BAD_ARG;
     int ndev = 0;
@@ -364,8 +373,8 @@ extern "C" int gpv_find_ordered_nn(int device, const double *locs, int64_t n, in
     (void)hipFree(d_locs);
     (void)hipFree(d_out);
     if (rc != GPV_OK) return rc;
-    for (int s = 0; s < p; ++s)                       // row-major shard -> column-major n x (m+1) R layout
-        for (int64_t r = 0; r < rows; ++r) NNarray[(row_begin + r) + (int64_t)s * n] = res[(size_t)r * p + s];
+    for (int s = 0; s < p; ++s)                       // row-major shard -> column-major R layout (ld = n: the n x (m+1) array)
+        for (int64_t r = 0; r < rows; ++r) NNarray[r + (int64_t)s * ld] = res[(size_t)r * p + s];
     return GPV_OK;
 }
 

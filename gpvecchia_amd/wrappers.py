@@ -474,7 +474,7 @@ def vecchia_estimate(data, locs, X="missing", m=20, covmodel="matern", theta_ini
 
 
 def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, local=False, groups=None, weights=None, return_cov=False,
-                 **specify_args):
+                 nsim=0, seed=0, **specify_args):
     """R/vecchia_wrappers.R:134-161: spatial prediction at new locations from the result of vecchia_estimate, with the
     exact prediction variances of the latent field (vecchia_prediction(..., return_values='meanvar')).  With prediction locations in two or more dimensions vecchia_specify defaults to
     cond.yz='zy' (R/vecchia_specify.R:92-96), whose posterior mean is one triangular solve on the GPU.
@@ -484,11 +484,16 @@ def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, local=Fals
     vecchia_estimate); the trend is added back as below.
     groups (with local=True): one integer label per prediction location; the members of a group are predicted jointly
     (vecchia_krige_groups, with weights and return_cov), and group_ids, group_mean (the trend included), group_var, n_failed
-    and, with return_cov, group_cov join what is returned.  Without groups it is the call it was."""
+    and, with return_cov, group_cov join what is returned.  Without groups it is the call it was.
+    nsim > 0 (with local=True, without groups): nsim spatially coherent conditional draws of the latent field over locs_pred
+    (vecchia_cond_sim, max-min sweep order, `seed`) join what is returned as draws (n_p, nsim), the trend included, with
+    n_failed; mean_pred and var_pred stay those of local kriging."""
     import warnings
     theta_hat = np.asarray(vecchia_est["theta_hat"], dtype=np.float64)                               # :140-143
     if groups is not None and not local:
         raise ValueError("groups are predicted by local kriging: local=True")
+    if nsim and (not local or groups is not None):
+        raise ValueError("conditional draws come from the sequential kriging sweep: local=True, no groups")
     extra = {}
     if local:
         if specify_args.setdefault("cond_yz", "z") != "z":
@@ -528,4 +533,13 @@ def vecchia_pred(vecchia_est, locs_pred, X_pred=None, m=30, device=0, local=Fals
     else:                                                                                            # :152-156
         mu_pred = preds["mu_pred"]
         warnings.warn("X.pred was not specified, so no trend was added back to the predictions")
+    if nsim:                                             # the draws of the latent field, the trend the mean got added to them too
+        cs = A.vecchia_cond_sim(vecchia_est["z"], va, locs_pred, theta_hat[:-1], theta_hat[-1],
+                                covmodel=vecchia_est.get("covmodel", "matern"), nsim=int(nsim), seed=seed,
+                                scale=specify_args.get("scale"), device=device)
+        if X_pred is not None:
+            trend = (np.asarray(X_pred, dtype=np.float64) @ vecchia_est["beta_hat"]).reshape(-1, 1)
+        else:
+            trend = vecchia_est["beta_hat"][0] if vecchia_est["trend"] == "constant" else 0.0
+        extra = dict(draws=cs["draws"] + trend, n_failed=cs["n_failed"])
     return dict(mean_pred=mu_pred, var_pred=preds["var_pred"], **extra)                                           # :159

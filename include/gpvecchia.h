@@ -841,6 +841,59 @@ int gpv_plan_krige_groups(gpv_plan *plan, const char *covType, const double *cov
                           double *cov,                                /* NULL, or the packed lower triangles */
                           int64_t *n_failed);
 
+/* Conditional simulation of a map under a cond.yz='z' model: the sequential kriging sweep (gpv_csim.hip).  The prediction
+ * locations s_0 .. s_{nq-1} are ordered after all observations, in the order they are given (the sweep order).  s_i conditions on
+ * N_i, the m nearest points among {the eligible observations} u {s_j : j < i}, in the arithmetic and with the tie rule of
+ * gpv_find_ordered_nn: its observations J_i through z (the nugget on the diagonal), its earlier prediction locations P_i
+ * through the latent y (no nugget).  With s_i as the last row of S = C(N_i u s_i, N_i u s_i) + diag(tau_J, 0_P, 0) and
+ * u = S^-1 e_last,
+ *     c_ij = -u_j / u_last,   sd[i] = 1 / sqrt(u_last),   y_i = sum_J c_ij z_j + sum_P c_ip y_p + sd[i] eps_i,
+ * that is (I - B) Y = A + D E with B the strictly lower-triangular matrix of the c_ip:
+ *     mean[:, c] = (I - B)^-1 A_c      the predictive mean of the joint model (the draw with eps = 0),
+ *     dev[:, s]  = (I - B)^-1 D eps_s  a deviation field; the draw (c, s) is mean[:, c] + dev[:, s].
+ * With m >= Nlocs + nq - 1 this is the exact GP conditional: mean = K_po (K_oo + tau)^-1 z, and the columns of dev for E = I are
+ * the lower Cholesky factor of K_pp - K_po (K_oo + tau)^-1 K_op in sweep order.  A location with P_i empty is gpv_plan_krige there.
+ *   covType ... ncols, scale, eligible_ord   as gpv_plan_krige
+ *   qlocs, nq, m                   nq x dim column-major, in sweep order; m + 1 <= 64
+ *   NNq                            NULL: the ordered search of the library on [observations ; qlocs] (divided by `scale` when
+ *                                  given, the ineligible observations taken out); else nq x m column-major ids, 1-based, 0 =
+ *                                  none: 1 .. Nlocs an ORDERED observation, Nlocs + 1 + p the sweep row p < own row
+ *   E, lde                         NULL: standard normals of the library's generator (gpv_philox.hpp) from (seed, Nlocs + i, draw
+ *                                  j), j = col0 .. col0 + nsim - 1, apart from those gpv_plan_simulate uses with the same seed;
+ *                                  draw j is always made in the batch [16 floor(j / 16), + 16), so its bits depend on neither
+ *                                  col0, nsim nor the other draws.  Else the caller's nq x nsim standard normals (lde >= nq)
+ *   mean, ldm; dev, ldd; sd        nq x ncols, nq x nsim (column-major), nq.  sd is the conditional standard deviation GIVEN
+ *                                  THE NEIGHBOURS, not the marginal one.  nsim == 0: means only (dev may be NULL)
+ *   n_levels, n_launches           levels of the schedule (level(i) = 0 if P_i is empty, else 1 + max level over P_i) and
+ *                                  launches per sweep: one per level of more than 256 rows, one per maximal run of narrower ones
+ *   n_failed                       locations whose block failed: "a pivot <= 0 or NaN, or u_last <= 0" (a location that
+ *                                  coincides with an earlier prediction location, or with an observation that has no nugget).
+ *                                  Their sd, mean and dev are NaN, and NaN reaches every location that depends on them (they
+ *                                  are not counted)
+ * Device memory grows with nq, unlike gpv_plan_krige: about 12 m + 8 (dim + 16 + 2 CP) bytes per location (coefficients and
+ * lists, the locations, the observation sums, the columns of a sweep and their staging copy; CP = the padded column count, 16
+ * for seeded draws), 0.8 GB for 10^6 locations at m = 30.  A column's bits depend on neither the other columns, the padded
+ * column count nor the chunking of the factor pass.
+ * Needs no evaluation and disturbs none; its buffers live for the call.  Arguments and state are validated before the device
+ * is touched, and a refused call writes nothing.  Statuses as gpv_plan_krige, and GPV_ERR_BAD_ARG: nsim < 0, col0 < 0, ldd < nq
+ * or (with E) lde < nq when nsim > 0, dev NULL with nsim > 0; GPV_ERR_INDEX: an entry of NNq outside [0, Nlocs + own row], or
+ * Nlocs + nq >= 2^31 - 1; GPV_ERR_UNSUPPORTED_M: m + 1 > 64.  nq == 0 is GPV_OK. */
+int gpv_plan_cond_sim(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms,
+                      const double *nuggets, int64_t n_nuggets,
+                      const double *Z_ord, int64_t ldz, int ncols,          /* as gpv_plan_krige; ncols <= 16 */
+                      const double *qlocs, int64_t nq, int m, const int *NNq,
+                      const double *scale, const unsigned char *eligible_ord,
+                      const double *E, int64_t lde, uint64_t seed, int64_t col0, int64_t nsim,
+                      double *mean, int64_t ldm,                            /* nq x ncols */
+                      double *dev, int64_t ldd,                             /* nq x nsim: draw (c, s) = mean_c + dev_s */
+                      double *sd,                                           /* nq: conditional sd given the neighbours */
+                      int64_t *n_levels, int64_t *n_launches, int64_t *n_failed);
+/* The level schedule of gpv_plan_cond_sim on the host, from the lists alone (no device): NN nq x m column-major ids as NNq.
+ * level[nq]; order[nq]: the rows by ascending level, ascending row inside a level; levptr[*n_levels + 1] (room for nq + 1):
+ * where each level starts in order.  GPV_ERR_INDEX for an id outside [0, Nlocs + own row]. */
+int gpv_csim_levels_host(const int32_t *NN, int64_t nq, int m, int64_t Nlocs, int32_t *level, int32_t *order, int64_t *levptr,
+                         int64_t *n_levels);
+
 #ifdef __cplusplus
 }
 #endif
