@@ -9,7 +9,8 @@ from .api import (Comm, EsqeFun, MaternFun, MultiPlan, Plan, ReplicaPlans, U2V, 
                   vecchia_profile_likelihood, vecchia_whiten, vecchia_likelihood_grad_replicates,
                   vecchia_likelihood_fisher_replicates, vecchia_unwhiten, vecchia_simulate, vecchia_likelihood_grad_sgv,
                   vecchia_precision_multiply, vecchia_loo, loo_summary, spatial_blocks, block_cv_summary,
-                  vecchia_block_cv, vecchia_krige, vecchia_krige_groups, vecchia_cond_sim)
+                  vecchia_block_cv, vecchia_krige, vecchia_krige_groups, vecchia_cond_sim,
+                  vecchia_cond_sim_summary)
 
 from .laplace import (calculate_posterior_VL, vecchia_laplace_likelihood,  # noqa: F401,E402
                       vecchia_laplace_likelihood_from_posterior, vecchia_laplace_prediction, vecchia_prediction)

@@ -49,7 +49,7 @@ EXPORTS = [
     "gpv_loo_nscores", "gpv_plan_whiten_t", "gpv_plan_precision", "gpv_plan_loo", "gpv_plan_loo_index", "gpv_loo_index_host",
     "gpv_blockcv_nscores", "gpv_blockcv_max_block", "gpv_plan_set_blocks", "gpv_plan_block_cv", "gpv_blocks_index_host",
     "gpv_find_query_nn", "gpv_krige_max_cols", "gpv_plan_krige", "gpv_krige_groups_max_rows", "gpv_plan_krige_groups",
-    "gpv_plan_cond_sim", "gpv_csim_levels_host",
+    "gpv_plan_cond_sim", "gpv_csim_levels_host", "gpv_plan_cond_sim_summary",
 ]
 
 
@@ -193,6 +193,11 @@ def lib():
     L.gpv_csim_levels_host.argtypes = [ip, i64, C.c_int, i64, ip, ip, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     L.gpv_plan_debug_csim_chunk.argtypes = [vp, i64]             # (developer aids, not in the public header)
     L.gpv_plan_debug_csim_ms.argtypes = [vp, dp]
+    i64p = C.POINTER(C.c_int64)
+    L.gpv_plan_cond_sim_summary.argtypes = [vp, C.c_char_p, dp, C.c_int, dp, i64, dp, C.c_int, dp, i64, C.c_int, ip, dp, u8p,
+                                            C.c_uint64, i64, i64, dp, C.c_int, C.c_int, dp, i64, i64p, i32p, dp,
+                                            dp, dp, dp, dp, dp, dp, dp, dp, dp, dp, i64p, i64p, i64p, i64p]
+    L.gpv_plan_debug_csim_summary_ms.argtypes = [vp, dp]
     L.gpv_nn_max_m.restype = C.c_int
     L.gpv_nn_max_m.argtypes = []
     L.gpv_whichCondOnLatent.argtypes = [ip, i64, C.c_int, i64, ip]

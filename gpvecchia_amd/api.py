@@ -536,6 +536,81 @@ class Plan:
             lib.gpv_plan_debug_csim_chunk(self._h, 0)
         return dict(mean=mean, dev=dev, sd=sd, n_levels=int(nlev.value), n_launches=int(nlaunch.value), n_failed=int(nf.value))
 
+    def cond_sim_summary(self, covmodel, covparms, nuggets_ord, qlocs, m, ndraws, seed=0, col0=0, Z_ord=None, NNq=None, scale=None,
+                         eligible_ord=None, offset=None, link=0, thresholds=None, regions=None, chunk=0):
+        """Summaries of the draws col0 .. col0 + ndraws - 1 of Plan.cond_sim(seed=, nsim=) over the prediction locations qlocs
+        (nq, dim) in sweep order, folded on the device (gpv_plan_cond_sim_summary): the draws never reach the host.  covmodel ..
+        eligible_ord, chunk: as Plan.cond_sim, with ONE data column (Z_ord None: the plan's data).  offset: None or nq values
+        added to the mean; link: 0 identity, 1 exp, 2 logistic; thresholds: up to 8, on the latent scale.  regions: None or
+        (regptr (nreg + 1,), regidx, regw or None), CSR over sweep rows.  The latent draw is y = (mean + offset) + dev.
+        Returns dict(mean, sd, mc_mean, mc_var (nq,), exceed (nthr, nq): NaN where the mean is NaN (sd: as Plan.cond_sim);
+        reg_total, reg_max, reg_min (nreg, ndraws): sum of w g(y), max and min of the latent y over the live members; reg_area
+        (nthr, nreg, ndraws): sum of w [y > thr]; reg_weight, reg_count (nreg,); n_levels, n_launches, n_failed)."""
+        q = np.asfortranarray(np.asarray(qlocs, dtype=np.float64).reshape(-1, self.dim))
+        nq = q.shape[0]
+        cp = np.ascontiguousarray(covparms, dtype=np.float64).reshape(-1)
+        nug = np.ascontiguousarray(np.atleast_1d(np.asarray(nuggets_ord, dtype=np.float64)))
+        Z = None
+        if Z_ord is not None:
+            Z = np.ascontiguousarray(Z_ord, dtype=np.float64)
+            if Z.ndim == 2 and Z.shape[1] == 1:
+                Z = np.ascontiguousarray(Z[:, 0])
+            if Z.ndim != 1 or Z.shape[0] != self.Nlocs:
+                raise ValueError("Z_ord must be one column with one value per ordered location of the plan")
+        nn = None
+        if NNq is not None:
+            nn = np.asfortranarray(NNq, dtype=np.int32)
+            if nn.shape != (nq, int(m)):
+                raise ValueError("NNq must be (nq, m)")
+        sc = None if scale is None else np.ascontiguousarray(scale, dtype=np.float64).reshape(-1)
+        if sc is not None and sc.size != self.dim:
+            raise ValueError("scale must hold one number per coordinate")
+        el = None
+        if eligible_ord is not None:
+            el = np.ascontiguousarray(np.asarray(eligible_ord).astype(bool).reshape(-1), dtype=np.uint8)
+            if el.shape[0] != self.Nlocs:
+                raise ValueError("eligible_ord must hold one flag per ordered location of the plan")
+        off = None
+        if offset is not None:
+            off = np.ascontiguousarray(offset, dtype=np.float64).reshape(-1)
+            if off.size != nq:
+                raise ValueError("offset must hold one value per prediction location")
+        thr = np.ascontiguousarray([] if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+        nthr, ndraws = thr.size, int(ndraws)
+        nreg, rp, ri, rw = 0, None, None, None
+        if regions is not None:
+            rp = np.ascontiguousarray(regions[0], dtype=np.int64).reshape(-1)
+            ri = np.ascontiguousarray(regions[1], dtype=np.int32).reshape(-1)
+            rw = None if len(regions) < 3 or regions[2] is None else np.ascontiguousarray(regions[2], dtype=np.float64).reshape(-1)
+            nreg = rp.size - 1
+            if nreg < 0 or ri.size != rp[-1] or (rw is not None and rw.size != ri.size):
+                raise ValueError("regions must be (regptr (nreg + 1,), regidx (regptr[-1],), regw or None)")
+        nd = max(ndraws, 0)
+        mean, sd, mc_mean, mc_var = np.zeros(nq), np.zeros(nq), np.zeros(nq), np.zeros(nq)
+        exceed = np.zeros((nthr, nq))
+        rtot, rmax, rmin = (np.zeros((nreg, nd), order="F") for _ in range(3))
+        rarea = np.zeros((nreg, nthr, nd), order="F")
+        rwt, rcnt = np.zeros(nreg), np.zeros(nreg, dtype=np.int64)
+        nlev, nlaunch, nf = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        u8, i64p, i32p = C.POINTER(C.c_uint8), C.POINTER(C.c_int64), C.POINTER(C.c_int32)
+        lib = L.lib()
+        L.check(lib.gpv_plan_debug_csim_chunk(self._h, int(chunk)), "gpv_plan_debug_csim_chunk")
+        try:
+            L.check(lib.gpv_plan_cond_sim_summary(
+                self._h, str(covmodel).encode(), L.dptr(cp), cp.size, L.dptr(nug), nug.size, None if Z is None else L.dptr(Z), 1,
+                L.dptr(q), nq, int(m), None if nn is None else L.iptr(nn), None if sc is None else L.dptr(sc),
+                None if el is None else el.ctypes.data_as(u8), int(seed), int(col0), ndraws, None if off is None else L.dptr(off),
+                int(link), nthr, L.dptr(thr) if nthr else None, nreg, None if rp is None else rp.ctypes.data_as(i64p),
+                None if ri is None else ri.ctypes.data_as(i32p), None if rw is None else L.dptr(rw),
+                L.dptr(mean), L.dptr(sd), L.dptr(mc_mean), L.dptr(mc_var), L.dptr(exceed), L.dptr(rtot), L.dptr(rmax), L.dptr(rmin),
+                L.dptr(rarea), L.dptr(rwt), rcnt.ctypes.data_as(i64p), C.byref(nlev), C.byref(nlaunch), C.byref(nf)),
+                "gpv_plan_cond_sim_summary")
+        finally:
+            lib.gpv_plan_debug_csim_chunk(self._h, 0)
+        return dict(mean=mean, sd=sd, mc_mean=mc_mean, mc_var=mc_var, exceed=exceed, reg_total=rtot, reg_max=rmax, reg_min=rmin,
+                    reg_area=np.ascontiguousarray(rarea.transpose(1, 0, 2)), reg_weight=rwt, reg_count=rcnt,
+                    n_levels=int(nlev.value), n_launches=int(nlaunch.value), n_failed=int(nf.value))
+
     def krige_groups(self, covmodel, covparms, nuggets_ord, qlocs, gptr, m, Z_ord=None, weights=None, NNg=None, scale=None,
                      eligible_ord=None, chunk=0, want_cov=False):
         """Grouped local kriging under the cond.yz='z' model of this plan (gpv_plan_krige_groups): group k is the rows
@@ -1994,6 +2069,143 @@ def vecchia_cond_sim(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="
         out["draws"] = mu_p[:, :1] + dev
     else:
         out["dev"] = dev
+    return out
+
+
+def cond_sim_regions(regions, weights, n_p, name="vecchia_cond_sim_summary"):
+    """The regions of vecchia_cond_sim_summary as lists: (members: one int64 index array per region, in the caller's numbering and
+    in the order given; wts: one float64 array per region; region_ids).  regions: None (one region of every location), one
+    integer label per location (-1: in none; the regions are the distinct labels, ascending = region_ids), or a list of index
+    arrays (region_ids = 0, 1, ..).  weights: None (1), one number per location, or for the list form a list of arrays, one
+    number per member.  Raises ValueError for anything else; touches no device."""
+    n_p = int(n_p)
+    wloc = None
+    per_member = False
+    if weights is not None:
+        if isinstance(weights, (list, tuple)) and len(weights) and not np.isscalar(weights[0]):
+            per_member = True
+        else:
+            wloc = np.asarray(weights, dtype=np.float64).reshape(-1)
+            if wloc.size != n_p:
+                raise ValueError(f"{name}: weights must hold one number per prediction location")
+            if not np.all(np.isfinite(wloc)):
+                raise ValueError(f"{name}: weights must be finite")
+    if regions is None:
+        members, ids = [np.arange(n_p, dtype=np.int64)], np.zeros(1, dtype=np.int64)
+    elif isinstance(regions, np.ndarray) or (len(regions) == n_p and all(np.isscalar(r) for r in regions)):
+        lab = np.asarray(regions)
+        if lab.ndim != 1 or lab.size != n_p or lab.dtype.kind not in "iu":
+            raise ValueError(f"{name}: region labels must be one integer per prediction location")
+        lab = lab.astype(np.int64)
+        if (lab < -1).any():
+            raise ValueError(f"{name}: a region label is a number >= 0, or -1 for a location in no region")
+        ids = np.unique(lab[lab >= 0])
+        order = np.argsort(lab, kind="stable")
+        first = np.searchsorted(lab[order], ids, side="left")
+        last = np.searchsorted(lab[order], ids, side="right")
+        members = [order[a:b].astype(np.int64) for a, b in zip(first, last)]
+    else:
+        members = []
+        for r in regions:
+            idx = np.asarray(r)
+            if idx.size and idx.dtype.kind not in "iu":
+                raise ValueError(f"{name}: a region is an array of location indices")
+            idx = idx.astype(np.int64).reshape(-1)
+            if idx.size and (idx.min() < 0 or idx.max() >= n_p):
+                raise ValueError(f"{name}: a region names a location outside range(n_p)")
+            members.append(idx)
+        ids = np.arange(len(members), dtype=np.int64)
+    if per_member:
+        if regions is None or len(weights) != len(members) or isinstance(regions, np.ndarray):
+            raise ValueError(f"{name}: a list of weights goes with a list of regions, one array per region")
+        wts = [np.asarray(w, dtype=np.float64).reshape(-1) for w in weights]
+        if any(w.size != idx.size for w, idx in zip(wts, members)):
+            raise ValueError(f"{name}: weights[r] must hold one number per member of region r")
+        if not all(np.all(np.isfinite(w)) for w in wts):
+            raise ValueError(f"{name}: weights must be finite")
+    else:
+        wts = [np.ones(idx.size) if wloc is None else wloc[idx] for idx in members]
+    return members, wts, ids
+
+
+def cond_sim_regions_csr(members, wts, pos):
+    """CSR over sweep rows of regions given in the caller's numbering: pos[i] is the sweep row of location i; the members of a
+    region are passed in ascending sweep row (a stable sort: equal rows keep their order)."""
+    regptr = np.zeros(len(members) + 1, dtype=np.int64)
+    idx, w = [], []
+    for r, (mem, wt) in enumerate(zip(members, wts)):
+        rows = pos[mem]
+        k = np.argsort(rows, kind="stable")
+        idx.append(rows[k])
+        w.append(wt[k])
+        regptr[r + 1] = regptr[r] + mem.size
+    regidx = np.concatenate(idx).astype(np.int32) if idx else np.zeros(0, dtype=np.int32)
+    regw = np.concatenate(w).astype(np.float64) if w else np.zeros(0)
+    return regptr, regidx, regw
+
+
+def vecchia_cond_sim_summary(z, vecchia_approx, locs_pred, covparms, nuggets, covmodel="matern", m=None, nsim=100, seed=0, col0=0,
+                             order="maxmin", mean=None, mean_pred=None, scale=None, link=None, thresholds=None, regions=None,
+                             weights=None, device=0):
+    """Monte-Carlo summaries of the conditional draws of vecchia_cond_sim(nsim=, seed=) over a map, folded on the GPU
+    (Plan.cond_sim_summary): totals, areas above thresholds and extremes of regions per draw, and moments and exceedance
+    probabilities per location, without the draws ever reaching the host; memory does not grow with nsim.
+    z (one column), vecchia_approx, locs_pred, covparms, nuggets, covmodel, m, order, mean, mean_pred, scale and the missing
+    values: as vecchia_cond_sim; the draws summarised are its draws col0 .. col0 + nsim - 1 under `seed`, nsim >= 2.
+    link: None / 'identity' / 'exp' / 'logistic', the g of vecchia_posterior_summary; thresholds: up to 8 numbers on the LATENT
+    scale, mean_pred included.  regions: None (one region of every location), an integer label per location (-1: in none;
+    returned in ascending label order), or a list of index arrays (overlap allowed).  weights: None, or one number per location
+    (cell areas; any sign), or with a list of regions a list of arrays.  Everything is in the CALLER's order.
+    Returns dict(mean, mc_mean, mc_var (n_p,), exceed (nthr, n_p), sd_cond (n_p,); region_ids, region_total = sum w g(y),
+    region_mean = total / weight, region_max, region_min (g of the extremes) (nreg, nsim); region_area = sum w [y > thr]
+    (nthr, nreg, nsim); region_weight, region_count (nreg,): over the members whose mean is not NaN; order, n_levels,
+    n_failed).  A failed location and those that depend on it are NaN per location and take no part in a region."""
+    from .lincomb import _LINKS
+    va = vecchia_approx
+    name = "vecchia_cond_sim_summary"
+    if link not in _LINKS:
+        raise ValueError(f"{name}: link must be None, 'identity', 'exp' or 'logistic'")
+    code, nsim, col0 = _LINKS[link], int(nsim), int(col0)
+    if nsim < 2 or col0 < 0:
+        raise ValueError(f"{name}: nsim must be at least 2 and col0 not negative")
+    thr = np.asarray([] if thresholds is None else thresholds, dtype=np.float64).reshape(-1)
+    if thr.size > 8 or np.isnan(thr).any():
+        raise ValueError(f"{name}: at most 8 thresholds, none of them NaN")
+    if np.ndim(z) != 1 and not (np.ndim(z) == 2 and np.shape(z)[1] == 1):
+        raise ValueError(f"{name}: z must be one column (the draws of several columns: vecchia_cond_sim)")
+    Z, vector, eligible, nug, lp, m, ordz = _krige_inputs(name, z, va, locs_pred, nuggets, covmodel, m, mean, "y")
+    n_p = lp.shape[0]
+    members, wts, ids = cond_sim_regions(regions, weights, n_p, name)
+    if isinstance(order, str):
+        if order not in ("maxmin", "given"):
+            raise ValueError(f"{name}: order must be 'maxmin', 'given' or a permutation")
+        o = (S.order_maxmin_exact(lp) - 1) if (order == "maxmin" and n_p > 1) else np.arange(n_p, dtype=np.int64)
+    else:
+        o = np.asarray(order, dtype=np.int64).reshape(-1)
+        if o.size != n_p or not np.array_equal(np.sort(o), np.arange(n_p)):
+            raise ValueError(f"{name}: order must be a permutation of range(n_p)")
+    pos = np.empty(n_p, dtype=np.int64)
+    pos[o] = np.arange(n_p)
+    off = None
+    if mean_pred is not None:
+        off = np.broadcast_to(np.asarray(mean_pred, dtype=np.float64).reshape(-1), (n_p,))[o]
+    plan = _plan_for(va, device)
+    r = plan.cond_sim_summary(covmodel, covparms, nug if nug.size == 1 else nug[ordz], lp[o], int(m), nsim, seed=seed, col0=col0,
+                              Z_ord=Z[ordz, 0], scale=scale, eligible_ord=None if eligible is None else eligible[ordz], offset=off,
+                              link=code, thresholds=thr, regions=cond_sim_regions_csr(members, wts, pos))
+    out = {}
+    for k_out, k_in in (("mean", "mean"), ("mc_mean", "mc_mean"), ("mc_var", "mc_var"), ("sd_cond", "sd")):
+        a = np.empty(n_p)
+        a[o] = r[k_in]
+        out[k_out] = a
+    ex = np.empty((thr.size, n_p))
+    ex[:, o] = r["exceed"]
+    g = [lambda y: y, np.exp, lambda y: 1.0 / (1.0 + np.exp(-y))][code]
+    with np.errstate(divide="ignore", invalid="ignore"):
+        rmean = r["reg_total"] / r["reg_weight"][:, None]
+    out.update(exceed=ex, region_ids=ids, region_total=r["reg_total"], region_mean=rmean, region_max=g(r["reg_max"]),
+               region_min=g(r["reg_min"]), region_area=r["reg_area"], region_weight=r["reg_weight"], region_count=r["reg_count"],
+               order=o, n_levels=r["n_levels"], n_failed=r["n_failed"])
     return out
 
 

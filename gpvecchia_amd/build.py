@@ -90,7 +90,7 @@ def units(plist, extra_flags=()):
     u.append(("gpv_aux_kernels.hip", "aux.o", list(x), kern))
     u.append(("gpv_api.hip", "api.o", list(x), internal + [pub, "gpv_laplace.h", "gpv_generic.h", "gpv_posterior_ext.h", "gpv_philox.hpp",
                                                      "gpv_grad.h", "gpv_whiten.h", "gpv_unwhiten.h", "gpv_loo.h", "gpv_blockcv.h",
-                                                     "gpv_krige.h", "gpv_krige_groups.h", "gpv_csim.h", "gpv_selinv.h", "gpv_grad_sgv.h", "gpv_hip_raii.hpp"]))
+                                                     "gpv_krige.h", "gpv_krige_groups.h", "gpv_csim.h", "gpv_csim_summary.h", "gpv_selinv.h", "gpv_grad_sgv.h", "gpv_hip_raii.hpp"]))
     u.append(("gpv_posterior.hip", "posterior.o", list(x), internal + ["gpv_posterior_ext.h"]))
     u.append(("gpv_lincomb.hip", "lincomb.o", list(x), internal + ["gpv_posterior_ext.h", "gpv_philox.hpp"]))
     u.append(("gpv_laplace.hip", "laplace.o", [], ["gpv_laplace.h"]))            # no extra_flags: nothing in it is tuned
@@ -108,6 +108,7 @@ def units(plist, extra_flags=()):
     u.append(("gpv_krige_groups.hip", "krige_groups.o", list(x), internal + ["gpv_krige.h", "gpv_krige_groups.h", "gpv_krige_dev.hpp"]))
     u.append(("gpv_krige.hip", "krige.o", list(x), internal + ["gpv_krige.h", "gpv_krige_dev.hpp"]))
     u.append(("gpv_csim.hip", "csim.o", list(x), internal + ["gpv_krige.h", "gpv_csim.h", "gpv_krige_dev.hpp", "gpv_philox.hpp"]))
+    u.append(("gpv_csim_summary.hip", "csim_summary.o", list(x), ["gpv_csim_summary.h"]))
     u.append(("gpv_selinv.hip", "selinv.o", list(x), ["gpv_selinv.h"]))
     u.append(("gpv_order.cpp", "order.o", ["-x", "c++"], [pub]))
     u.append(("gpv_nn.hip", "nn.o", ["-ffp-contract=off"], internal + [pub, "gpv_krige.h"]))

@@ -16,6 +16,7 @@
 #include "gpv_krige.h"
 #include "gpv_krige_groups.h"
 #include "gpv_csim.h"
+#include "gpv_csim_summary.h"
 #include "gpv_selinv.h"
 #include "gpv_grad_sgv.h"
 #include "gpv_hip_raii.hpp"
@@ -515,6 +516,9 @@ struct gpv_plan {
     // of all sweeps and of the last sweep.  Its buffers live for the call.
     int64_t cs_chunk = 0;
     double cs_search_ms = 0.0, cs_factor_ms = 0.0, cs_sweep_ms = 0.0, cs_last_sweep_ms = 0.0;
+    // gpv_plan_cond_sim_summary (gpv_csim_summary.hip): device time of the latest call's folds, all batches and the last one
+    // (gpv_plan_debug_csim_summary_ms); the other times of such a call are those above
+    double cs_fold_ms = 0.0, cs_last_fold_ms = 0.0, cs_copy_ms = 0.0, cs_last_copy_ms = 0.0;
     // d_L and the nuggets on the device (d_nuggets / nug_scalar) belong to evaluation L_of_eval of the plan (evaluations are
     // counted from 1; 0: to none).  Set at the end of an evaluation that materialised U, cleared before anything of the two is
     // rewritten: an evaluation that starts, a Vecchia-Laplace step that writes its pseudo-nuggets, a rebuilt posterior structure.
@@ -3611,6 +3615,154 @@ static int csim_search(gpv_plan *pl, const double *qlocs, int64_t nq, int m, con
     return GPV_OK;
 }
 
+// the caller's lists (or none): GPV_ERR_INDEX for an id outside [0, Nlocs + own row], and for more rows than 32-bit ids name
+static int csim_check_lists(const int *NNq, int64_t nq, int m, int64_t n)
+{
+    if (n + nq >= ((int64_t)1 << 31) - 1) return GPV_ERR_INDEX;
+    if (NNq)
+        for (int64_t i = 0; i < nq; ++i)
+            for (int s = 0; s < m; ++s) {
+                const int64_t id = NNq[i + (int64_t)s * nq];
+                if (id < 0 || id > n + i) return GPV_ERR_INDEX;
+            }
+    return GPV_OK;
+}
+
+// The operator (I - B)^-1 of one call, shared by gpv_plan_cond_sim and gpv_plan_cond_sim_summary: open() takes a validated call
+// from the plan's resident records through the search, the level schedule, the uploads and the chunked factor pass (sd goes to
+// the caller there); mean_sweep() leaves the means in d_X at cpm columns; draw_sweep() leaves one batch of 16 seeded deviation
+// fields in d_X; sweep() is the level-scheduled pass over whatever d_X holds.  Its buffers live as long as the object.
+namespace {
+struct CsimOp {
+    gpv_plan *pl = nullptr;
+    hipStream_t st = nullptr;
+    int64_t nq = 0, n = 0;
+    int m = 0, ncols = 1, cpm = 1, nlev = 0;
+    KrigeCall kc;
+    CsimFactorArgs f{};
+    CsimSweepArgs w{};
+    std::vector<int64_t> levptr;
+    std::vector<CsimLaunch> launches;
+    DevBuf<double> d_q, d_coef, d_sd, d_a, d_X, d_io;
+    DevBuf<int32_t> d_nn, d_order, d_levptr;
+    DevBuf<unsigned> d_nfail;
+    Event ev[2];
+
+    // cpx: the columns of d_X at most; io_cols: the columns of the staging copy d_io (0: none)
+    int open(gpv_plan *plan, const double *covparms, int ncovparms, const double *nuggets, int64_t n_nuggets, const double *Z_ord,
+             int64_t ldz, int ncols_, const double *qlocs, int64_t nq_, int m_, const int *NNq, const double *scale,
+             const unsigned char *eligible_ord, int cpx, int io_cols, double *sd)
+    {
+        pl = plan; nq = nq_; m = m_; ncols = ncols_; n = pl->Nlocs;
+        if (const int rc = enter(pl)) return rc;
+        st = pl->stream;
+        const int dim = pl->dim;
+        if (const int rc = krige_resident(pl, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, m, kc, f.k, st)) return rc;
+        pl->cs_search_ms = pl->cs_factor_ms = pl->cs_sweep_ms = pl->cs_last_sweep_ms = 0.0;
+        // the lists, row-major, and the schedule
+        std::vector<int32_t> hnn;
+        if (NNq) {
+            hnn.resize((size_t)nq * m);
+            for (int s = 0; s < m; ++s)
+                for (int64_t i = 0; i < nq; ++i) hnn[(size_t)i * m + s] = NNq[i + (int64_t)s * nq];
+        } else {
+            const auto t0 = std::chrono::steady_clock::now();
+            if (const int rc = csim_search(pl, qlocs, nq, m, scale, eligible_ord, hnn, st)) return rc;
+            pl->cs_search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        }
+        std::vector<int32_t> level, order;
+        if (csim_levels_core(hnn.data(), m, 1, nq, m, n, level, order, levptr)) return GPV_ERR_STATE;   // (given lists were checked by the entry)
+        nlev = (int)levptr.size() - 1;
+        std::vector<int32_t> levptr32(levptr.begin(), levptr.end());
+        for (int l = 0; l < nlev; ++l) {
+            const bool narrow = levptr[(size_t)l + 1] - levptr[(size_t)l] <= kCsimNarrow;
+            if (narrow && !launches.empty() && launches.back().narrow) launches.back().lev1 = l + 1;
+            else launches.push_back(CsimLaunch{l, l + 1, narrow});
+        }
+        // what stays resident for the call
+        cpm = whiten_cp(ncols);
+        {
+            std::vector<double> hq((size_t)nq * dim);
+            for (int t = 0; t < dim; ++t)
+                for (int64_t i = 0; i < nq; ++i) hq[(size_t)i * dim + t] = qlocs[i + (int64_t)t * nq];
+            GPV_BUF(d_q, upload(hq.data(), hq.size()));
+        }
+        GPV_BUF(d_nn, upload(hnn.data(), hnn.size()));
+        GPV_BUF(d_order, upload(order.data(), order.size()));
+        GPV_BUF(d_levptr, upload(levptr32.data(), levptr32.size()));
+        GPV_BUF(d_coef, resize((size_t)nq * m));
+        GPV_BUF(d_sd, resize((size_t)nq));
+        GPV_BUF(d_a, resize((size_t)nq * ncols));
+        GPV_BUF(d_X, resize((size_t)nq * cpx));
+        if (io_cols > 0) GPV_BUF(d_io, resize((size_t)nq * io_cols));
+        GPV_BUF(d_nfail, resize(2));
+        if (GPV_HIP_FAILED(hipMemsetAsync(d_nfail, 0, sizeof(unsigned), st))) return drain_fail(st, GPV_ERR_HIP);
+        for (auto &e : ev) GPV_HIP(hipEventCreate(e.put()));
+        // ---- the factor pass
+        f.k.nnq = d_nn; f.k.nfail = d_nfail;
+        f.qall = d_q; f.nrows = nq; f.Nlocs = n; f.coef = d_coef; f.sd = d_sd; f.a = d_a;
+        const int64_t cap = std::min<int64_t>(pl->cs_chunk > 0 ? pl->cs_chunk : kCsimChunk, nq);
+        if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return drain_fail(st, GPV_ERR_HIP);
+        for (int64_t c0 = 0; c0 < nq; c0 += cap) {
+            f.row0 = c0;
+            f.k.nq = std::min(cap, nq - c0);
+            if (GPV_HIP_FAILED(launch_csim_factor(f, krige_grid(f.k.nq, pl->cus), st))) return drain_fail(st, GPV_ERR_HIP);
+        }
+        if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipMemcpyAsync(sd, d_sd, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
+        {
+            float t = 0.f;
+            if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) pl->cs_factor_ms = (double)t;
+        }
+        // ---- the sweeps: d_X holds the right-hand sides, then the solution
+        w.coef = d_coef; w.nn = d_nn; w.X = d_X; w.order = d_order; w.levptr = d_levptr; w.Nlocs = n; w.m = m;
+        return GPV_OK;
+    }
+    // the level-scheduled pass over d_X at cp columns, between the call's event pair; the caller drains the stream on failure
+    int sweep(int cp)
+    {
+        if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return GPV_ERR_HIP;
+        for (const CsimLaunch &u : launches)
+            if (GPV_HIP_FAILED(u.narrow ? launch_csim_narrow(w, cp, u.lev0, u.lev1, st)
+                                        : launch_csim_wide(w, cp, levptr[(size_t)u.lev0], levptr[(size_t)u.lev1], st)))
+                return GPV_ERR_HIP;
+        if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return GPV_ERR_HIP;
+        return GPV_OK;
+    }
+    // after the stream was waited for: the device time of the latest sweep()
+    void sweep_time()
+    {
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) {
+            pl->cs_sweep_ms += (double)t;
+            pl->cs_last_sweep_ms = (double)t;
+        }
+    }
+    // the means: (I - B)^-1 A, left in d_X[nq][cpm]
+    int mean_sweep()
+    {
+        if (GPV_HIP_FAILED(launch_csim_pack(d_a, nq, nullptr, nq, ncols, cpm, d_X, st))) return GPV_ERR_HIP;
+        return sweep(cpm);
+    }
+    // the deviation fields of the draws base .. base + 15 of the library's generator, left in d_X[nq][16].  Draw j is always made
+    // in the batch [16 floor(j / 16), + 16) at CP = 16: its bits depend on (seed, j) alone; the normals of sweep row i are those of
+    // the id Nlocs + i, apart from what gpv_plan_simulate draws for the observations
+    int draw_sweep(uint64_t seed, int64_t base)
+    {
+        if (GPV_HIP_FAILED(launch_csim_normals(d_X, d_sd, nq, seed, n, base, st))) return GPV_ERR_HIP;
+        return sweep(kCsimMaxCols);
+    }
+    int failed(int64_t *n_failed)
+    {
+        unsigned nbad = 0;
+        GPV_HIP(hipMemcpy(&nbad, d_nfail, sizeof(nbad), hipMemcpyDeviceToHost));
+        *n_failed = (int64_t)nbad;
+        return GPV_OK;
+    }
+};
+}  // namespace
+
 // The contract of gpv_plan_krige: buffers that live for the call, no evaluation needed and none disturbed, every refusal before
 // the device is touched and before anything is written.  The factor pass may be chunked over the rows (the locations stay
 // resident: a row reads those of its list); the sweeps run on what it left.
@@ -3625,150 +3777,223 @@ int gpv_plan_cond_sim(gpv_plan *pl, const char *covType, const double *covparms,
     if (nsim < 0 || col0 < 0 || col0 > INT64_MAX - nsim) return GPV_ERR_BAD_ARG;
     if (nq > 0 && (!qlocs || !mean || !sd || (nsim > 0 && !dev))) return GPV_ERR_BAD_ARG;
     if (ldm < nq || (nsim > 0 && (ldd < nq || (E && lde < nq)))) return GPV_ERR_BAD_ARG;
-    KrigeCall kc;
-    if (const int rc = krige_check_args(pl, covType, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, scale, kc.cs)) return rc;
+    CsimOp op;
+    if (const int rc = krige_check_args(pl, covType, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, scale, op.kc.cs)) return rc;
     if (m + 1 > kKrigeMaxP) return GPV_ERR_UNSUPPORTED_M;
     if (const int rc = krige_check_state(pl, !Z_ord, nullptr, 0)) return rc;
-    const int64_t n = pl->Nlocs;
-    if (n + nq >= ((int64_t)1 << 31) - 1) return GPV_ERR_INDEX;
-    if (NNq)
-        for (int64_t i = 0; i < nq; ++i)
-            for (int s = 0; s < m; ++s) {
-                const int64_t id = NNq[i + (int64_t)s * nq];
-                if (id < 0 || id > n + i) return GPV_ERR_INDEX;
-            }
+    if (const int rc = csim_check_lists(NNq, nq, m, pl->Nlocs)) return rc;
     *n_failed = 0;
     *n_levels = 0;
     *n_launches = 0;
     if (nq == 0) return GPV_OK;
 
-    if (const int rc = enter(pl)) return rc;
-    hipStream_t st = pl->stream;
-    const int dim = pl->dim;
-    CsimFactorArgs f{};
-    if (const int rc = krige_resident(pl, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, m, kc, f.k, st)) return rc;
-    pl->cs_search_ms = pl->cs_factor_ms = pl->cs_sweep_ms = pl->cs_last_sweep_ms = 0.0;
-    // the lists, row-major, and the schedule
-    std::vector<int32_t> hnn;
-    if (NNq) {
-        hnn.resize((size_t)nq * m);
-        for (int s = 0; s < m; ++s)
-            for (int64_t i = 0; i < nq; ++i) hnn[(size_t)i * m + s] = NNq[i + (int64_t)s * nq];
-    } else {
-        const auto t0 = std::chrono::steady_clock::now();
-        if (const int rc = csim_search(pl, qlocs, nq, m, scale, eligible_ord, hnn, st)) return rc;
-        pl->cs_search_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    }
-    std::vector<int32_t> level, order;
-    std::vector<int64_t> levptr;
-    if (csim_levels_core(hnn.data(), m, 1, nq, m, n, level, order, levptr)) return GPV_ERR_STATE;   // (given lists were checked above)
-    const int nlev = (int)levptr.size() - 1;
-    std::vector<int32_t> levptr32(levptr.begin(), levptr.end());
-    std::vector<CsimLaunch> launches;
-    for (int l = 0; l < nlev; ++l) {
-        const bool narrow = levptr[(size_t)l + 1] - levptr[(size_t)l] <= kCsimNarrow;
-        if (narrow && !launches.empty() && launches.back().narrow) launches.back().lev1 = l + 1;
-        else launches.push_back(CsimLaunch{l, l + 1, narrow});
-    }
-    // what stays resident for the call
     const int cpm = whiten_cp(ncols);
     const int cpx = nsim > 0 ? (E ? std::max(cpm, whiten_cp((int)std::min<int64_t>(nsim, NB))) : NB) : cpm;
-    DevBuf<double> d_q, d_coef, d_sd, d_a, d_X, d_io;
-    DevBuf<int32_t> d_nn, d_order, d_levptr;
-    DevBuf<unsigned> d_nfail;
-    {
-        std::vector<double> hq((size_t)nq * dim);
-        for (int t = 0; t < dim; ++t)
-            for (int64_t i = 0; i < nq; ++i) hq[(size_t)i * dim + t] = qlocs[i + (int64_t)t * nq];
-        GPV_BUF(d_q, upload(hq.data(), hq.size()));
-    }
-    GPV_BUF(d_nn, upload(hnn.data(), hnn.size()));
-    GPV_BUF(d_order, upload(order.data(), order.size()));
-    GPV_BUF(d_levptr, upload(levptr32.data(), levptr32.size()));
-    GPV_BUF(d_coef, resize((size_t)nq * m));
-    GPV_BUF(d_sd, resize((size_t)nq));
-    GPV_BUF(d_a, resize((size_t)nq * ncols));
-    GPV_BUF(d_X, resize((size_t)nq * cpx));
-    GPV_BUF(d_io, resize((size_t)nq * std::max(cpx, ncols)));
-    GPV_BUF(d_nfail, resize(2));
-    if (GPV_HIP_FAILED(hipMemsetAsync(d_nfail, 0, sizeof(unsigned), st))) return drain_fail(st, GPV_ERR_HIP);
-    Event ev[2];
-    for (auto &e : ev) GPV_HIP(hipEventCreate(e.put()));
-    // ---- the factor pass
-    f.k.nnq = d_nn; f.k.nfail = d_nfail;
-    f.qall = d_q; f.nrows = nq; f.Nlocs = n; f.coef = d_coef; f.sd = d_sd; f.a = d_a;
-    const int64_t cap = std::min<int64_t>(pl->cs_chunk > 0 ? pl->cs_chunk : kCsimChunk, nq);
-    if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return drain_fail(st, GPV_ERR_HIP);
-    for (int64_t c0 = 0; c0 < nq; c0 += cap) {
-        f.row0 = c0;
-        f.k.nq = std::min(cap, nq - c0);
-        if (GPV_HIP_FAILED(launch_csim_factor(f, krige_grid(f.k.nq, pl->cus), st))) return drain_fail(st, GPV_ERR_HIP);
-    }
-    if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return drain_fail(st, GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipMemcpyAsync(sd, d_sd, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
-    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
-    {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) pl->cs_factor_ms = (double)t;
-    }
-    // ---- the sweeps: d_X holds the right-hand sides, then the solution
-    CsimSweepArgs w{};
-    w.coef = d_coef; w.nn = d_nn; w.X = d_X; w.order = d_order; w.levptr = d_levptr; w.Nlocs = n; w.m = m;
-    const auto sweep = [&](int cp) -> int {
-        if (GPV_HIP_FAILED(hipEventRecord(ev[0], st))) return GPV_ERR_HIP;
-        for (const CsimLaunch &u : launches)
-            if (GPV_HIP_FAILED(u.narrow ? launch_csim_narrow(w, cp, u.lev0, u.lev1, st)
-                                        : launch_csim_wide(w, cp, levptr[(size_t)u.lev0], levptr[(size_t)u.lev1], st)))
-                return GPV_ERR_HIP;
-        if (GPV_HIP_FAILED(hipEventRecord(ev[1], st))) return GPV_ERR_HIP;
-        return GPV_OK;
-    };
-    const auto sweep_time = [&] {
-        float t = 0.f;
-        if (hipEventElapsedTime(&t, ev[0], ev[1]) == hipSuccess) {
-            pl->cs_sweep_ms += (double)t;
-            pl->cs_last_sweep_ms = (double)t;
-        }
-    };
-    // the means: (I - B)^-1 A
-    if (GPV_HIP_FAILED(launch_csim_pack(d_a, nq, nullptr, nq, ncols, cpm, d_X, st))) return drain_fail(st, GPV_ERR_HIP);
-    if (sweep(cpm)) return drain_fail(st, GPV_ERR_HIP);
+    if (const int rc = op.open(pl, covparms, ncovparms, nuggets, n_nuggets, Z_ord, ldz, ncols, qlocs, nq, m, NNq, scale, eligible_ord, cpx,
+                               std::max(cpx, ncols), sd))
+        return rc;
+    hipStream_t st = op.st;
+    double *const d_X = op.d_X, *const d_io = op.d_io;
+    // the means
+    if (op.mean_sweep()) return drain_fail(st, GPV_ERR_HIP);
     if (GPV_HIP_FAILED(launch_csim_unpack(d_X, nq, ncols, cpm, d_io, st))) return drain_fail(st, GPV_ERR_HIP);
     if (cols_to_host(mean, ldm, d_io, nq, ncols, st)) return drain_fail(st, GPV_ERR_HIP);
     if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
-    sweep_time();
+    op.sweep_time();
     // the deviation fields: (I - B)^-1 D E, sixteen columns at a time
     if (nsim > 0 && E) {
         for (int64_t b0 = 0; b0 < nsim; b0 += NB) {
             const int nb = (int)std::min<int64_t>(NB, nsim - b0), cp = whiten_cp(nb);
             if (cols_to_device(d_io, E + b0 * lde, lde, nq, nb, st)) return drain_fail(st, GPV_ERR_HIP);
-            if (GPV_HIP_FAILED(launch_csim_pack(d_io, nq, d_sd, nq, nb, cp, d_X, st))) return drain_fail(st, GPV_ERR_HIP);
-            if (sweep(cp)) return drain_fail(st, GPV_ERR_HIP);
+            if (GPV_HIP_FAILED(launch_csim_pack(d_io, nq, op.d_sd, nq, nb, cp, d_X, st))) return drain_fail(st, GPV_ERR_HIP);
+            if (op.sweep(cp)) return drain_fail(st, GPV_ERR_HIP);
             if (GPV_HIP_FAILED(launch_csim_unpack(d_X, nq, nb, cp, d_io, st))) return drain_fail(st, GPV_ERR_HIP);
             if (cols_to_host(dev + b0 * ldd, ldd, d_io, nq, nb, st)) return drain_fail(st, GPV_ERR_HIP);
             if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
-            sweep_time();
+            op.sweep_time();
         }
     } else if (nsim > 0) {
-        // draw j is always made in the batch [16 floor(j / 16), + 16) at CP = 16: its bits depend on (seed, j) alone; the normals
-        // of sweep row i are those of the id Nlocs + i, apart from what gpv_plan_simulate draws for the observations
         const int64_t end = col0 + nsim;
         for (int64_t b = col0 / NB; b * NB < end; ++b) {
             const int64_t base = b * NB;
-            if (GPV_HIP_FAILED(launch_csim_normals(d_X, d_sd, nq, seed, n, base, st))) return drain_fail(st, GPV_ERR_HIP);
-            if (sweep(NB)) return drain_fail(st, GPV_ERR_HIP);
+            if (op.draw_sweep(seed, base)) return drain_fail(st, GPV_ERR_HIP);
             if (GPV_HIP_FAILED(launch_csim_unpack(d_X, nq, NB, NB, d_io, st))) return drain_fail(st, GPV_ERR_HIP);
             const int64_t j0 = std::max(base, col0), j1 = std::min(base + NB, end);
             if (cols_to_host(dev + (j0 - col0) * ldd, ldd, d_io + (size_t)(j0 - base) * nq, nq, j1 - j0, st)) return drain_fail(st, GPV_ERR_HIP);
             if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
-            sweep_time();
+            op.sweep_time();
         }
     }
-    unsigned nbad = 0;
-    GPV_HIP(hipMemcpy(&nbad, d_nfail, sizeof(nbad), hipMemcpyDeviceToHost));
-    *n_failed = (int64_t)nbad;
-    *n_levels = nlev;
-    *n_launches = (int64_t)launches.size();
+    if (const int rc = op.failed(n_failed)) return rc;
+    *n_levels = op.nlev;
+    *n_launches = (int64_t)op.launches.size();
+    return GPV_OK;
+}
+
+// ---- summaries of conditional draws, folded on the device (gpv_csim_summary.hip) --------------------------------------------
+// The operator of gpv_plan_cond_sim, built once; each batch of 16 seeded draws is swept as there and folded while it is in
+// d_X: no unpacking and no copy of nq numbers per batch.  What leaves the device: per batch the region block of the requested
+// columns, at the end the per-location moments.
+int gpv_plan_cond_sim_summary(gpv_plan *pl, const char *covType, const double *covparms, int ncovparms, const double *nuggets,
+                              int64_t n_nuggets, const double *Z_ord, int ncols, const double *qlocs, int64_t nq, int m, const int *NNq,
+                              const double *scale, const unsigned char *eligible_ord, uint64_t seed, int64_t col0, int64_t ndraws,
+                              const double *offset, int link, int nthr, const double *thr, int64_t nreg, const int64_t *regptr,
+                              const int32_t *regidx, const double *regw, double *mean, double *sd, double *mc_mean, double *mc_var,
+                              double *exceed, double *reg_total, double *reg_max, double *reg_min, double *reg_area, double *reg_weight,
+                              int64_t *reg_count, int64_t *n_levels, int64_t *n_launches, int64_t *n_failed)
+{
+    constexpr int NB = kCsimMaxCols;
+    static_assert(kCsumCols == kCsimMaxCols, "the folds read the sweep's rows");
+    if (!pl || !covType || !covparms || !nuggets || !n_levels || !n_launches || !n_failed || nq < 0 || m < 1) return GPV_ERR_BAD_ARG;
+    if (ncols != 1 || ndraws < 2 || col0 < 0 || col0 > INT64_MAX - ndraws) return GPV_ERR_BAD_ARG;
+    if (link < 0 || link > 2 || nthr < 0 || nthr > kCsumMaxThr || (nthr > 0 && !thr)) return GPV_ERR_BAD_ARG;
+    if (nq > 0 && (!qlocs || !mean || !sd || !mc_mean || !mc_var || (nthr > 0 && !exceed))) return GPV_ERR_BAD_ARG;
+    if (nreg < 0 || nreg >= ((int64_t)1 << 31) - 1) return GPV_ERR_BAD_ARG;
+    if (nreg > 0 && (!regptr || !reg_total || !reg_max || !reg_min || (nthr > 0 && !reg_area) || !reg_weight || !reg_count)) return GPV_ERR_BAD_ARG;
+    int64_t nnz = 0;
+    if (nreg > 0) {
+        if (regptr[0] != 0) return GPV_ERR_BAD_ARG;
+        for (int64_t r = 0; r < nreg; ++r)
+            if (regptr[r + 1] < regptr[r]) return GPV_ERR_BAD_ARG;
+        nnz = regptr[nreg];
+        if (nnz > 0 && !regidx) return GPV_ERR_BAD_ARG;
+        if (regw)
+            for (int64_t e = 0; e < nnz; ++e)
+                if (!std::isfinite(regw[e])) return GPV_ERR_BAD_ARG;
+    }
+    CsimOp op;
+    if (const int rc = krige_check_args(pl, covType, covparms, ncovparms, nuggets, n_nuggets, Z_ord, pl->Nlocs, ncols, scale, op.kc.cs)) return rc;
+    if (m + 1 > kKrigeMaxP) return GPV_ERR_UNSUPPORTED_M;
+    if (const int rc = krige_check_state(pl, !Z_ord, nullptr, 0)) return rc;
+    if (const int rc = csim_check_lists(NNq, nq, m, pl->Nlocs)) return rc;
+    for (int64_t e = 0; e < nnz; ++e)
+        if (regidx[e] < 0 || regidx[e] >= nq) return GPV_ERR_INDEX;
+    // the chunks of the regions' lists and the regions whose chunks a second launch joins (none, or several)
+    std::vector<CsumChunk> chunks;
+    std::vector<CsumJoin> joins;
+    int64_t nslots = 0;
+    for (int64_t r = 0; r < nreg; ++r) {
+        const int64_t b = regptr[r], len = regptr[r + 1] - b, nc = (len + kCsumChunkRows - 1) / kCsumChunkRows;
+        if (nc > INT32_MAX) return GPV_ERR_INDEX;
+        if (nc != 1) joins.push_back(CsumJoin{nslots, (int32_t)nc, (int32_t)r});
+        for (int64_t k = 0; k < nc; ++k)
+            chunks.push_back(CsumChunk{b + k * kCsumChunkRows, nc == 1 ? -1 : nslots + k,
+                                       (int32_t)std::min<int64_t>(kCsumChunkRows, len - k * kCsumChunkRows), (int32_t)r});
+        if (nc != 1) nslots += nc;
+    }
+    *n_failed = 0;
+    *n_levels = 0;
+    *n_launches = 0;
+    pl->cs_fold_ms = pl->cs_last_fold_ms = pl->cs_copy_ms = pl->cs_last_copy_ms = 0.0;
+    const int64_t end = col0 + ndraws;
+    const double nan = (double)NAN;
+    if (nq == 0) {                                      // every region is empty
+        std::fill_n(reg_total, (size_t)(nreg * ndraws), 0.0);
+        std::fill_n(reg_max, (size_t)(nreg * ndraws), nan);
+        std::fill_n(reg_min, (size_t)(nreg * ndraws), nan);
+        if (nthr > 0) std::fill_n(reg_area, (size_t)(nreg * ndraws * nthr), 0.0);
+        std::fill_n(reg_weight, (size_t)nreg, 0.0);
+        std::fill_n(reg_count, (size_t)nreg, (int64_t)0);
+        return GPV_OK;
+    }
+
+    if (const int rc = op.open(pl, covparms, ncovparms, nuggets, n_nuggets, Z_ord, pl->Nlocs, ncols, qlocs, nq, m, NNq, scale, eligible_ord, NB,
+                               0, sd))
+        return rc;
+    hipStream_t st = op.st;
+    const int V = 3 + nthr;
+    DevBuf<double> d_mu, d_S, d_off, d_regw, d_part, d_res;
+    DevBuf<uint8_t> d_live;
+    DevBuf<uint32_t> d_cnt;
+    DevBuf<int32_t> d_regidx;
+    DevBuf<CsumChunk> d_chunk;
+    DevBuf<CsumJoin> d_join;
+    GPV_BUF(d_mu, resize((size_t)nq));
+    GPV_BUF(d_live, resize((size_t)nq));
+    GPV_BUF(d_S, resize((size_t)nq * 2));
+    GPV_BUF(d_cnt, resize((size_t)nq * nthr));
+    if (offset) GPV_BUF(d_off, upload(offset, (size_t)nq));
+    if (nreg > 0) {
+        if (nnz > 0) GPV_BUF(d_regidx, upload(regidx, (size_t)nnz));
+        if (nnz > 0 && regw) GPV_BUF(d_regw, upload(regw, (size_t)nnz));
+        if (!chunks.empty()) GPV_BUF(d_chunk, upload(chunks.data(), chunks.size()));
+        if (!joins.empty()) GPV_BUF(d_join, upload(joins.data(), joins.size()));
+        GPV_BUF(d_part, resize((size_t)nslots * V * NB));
+        GPV_BUF(d_res, resize((size_t)nreg * V * NB));
+    }
+    Event evf[3];                                       // around the folds of a batch, and behind the copies of its region block
+    for (auto &e : evf) GPV_HIP(hipEventCreate(e.put()));
+    CsumArgs a{};
+    a.X = op.d_X; a.mu = d_mu; a.live = d_live; a.nq = nq; a.nthr = nthr;
+    for (int t = 0; t < nthr; ++t) a.thr[t] = thr[t];
+    a.S1 = d_S; a.S2 = d_S + nq; a.cnt = d_cnt;
+    a.nreg = nreg; a.regidx = d_regidx; a.regw = d_regw; a.chunk = d_chunk; a.nchunks = (int64_t)chunks.size();
+    a.join = d_join; a.njoin = (int64_t)joins.size(); a.part = d_part;
+    a.rtot = d_res; a.rmax = d_res + (size_t)nreg * NB; a.rmin = d_res + (size_t)nreg * NB * 2; a.rarea = d_res + (size_t)nreg * NB * 3;
+    // ---- the means (one column: d_X[nq][1]), mu and the live mask
+    if (op.mean_sweep()) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(launch_csum_prepare(op.d_X, d_off, nq, d_mu, d_live, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemsetAsync(d_S, 0, sizeof(double) * (size_t)nq * 2, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (nthr > 0 && GPV_HIP_FAILED(hipMemsetAsync(d_cnt, 0, sizeof(uint32_t) * (size_t)nq * nthr, st))) return drain_fail(st, GPV_ERR_HIP);
+    std::vector<uint8_t> live((size_t)nq);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(live.data(), d_live, (size_t)nq, hipMemcpyDeviceToHost, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
+    op.sweep_time();
+    for (int64_t r = 0; r < nreg; ++r) {                // once per region, in the order of its list
+        double wsum = 0.0;
+        int64_t cnt = 0;
+        for (int64_t e = regptr[r]; e < regptr[r + 1]; ++e)
+            if (live[(size_t)regidx[e]]) {
+                wsum += regw ? regw[e] : 1.0;
+                ++cnt;
+            }
+        reg_weight[r] = wsum;
+        reg_count[r] = cnt;
+    }
+    // ---- the batches: normals, sweep, folds, and the region block of the requested columns
+    for (int64_t b = col0 / NB; b * NB < end; ++b) {
+        const int64_t base = b * NB;
+        const int64_t j0 = std::max(base, col0), j1 = std::min(base + NB, end);
+        const unsigned colmask = (unsigned)(((1ull << (j1 - base)) - 1ull) & ~((1ull << (j0 - base)) - 1ull));
+        if (op.draw_sweep(seed, base)) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipEventRecord(evf[0], st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(launch_csum_accum(a, link, colmask, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (nreg > 0 && GPV_HIP_FAILED(launch_csum_fold(a, link, st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipEventRecord(evf[1], st))) return drain_fail(st, GPV_ERR_HIP);
+        if (nreg > 0) {
+            const size_t cols = (size_t)(j1 - j0) * (size_t)nreg, src = (size_t)(j0 - base) * (size_t)nreg, dst = (size_t)(j0 - col0) * (size_t)nreg;
+            if (GPV_HIP_FAILED(hipMemcpyAsync(reg_total + dst, a.rtot + src, sizeof(double) * cols, hipMemcpyDeviceToHost, st)) ||
+                GPV_HIP_FAILED(hipMemcpyAsync(reg_max + dst, a.rmax + src, sizeof(double) * cols, hipMemcpyDeviceToHost, st)) ||
+                GPV_HIP_FAILED(hipMemcpyAsync(reg_min + dst, a.rmin + src, sizeof(double) * cols, hipMemcpyDeviceToHost, st)) ||
+                (nthr > 0 && GPV_HIP_FAILED(hipMemcpyAsync(reg_area + dst * nthr, a.rarea + src * nthr, sizeof(double) * cols * nthr,
+                                                           hipMemcpyDeviceToHost, st))))
+                return drain_fail(st, GPV_ERR_HIP);
+        }
+        if (GPV_HIP_FAILED(hipEventRecord(evf[2], st))) return drain_fail(st, GPV_ERR_HIP);
+        if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
+        op.sweep_time();
+        float t = 0.f;
+        if (hipEventElapsedTime(&t, evf[0], evf[1]) == hipSuccess) {
+            pl->cs_fold_ms += (double)t;
+            pl->cs_last_fold_ms = (double)t;
+        }
+        if (hipEventElapsedTime(&t, evf[1], evf[2]) == hipSuccess) {
+            pl->cs_copy_ms += (double)t;
+            pl->cs_last_copy_ms = (double)t;
+        }
+    }
+    // ---- the per-location results, staged in d_X: the last batch is folded
+    double *const d_out = op.d_X;
+    if (GPV_HIP_FAILED(launch_csum_finish(a, link, ndraws, d_out, st))) return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipMemcpyAsync(mean, d_out, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st)) ||
+        GPV_HIP_FAILED(hipMemcpyAsync(mc_mean, d_out + nq, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st)) ||
+        GPV_HIP_FAILED(hipMemcpyAsync(mc_var, d_out + 2 * nq, sizeof(double) * (size_t)nq, hipMemcpyDeviceToHost, st)) ||
+        (nthr > 0 && GPV_HIP_FAILED(hipMemcpyAsync(exceed, d_out + 3 * nq, sizeof(double) * (size_t)nq * nthr, hipMemcpyDeviceToHost, st))))
+        return drain_fail(st, GPV_ERR_HIP);
+    if (GPV_HIP_FAILED(hipStreamSynchronize(st))) return drain_fail(st, GPV_ERR_HIP);
+    if (const int rc = op.failed(n_failed)) return rc;
+    *n_levels = op.nlev;
+    *n_launches = (int64_t)op.launches.size();
     return GPV_OK;
 }
 
@@ -3790,6 +4015,19 @@ extern "C" int gpv_plan_debug_csim_ms(gpv_plan *pl, double *ms)
     ms[1] = pl->cs_factor_ms;
     ms[2] = pl->cs_sweep_ms;
     ms[3] = pl->cs_last_sweep_ms;
+    return GPV_OK;
+}
+
+// the folds of the latest gpv_plan_cond_sim_summary: {folds of all batches, of the last batch, the copies of the region blocks of
+// all batches, of the last batch} in milliseconds, device time by event pairs around the accumulation and the region fold
+// alone, and from there to behind the copies (the sweeps of that call: gpv_plan_debug_csim_ms)
+extern "C" int gpv_plan_debug_csim_summary_ms(gpv_plan *pl, double *ms)
+{
+    if (!pl || !ms) return GPV_ERR_BAD_ARG;
+    ms[0] = pl->cs_fold_ms;
+    ms[1] = pl->cs_last_fold_ms;
+    ms[2] = pl->cs_copy_ms;
+    ms[3] = pl->cs_last_copy_ms;
     return GPV_OK;
 }
 

@@ -894,6 +894,58 @@ int gpv_plan_cond_sim(gpv_plan *plan, const char *covType, const double *covparm
 int gpv_csim_levels_host(const int32_t *NN, int64_t nq, int m, int64_t Nlocs, int32_t *level, int32_t *order, int64_t *levptr,
                          int64_t *n_levels);
 
+/* Summaries of conditional draws of a map, folded on the device (gpv_csim_summary.hip): the operator of gpv_plan_cond_sim is
+ * built once, each batch of 16 seeded draws is swept as there and folded while it is in device memory; the draws themselves
+ * never reach the host.  Device memory: what gpv_plan_cond_sim keeps, less its staging copy, plus 8 (3 + nthr / 2) + 1 bytes
+ * per location, the regions' lists and one batch's region block; nothing grows with ndraws.
+ *   covType ... eligible_ord       as gpv_plan_cond_sim, with ONE data column: Z_ord NULL (the plan's data) or Nlocs values in
+ *                                  the ORDERED layout; ncols must be 1
+ *   seed, col0, ndraws             the draws j = col0 .. col0 + ndraws - 1 of the library's generator, the bits of
+ *                                  gpv_plan_cond_sim with E == NULL (draw j is made in the batch [16 floor(j / 16), + 16));
+ *                                  ndraws >= 2
+ *   offset                         NULL or nq values in sweep order (a trend).  With mean_i and dev_ij of gpv_plan_cond_sim,
+ *                                      mu_i = mean_i + offset_i,   y_ij = mu_i + dev_ij
+ *                                  (two rounded adds in that order: the host's (mean + offset) + dev has the same bits)
+ *   link                           g: 0 identity, 1 exp, 2 logistic (the codes of gpv_plan_draws_summary)
+ *   nthr, thr                      0 .. 8 thresholds on the latent scale of y, offset included
+ * A location is LIVE when mean_i is not NaN (the failed locations and all that depend on them: the same set in every column).
+ * Per location (nq each, sweep order; NaN where the location is not live, but sd, which is that of gpv_plan_cond_sim):
+ *   mean = mu;  sd;  with d_ij = g(y_ij) - g(mu_i) and N = ndraws:
+ *   mc_mean = g(mu_i) + sum_j d_ij / N,   mc_var = (sum d^2 - (sum d)^2 / N) / (N - 1), clamped at 0,
+ *   exceed[t * nq + i] = #{j : y_ij > thr_t} / N.
+ * The sums run over the batches in ascending order and inside a batch over one fixed tree of its 16 columns (the columns
+ * outside [col0, col0 + ndraws) are exact zeros).
+ * Regions in CSR form over sweep rows: region r holds regidx[regptr[r] .. regptr[r + 1]) with the weights regw there (regw NULL:
+ * weights 1; any sign, finite).  A location may be in several regions or in none, a region may be empty.  Over the LIVE members:
+ *   reg_total[j * nreg + r]              = sum_i w_i g(y_ij)                (j counted from col0)
+ *   reg_max, reg_min (same layout)       of y_ij, on the latent scale: g is monotone
+ *   reg_area[(j * nthr + t) * nreg + r]  = sum_i w_i [y_ij > thr_t]
+ *   reg_weight[r] = sum_i w_i, reg_count[r] = their number                  (once per region)
+ * A region without a live member: total 0, areas 0, max = min = NaN, weight 0, count 0.  A region's list is cut from its start
+ * into chunks of 128 entries, a chunk is added entry by entry, the chunks meet in ascending order, and there are no
+ * floating-point atomics: results are bitwise reproducible, and the region outputs of draw j depend on (seed, j, the region's
+ * own list and weights) alone, not on col0, ndraws, nreg, the region's place among the regions or the factor pass's chunks.
+ *   n_levels, n_launches, n_failed  as gpv_plan_cond_sim (launches per sweep)
+ * Needs no evaluation and disturbs none.  Arguments, then state, are validated before the device is touched, and a refused
+ * call writes nothing.  Statuses as gpv_plan_cond_sim, and GPV_ERR_BAD_ARG: ncols != 1, ndraws < 2, col0 < 0 or col0 + ndraws
+ * overflows, link outside 0 .. 2, nthr outside 0 .. 8, a required pointer NULL (thr and exceed with nthr > 0; the region
+ * arrays with nreg > 0, reg_area with both), nreg < 0, regptr not non-decreasing from 0, a weight that is not finite;
+ * GPV_ERR_INDEX: an entry of regidx outside [0, nq).  nq == 0 is GPV_OK (every region is then empty). */
+int gpv_plan_cond_sim_summary(gpv_plan *plan, const char *covType, const double *covparms, int ncovparms,
+                              const double *nuggets, int64_t n_nuggets,
+                              const double *Z_ord, int ncols,               /* NULL or Nlocs values; ncols == 1 */
+                              const double *qlocs, int64_t nq, int m, const int *NNq,
+                              const double *scale, const unsigned char *eligible_ord,
+                              uint64_t seed, int64_t col0, int64_t ndraws,
+                              const double *offset, int link, int nthr, const double *thr,
+                              int64_t nreg, const int64_t *regptr, const int32_t *regidx, const double *regw,
+                              double *mean, double *sd, double *mc_mean, double *mc_var,    /* nq each */
+                              double *exceed,                                               /* nthr x nq */
+                              double *reg_total, double *reg_max, double *reg_min,          /* nreg x ndraws, column-major */
+                              double *reg_area,                                             /* nreg x nthr x ndraws */
+                              double *reg_weight, int64_t *reg_count,                       /* nreg */
+                              int64_t *n_levels, int64_t *n_launches, int64_t *n_failed);
+
 #ifdef __cplusplus
 }
 #endif

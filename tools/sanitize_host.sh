@@ -18,7 +18,7 @@ mkdir -p "$OUT"
 # which takes the library's units from gpvecchia_amd/build.py units()
 DRIVERS="solve_t_driver draws_summary_driver loglik_grad_driver loglik_grad_nu_driver whiten_driver loglik_rep_driver
   scaledim_driver selinv_driver sgv_grad_driver nn_driver loo_driver blockcv_driver krige_driver krige_groups_driver
-  csim_driver"
+  csim_driver csim_summary_driver"
 python "$ROOT/tests/_host_driver_build.py" --sanitize asan --plist "$PLIST" --out "$OUT/asan" host_driver $DRIVERS \
   unwhiten_driver loglik_fisher_driver alloc_failure_driver
 python "$ROOT/tests/_host_driver_build.py" --sanitize tsan --plist "$PLIST" --out "$OUT/tsan" host_driver=--quick $DRIVERS
